@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the EgoNet hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One *step* = one batch of B synthetic 256x256 crops per GPU through the whole
 hot path with inputs resident in HBM:
@@ -12,9 +12,13 @@ soft-argmax", extended by the lift so that the number is the headline metric
 crops/s "heatmap+decode+lift").  Crops shard across ranks with no data-path
 collective (weak scaling, B per GPU fixed).
 
-The same run then measures the two TRAINING configurations of BASELINE.json, each with its
-own warm-up + timed steps bracketed by barrier + synchronize (max over ranks), and adds them to
-the same JSON line (``--no-train`` skips them):
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the headline
+`value` and `ms_per_step`.  ``--dump-outputs DIR`` then writes what the last timed step returned as
+DIR/<name>.npy; inputs and weights are seeded, so two builds can be compared output for output.
+
+Everything else runs with ``--full`` only.  The same run then measures the two TRAINING configurations
+of BASELINE.json, each with its own warm-up + timed steps bracketed by barrier + synchronize (max over
+ranks), and adds them to the same JSON line (``--no-train`` skips them):
   train_hc      configs[3]: HRNet-W48 forward + backward + Adam, 32 crops/GPU, native HIP step,
                 RCCL all-reduce of the flat gradient when N > 1 (whole-job crops/s)
   train_lifter  configs[2]: FC lifter forward + backward + Adam, batch 4096 (N = 1 only)
@@ -22,7 +26,7 @@ each with ms/step, algorithmic TFLOP/s, the dominant conv/GEMM kernel's roofline
 (hipEvents around every launch in one extra single-stream step) and the CPU training oracle's
 rate on a bounded sample.
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+With ``--full`` the line also carries
   roofline      the dominant kernel (by time; keyed by the kernel SYMBOL that
                 rocprofv3 prints) of the backbone, measured live with hipEvents
                 around every launch of the native program on the stream the
@@ -61,10 +65,16 @@ def parse():
     p.add_argument('--warmup', type=int, default=5)
     p.add_argument('--batch', type=int, default=64, help='crops per GPU per step')
     p.add_argument('--head', default='heatmap', choices=['heatmap', 'coordinates'])
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--dump-outputs', default='', metavar='DIR',
+                   help='after the timed steps write what the last timed step returned (rank 0\'s crops) as '
+                        'DIR/<name>.npy, float32 / float64 as the path returns them')
+    p.add_argument('--full', action='store_true',
+                   help='everything beyond the headline figure: per-kernel timing and roofline of the backbone, the '
+                        'CPU oracle baseline and the two training blocks (configs 3 and 4)')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle baselines')
     p.add_argument('--cpu-seconds', type=float, default=15.0)
-    p.add_argument('--profile-json', default='', help='write the per-op timing table here')
-    p.add_argument('--no-train', action='store_true', help='skip the training blocks (configs 3 and 4)')
+    p.add_argument('--profile-json', default='', help='write the per-op timing table here (implies --full)')
+    p.add_argument('--no-train', action='store_true', help='with --full: skip the training blocks (configs 3 and 4)')
     p.add_argument('--train-batch', type=int, default=32, help='crops per GPU of the train_hc block')
     p.add_argument('--lifter-batch', type=int, default=4096)
     p.add_argument('--pipelined', action='store_true',
@@ -73,12 +83,16 @@ def parse():
     p.add_argument('--live-traffic', action='store_true',
                    help='measure roofline.traffic IN THIS RUN: two short child passes of the forward under '
                         '`rocprofv3 --kernel-trace --pmc FETCH_SIZE` / `WRITE_SIZE` (own runs, 120 s limit each; off by '
-                        'default: the driver\'s bench run must not depend on the profiler)')
+                        'default: a bench run must not depend on the profiler; implies --full)')
     p.add_argument('--traffic-child', action='store_true', help=argparse.SUPPRESS)
     p.add_argument('--dry-run', action='store_true',
                    help='launcher / rendezvous / timing-reduction plumbing only (no GPU work): what the CPU test of '
                         '`--gpus N` runs with EGONET_AMD_DIST_BACKEND=gloo')
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error('--steps must be at least 1 and --warmup at least 0')
+    args.full = args.full or bool(args.profile_json) or args.live_traffic
+    return args
 
 
 def build_model(head, device):
@@ -254,6 +268,69 @@ def traffic_child(args):
     for _ in range(3):
         eng.forward(crops, decode_mode=1 if args.head == 'heatmap' else None)
     torch.cuda.synchronize()
+
+
+def dump_outputs(out, path):
+    """What the timed path returned in its last step, one ``path/<name>.npy`` per array, in the dtype the path returns
+    (kpts_2d / kpts_3d / euler / translation / alpha float64, local float32): a few kB per crop."""
+    os.makedirs(path, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(path, name + '.npy'), v.detach().cpu().numpy())
+
+
+def backbone_tables(args, eng, crops, decode, world):
+    """--full: per-kernel timing of the backbone program -- hipEvents around every launch, serial on the stream the
+    kernels run on, outside the timed region -- as the `roofline`, `backbone`, `kernel_symbols` and `kernels` entries of
+    the line (and the --profile-json table)."""
+    B = crops.shape[0]
+    mode = 1 if decode == 'soft' else None
+    samples = []
+    for it in range(5):
+        eng.forward(crops, decode_mode=mode, timed=True)
+        if it >= 2:
+            samples.append(eng.last_ms)
+    ms = np.mean(samples, axis=0)
+    prog = eng.program(crops, mode)
+    (rows, total_ms), (syms, _) = kernel_tables(prog, ms)
+    dom = syms[0]
+    mfma_bound = dom['flops'] > 0 and dom['flops'] / max(dom['bytes'], 1) > 20
+    if mfma_bound:
+        roof = mfma_roofline(dom['name'], dom['tflops'], dom['executed_tflops'])
+    else:
+        traffic, src = measured_traffic(dom['name'])
+        roof = {'bound': 'hbm', 'kernel': dom['name'], 'achieved': dom['gbps'], 'peak': PEAK_HBM_GBPS,
+                'unit': 'GB/s', 'frac': dom['gbps'] / PEAK_HBM_GBPS, 'traffic': traffic,
+                'traffic_source': None if traffic is None else src + ' (committed rocprofv3 --pmc passes)'}
+    roof.update(launches=dom['launches'], avg_us=dom['avg_us'], time_share=dom['share'],
+                algorithmic_gflop_per_launch=dom['flops'] / dom['launches'] / 1e9,
+                algorithmic_mb_per_launch=dom['bytes'] / dom['launches'] / 1e6)
+    if args.live_traffic and world == 1:
+        lt, how = live_traffic(dom['name'], args)
+        if lt is not None:
+            roof['traffic'], roof['traffic_source'] = lt, how
+        else:
+            roof['traffic_live_error'] = how
+    conv_flops = sum(a['flops'] for a in rows)
+    conv_xflops = sum(a['xflops'] for a in rows)
+
+    def slim(a):
+        return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in a.items()
+                if k in ('name', 'launches', 'ms', 'share', 'tflops', 'executed_tflops', 'gbps', 'avg_us')}
+    if args.profile_json:
+        with open(args.profile_json, 'w') as f:
+            json.dump({'ops': [dict(m, ms=float(t)) for m, t in zip(prog.meta, ms)], 'classes': rows,
+                       'symbols': syms}, f, indent=1)
+    return {
+        'roofline': roof,
+        'backbone': {'ms_sum_of_kernels': total_ms, 'gflop_per_crop': conv_flops / B / 1e9,
+                     'direct_equivalent_tflops_overall': conv_flops / (total_ms * 1e-3) / 1e12,
+                     'executed_tflops_overall': conv_xflops / (total_ms * 1e-3) / 1e12,
+                     'executed_frac_of_fp32_peak': conv_xflops / (total_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS,
+                     'launches': int(sum(a['launches'] for a in rows)), 'arena_mb': prog.arena_bytes / 2 ** 20,
+                     'weights_mb': prog.weight_bytes / 2 ** 20},
+        'kernel_symbols': [slim(a) for a in syms[:8]],
+        'kernels': [slim(a) for a in rows[:12]],
+    }
 
 
 def cpu_baseline(cfg, hc_sd, l_sd, stats, head, seconds):
@@ -597,6 +674,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert torch.isfinite(out['kpts_3d']).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     # ---- the same K steps with TWO batches in flight (serving form): two streams alternate, each with its own copy of
     # the launch programs (slot 0 / 1: own arena, own launch lanes), so that the low-occupancy head and tail of one batch
@@ -624,42 +703,7 @@ def main():
                'in_flight': 2, 'note': 'two streams alternate, a program copy per stream; same K steps, same bits'}
 
     if rank == 0:
-        # per-kernel timing of the backbone program: hipEvents around every launch,
-        # serial on the stream the kernels run on, outside the timed region
         eng = ego.HC._hip_engine()
-        mode = 1 if decode == 'soft' else None
-        samples = []
-        for it in range(5):
-            eng.forward(crops, decode_mode=mode, timed=True)
-            if it >= 2:
-                samples.append(eng.last_ms)
-        ms = np.mean(samples, axis=0)
-        prog = eng.program(crops, mode)
-        (rows, total_ms), (syms, _) = kernel_tables(prog, ms)
-        dom = syms[0]
-        mfma_bound = dom['flops'] > 0 and dom['flops'] / max(dom['bytes'], 1) > 20
-        if mfma_bound:
-            roof = mfma_roofline(dom['name'], dom['tflops'], dom['executed_tflops'])
-        else:
-            traffic, src = measured_traffic(dom['name'])
-            roof = {'bound': 'hbm', 'kernel': dom['name'], 'achieved': dom['gbps'], 'peak': PEAK_HBM_GBPS,
-                    'unit': 'GB/s', 'frac': dom['gbps'] / PEAK_HBM_GBPS, 'traffic': traffic,
-                    'traffic_source': None if traffic is None else src + ' (committed rocprofv3 --pmc passes)'}
-        roof.update(launches=dom['launches'], avg_us=dom['avg_us'], time_share=dom['share'],
-                    algorithmic_gflop_per_launch=dom['flops'] / dom['launches'] / 1e9,
-                    algorithmic_mb_per_launch=dom['bytes'] / dom['launches'] / 1e6)
-        if args.live_traffic and world == 1:
-            lt, how = live_traffic(dom['name'], args)
-            if lt is not None:
-                roof['traffic'], roof['traffic_source'] = lt, how
-            else:
-                roof['traffic_live_error'] = how
-        conv_flops = sum(a['flops'] for a in rows)
-        conv_xflops = sum(a['xflops'] for a in rows)
-
-        def slim(a):
-            return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in a.items()
-                    if k in ('name', 'launches', 'ms', 'share', 'tflops', 'executed_tflops', 'gbps', 'avg_us')}
         value = world * B * args.steps / dt
         result = {
             'metric': 'crops/sec (256x256, heatmap+decode+lift)', 'value': value, 'unit': 'crops/s',
@@ -672,26 +716,15 @@ def main():
                        'parallelism': 'replicas x%d, crops sharded by rank, no collective' % world,
                        'ranks': dist.get_world_size() if dist else 1, 'backend': backend,
                        'launch_lanes': int(eng.lanes)},
-            'roofline': roof,
-            'backbone': {'ms_sum_of_kernels': total_ms, 'gflop_per_crop': conv_flops / B / 1e9,
-                         'direct_equivalent_tflops_overall': conv_flops / (total_ms * 1e-3) / 1e12,
-                         'executed_tflops_overall': conv_xflops / (total_ms * 1e-3) / 1e12,
-                         'executed_frac_of_fp32_peak': conv_xflops / (total_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS,
-                         'launches': int(sum(a['launches'] for a in rows)), 'arena_mb': prog.arena_bytes / 2 ** 20,
-                         'weights_mb': prog.weight_bytes / 2 ** 20},
-            'kernel_symbols': [slim(a) for a in syms[:8]],
-            'kernels': [slim(a) for a in rows[:12]],
         }
+        if args.full:
+            result.update(backbone_tables(args, eng, crops, decode, world))
         if two is not None:
             result['two_batches_in_flight'] = two
-        if args.profile_json:
-            with open(args.profile_json, 'w') as f:
-                json.dump({'ops': [dict(m, ms=float(t)) for m, t in zip(prog.meta, ms)], 'classes': rows,
-                           'symbols': syms}, f, indent=1)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result['cpu_baseline'] = cpu_baseline(cfg, hc_sd, l_sd, ego.LS, args.head, args.cpu_seconds)
-    # ---- the training configurations, same run, their own timed regions ----
-    if not args.no_train:
+    # ---- --full: the training configurations, same run, their own timed regions ----
+    if args.full and not args.no_train:
         del ego, crops
         torch.cuda.empty_cache()
         try:

@@ -47,5 +47,13 @@ def test_help_prints_every_option():
     """argparse expands `%` in help strings: a literal per-cent sign there made `--help` raise (found in round 4)."""
     r = _run(['--help'])
     assert r.returncode == 0, r.stderr[-2000:]
-    for opt in ('--gpus', '--steps', '--warmup', '--batch', '--pipelined', '--live-traffic', '--profile-json'):
+    for opt in ('--gpus', '--steps', '--warmup', '--batch', '--pipelined', '--live-traffic', '--profile-json', '--full',
+                '--dump-outputs'):
         assert opt in r.stdout
+
+
+def test_zero_steps_is_refused_before_any_work():
+    """`ms_per_step` divides by --steps: zero timed steps is an argument error, not a division by zero after the run."""
+    r = _run(['--gpus', '1', '--steps', '0'])
+    assert r.returncode == 2 and '--steps' in r.stderr
+    assert not [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

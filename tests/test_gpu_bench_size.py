@@ -124,6 +124,32 @@ def test_w48_forward_and_decode_at_bench_batch_64_vs_oracle():
     np.testing.assert_allclose(xy.cpu().numpy(), sxy, rtol=0, atol=1e-3)
 
 
+def test_plain_bench_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py` without --full times exactly --steps steps, prints the headline fields and none of --full's, and
+    --dump-outputs writes the arrays the last timed step returned."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--dump-outputs', str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       universal_newlines=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out['steps'] == 3 and out['warmup'] == 1 and out['n_gpus'] == 1
+    assert out['unit'] == 'crops/s' and out['higher_is_better'] is True and out['dtype'] == 'f32'
+    assert out['ms_per_step'] > 0 and abs(out['value'] - 64e3 / out['ms_per_step']) < 1e-9 * out['value']
+    assert not {'roofline', 'backbone', 'kernels', 'cpu_baseline', 'train_hc', 'train_lifter'} & set(out)
+    got = {f[:-len('.npy')]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    want = {'local': ((64, 33, 2), np.float32), 'kpts_2d': ((64, 66), np.float64),
+            'kpts_3d': ((64, 32, 3), np.float64), 'euler': ((64, 3), np.float64), 'alpha': ((64,), np.float64),
+            'translation': ((64, 3), np.float64)}
+    assert sorted(got) == sorted(want)
+    for k, (shape, dtype) in want.items():
+        assert got[k].shape == shape and got[k].dtype == dtype and np.isfinite(got[k]).all(), k
+    np.testing.assert_array_equal(got['translation'], got['kpts_3d'][:, 0])
+
+
 def _committed_ties(batch):
     """[(crop, joint), ...] of tests/golden/argmax_ties.json for this batch size: the ONLY maps whose arg-max index may
     differ from the oracle's (the allowance is a committed list, not a count)."""

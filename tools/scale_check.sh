@@ -31,7 +31,7 @@ mkdir -p "$OUT"
 N=1
 while [ "$N" -le "$MAX" ] && [ "$N" -le "$NDEV" ]; do
   echo "== bench.py --gpus $N" >&2
-  python bench.py --gpus "$N" --steps "${STEPS:-50}" --warmup "${WARMUP:-5}" --no-cpu-baseline \
+  python bench.py --gpus "$N" --steps "${STEPS:-50}" --warmup "${WARMUP:-5}" --full --no-cpu-baseline \
       > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err" || { echo "bench.py --gpus $N failed (see $OUT/bench_n$N.err)"; tail -5 "$OUT/bench_n$N.err"; exit 1; }
   N=$((N * 2))
 done
