@@ -47,6 +47,7 @@ SIGNATURES = {
     'egn_nchw_to_nhwc_f32': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     'egn_nhwc_to_nchw_f32': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     'egn_pixel_shuffle_nhwc_to_nchw_f32': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    'egn_pixel_unshuffle_nchw_to_nhwc_f32': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     'egn_fill_coord_ramps_f32': (_i, [_p, _i, _i, _i, _i, _i, _p]),
     'egn_decode_heatmaps_f32': (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     'egn_keypoints_to_screen_f64': (_i, [_p, _i, _i, _d, _d, _p, _p, _i, _i, _p, _p, _p, _p, _i, _p]),
@@ -82,6 +83,9 @@ SIGNATURES = {
     'egn_mse_f32': (_i, [_p, _p, _i, _i, _i, _i, C.c_float, _i, _p, _p, _p]),
     'egn_l1_f32': (_i, [_p, _p, C.c_long, C.c_float, _p, _p, _p]),
     'egn_elem_loss_f32': (_i, [_p, _p, _i, _i, _i, _i, _i, C.c_float, _i, _p, _p, _p]),
+    'egn_pixshuf_loss_f32': (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, C.c_float, _p, _p, _p]),
+    'egn_avgpool_fwd_f32': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    'egn_avgpool_bwd_f32': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     'egn_cross_ratio_ws_bytes': (C.c_long, [_i, _i]),
     'egn_cross_ratio_f32': (_i, [_p, _i, _i, _p, _i, _d, C.c_float, _i, C.c_float, _p, _p, _p, _p]),
     'egn_sigmoid_bwd_f32': (_i, [_p, _p, _p, C.c_long, _p]),

@@ -15,8 +15,13 @@ torch hands in.  torch keeps what the reference's loop owns: the loss (``JointsC
 run.  The fully native steps (``HRNetTrainStep`` / ``LifterTrainStep``: loss + Adam as HIP kernels, flat
 gradient buffer, overlapped all-reduce) stay the faster path; this is the drop-in one.
 
+Every head of ``PoseHighResolutionNet`` trains here: 'coordinates', 'heatmap' (plain or with the pixel-shuffle
+upsampler: the maps' gradient is unshuffled into the pre-shuffle activations, csrc/heads.hip) and 'angleregression'
+(AvgPool2d + Linear/BatchNorm1d/ReLU + Linear on the tape; the reference defines no loss for it, so the caller's
+criterion on the returned [N, 2] is the only way to train it).
+
 Limits (raise or fall back loudly, never silently): the input must not require a gradient (the modules
-route such calls to the torch graph); heads as in ``HRNetTrainStep`` ('coordinates', 'heatmap').
+route such calls to the torch graph).
 """
 import torch
 
@@ -80,6 +85,10 @@ class HRNetAutograd(TapeOwner):
             J = m.num_joints
             if m.head_type == 'coordinates':
                 outs = (tape.maps_user, tape.user['head2.4'].view(n, J, 2))
+            elif m.head_type == 'angleregression':
+                outs = (tape.user['final_fc.3'].view(n, -1),)
+            elif m.pixel_shuffle:
+                outs = (tape.user['upsample_layer.3'],)
             else:
                 outs = (tape.user['final_layer'],)
         return tape, outs
@@ -110,6 +119,23 @@ class HRNetAutograd(TapeOwner):
                     dpad = tape._empty(n * coords.cs)             # back to the padded NHWC row layout
                     _lib.check(L.egn_nchw_to_nhwc_f32(_lib.ptr(dc), _lib.ptr(dpad), n, 2 * J, 1, 1, coords.cs, st))
                     tape.grad[id(coords)] = [dpad, True]
+            elif m.head_type == 'angleregression':
+                aug, g_maps = None, None
+                out = tape.named['final_fc.3']
+                if gouts[0] is not None:
+                    g = gouts[0].contiguous().float().view(n, out.c)
+                    dpad = tape._empty(n * out.cs)                # [N, 2] -> the padded row layout of final_fc.3
+                    _lib.check(L.egn_nchw_to_nhwc_f32(_lib.ptr(g), _lib.ptr(dpad), n, out.c, 1, 1, out.cs, st))
+                    tape.grad[id(out)] = [dpad, True]
+            elif m.pixel_shuffle:
+                aug, g_maps = None, None
+                u = tape.named['upsample_layer.3']               # the pre-shuffle activations
+                if gouts[0] is not None:
+                    gm = gouts[0].contiguous().float()
+                    du = tape._empty(n * u.h * u.w * u.cs)
+                    _lib.check(L.egn_pixel_unshuffle_nchw_to_nhwc_f32(_lib.ptr(gm), _lib.ptr(du), n, J, u.h, u.w, u.cs,
+                                                                     int(m.upsamp_fact), st), 'pixel_unshuffle')
+                    tape._accum(u, du)
             else:
                 aug = tape.named['final_layer']
                 g_maps = gouts[0]

@@ -771,12 +771,19 @@ class HRNetEngine(object):
                 raise ValueError('angle head expects a %dx%d map in front of AvgPool2d(%d), got %dx%d'
                                  % (ks, ks, ks, t.h, t.w))
             fc1, bn1, fc2 = m.final_fc[0], m.final_fc[1], m.final_fc[3]
-            w1 = (fc1.weight.detach() / float(ks * ks)).view(fc1.out_features, fc1.in_features, 1, 1) \
-                .expand(-1, -1, ks, ks).contiguous()
-            y = r.conv(t, w1, fc1.bias, bn1, ACT_RELU, None, 1, 0, tag='final_fc.0')
+            if hasattr(r, 'avgpool'):
+                # the training tape: the layers as the module defines them (AvgPool2d, then the Linear layers as
+                # parameters of their own -- their gradients belong to fc1.weight / fc2.weight, not to a derived filter)
+                t = r.avgpool(t, ks, tag='head.5')
+                y = r.conv(t, fc1.weight, fc1.bias, bn1, ACT_RELU, None, 1, 0, tag='final_fc.0')
+                w2 = fc2.weight
+            else:
+                w1 = (fc1.weight.detach() / float(ks * ks)).view(fc1.out_features, fc1.in_features, 1, 1) \
+                    .expand(-1, -1, ks, ks).contiguous()
+                y = r.conv(t, w1, fc1.bias, bn1, ACT_RELU, None, 1, 0, tag='final_fc.0')
+                w2 = fc2.weight.view(fc2.out_features, fc2.in_features, 1, 1)
             out = Buf(n, 1, 1, fc2.out_features, cs=fc2.out_features, slot=SLOT_USER0 + 1, name='angles')
-            r.conv(y, fc2.weight.view(fc2.out_features, fc2.in_features, 1, 1), fc2.bias, None, ACT_NONE, None,
-                   1, 0, dst=out, out_nchw=True, tag='final_fc.3')
+            r.conv(y, w2, fc2.bias, None, ACT_NONE, None, 1, 0, dst=out, out_nchw=True, tag='final_fc.3')
             out_shapes = {'maps': (n, fc2.out_features)}          # the module returns [N, 2]
             nslots = 2
             decode_mode = None

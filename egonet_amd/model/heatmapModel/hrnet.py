@@ -286,9 +286,8 @@ class PoseHighResolutionNet(nn.Module):
         Train mode under autograd -- the reference's hot loop ``model(data); loss.backward(); optim.step()``
         (libs/trainer/trainer.py:183-209), unchanged: ONE autograd node whose forward / backward are the
         native train-mode tape (egonet_amd.autograd.HRNetAutograd); torch owns loss and optimiser.
-        ``EGONET_AMD_AUTOGRAD=0``, an input that requires a gradient, heads the tape does not train
-        (pixel shuffle / angle regression) and train mode WITHOUT autograd (``get_model_summary``) run the
-        module graph in torch.  CPU tensors: torch on the CPU (the reference's CPU path)."""
+        ``EGONET_AMD_AUTOGRAD=0``, an input that requires a gradient and train mode WITHOUT autograd
+        (``get_model_summary``) run the module graph in torch.  CPU tensors: torch on the CPU (the reference's CPU path)."""
         if x.is_cuda:
             wants_input_grad = torch.is_grad_enabled() and x.requires_grad
             if not self.training:
@@ -305,9 +304,9 @@ class PoseHighResolutionNet(nn.Module):
         not executed.  Whatever needs that graph takes the module's torch forward instead (explicit opt-outs, never a
         silent difference): forward / backward hooks on any submodule (they would not fire), nn.DataParallel replicas
         (a replica is re-created on every forward, so its bridge -- walker, packed filters, side stream -- would be
-        rebuilt per step; the rank-per-GPU launcher is the performance path), head variants the tape does not cover."""
-        return (os.environ.get('EGONET_AMD_AUTOGRAD', '1') != '0' and not self.pixel_shuffle
-                and self.head_type in ('coordinates', 'heatmap')
+        rebuilt per step; the rank-per-GPU launcher is the performance path), a model with every parameter frozen.  Every
+        head type trains on the tape (pixel shuffle and angle regression included)."""
+        return (os.environ.get('EGONET_AMD_AUTOGRAD', '1') != '0'
                 and not getattr(self, '_is_replica', False)
                 and not _has_submodule_hooks(self)
                 and any(p.requires_grad for p in self.parameters()))

@@ -373,7 +373,8 @@ class _Tape(object):
             self.side.wait_event(ev)
             self.side_keep.append((xd, dy))
             st = self.side_st
-        _lib.check(L.egn_conv2d_wgrad_f32(_lib.ptr(xd), _lib.ptr(dy), _lib.ptr(self.o.grad_of(weight)), x.n, x.h, x.w, cin, x.cs,
+        _lib.check(L.egn_conv2d_wgrad_f32(_lib.ptr(xd), _lib.ptr(dy), _lib.ptr(self.o.grad_of(self.o.param_of(weight))),
+                                          x.n, x.h, x.w, cin, x.cs,
                                           cout, cs_out, kh, kw, stride, pad, _lib.ptr(ws), ws.numel() * 4, st),
                    'wgrad')
 
@@ -465,6 +466,35 @@ class _Tape(object):
         _lib.check(self.L.egn_nhwc_to_nchw_f32(_lib.ptr(self.data[id(x)]), _lib.ptr(self.maps_user), x.n, c, x.h, x.w,
                                                x.cs, self.st), 'to_nchw')
 
+    def pixel_shuffle(self, x, c, up, dst_ext, tag=''):
+        """nn.PixelShuffle(up) of the heat-map upsampler (hrnet.py:373-383, 598-600) into an NCHW user tensor
+        (``user[tag]``); ``named[tag]`` is the pre-shuffle Buf, where the gradient of the maps arrives (the step's
+        fused loss, egn_pixshuf_loss_f32, or the autograd bridge's unshuffle writes it there)."""
+        u = torch.empty(x.n, c, x.h * up, x.w * up, dtype=torch.float32, device=self.dev)
+        _lib.check(self.L.egn_pixel_shuffle_nhwc_to_nchw_f32(_lib.ptr(self.data[id(x)]), _lib.ptr(u), x.n, c, x.h, x.w,
+                                                             x.cs, up, self.st), 'pixel_shuffle')
+        self.user[tag] = u
+        self.named[tag] = x
+
+    def avgpool(self, x, k, tag=''):
+        """AvgPool2d(k) (the angle head's, hrnet.py:384-422) on csrc/heads.hip."""
+        L = self.L
+        y = self.new(x.n, x.h // k, x.w // k, x.c, cs=x.cs, name=tag)
+        xd, yd = self.data[id(x)], self.data[id(y)]
+        _lib.check(L.egn_avgpool_fwd_f32(_lib.ptr(xd), _lib.ptr(yd), x.n, x.h, x.w, x.cs, k, self.st), 'avgpool')
+        self.named[tag] = y
+
+        def backward():
+            dy = self._take_grad(y)
+            if dy is None or id(x) in self.no_grad:
+                return
+            dx = self._empty(xd.numel())
+            _lib.check(L.egn_avgpool_bwd_f32(_lib.ptr(dy), _lib.ptr(dx), x.n, x.h, x.w, x.cs, k, 0, self.st),
+                       'avgpool_bwd')
+            self._accum(x, dx)
+        self.back.append(backward)
+        return y
+
     def ramps(self, y, c0, tag=''):
         _lib.check(self.L.egn_fill_coord_ramps_f32(_lib.ptr(self.data[id(y)]), y.n, y.h, y.w, y.cs, c0, self.st),
                    'ramps')
@@ -472,6 +502,9 @@ class _Tape(object):
     def conv(self, x, weight, bias=None, bn=None, act=ACT_NONE, res=None, stride=1, pad=0,
              dst=None, out_nchw=False, cout_cs=None, tag=''):
         L = self.L
+        param = weight
+        if weight.dim() == 2:            # nn.Linear (the angle head's final_fc): a 1x1 convolution on a 1x1 map
+            weight = self.o.linear4(weight)
         cout, cin, kh, kw = weight.shape
         assert cin == x.c, (cin, x.c, tag)
         ho = (x.h + 2 * pad - kh) // stride + 1
@@ -510,17 +543,22 @@ class _Tape(object):
                 if bias is not None and bias.requires_grad:
                     _lib.check(L.egn_colsum_f32(_lib.ptr(dy), rows, cout, z.cs, _lib.ptr(self.o.grad_of(bias)),
                                                 _lib.ptr(self.o.col_ws), self.st), 'bias grad')
-                if weight.requires_grad:
+                if param.requires_grad:
                     self._wgrad(x, xd, dy, z.cs, weight, stride, pad)
                 self._accum_dgrad(x, dy, ho, wo, z.cs, weight, stride, pad)
-            backward.params = [weight] + ([bias] if bias is not None else [])     # gradients final after it
+            backward.params = [param] + ([bias] if bias is not None else [])     # gradients final after it
             self.back.append(backward)
             return z
 
+        shift = self.o.zeros
         if bias is not None:
-            raise NotImplementedError('conv bias followed by BatchNorm')
-        stats = self._conv_launch(xd, wp, self.o.zeros, zd, x.n, x.h, x.w, cin, x.cs, cout, z.cs, kh, kw, stride, pad,
-                                  ACT_NONE, weight=weight, want_stats=True)
+            # a bias in front of BatchNorm (the pixel-shuffle upsampler's 1x1 conv, the angle head's first Linear):
+            # it goes into the conv epilogue, so the batch statistics -- and running_mean -- include it like the
+            # reference's; the statistics then come from the separate reduction over z
+            shift = torch.zeros(_round_up(cout, 16), dtype=torch.float32, device=self.dev)
+            shift[:cout].copy_(bias.detach())
+        stats = self._conv_launch(xd, wp, shift, zd, x.n, x.h, x.w, cin, x.cs, cout, z.cs, kh, kw, stride, pad,
+                                  ACT_NONE, weight=weight, want_stats=bias is None)
         mean, istd = self._empty(cout), self._empty(cout)
         mom = 0.1 if bn.momentum is None else bn.momentum
         if stats is not None:      # the conv epilogue wrote per-tile partial sums: only the finalise stage is left
@@ -564,10 +602,14 @@ class _Tape(object):
                                        dgamma=dgamma, dz=dz, dres=dres, relu=relu, rows=rows, cols=cout, ld=z.cs))
             if dres is not None:
                 self._accum(res, dres)
-            if weight.requires_grad:
+            if bias is not None and bias.requires_grad:
+                # colsum(dz): zero up to rounding (BatchNorm removes a constant shift), as in the reference
+                _lib.check(L.egn_colsum_f32(_lib.ptr(dz), rows, cout, z.cs, _lib.ptr(self.o.grad_of(bias)),
+                                            _lib.ptr(self.o.col_ws), self.st), 'bias grad')
+            if param.requires_grad:
                 self._wgrad(x, xd, dz, z.cs, weight, stride, pad)
             self._accum_dgrad(x, dz, ho, wo, z.cs, weight, stride, pad)
-        backward.params = [weight, bn.weight, bn.bias]
+        backward.params = [param, bn.weight, bn.bias] + ([bias] if bias is not None else [])
         self.back.append(backward)
         return y
 
@@ -614,10 +656,11 @@ class TapeOwner(object):
         p0 = next(model.parameters())
         if not p0.is_cuda:
             raise ValueError('%s needs the model on a GPU' % type(self).__name__)
-        if model.head_type not in ('coordinates', 'heatmap') or model.pixel_shuffle:
-            raise NotImplementedError('native training: head_type %r pixel_shuffle %r'
-                                      % (model.head_type, model.pixel_shuffle))
+        if model.head_type not in ('coordinates', 'heatmap', 'angleregression'):
+            raise NotImplementedError('native training: head_type %r' % (model.head_type,))
         self.model = model
+        self._lin4 = {}               # id(nn.Linear weight) -> (weight, its [out, in, 1, 1] view)
+        self._lin_of = {}             # id(view) -> the Linear weight
         self.dev = p0.device
         self.L = _lib.lib()
         widest = max(p.shape[0] for p in model.parameters()) + 32
@@ -652,6 +695,23 @@ class TapeOwner(object):
     def grad_of(self, p):
         return p.grad
 
+    def linear4(self, p):
+        """The [out, in, 1, 1] view of an nn.Linear weight the tape convolves with: ONE view object per parameter
+        (the packed-filter cache is keyed by its id), re-made when the parameter's storage moved."""
+        ent = self._lin4.get(id(p))
+        if ent is None or ent[1].data_ptr() != p.data_ptr():
+            v = p.detach().view(p.shape[0], p.shape[1], 1, 1)
+            ent = (p, v)
+            self._lin4[id(p)] = ent
+            self._lin_of[id(v)] = (v, p)
+        return ent[1]
+
+    def param_of(self, weight):
+        """The parameter whose gradient a conv filter's weight-gradient launch writes (a Linear's view -> the Linear
+        weight: ``grad_of`` is keyed by the parameter)."""
+        ent = self._lin_of.get(id(weight))
+        return ent[1] if ent is not None and ent[0] is weight else weight
+
     def wgrad_ws(self, nbytes):
         if self._wgrad_ws is None or self._wgrad_ws.numel() * 4 < nbytes:
             # allocated in the pool of the stream that uses it: when it has to grow, the old block is
@@ -672,6 +732,11 @@ class HRNetTrainStep(TapeOwner):
                  use_target_weight=False):
         self._init_tape_owner(model)
         p0 = next(model.parameters())
+        if model.head_type == 'angleregression':
+            raise NotImplementedError(
+                "the 'angleregression' head has no loss in the reference (libs/loss defines none for it), so its "
+                "training loop cannot train it and neither can this step; train it through the autograd bridge: "
+                "model.train(); loss = criterion(model(x), target); loss.backward() runs the native tape")
         if model.head_type == 'heatmap' and w_coor:
             raise NotImplementedError("the 'heatmap' head trains with the heat-map term only (w_coor=0)")
         # JointsMSELoss(use_target_weight) (function.py:22-46, the heat-map head's criterion): both maps are multiplied
@@ -712,6 +777,41 @@ class HRNetTrainStep(TapeOwner):
         self.loss_dev = torch.zeros(1, dtype=torch.float64, device=self.dev)
         self.counters = StepCounters()
         self.last_maps = self.last_coords = None
+
+    def _pixshuf_loss(self, tape, target, joints_xy, joints_vis, target_weight, n, h, w, st):
+        """The pixel-shuffle head's JointsMSELoss-style term (hrnet.py:373-383, 598-600; function.py:22-46) as ONE
+        launch, egn_pixshuf_loss_f32: it reads the pre-shuffle activations and the NCHW target and writes the gradient
+        in the pre-shuffle layout (the shuffled maps in ``last_maps`` are for the caller only)."""
+        m, L, J = self.model, self.L, self.model.num_joints
+        u = tape.named['upsample_layer.3']                # pre-shuffle Buf [N, h, w, J*f*f (padded)]
+        f = int(m.upsamp_fact)
+        mh, mw = u.h * f, u.w * f
+        if target is None:
+            # Gaussian targets drawn on the device at heatmap_size (img_proc.py:347-409)
+            if joints_xy is None:
+                raise ValueError('step() needs target heat-maps or joints_xy to draw them from')
+            if mh != mw or h != w:
+                raise NotImplementedError('device-side targets: square maps only (the reference mixes the '
+                                          'width/height indices of input_size / heatmap_size, img_proc.py:376-383)')
+            from .common import img_proc
+            target, self.last_target_weight = img_proc.generate_target_batch(
+                joints_xy, torch.ones(n, J) if joints_vis is None else joints_vis,
+                dict(target_type='gaussian', input_size=(w, h), heatmap_size=(mh, mw), sigma=self.sigma),
+                device=self.dev)
+        if tuple(target.shape) != (n, J, mh, mw):
+            raise ValueError('target must be %s, got %s' % ((n, J, mh, mw), tuple(target.shape)))
+        target = target.contiguous().float()
+        twd = None
+        if self.use_target_weight:
+            tw = target_weight if target_weight is not None else self.last_target_weight
+            if tw is None:
+                raise ValueError('use_target_weight needs target_weight [N,K(,1)] (or device-drawn targets)')
+            twd = torch.as_tensor(tw, dtype=torch.float32).reshape(n, J).to(self.dev).contiguous()
+        du = tape._empty(n * u.h * u.w * u.cs)
+        _lib.check(L.egn_pixshuf_loss_f32(_lib.ptr(tape.data[id(u)]), _lib.ptr(target), _lib.ptr(twd), n, u.h, u.w, J,
+                                          f, u.cs, self.hm_crit, 0.5 * self.w_hm, _lib.ptr(du), _lib.ptr(self.loss_dev),
+                                          st), 'pixel-shuffle loss')
+        tape._accum(u, du)
 
     @torch.no_grad()
     def step(self, images, target, joints_xy=None, update=True, joints_vis=None, target_weight=None):
@@ -775,46 +875,52 @@ class HRNetTrainStep(TapeOwner):
                     dpad = tape._empty(n * coords.cs)             # back to the padded NHWC row layout
                     _lib.check(L.egn_nchw_to_nhwc_f32(_lib.ptr(dc), _lib.ptr(dpad), n, 2 * J, 1, 1, coords.cs, st))
                     tape.grad[id(coords)] = [dpad, True]
+            elif m.pixel_shuffle:
+                aug = None                                        # its loss reads the pre-shuffle activations
+                self.last_maps = tape.user['upsample_layer.3']
             else:
                 aug = tape.named['final_layer']
                 self.last_maps = tape.user['final_layer']
-            if target is None:
-                # heat-map targets drawn on the device from the joints (img_proc.py:347-409):
-                # the [N,K,h,w] target never crosses PCIe
-                if joints_xy is None:
-                    raise ValueError('step() needs target heat-maps or joints_xy to draw them from')
-                if aug.h != aug.w or h != w:
-                    raise NotImplementedError('device-side targets: square maps only (the reference mixes the '
-                                              'width/height indices of input_size / heatmap_size, img_proc.py:376-383)')
-                from .common import img_proc
-                target, self.last_target_weight = img_proc.generate_target_batch(
-                    joints_xy, torch.ones(n, J) if joints_vis is None else joints_vis,
-                    dict(target_type='gaussian', input_size=(w, h), heatmap_size=(aug.h, aug.w), sigma=self.sigma),
-                    device=self.dev)
-            if tuple(target.shape) != (n, J, aug.h, aug.w):
-                raise ValueError('target must be %s, got %s' % ((n, J, aug.h, aug.w), tuple(target.shape)))
-            tg = tape._empty(n * aug.h * aug.w * aug.cs)
-            _lib.check(L.egn_nchw_to_nhwc_f32(_lib.ptr(target), _lib.ptr(tg), n, J, aug.h, aug.w, aug.cs, st))
-            da = torch.zeros(n * aug.h * aug.w * aug.cs, dtype=torch.float32, device=self.dev)
-            pred_flat = tape.data[id(aug)]
-            wv = None
-            if self.use_target_weight:
-                # 0.5 * mean((pred * w - gt * w)^2): the same kernel on the weighted maps, gradient * w afterwards
-                # (three broadcast multiplies over [N,h,w,K]; an option no shipped configuration switches on)
-                tw = target_weight if target_weight is not None else self.last_target_weight
-                if tw is None:
-                    raise ValueError('use_target_weight needs target_weight [N,K(,1)] (or device-drawn targets)')
-                wv = torch.zeros(n, 1, 1, aug.cs, dtype=torch.float32, device=self.dev)
-                wv[:, 0, 0, :J] = torch.as_tensor(tw, dtype=torch.float32).reshape(n, J).to(self.dev)
-                pred_flat = (pred_flat.view(n, aug.h, aug.w, aug.cs) * wv).reshape(-1)
-                tg = (tg.view(n, aug.h, aug.w, aug.cs) * wv).reshape(-1)
-            # (1/K) sum_k 0.5*crit_k = 0.5 * crit over all joints (equal element counts), function.py:95-111
-            _lib.check(L.egn_elem_loss_f32(_lib.ptr(pred_flat), _lib.ptr(tg), n * aug.h * aug.w, J, aug.cs,
-                                           aug.cs, self.hm_crit, 0.5 * self.w_hm, 0, _lib.ptr(da),
-                                           _lib.ptr(self.loss_dev), st), 'hm loss')
-            if wv is not None:
-                da = (da.view(n, aug.h, aug.w, aug.cs) * wv).reshape(-1)
-            tape._accum(aug, da)
+            if aug is None:
+                self._pixshuf_loss(tape, target, joints_xy, joints_vis, target_weight, n, h, w, st)
+            else:
+                if target is None:
+                    # heat-map targets drawn on the device from the joints (img_proc.py:347-409):
+                    # the [N,K,h,w] target never crosses PCIe
+                    if joints_xy is None:
+                        raise ValueError('step() needs target heat-maps or joints_xy to draw them from')
+                    if aug.h != aug.w or h != w:
+                        raise NotImplementedError('device-side targets: square maps only (the reference mixes the '
+                                                  'width/height indices of input_size / heatmap_size, img_proc.py:376-383)')
+                    from .common import img_proc
+                    target, self.last_target_weight = img_proc.generate_target_batch(
+                        joints_xy, torch.ones(n, J) if joints_vis is None else joints_vis,
+                        dict(target_type='gaussian', input_size=(w, h), heatmap_size=(aug.h, aug.w), sigma=self.sigma),
+                        device=self.dev)
+                if tuple(target.shape) != (n, J, aug.h, aug.w):
+                    raise ValueError('target must be %s, got %s' % ((n, J, aug.h, aug.w), tuple(target.shape)))
+                tg = tape._empty(n * aug.h * aug.w * aug.cs)
+                _lib.check(L.egn_nchw_to_nhwc_f32(_lib.ptr(target), _lib.ptr(tg), n, J, aug.h, aug.w, aug.cs, st))
+                da = torch.zeros(n * aug.h * aug.w * aug.cs, dtype=torch.float32, device=self.dev)
+                pred_flat = tape.data[id(aug)]
+                wv = None
+                if self.use_target_weight:
+                    # 0.5 * mean((pred * w - gt * w)^2): the same kernel on the weighted maps, gradient * w afterwards
+                    # (three broadcast multiplies over [N,h,w,K]; an option no shipped configuration switches on)
+                    tw = target_weight if target_weight is not None else self.last_target_weight
+                    if tw is None:
+                        raise ValueError('use_target_weight needs target_weight [N,K(,1)] (or device-drawn targets)')
+                    wv = torch.zeros(n, 1, 1, aug.cs, dtype=torch.float32, device=self.dev)
+                    wv[:, 0, 0, :J] = torch.as_tensor(tw, dtype=torch.float32).reshape(n, J).to(self.dev)
+                    pred_flat = (pred_flat.view(n, aug.h, aug.w, aug.cs) * wv).reshape(-1)
+                    tg = (tg.view(n, aug.h, aug.w, aug.cs) * wv).reshape(-1)
+                # (1/K) sum_k 0.5*crit_k = 0.5 * crit over all joints (equal element counts), function.py:95-111
+                _lib.check(L.egn_elem_loss_f32(_lib.ptr(pred_flat), _lib.ptr(tg), n * aug.h * aug.w, J, aug.cs,
+                                               aug.cs, self.hm_crit, 0.5 * self.w_hm, 0, _lib.ptr(da),
+                                               _lib.ptr(self.loss_dev), st), 'hm loss')
+                if wv is not None:
+                    da = (da.view(n, aug.h, aug.w, aug.cs) * wv).reshape(-1)
+                tape._accum(aug, da)
             # the gradient all-reduce of a slice of the flat buffer starts (on a communication
             # stream) as soon as every parameter in it has its gradient kernels issued
             sess = None

@@ -145,6 +145,12 @@ int egn_nhwc_to_nchw_f32(const float* x, float* y, int N, int C, int H, int W,
  * x [N,H,W,cs] with cs >= C*up*up, y [N,C,H*up,W*up] */
 int egn_pixel_shuffle_nhwc_to_nchw_f32(const float* x, float* y, int N, int C,
                                        int H, int W, int cs, int up, void* stream);
+/* nn.PixelUnshuffle(up) fused with the NCHW -> padded NHWC hand-over, the exact inverse of
+ * egn_pixel_shuffle_nhwc_to_nchw_f32: y[n,h,w,(j*up+a)*up+b] = x[n,j,h*up+a,w*up+b], pad
+ * channels (>= C*up*up) zero; x [N,C,H*up,W*up], y [N,H,W,cs], cs % 4 == 0 (the backward of
+ * the pixel-shuffle head under the autograd bridge) */
+int egn_pixel_unshuffle_nchw_to_nhwc_f32(const float* x, float* y, int N, int C, int H,
+                                         int W, int cs, int up, void* stream);
 /* write the two coordinate ramps linspace(0,1) (hrnet.py:461-467) into
  * channels [c0, c0+1] of an NHWC tensor */
 int egn_fill_coord_ramps_f32(float* y, int N, int H, int W, int cs, int c0,
@@ -414,6 +420,25 @@ int egn_mse_f32(const float* pred, const float* tgt, int rows, int cols,
 int egn_elem_loss_f32(const float* pred, const float* tgt, int rows, int cols,
                       int ld_pred, int ld_tgt, int crit, float weight,
                       int accumulate, float* dpred, double* loss, void* stream);
+/* The heat-map criterion on pixel-shuffled maps (hrnet.py:373-383, 598-600 +
+ * JointsMSELoss / loss_dict, function.py:17-46) without materialising the shuffled
+ * prediction: x = the pre-shuffle NHWC activations [N,H,W,cs] (channel j*up*up+a*up+b),
+ * tgt = the NCHW target [N,C,H*up,W*up], tw = per-(n, j) weights [N,C] or NULL
+ * (use_target_weight); crit as egn_elem_loss_f32.
+ *   *loss += weight * mean(c(pred*w - tgt*w)) (zero it first);
+ *   dx = weight * c'(pred*w - tgt*w) * w / (N*C*H*up*W*up) in the pre-shuffle layout
+ *   (pad channels zero; dx may be NULL).  x, dx 16-byte aligned, cs % 4 == 0. */
+int egn_pixshuf_loss_f32(const float* x, const float* tgt, const float* tw, int N, int H,
+                         int W, int C, int up, int cs, int crit, float weight, float* dx,
+                         double* loss, void* stream);
+/* AvgPool2d(k) (stride k, no padding, floor) over NHWC: x [N,H,W,cs] -> y [N,H/k,W/k,cs],
+ * the k*k taps summed, then / (k*k) (the angle head's AvgPool2d(4), hrnet.py:384-422) */
+int egn_avgpool_fwd_f32(const float* x, float* y, int N, int H, int W, int cs, int k,
+                        void* stream);
+/* its backward: dx [N,H,W,cs] (= or, with accumulate, +=) dy[n, y/k, x/k, c] / (k*k);
+ * positions outside every window get 0 */
+int egn_avgpool_bwd_f32(const float* dy, float* dx, int N, int H, int W, int cs, int k,
+                        int accumulate, void* stream);
 /* *loss += weight*mean(|pred-tgt|); dpred = weight*sign(pred-tgt)/n
  * (nn.L1Loss, the coordinate term, function.py:155-168) */
 int egn_l1_f32(const float* pred, const float* tgt, long n, float weight,
