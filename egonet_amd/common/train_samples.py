@@ -1,0 +1,289 @@
+"""Training-sample front end: decoded frames + boxes + key points -> the HRNet training batch
+``(images, targets, target_weights, meta)`` that ``trainer.train`` consumes.
+
+It reproduces the reference's ``instanceto2d`` dataset (libs/dataset/KITTI/car_instance.py:1272-1299 ->
+libs/common/img_proc.py:213-345) followed by ``my_collate_fn`` / ``length_limit`` (car_instance.py:1344-1391):
+per box an optional jitter (four draws of the global ``np.random``), ``resize_bbox`` to the input aspect
+ratio, the three-point ``get_affine_transform``, ``cv2.warpAffine`` + ToTensor + Normalize, the visible joints
+moved into the crop and one Gaussian heat-map per joint (``generate_target``); then a random subset of
+``MAX_INS_CNT`` instances when the batch holds more.
+
+Split of work.  The per-box math (4 draws, one resize, one 3x3 solve, 33 two-by-three products) stays on the
+host in float64, vectorised over the batch, with the reference's operation order: the same seed gives the same
+boxes, affines and subset.  What is heavy runs on the device: the uint8 frames go up once, one launch of
+``egn_crop_frames_warp_normalize_u8`` cuts the crops of every kept box of every frame, one launch of
+``egn_gaussian_targets_f32`` draws all maps.  ``meta`` is host numpy, computed before the upload, so reading it
+needs no device synchronisation.
+
+Upload.  Frames, the frame table, the per-box frame index, the affines, joints and visibilities are packed into
+one pinned staging buffer and sent by ONE ``non_blocking`` copy on the current stream; the kernels and the
+training step that follow run on that stream, so their ordering needs nothing more.  The staging buffers are
+double-buffered and each is guarded by an event recorded after its copy: a call refills buffer ``k`` only after
+waiting on ``k``'s event (the copy two calls back), so a copy still in flight is never overwritten.
+
+Decode stays in the ``DataLoader`` workers: a Dataset returns records (see ``INTEGRATION.md``), ``collate_frames``
+keeps them as a list, ``TrainSampleBuilder`` turns the list into the batch.
+"""
+import time
+
+import numpy as np
+import torch
+
+from .. import _lib
+from . import crop_gpu
+
+MAX_INS_CNT = 140              # car_instance.py:33
+SIZE = 200.0
+_ALIGN = 256                   # byte alignment of every section of the staging buffer
+
+
+def collate_frames(batch):
+    """DataLoader ``collate_fn``: the records of a batch, kept as a list (decoded frames stay uint8 on the host)."""
+    return list(batch)
+
+
+def _hm_value(hm, key, default):
+    return hm[key] if key in hm and hm[key] is not None else default
+
+
+class TrainSampleBuilder(object):
+    """``builder(records, rng=np.random)`` -> ``(images [N,3,h,w], targets [N,K,hm_h,hm_w], target_weights [N,K,1],
+    meta)``, the first three CUDA fp32, ``meta`` host numpy with the reference's keys.
+
+    A record is ``{'image': [H,W,3] uint8 RGB, 'boxes': [n,4], 'joints': [n,K,2|3], 'path': str}`` (the fields
+    ``annot_2dpose`` holds for ``instanceto2d``); a missing visibility column means 1 (car_instance.py:1278-1279)."""
+
+    def __init__(self, cfgs, split='train', device=None):
+        hm = cfgs['heatmapModel']
+        if _hm_value(hm, 'target_type', 'gaussian') != 'gaussian':
+            raise NotImplementedError('target_type %r: the reference draws gaussian targets only '
+                                      '(img_proc.py:368)' % hm['target_type'])
+        if hm.get('use_different_joints_weight'):
+            raise NotImplementedError('use_different_joints_weight: the reference never sets hm_para["joints_weight"] '
+                                      '(car_instance.py:499-519) and raises KeyError in generate_target')
+        if hm.get('add_xy'):
+            raise NotImplementedError('add_xy: 5-channel inputs (img_proc.py:232-234) are not built by this front end')
+        norm = (cfgs.get('dataset', {}) or {}).get('pth_transform') or {}
+        self.mean = tuple(float(v) for v in norm.get('mean', crop_gpu.IMAGENET_MEAN))
+        self.std = tuple(float(v) for v in norm.get('std', crop_gpu.IMAGENET_STD))
+        if len(self.mean) != 3 or len(self.std) != 3:
+            raise ValueError('pth_transform mean/std must have 3 entries (RGB), got %d / %d'
+                             % (len(self.mean), len(self.std)))
+        # the reference's hm_para holds sizes as (height, width) (car_instance.py:506-509)
+        self.input_hw = (int(hm['input_size'][1]), int(hm['input_size'][0]))
+        self.heatmap_hw = (int(hm['heatmap_size'][1]), int(hm['heatmap_size'][0]))
+        self.num_joints = int(hm['num_joints'])
+        self.sigma = float(_hm_value(hm, 'sigma', 1))
+        self.jitter = bool(hm.get('jitter_bbox', False)) and split == 'train' and bool(cfgs.get('train', False))
+        self.scaling = tuple(hm['jitter_params']['scaling']) if self.jitter else None
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self._pinned = [None, None]
+        self._events = [None, None]
+        self._turn = 0
+        # True: every call keeps {'host_ms', 'events'} in last_timings -- four timing events: before the upload,
+        # after it, after the crop launch, after the targets launch (tools/train_samples_bench.py reads them after a synchronise)
+        self.record_timings = False
+        self.last_timings = None
+
+    # -- host math (float64, vectorised over the batch) -------------------------------------------------------
+    def gather(self, records):
+        """(boxes [N,4] f64, joints [N,K,3] f64, frame index [N] int64) of all boxes in record order."""
+        boxes, joints, frame = [], [], []
+        for f, rec in enumerate(records):
+            b = np.asarray(rec['boxes'], dtype=np.float64).reshape(-1, 4)
+            j = np.asarray(rec['joints'], dtype=np.float64)
+            if j.ndim != 3 or len(j) != len(b) or j.shape[2] not in (2, 3):
+                raise ValueError('record %d: joints must be [n,K,2|3] for its %d boxes, got %s'
+                                 % (f, len(b), j.shape))
+            if j.shape[2] == 2:
+                j = np.concatenate([j, np.ones(j.shape[:2] + (1,))], axis=2)
+            boxes.append(b)
+            joints.append(j)
+            frame.append(np.full(len(b), f, dtype=np.int64))
+        if not boxes or sum(len(b) for b in boxes) == 0:
+            raise ValueError('the batch holds no box')
+        joints = np.concatenate(joints)
+        if joints.shape[1] != self.num_joints:
+            raise ValueError('joints have %d key points, heatmapModel.num_joints is %d'
+                             % (joints.shape[1], self.num_joints))
+        return np.concatenate(boxes), joints, np.concatenate(frame)
+
+    def jitter_boxes(self, boxes, draws):
+        """jitter_bbox_with_kpts_no_occlu (img_proc.py:174-191); draws [N,4] = the four rand() of each box."""
+        width, height = boxes[:, 2] - boxes[:, 0], boxes[:, 3] - boxes[:, 1]
+        cx, cy = 0.5 * (boxes[:, 0] + boxes[:, 2]), 0.5 * (boxes[:, 1] + boxes[:, 3])
+        sx = self.scaling[0] * draws[:, 0] + 1
+        sy = self.scaling[1] * draws[:, 1] + 1
+        shift_x = 0.5 * (sx - 1) * width * (draws[:, 2] * 2 - 1)
+        shift_y = 0.5 * (sy - 1) * height * (draws[:, 3] * 2 - 1)
+        ncx, ncy = cx + shift_x, cy + shift_y
+        nw, nh = width * sx, height * sy
+        return np.stack([ncx - 0.5 * nw, ncy - 0.5 * nh, ncx + 0.5 * nw, ncy + 0.5 * nh], axis=1)
+
+    def resize_boxes(self, boxes):
+        """resize_bbox (img_proc.py:411-435) to target_ar = input h / input w -> (c [N,2], s [N,2])."""
+        h, w = self.input_hw
+        target_ar = np.float64(h) / np.float64(w)
+        left, top, right, bottom = boxes[:, 0], boxes[:, 1], boxes[:, 2], boxes[:, 3]
+        width, height = right - left, bottom - top
+        cx, cy = (left + right) / 2, (top + bottom) / 2
+        wide = height / width > target_ar
+        new_w = height * (1 / target_ar)
+        new_h = width * target_ar
+        nl = np.where(wide, cx - 0.5 * new_w, left)
+        nr = np.where(wide, cx + 0.5 * new_w, right)
+        nt = np.where(wide, top, cy - 0.5 * new_h)
+        nb = np.where(wide, bottom, cy + 0.5 * new_h)
+        return np.stack([cx, cy], axis=1), np.stack([(nr - nl) / SIZE, (nb - nt) / SIZE], axis=1)
+
+    def affines(self, c, s):
+        """get_affine_transform(c, s, 0, (h, w)) of every box (img_proc.py:26-64) -> [N,2,3] f64: the float32
+        three-point construction, solved exactly like cv2.getAffineTransform."""
+        h, w = self.input_hw
+        n = len(c)
+        src = np.zeros((n, 3, 2), dtype=np.float32)
+        src[:, 0] = c
+        src[:, 1, 0] = c[:, 0]
+        src[:, 1, 1] = c[:, 1] + s[:, 0] * SIZE * -0.5
+        dst = np.zeros((3, 2), dtype=np.float32)
+        dst[0] = [w * 0.5, h * 0.5]
+        dst[1] = np.array([w * 0.5, h * 0.5]) + np.array([0, w * -0.5], np.float32)
+        d = src[:, 0] - src[:, 1]
+        src[:, 2] = src[:, 1] + np.stack([-d[:, 1], d[:, 0]], axis=1)
+        dd = dst[0] - dst[1]
+        dst[2] = dst[1] + np.array([-dd[1], dd[0]], dtype=np.float32)
+        m = np.concatenate([src.astype(np.float64), np.ones((n, 3, 1))], axis=2)
+        rhs = np.broadcast_to(dst.astype(np.float64), (n, 3, 2)).copy()
+        return np.linalg.solve(m, rhs).transpose(0, 2, 1)
+
+    @staticmethod
+    def transform_joints(joints, trans):
+        """Joints with vis > 0 through their box's affine (img_proc.py:240-242); the others keep image coordinates."""
+        out = joints.copy()
+        x, y = joints[..., 0], joints[..., 1]
+        tx = trans[:, None, 0, 0] * x + trans[:, None, 0, 1] * y + trans[:, None, 0, 2]
+        ty = trans[:, None, 1, 0] * x + trans[:, None, 1, 1] * y + trans[:, None, 1, 2]
+        vis = joints[..., 2] > 0.0
+        out[..., 0] = np.where(vis, tx, x)
+        out[..., 1] = np.where(vis, ty, y)
+        return out
+
+    def plan(self, records, rng=np.random):
+        """All host work of a batch, in the reference's draw order (per frame, per box: 4 draws; then the
+        length_limit choice).  Returns a dict: 'kept' [n] (indices into the batch's boxes), 'frame' [n],
+        'trans' [n,2,3], 'draws' [N,4] or None, and 'meta' (the reference's keys)."""
+        boxes, joints, frame = self.gather(records)
+        n_all = len(boxes)
+        draws = None
+        if self.jitter:
+            draws = rng.rand(n_all, 4)
+            boxes = self.jitter_boxes(boxes, draws)
+        c, s = self.resize_boxes(boxes)
+        trans = self.affines(c, s)
+        tj = self.transform_joints(joints, trans)
+        kept = np.arange(n_all)
+        if n_all > MAX_INS_CNT:
+            kept = rng.choice(n_all, MAX_INS_CNT, replace=False)
+        meta = {'path': [r.get('path', '') for r in records],
+                'original_joints': joints[kept], 'transformed_joints': tj[kept],
+                'center': c[kept], 'scale': s[kept], 'joints_vis': tj[kept][:, :, 2]}
+        return {'kept': kept, 'frame': frame[kept], 'trans': trans[kept], 'draws': draws, 'meta': meta}
+
+    # -- device work ---------------------------------------------------------------------------------------------
+    def _staging(self, nbytes):
+        """The pinned buffer of this call (double-buffered, event-guarded: see the module docstring)."""
+        k = self._turn
+        self._turn ^= 1
+        if self._events[k] is not None:
+            self._events[k].synchronize()           # the copy that last read buffer k has finished
+        buf = self._pinned[k]
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
+            self._pinned[k] = buf
+        return k, buf
+
+    def __call__(self, records, rng=np.random):
+        t0 = time.perf_counter()
+        p = self.plan(records, rng)
+        meta, n = p['meta'], len(p['kept'])
+        K = self.num_joints
+        h, w = self.input_hw
+        hm_h, hm_w = self.heatmap_hw
+        used = np.unique(p['frame'])
+        remap = np.full(len(records), -1, dtype=np.int64)
+        remap[used] = np.arange(len(used))
+        frames = []
+        for f in used:
+            img = records[f]['image']
+            img = img.numpy() if torch.is_tensor(img) else np.asarray(img)
+            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+                raise ValueError('record %d: image must be [H,W,3] uint8 RGB, got %s %s' % (f, img.dtype, img.shape))
+            frames.append(img)
+
+        def up(nbytes):
+            return (nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
+        offs, total = [], 0
+        for img in frames:
+            offs.append(total)
+            total += up(img.nbytes)
+        sections = [('tab', (len(frames), 4), np.int64), ('box_frame', (n,), np.int32), ('M', (n, 6), np.float64),
+                    ('joints', (n, K, 3), np.float64), ('vis', (n, K), np.float32)]
+        where = {}
+        for name, shape, dt in sections:
+            where[name] = total
+            total += up(int(np.prod(shape)) * np.dtype(dt).itemsize)
+        k, pinned = self._staging(total)
+        host = pinned.numpy()
+        for img, off in zip(frames, offs):
+            host[off:off + img.nbytes] = np.ascontiguousarray(img).reshape(-1)
+        tab = np.array([[off, img.shape[0], img.shape[1], 3 * img.shape[1]] for img, off in zip(frames, offs)],
+                       dtype=np.int64)
+        values = {'tab': tab, 'box_frame': remap[p['frame']].astype(np.int32), 'M': p['trans'].reshape(n, 6),
+                  'joints': meta['transformed_joints'], 'vis': meta['joints_vis'].astype(np.float32)}
+        for name, shape, dt in sections:
+            a = np.ascontiguousarray(values[name], dtype=dt).reshape(-1)
+            host[where[name]:where[name] + a.nbytes] = a.view(np.uint8)
+        dev = self.device
+        host_ms = (time.perf_counter() - t0) * 1e3
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if self.record_timings else None
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            staged = torch.empty(total, dtype=torch.uint8, device=dev)
+            if ev:
+                ev[0].record(stream)
+            staged.copy_(pinned[:total], non_blocking=True)
+            if self._events[k] is None:
+                self._events[k] = torch.cuda.Event()
+            self._events[k].record(stream)
+            if ev:
+                ev[1].record(stream)
+
+            def view(name, shape, dt):
+                nb = int(np.prod(shape)) * torch.empty(0, dtype=dt).element_size()
+                return staged[where[name]:where[name] + nb].view(dt).view(*shape)
+            tab_d = view('tab', (len(frames), 4), torch.int64)
+            frame_d = view('box_frame', (n,), torch.int32)
+            M_d = view('M', (n, 6), torch.float64)
+            joints_d = view('joints', (n, K, 3), torch.float64)
+            vis_d = view('vis', (n, K), torch.float32)
+            mean_t, std_t = crop_gpu._norm_consts(self.mean, self.std, dev)
+            images = torch.empty(n, 3, h, w, dtype=torch.float32, device=dev)
+            targets = torch.empty(n, K, hm_h, hm_w, dtype=torch.float32, device=dev)
+            weights = torch.empty(n, K, 1, dtype=torch.float32, device=dev)
+            L = _lib.lib()
+            st = _lib.current_stream(dev)
+            _lib.check(L.egn_crop_frames_warp_normalize_u8(_lib.ptr(staged), _lib.ptr(tab_d), len(frames),
+                                                           _lib.ptr(frame_d), _lib.ptr(M_d), n, h, w,
+                                                           _lib.ptr(mean_t), _lib.ptr(std_t), _lib.ptr(images), st),
+                       'crop frames')
+            if ev:
+                ev[2].record(stream)
+            # the reference's stride quirk (img_proc.py:376-378): input_size / heatmap_size in (h, w) order, the
+            # first of them divides x -- egn_gaussian_targets_f32 takes the two strides in that order
+            _lib.check(L.egn_gaussian_targets_f32(_lib.ptr(joints_d), _lib.ptr(vis_d), n, K, hm_h, hm_w,
+                                                  float(h) / float(hm_h), float(w) / float(hm_w), self.sigma,
+                                                  _lib.ptr(targets), _lib.ptr(weights), st), 'gaussian targets')
+            if ev:
+                ev[3].record(stream)
+                self.last_timings = {'host_ms': host_ms, 'events': ev}
+        return images, targets, weights, meta

@@ -75,3 +75,22 @@ def synth_boxes(n, seed=0, img_w=1242, img_h=375):
     x1 = rng.uniform(0, img_w - w)
     y1 = rng.uniform(0, np.maximum(img_h - h, 1))
     return np.stack([x1, y1, x1 + w, y1 + h], axis=1)
+
+
+def synth_frame_records(n_frames, boxes_per_frame, num_joints, seed=0, hw=(375, 1242)):
+    """Training records in the form ``common.train_samples.TrainSampleBuilder`` takes: per frame a seeded
+    [H,W,3] uint8 RGB image, ``boxes_per_frame`` boxes from ``synth_boxes``, joints [n,K,3] inside and around
+    the boxes (up to 20 % of the box size outside) with visibilities 0 / 0.3 / 1, and a path."""
+    rng = np.random.RandomState(7177 + seed)
+    H, W = int(hw[0]), int(hw[1])
+    records = []
+    for f in range(n_frames):
+        img = rng.randint(0, 256, (H, W, 3)).astype(np.uint8)
+        boxes = synth_boxes(boxes_per_frame, seed=seed * 1000 + f, img_w=W, img_h=H)
+        u = rng.uniform(-0.2, 1.2, (boxes_per_frame, num_joints, 2))
+        x = boxes[:, None, 0] + u[..., 0] * (boxes[:, None, 2] - boxes[:, None, 0])
+        y = boxes[:, None, 1] + u[..., 1] * (boxes[:, None, 3] - boxes[:, None, 1])
+        vis = rng.choice(np.array([0.0, 0.3, 1.0]), size=(boxes_per_frame, num_joints), p=[0.2, 0.2, 0.6])
+        records.append({'image': img, 'boxes': boxes, 'joints': np.stack([x, y, vis], axis=2),
+                        'path': 'synth/%06d_%03d.png' % (seed, f)})
+    return records

@@ -260,10 +260,14 @@ def evaluate(eval_dataset, model, loss_func, cfgs, logger, evaluator, save=False
 
 
 def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_func=None, stats=None,
-          valid_dataset=None, collate_fn=None, save_debug=False, evaluate_fn=None, evaluator=None):
+          valid_dataset=None, collate_fn=None, save_debug=False, evaluate_fn=None, evaluator=None,
+          sample_builder=None):
     """trainer.py:127-263.  Validation during training (``eval_during``): ``evaluate_fn(valid_dataset,
     model, epoch)`` if given, else this module's ``evaluate`` with ``evaluator`` (the reference builds
-    its ``Evaluator`` from libs/metric, which is outside this package: pass one in)."""
+    its ``Evaluator`` from libs/metric, which is outside this package: pass one in).
+    ``sample_builder``: a callable (``common.train_samples.TrainSampleBuilder``) that turns each loader item
+    -- e.g. the list of decoded frame records ``common.train_samples.collate_frames`` yields -- into the
+    ``(data, target, weights, meta)`` batch; None: the loader yields that batch itself."""
     ts = cfgs['training_settings']
     total_epochs, report_every = ts['total_epochs'], ts['report_every']
     eval_during = bool(ts.get('eval_during', False)) and valid_dataset is not None
@@ -296,7 +300,10 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
             loader = get_loader(train_dataset, cfgs, 'training', collate_fn)
             total_batches, t_epoch = len(loader), time.time()
             acc = _Acc()
-            for batch_idx, (data, target, weights, meta) in enumerate(loader):
+            for batch_idx, batch in enumerate(loader):
+                if sample_builder is not None:
+                    batch = sample_builder(batch)
+                data, target, weights, meta = batch
                 data = data.to(dev, non_blocking=True)
                 target = target.to(dev, non_blocking=True)
                 if is_hc:

@@ -242,6 +242,17 @@ int egn_crop_warp_normalize_u8(const uint8_t* img, int H, int W, int pitch,
                                const double* M, int n, int out_h, int out_w,
                                const float* mean, const float* stdv, float* out,
                                void* stream);
+/* The same warp + ToTensor + Normalize for the boxes of MANY frames in one launch
+ * (training-sample front end, car_instance.py:1272-1299 -> img_proc.py:213-345).
+ *   frames     all frames packed in one buffer, each [H,W,3] uint8 RGB
+ *   frame_tab  [n_frames][4] int64: byte offset into `frames`, H, W, row pitch (bytes)
+ *   box_frame  [n] int32 frame index of each box (outside [0, n_frames): border only)
+ *   M          [n,6] f64 forward affines image -> crop; out [n,3,out_h,out_w] f32
+ * Per-pixel semantics are exactly those of egn_crop_warp_normalize_u8.  n <= 65535, out_w <= 4096. */
+int egn_crop_frames_warp_normalize_u8(const uint8_t* frames, const long long* frame_tab,
+                                      int n_frames, const int* box_frame, const double* M,
+                                      int n, int out_h, int out_w, const float* mean,
+                                      const float* stdv, float* out, void* stream);
 
 /* ------------------------------------------------------------------------
  * Training step building blocks (reference: libs/trainer/trainer.py:183-209
