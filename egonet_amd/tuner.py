@@ -148,7 +148,8 @@ def _forced_wino(args, kind=1, order=None):
     """EGONET_AMD_WINO=1 / =43 / =43b: the Winograd F(2x2,3x3) / F(4x4,3x3) configuration for every shape one plans
     for (parity tests pin the kernel families on the same fixtures); returns 0 if none does.  ``order``: the ids to
     try first (=43 prefers conv_wino4_kernel's 16 x 32 regions, cfg 70, and takes conv_wino4b_kernel, cfg 80, for the
-    maps only it plans; =43b prefers cfg 80 everywhere)."""
+    maps only it plans; =43b prefers cfg 80 everywhere; =43w prefers cfg 86, the kernel the table picks at 16 crops and
+    above, then 80, then 70)."""
     n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, has_res, out_nchw = args
     L = _lib.lib()
     out = (C.c_int * 12)()
@@ -162,19 +163,21 @@ def _forced_wino(args, kind=1, order=None):
 def choose(device, args, allow_wino=False, allow_f43=False):
     """``allow_wino`` / ``allow_f43``: the caller packs the filter for whatever configuration kind comes back
     (egn_conv_config_kind 1 / 2).  EGONET_AMD_WINO=0 never returns a Winograd configuration, =1 always the
-    F(2x2,3x3) one where it plans, =43 / =43b an F(4x4,3x3) one where one plans (cfg 70 / cfg 80 first; else
-    F(2x2,3x3)); EGONET_AMD_F43=0 keeps F(4x4,3x3) out; default: whichever measured fastest."""
+    F(2x2,3x3) one where it plans, =43 / =43b / =43w an F(4x4,3x3) one where one plans (cfg 70 / cfg 80 / cfg 86,
+    conv_wino4w_kernel, first; else F(2x2,3x3)); EGONET_AMD_F43=0 keeps F(4x4,3x3) out; default: whichever measured
+    fastest."""
     mode = os.environ.get('EGONET_AMD_WINO', '')
     if os.environ.get('EGONET_AMD_F43', '1') == '0' or mode in ('0', '1'):
         allow_f43 = False
     if mode == '0':
         allow_wino = False
-    elif mode in ('43', '43b') and allow_f43:
-        cfg = _forced_wino(args, 3, (70, 80) if mode == '43' else (80, 70)) or _forced_wino(args, 2) or \
+    elif mode in ('43', '43b', '43w') and allow_f43:
+        order = {'43': (70, 80), '43b': (80, 70), '43w': (86, 80, 70)}[mode]
+        cfg = _forced_wino(args, 3, order) or _forced_wino(args, 2) or \
             (_forced_wino(args, 1) if allow_wino else 0)
         if cfg:
             return cfg
-    elif mode in ('1', '43', '43b') and allow_wino:
+    elif mode in ('1', '43', '43b', '43w') and allow_wino:
         cfg = _forced_wino(args)
         if cfg:
             return cfg

@@ -1,0 +1,312 @@
+"""Every tile configuration the tuner can pick, on every convolution request the product makes, against float64.
+
+``tuner.choose`` answers a shape outside the shipped table with whichever configuration the planner accepts and that
+measured fastest; the training tape and the GEMM callers pick among table entries by the kinds they can feed.  So each
+(request, candidate) pair of tests/conv_sweep.py runs here through the entry point the product would use -- a one-op
+program for the inference engine; egn_conv2d_ex_f32 / egn_conv2d_bnstats_f32 / egn_conv2d_f32 as the tape calls them;
+K-split configurations also in egn_conv2d_f32's three-launch form -- and every launch is checked for:
+  1. |y - y64| <= C_BOUND[kind] * 2^-24 * A (y64: train_checks.conv_ref64, A: the same on absolute values);
+  2. every element written (y pre-filled with NaN; NHWC pad channels exactly 0);
+  3. no write outside y / the statistics partials / the ticket words (sentinel guard bands, bit-identical after);
+  4. the same bits from a second launch (the statistics partials of a K split with ticket words excepted: their rows
+     follow arrival order by design, so there both launches' totals are held to the bound of 6.);
+  5. caller-owned ticket words zero again after the launch;
+  6. fused BatchNorm partials that sum (in float64) to the channel sums / sums of squares of y64;
+  7. the tape's in-place residual (res is y) for its data-gradient requests.
+A summary per configuration (requests, worst |err| / (2^-24 A) and where) is printed, and written as JSON to
+conv_sweep.json in the directory EGONET_AMD_PARITY_DIR names, if it is set.
+"""
+import ctypes as C
+import json
+import os
+import time
+import zlib
+
+import pytest
+import torch
+
+import conv_sweep as S
+from egonet_amd import _lib, engine
+from train_checks import conv_ref64
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 1 << 14                  # elements of sentinel on each side of every written buffer
+SENT32 = 0x5A5A5A5A
+SENT64 = 0x5A5A5A5A5A5A5A5A
+
+
+def _guarded(numel, dtype, fill):
+    """(whole buffer, body view): the body sits between two sentinel bands."""
+    it = torch.int32 if dtype == torch.float32 else torch.int64
+    whole = torch.full((numel + 2 * GUARD,), SENT32 if it == torch.int32 else SENT64, dtype=it, device='cuda')
+    body = whole[GUARD:GUARD + numel].view(dtype)
+    if fill is not None:
+        body.fill_(fill)
+    return whole, body
+
+
+def _guards_intact(whole):
+    s = SENT32 if whole.dtype == torch.int32 else SENT64
+    return bool((whole[:GUARD] == s).all()) and bool((whole[-GUARD:] == s).all())
+
+
+class _Case(object):
+    """Inputs and float64 reference of one request."""
+
+    def __init__(self, req):
+        n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, has_res, nchw = req['key']
+        self.req = req
+        self.ho, self.wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+        self.coutp = (cout + 15) // 16 * 16
+        g = torch.Generator().manual_seed(zlib.crc32(repr((req['key'], req['act'], req['entry'])).encode()))
+        self.x = S.act_like(n, h, w, cin, cs_in, g, 'cuda')
+        self.w = S.filt(cout, cin, kh, kw, g)
+        pad_val = 0.0 if req['entry'] == 'program' else 1.0     # fold_scale_shift zero-pads; the tape's ones do not
+        if req['stats']:
+            # the statistics entry points take the raw convolution (egonet_hip.h): the tape passes ones / zeros
+            sc, sh = torch.ones(self.coutp + 16), torch.zeros(self.coutp + 16)
+        else:
+            sgn = torch.where(torch.rand(cout, generator=g) < 0.3, -1.0, 1.0)
+            sc = torch.full((self.coutp + 16,), pad_val)
+            sc[:cout] = sgn * (0.5 + torch.rand(cout, generator=g))
+            sh = torch.zeros(self.coutp + 16)
+            sh[:cout] = 0.5 * torch.randn(cout, generator=g)
+        self.sc, self.sh = sc.cuda(), sh.cuda()
+        self.ny = n * self.ho * self.wo * (cout if nchw else cs_out)
+        self.res = None
+        if has_res:
+            r = S.act_like(n, self.ho, self.wo, cout, cs_out, g, 'cuda') - 0.5 * (torch.rand(1, generator=g).item())
+            r.view(-1, cs_out)[:, cout:] = 0
+            if nchw:
+                r = r[..., :cout].permute(0, 3, 1, 2).contiguous()
+            self.res = r.reshape(-1)
+        self.packs = {}
+        # the reference, float64 on the GPU
+        x64 = self.x.view(n, h, w, cs_in)[..., :cin].permute(0, 3, 1, 2).double()
+        w64 = self.w.double().cuda()
+        r64 = None if self.res is None else self._nchw(self.res).double()
+        sc64, sh64 = self.sc.double(), self.sh.double()
+        self.y64 = conv_ref64(x64, w64, stride, pad, sc64, sh64, r64, req['act'])
+        self.A = S.bound_A(x64, w64, stride, pad, sc64, sh64, r64, req['act'])
+        if req['stats']:
+            self.sum64 = self.y64.sum((0, 2, 3))
+            self.sq64 = (self.y64 ** 2).sum((0, 2, 3))
+            self.sumA = self.A.sum((0, 2, 3))
+            self.sqA = (2 * self.y64.abs() * self.A + S.U * self.A ** 2).sum((0, 2, 3))
+
+    def _nchw(self, flat):
+        n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, has_res, nchw = self.req['key']
+        if nchw:
+            return flat.view(n, cout, self.ho, self.wo)
+        return flat.view(n, self.ho, self.wo, cs_out)[..., :cout].permute(0, 3, 1, 2)
+
+    def packed(self, kind):
+        if kind not in self.packs:
+            self.packs[kind] = engine.pack_for_kind(self.w, kind).cuda()
+        return self.packs[kind]
+
+
+def _modes(req, cfg):
+    """The launches of one (request, candidate) pair: (entry, with statistics, with ticket words)."""
+    kind = S.kind_of(cfg)
+    entry = req['entry']
+    if entry == 'program':
+        out = [('program', False, False)]
+    elif entry == 'tape':               # train_hrnet._Tape._conv_launch
+        rows = S.bnstats_rows(req['key'], cfg) if cfg > 0 else 0
+        stats = req['stats'] and cfg > 0 and rows > 0
+        if kind == 3:
+            out = [('ex', stats, S.ticket_words(req['key'], cfg) > 0)]
+        else:
+            out = [('bnstats' if stats else 'conv2d', stats, False)]
+    else:
+        out = [('conv2d', False, False)]
+    if cfg in S.K_SPLIT and not req['alias'] and out[0] != ('conv2d', False, False):
+        out.append(('conv2d', False, False))          # the three-launch form (egonet_hip.h: egn_conv_config_kind)
+    return out
+
+
+def _run_pair(case, cfg, mode, stats, tickets):
+    """Both launches of one mode; returns (worst ratio, [failure strings])."""
+    L = _lib.lib()
+    req = case.req
+    n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, has_res, nchw = req['key']
+    key = req['key']
+    wp = case.packed(S.kind_of(cfg))
+    stream = _lib.current_stream()
+    fails = []
+    ywhole, y = _guarded(case.ny, torch.float32, None if req['alias'] else float('nan'))
+    res = case.res
+    if req['alias']:
+        y.copy_(case.res)                 # the gradient x already holds; the conv adds to it in place
+        res = y
+    rows = S.bnstats_rows(key, cfg) if stats else 0
+    pwhole = part = None
+    if stats:
+        pwhole, part = _guarded(rows * 2 * cout, torch.float64, float('nan'))
+    ntk = S.ticket_words(key, cfg) if tickets else 0
+    twhole = tk = None
+    if tickets:
+        twhole, tk = _guarded(ntk, torch.int32, 0)
+    prog = None
+    if mode == 'program':
+        prog = C.c_void_p(L.egn_program_create(8))
+        refs = []
+        for slot, t in enumerate((case.x, wp, case.sc, case.sh, res, y)):
+            if t is None:
+                refs.append(_lib.NULL_REF)
+                continue
+            _lib.check(L.egn_program_bind(prog, slot, _lib.ptr(t)))
+            refs.append(_lib.Ref(slot, 0))
+        _lib.check(L.egn_program_add_conv2d(prog, *refs, n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad,
+                                            req['act'], int(nchw), cfg), 'add_conv2d')
+
+    def launch():
+        if mode == 'program':
+            return L.egn_program_run(prog, stream)
+        if mode == 'ex':
+            return L.egn_conv2d_ex_f32(_lib.ptr(case.x), _lib.ptr(wp), _lib.ptr(case.sc), _lib.ptr(case.sh),
+                                       _lib.ptr(res), _lib.ptr(y), n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride,
+                                       pad, req['act'], cfg, _lib.ptr(part), rows, _lib.ptr(tk), ntk, stream)
+        if mode == 'bnstats':
+            return L.egn_conv2d_bnstats_f32(_lib.ptr(case.x), _lib.ptr(wp), _lib.ptr(case.sc), _lib.ptr(case.sh),
+                                            _lib.ptr(y), n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, cfg,
+                                            _lib.ptr(part), rows, stream)
+        return L.egn_conv2d_f32(_lib.ptr(case.x), _lib.ptr(wp), _lib.ptr(case.sc), _lib.ptr(case.sh), _lib.ptr(res),
+                                _lib.ptr(y), n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, req['act'],
+                                int(nchw), cfg, stream)
+
+    worst = 0.0
+    try:
+        first = None
+        for rep in range(2):
+            if rep and req['alias']:
+                y.copy_(case.res)
+            elif rep:
+                y.fill_(float('nan'))
+                if stats:
+                    part.fill_(float('nan'))
+            rc = launch()
+            torch.cuda.synchronize()
+            if rc != 0:
+                fails.append('launch %d returned %d (%s)' % (rep, rc, L.egn_strerror(rc).decode()))
+                break
+            if not _guards_intact(ywhole):
+                fails.append('write outside y')
+            if stats and not _guards_intact(pwhole):
+                fails.append('write outside the statistics partials')
+            if tickets:
+                if not _guards_intact(twhole):
+                    fails.append('write outside the ticket words')
+                if bool((tk != 0).any()):
+                    fails.append('ticket words not zero after the launch')
+            if rep == 0:
+                got = case._nchw(y)
+                if not bool(torch.isfinite(got).all()):
+                    fails.append('%d elements not written / not finite' % int((~torch.isfinite(got)).sum()))
+                if not nchw and cs_out > cout and bool((y.view(-1, cs_out)[:, cout:] != 0).any()):
+                    fails.append('pad channels not 0')
+                r = S.ratio(got, case.y64, case.A)
+                worst = float(r.max())
+                if not worst <= S.C_BOUND[S.kind_of(cfg)]:
+                    fails.append('error %.1f x 2^-24 A > %g' % (worst, S.C_BOUND[S.kind_of(cfg)]))
+                if stats:
+                    tot = part.view(rows, 2, cout).sum(0)
+                    c = S.C_BOUND[S.kind_of(cfg)] * S.U
+                    if not bool(((tot[0] - case.sum64).abs() <= c * case.sumA).all()) or \
+                            not bool(((tot[1] - case.sq64).abs() <= c * case.sqA).all()):
+                        fails.append('fused BatchNorm statistics off')
+                first = (y.clone(), part.clone() if stats else None)
+            else:
+                if not torch.equal(y.view(torch.int32), first[0].view(torch.int32)):
+                    fails.append('second launch: different bits')
+                if stats and tickets:
+                    # the K split with ticket words: the half that finishes second stores an output pair and owns its
+                    # statistics, so WHICH block's row holds them follows arrival order (csrc/conv_wino4.hip, ST):
+                    # the rows may differ in bits, their float64 totals must still meet the bound
+                    tot = part.view(rows, 2, cout).sum(0)
+                    c = S.C_BOUND[S.kind_of(cfg)] * S.U
+                    if not bool(((tot[0] - case.sum64).abs() <= c * case.sumA).all()) or \
+                            not bool(((tot[1] - case.sq64).abs() <= c * case.sqA).all()):
+                        fails.append('second launch: fused BatchNorm statistics off')
+                elif stats and not torch.equal(part.view(torch.int64), first[1].view(torch.int64)):
+                    fails.append('second launch: different statistics bits')
+    finally:
+        if prog is not None:
+            torch.cuda.synchronize()
+            L.egn_program_destroy(prog)
+    return worst, fails
+
+
+@pytest.fixture(scope='module')
+def sweep_pairs():
+    t0 = time.time()
+    reqs = S.inference_requests() + S.tape_requests('cuda')
+    return reqs, S.pairs(reqs), time.time() - t0
+
+
+def test_every_candidate_config_matches_float64(sweep_pairs):
+    reqs, prs, t_collect = sweep_pairs
+    t0 = time.time()
+    groups = {}
+    for p in prs:
+        groups.setdefault((p['key'], p['act'], p['entry'], p['alias'], p['stats']), []).append(p)
+    per_cfg, per_entry, fails = {}, {}, []
+    kinds_worst = {}
+    n_launch = 0
+    for gk, ps in groups.items():
+        case = _Case(ps[0])
+        for p in ps:
+            cfg = p['cfg']
+            ent = per_cfg.setdefault(cfg, dict(requests=0, launches=0, worst=0.0, where=''))
+            ent['requests'] += 1
+            for mode, stats, tickets in _modes(p, cfg):
+                worst, f = _run_pair(case, cfg, mode, stats, tickets)
+                n_launch += 1
+                name = mode + ('+stats' if stats else '') + ('+tickets' if tickets else '') + \
+                    ('(3 launches)' if cfg in S.K_SPLIT and mode == 'conv2d' else '')
+                per_entry[name] = per_entry.get(name, 0) + 1
+                ent['launches'] += 1
+                if worst >= ent['worst']:
+                    ent['worst'], ent['where'] = worst, '%s %s act %d %s' % (name, p['srcs'][0], p['act'],
+                                                                             'alias' if p['alias'] else '')
+                k = S.kind_of(cfg)
+                kinds_worst[k] = max(kinds_worst.get(k, 0.0), worst)
+                for msg in f:
+                    fails.append('cfg %d %s key %s act %d alias %d (%s): %s'
+                                 % (cfg, name, p['key'], p['act'], p['alias'], p['srcs'][0], msg))
+        del case
+        torch.cuda.empty_cache()
+    wall = time.time() - t0
+    L = _lib.lib()
+    summary = dict(requests=len(reqs), distinct_requests=len(groups), pairs=len(prs), launches_checked=n_launch,
+                   collect_s=round(t_collect, 1), sweep_s=round(wall, 1), entries=per_entry,
+                   worst_ratio_per_kind={S.KIND_NAMES.get(k, str(k)): round(v, 2) for k, v in kinds_worst.items()},
+                   bound_per_kind={S.KIND_NAMES[k]: v for k, v in S.C_BOUND.items()},
+                   configs={str(c): dict(v, worst=round(v['worst'], 2)) for c, v in sorted(per_cfg.items())},
+                   failures=fails[:200])
+    print('\nconv sweep: %d requests (%d distinct), %d pairs, %d checked launches, %.0f s + %.0f s collection'
+          % (len(reqs), len(groups), len(prs), n_launch, wall, t_collect))
+    print('entries: %s' % per_entry)
+    for c, v in sorted(per_cfg.items()):
+        buf = C.create_string_buffer(96)
+        if c > 0:
+            L.egn_conv_config_name(c, buf, 96)
+        print('cfg %2d %-44s %5d requests %5d launches  worst %7.2f  %s'
+              % (c, buf.value.decode() or 'cost model', v['requests'], v['launches'], v['worst'], v['where']))
+    print('worst |err| / (2^-24 A) per kind: %s (bounds %s)' % (summary['worst_ratio_per_kind'],
+                                                                summary['bound_per_kind']))
+    out_dir = os.environ.get('EGONET_AMD_PARITY_DIR')
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, 'conv_sweep.json'), 'w') as fh:
+            json.dump(summary, fh, indent=1)
+    assert not fails, '%d failing launches:\n%s' % (len(fails), '\n'.join(fails[:40]))
+    # the sweep reached what it is meant to reach
+    product = [0] + list(range(1, 31)) + [42, 44, 51, 52, 56, 57, 59, 60, 61, 62, 64, 70, 79, 80, 82, 83, 84, 85, 86]
+    assert all(per_cfg.get(c, {}).get('requests', 0) > 0 for c in product), \
+        sorted(c for c in product if c not in per_cfg)
+    assert {'program', 'ex', 'bnstats', 'conv2d'} <= {k.split('+')[0].split('(')[0] for k in per_entry}, per_entry
+    assert any(k.startswith('ex') and 'tickets' in k for k in per_entry), per_entry
+    assert any(p['alias'] for p in prs)

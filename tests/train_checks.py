@@ -56,6 +56,40 @@ def dgrad_ref64(dy, w, stride, pad, h, wd):
     return dxp[:, :, pad:pad + h, pad:pad + wd]
 
 
+def conv_ref64(x, w, stride, pad, scale=None, shift=None, res=None, act=0):
+    """The forward of the conv kernels in float64: y = act(conv(x, W) * scale + shift + res), or with the
+    EGN_ACT_RES_AFTER flag (0x10) y = res + act(conv(x, W) * scale + shift); one matrix product per tap like
+    ``wgrad_ref64`` (on a GPU: rocBLAS dgemm).  x [N,Cin,H,W], W [Cout,Cin,KH,KW], res [N,Cout,Ho,Wo] float64;
+    scale / shift: at least Cout entries (None: 1 / 0); act as egonet_hip.h (LeakyReLU slope 0.01)."""
+    n, ci, h, wd = x.shape
+    co, _, kh, kw = w.shape
+    ho, wo = (h + 2 * pad - kh) // stride + 1, (wd + 2 * pad - kw) // stride + 1
+    xp = F.pad(x, (pad, pad, pad, pad)).permute(0, 2, 3, 1)
+    z = torch.zeros(n * ho * wo, co, dtype=torch.float64, device=x.device)
+    for ky in range(kh):
+        for kx in range(kw):
+            xs = xp[:, ky:ky + stride * (ho - 1) + 1:stride, kx:kx + stride * (wo - 1) + 1:stride]
+            z += xs.reshape(-1, ci) @ w[:, :, ky, kx].t()
+    z = z.view(n, ho, wo, co).permute(0, 3, 1, 2)
+    if scale is not None:
+        z = z * scale[:co].view(1, co, 1, 1)
+    if shift is not None:
+        z = z + shift[:co].view(1, co, 1, 1)
+    after = bool(act & 0x10)
+    if res is not None and not after:
+        z = z + res
+    a = act & 0xf
+    if a == 1:
+        z = torch.relu(z)
+    elif a == 2:
+        z = torch.sigmoid(z)
+    elif a == 3:
+        z = torch.where(z > 0, z, 0.01 * z)
+    if res is not None and after:
+        z = z + res
+    return z
+
+
 def _rel_t(got, want):
     return float((got - want).abs().max()) / max(float(want.abs().max()), 1e-30)
 
