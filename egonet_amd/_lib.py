@@ -133,6 +133,12 @@ SIGNATURES = {
     'egn_gemm_ex_f32': (_i, [_i, _p, _p, _p, _p, _p, _p, C.c_long] + [_i] * 7 + [_p, C.c_long, _p]),
     'egn_launch_count': (C.c_long, []),
     'egn_direct_conv_count': (C.c_long, []),
+    'egn_lifter_pairs_ws_bytes': (C.c_long, [_i, _i]),
+    'egn_lifter_pairs_f64': (_i, [_p, _p, _i, _p, _i, _p, _i, _d, _d, _i, _i, _p, C.c_long, _p, _p, _p, _p]),
+    'egn_col_mean_std_ws_bytes': (C.c_long, [_i]),
+    'egn_col_mean_std_f32': (_i, [_p, C.c_long, _i, _p, C.c_long, _p, _p, _p]),
+    'egn_normalize_rows_f32': (_i, [_p, C.c_long, _i, _p, _p, _p]),
+    'egn_gather_rows_f32': (_i, [_p, C.c_long, _i, _p, _i, _p, _p]),
     'egn_program_op_info': (_i, [_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), C.c_char_p, _i]),
 }
 

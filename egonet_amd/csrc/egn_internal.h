@@ -72,3 +72,6 @@ int egn_conv_plan(ConvArgs& a, int& cfg_id, size_t& lds_bytes);
 const ConvConfig* egn_conv_config(int cfg);
 int egn_conv_stats_rows(const ConvArgs& a, int cfg_id);
 int egn_conv_ticket_count(const ConvArgs& a, int cfg_id);   // a planned for cfg_id; 0 = the config uses none
+
+// adds n to egn_launch_count() (program.hip): entry points outside programs that want their launches provable
+void egn_count_launches(long n);

@@ -494,6 +494,7 @@ extern "C" int egn_program_op_info(const egn_program* p, int i, int* kind, doubl
 static std::atomic<long> g_launches{0};
 static thread_local bool t_recording = false;   // this thread is inside egn_program_capture
 extern "C" long egn_launch_count(void) { return g_launches.load(std::memory_order_relaxed); }
+void egn_count_launches(long n) { g_launches.fetch_add(n, std::memory_order_relaxed); }
 
 static int launch_op(egn_program* p, Op& op, hipStream_t s) {
   if (!t_recording) g_launches.fetch_add(1, std::memory_order_relaxed);

@@ -94,3 +94,32 @@ def synth_frame_records(n_frames, boxes_per_frame, num_joints, seed=0, hw=(375, 
         records.append({'image': img, 'boxes': boxes, 'joints': np.stack([x, y, vis], axis=2),
                         'path': 'synth/%06d_%03d.png' % (seed, f)})
     return records
+
+
+KITTI_P2 = [[721.5377, 0.0, 609.5593, 44.85728], [0.0, 721.5377, 172.854, 0.2163791], [0.0, 0.0, 1.0, 0.002745884]]
+
+
+def synth_kitti_labels(n_labels, seed=0, per_frame=4, size=(1242, 375)):
+    """Seeded KITTI-like car labels in the form ``common.lifter_pairs.LifterPairBuilder`` takes: records of
+    ``per_frame`` labels [n,7] float64 (l, h, w, x, y, z, rot_y, rounded to the label files' two decimals), a [3,4]
+    float32 ``P`` that varies a little from frame to frame, the image ``size`` (width, height) and a path.  Depths run
+    from 2.5 m to 60 m and |x| up to 1.1 z, so a share of the samples falls off the image."""
+    rng = np.random.RandomState(5150 + seed)
+    records, left, f = [], int(n_labels), 0
+    while left > 0:
+        n = min(per_frame, left)
+        z = rng.uniform(2.5, 60.0, n)
+        x = z * rng.uniform(-1.1, 1.1, n)
+        y = rng.uniform(1.2, 2.2, n)
+        dims = np.stack([rng.uniform(3.2, 5.0, n), rng.uniform(1.3, 1.9, n), rng.uniform(1.5, 1.9, n)], axis=1)
+        ry = rng.uniform(-np.pi, np.pi, n)
+        labels = np.round(np.concatenate([dims, np.stack([x, y, z, ry], axis=1)], axis=1), 2)
+        P = np.array(KITTI_P2, dtype=np.float64)
+        P[0, 0] = P[1, 1] = P[0, 0] + rng.uniform(-15, 15)
+        P[0, 2] += rng.uniform(-8, 8)
+        P[1, 2] += rng.uniform(-8, 8)
+        records.append({'labels': labels, 'P': P.astype(np.float32), 'size': (int(size[0]), int(size[1])),
+                        'path': 'synth/%06d_%06d.png' % (seed, f)})
+        left -= n
+        f += 1
+    return records

@@ -35,6 +35,10 @@ from .train_lifter import LifterTrainStep
 
 def get_loader(dataset, cfgs, split, collate_fn=None):
     setting = cfgs[split + '_settings']
+    if hasattr(dataset, 'device_loader'):
+        # rows that live on the device (common.lifter_pairs.LifterPairs): the same order as the DataLoader below
+        # for the same torch seed, one row fetch per batch instead of worker processes and a host collate
+        return dataset.device_loader(setting['batch_size'], setting['shuffle'])
     kw = dict(batch_size=setting['batch_size'], num_workers=setting['num_threads'], shuffle=setting['shuffle'])
     if collate_fn is not None:
         kw['collate_fn'] = collate_fn

@@ -619,6 +619,36 @@ long egn_direct_conv_count(void);
 int egn_program_op_info(const egn_program* p, int i, int* kind, double* flops,
                         double* bytes, char* tag, int tag_len);
 
+/* ------------------------------------------------------------------------
+ * The lifter's training pairs, built and kept on the device (csrc/lifter_pairs.hip).  Replaces the host loops of
+ * libs/dataset/KITTI/car_instance.py:611-644, 730-790, 902-1010, 1051-1086 and basic_classes.py:26-44.
+ * Every launch of this group is added to egn_launch_count().
+ *
+ * egn_lifter_pairs_f64: all samples of all labels, filtered and compacted in the reference's order.
+ *   labels [A][7] f64 (l h w x y z rot_y), label_frame [A] i32 in [0, F) (the caller checks it; an index outside is
+ *   clamped into the table, never read out of bounds), frames [F][14] f64 (K row major, shift, width, height),
+ *   draws [A][7T+1] f64 (T x 3 rotation, T x 3 translation, T + 1 yaw draws; NULL = none, then T must be 0),
+ *   coef0 / coef1 / ncoef (1 or 2): the edge interpolation coefficients, J = 9 + 12 * ncoef key points,
+ *   out_root != 0: 'R3d+T' rows (3J values), else 'R3d' (3(J-1)).
+ *   ws: egn_lifter_pairs_ws_bytes(A, T) bytes; afterwards its first 8 bytes hold the kept row count N (int64) and
+ *   its tail the A(T+1) keep flags (uint8, at ws + ws_bytes(A, T) - A(T+1)).
+ *   in2d [A(T+1)][2J] f32, out3d [A(T+1)][3(J-1)|3J] f32, roots [A(T+1)][3] f64: the first N rows are written.
+ *   A(T+1) must stay below 2^31 (else EGN_E_BADARG / a negative ws size): build a larger set in parts.  Row and byte
+ *   offsets are 64-bit throughout. */
+long egn_lifter_pairs_ws_bytes(int A, int T);
+int egn_lifter_pairs_f64(const double* labels, const int* label_frame, int A, const double* frames, int F,
+                         const double* draws, int T, double coef0, double coef1, int ncoef, int out_root,
+                         void* ws, long ws_bytes, float* in2d, float* out3d, double* roots, void* stream);
+/* column mean and population deviation (np.std, ddof 0) of x [N][C] f32, C <= 128: float64 sums in a fixed order
+ * (bit-reproducible), two passes, rounded to float32 at the end.  ws: egn_col_mean_std_ws_bytes(C) bytes. */
+long egn_col_mean_std_ws_bytes(int C);
+int egn_col_mean_std_f32(const float* x, long N, int C, void* ws, long ws_bytes, float* mean, float* stdv,
+                         void* stream);
+/* x[r][c] = (x[r][c] - mean[c]) / stdv[c] in place, float32, both operations correctly rounded (operations.py:47) */
+int egn_normalize_rows_f32(float* x, long N, int C, const float* mean, const float* stdv, void* stream);
+/* dst[i][:] = src[idx[i]][:], i < n; idx int64 on the device; an index outside [0, nrows) yields zeros */
+int egn_gather_rows_f32(const float* src, long nrows, int C, const int64_t* idx, int n, float* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,107 @@
+#!/usr/bin/env python
+"""Train the lifter sub-model L from KITTI labels: the counterpart of the reference's tools/train_lifting.py.
+
+    python tools/train_lifting.py --label-dir <label_2> --calib-dir <calib> --train-list train.txt \
+        --valid-list val.txt --out <dir> [--size 1242 375] [--epochs 300] [--batch-size 2048]
+    python tools/train_lifting.py --synthetic 2000 --out <dir>       # seeded synthetic labels, no KITTI tree
+
+Pairs are built on the device (egonet_amd.common.lifter_pairs), normalised with the train set's statistics, fed to
+``trainer.train_cascade`` from HBM, and ``L.pth`` + ``LS.npy`` are written like train_lifting.py:51-54.  A split
+list holds one frame name per line ('000123'); the image size is taken from ``--size`` (the reference opens every
+image for it; KITTI frames differ by a few pixels -- pass records with their own sizes through the Python API
+where that matters)."""
+import argparse
+import logging
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from egonet_amd import configs, synth, trainer          # noqa: E402
+from egonet_amd.common import lifter_pairs as lp        # noqa: E402
+
+
+def lifting_cfgs(args):
+    """The keys of configs/KITTI_train_lifting.yml that the builder and the trainer read."""
+    cfg = configs.clone(configs.w48_config())
+    cfg['FCModel'].update(num_neurons=args.neurons, num_blocks=args.blocks, dropout=args.dropout)
+    cfg.update(use_gpu=True, exp_type='2dto3d', cascade={'num_stages': 1},
+               dataset={'detect_classes': ['Car'], '3d_kpt_sample_style': 'bbox9',
+                        'interpolate': {'flag': True, 'style': 'bbox12', 'coef': [0.332, 0.667]},
+                        'lft_in_rep': 'coordinates2d', 'lft_out_rep': args.out_rep},
+               optimizer={'optim_type': 'adam', 'lr': args.lr, 'weight_decay': 0.0, 'momentum': 0.9,
+                          'milestones': [int(0.5 * args.epochs) or 1, int(0.75 * args.epochs) or 1], 'gamma': 0.1},
+               training_settings={'total_epochs': args.epochs, 'batch_size': args.batch_size, 'num_threads': 4,
+                                  'shuffle': True, 'report_every': args.report_every, 'eval_during': False,
+                                  'plot_loss': False, 'lft_aug': True, 'lft_aug_times': args.aug_times},
+               testing_settings={'batch_size': args.batch_size, 'num_threads': 4, 'shuffle': False,
+                                 'unnormalize': False})
+    return cfg
+
+
+def _mse(prediction, target, weights, meta):
+    return torch.nn.functional.mse_loss(prediction, target)
+
+
+def kitti_records(label_dir, calib_dir, list_path, size, classes):
+    with open(list_path) as fh:
+        names = [ln.strip() for ln in fh if ln.strip()]
+    return [{'labels': lp.read_label_file(os.path.join(label_dir, n + '.txt'), classes),
+             'P': lp.read_calib_file(os.path.join(calib_dir, n + '.txt')), 'size': size, 'path': n + '.png'}
+            for n in names]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--label-dir')
+    ap.add_argument('--calib-dir')
+    ap.add_argument('--train-list')
+    ap.add_argument('--valid-list')
+    ap.add_argument('--synthetic', type=int, default=0, metavar='N', help='N seeded synthetic labels instead of KITTI')
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--size', type=int, nargs=2, default=[1242, 375], metavar=('W', 'H'))
+    ap.add_argument('--out-rep', default='R3d', choices=['R3d', 'R3d+T'])
+    ap.add_argument('--aug-times', type=int, default=100)
+    ap.add_argument('--epochs', type=int, default=300)
+    ap.add_argument('--batch-size', type=int, default=2048)
+    ap.add_argument('--lr', type=float, default=1e-3)
+    ap.add_argument('--neurons', type=int, default=1024)
+    ap.add_argument('--blocks', type=int, default=2)
+    ap.add_argument('--dropout', type=float, default=0.5)
+    ap.add_argument('--report-every', type=int, default=100)
+    ap.add_argument('--seed', type=int, default=0)
+    args = ap.parse_args()
+    logging.basicConfig(level=logging.INFO, format='%(message)s')
+    logger = logging.getLogger('train_lifting')
+    cfgs = lifting_cfgs(args)
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    if args.synthetic:
+        train_rec = synth.synth_kitti_labels(args.synthetic, seed=args.seed)
+        valid_rec = synth.synth_kitti_labels(max(args.synthetic // 10, 4), seed=args.seed + 1)
+    else:
+        if not (args.label_dir and args.calib_dir and args.train_list):
+            ap.error('--label-dir, --calib-dir and --train-list are needed without --synthetic')
+        classes = tuple(cfgs['dataset']['detect_classes'])
+        train_rec = kitti_records(args.label_dir, args.calib_dir, args.train_list, tuple(args.size), classes)
+        valid_rec = kitti_records(args.label_dir, args.calib_dir, args.valid_list, tuple(args.size), classes) \
+            if args.valid_list else None
+    train_set = lp.LifterPairBuilder(cfgs, 'train')(train_rec).normalize()
+    logger.info('train: %d pairs of %d samples kept' % (len(train_set), len(train_set.keep)))
+    valid_set = None
+    if valid_rec:
+        valid_set = lp.LifterPairBuilder(cfgs, 'valid')(valid_rec).normalize(train_set.statistics)
+        logger.info('valid: %d pairs' % len(valid_set))
+    record = trainer.train_cascade(train_set, valid_set, cfgs, logger)
+    if valid_set is not None:                               # trainer.py:395-513 over the valid pairs, from HBM too
+        trainer.evaluate(valid_set, record['cascade'][0].cuda(), _mse, cfgs, logger, None)
+    os.makedirs(args.out, exist_ok=True)
+    torch.save(record['cascade'][0].cpu().state_dict(), os.path.join(args.out, 'L.pth'))
+    np.save(os.path.join(args.out, 'LS.npy'), train_set.statistics)
+    logger.info('=> wrote %s and %s' % (os.path.join(args.out, 'L.pth'), os.path.join(args.out, 'LS.npy')))
+
+
+if __name__ == '__main__':
+    main()
