@@ -84,6 +84,45 @@ EGN_HD inline void egn_cross3(const double a[3], const double b[3], double c[3])
   c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
+// Kabsch rotation of a 3x3 cross-covariance H = (X - mx)(Y - my)^T (transformation.py:121-132), shared by the pose
+// solve below and the lifter's validation metrics (metric_math.h).
+// H = U S V^T.  v_k (Y space) = eigenvectors of H^T H for the two largest eigenvalues, u_k = H v_k / |H v_k| (X
+// space).  R = V U^T with the third pair replaced by cross products equals the reference's det-corrected
+// V diag(1,1,d) U^T and needs no third singular value.  H of rank < 2 divides by zero here (NaN entries): the pose
+// solve passes that on like before, metric_math.h tests for it.
+EGN_HD inline void egn_kabsch_rotation(const double Hm[3][3], double R[3][3]) {
+  double A[3][3], V[3][3], ev[3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c)
+      A[r][c] = Hm[0][r] * Hm[0][c] + Hm[1][r] * Hm[1][c] + Hm[2][r] * Hm[2][c];
+  egn_jacobi3(A, V, ev);
+  int i0 = 0;
+  if (ev[1] > ev[i0]) i0 = 1;
+  if (ev[2] > ev[i0]) i0 = 2;
+  int i1 = (i0 == 0) ? 1 : 0;
+  for (int k = 0; k < 3; ++k)
+    if (k != i0 && ev[k] > ev[i1]) i1 = k;
+  double v0[3], v1[3], v2[3], u0[3], u1[3], u2[3];
+  for (int d = 0; d < 3; ++d) {
+    v0[d] = V[d][i0];
+    v1[d] = V[d][i1];
+  }
+  for (int r = 0; r < 3; ++r) {
+    u0[r] = Hm[r][0] * v0[0] + Hm[r][1] * v0[1] + Hm[r][2] * v0[2];
+    u1[r] = Hm[r][0] * v1[0] + Hm[r][1] * v1[1] + Hm[r][2] * v1[2];
+  }
+  const double n0 = sqrt(u0[0] * u0[0] + u0[1] * u0[1] + u0[2] * u0[2]);
+  for (int d = 0; d < 3; ++d) u0[d] /= n0;
+  const double dot = u0[0] * u1[0] + u0[1] * u1[1] + u0[2] * u1[2];
+  for (int d = 0; d < 3; ++d) u1[d] -= dot * u0[d];
+  const double n1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+  for (int d = 0; d < 3; ++d) u1[d] /= n1;
+  egn_cross3(u0, u1, u2);
+  egn_cross3(v0, v1, v2);
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) R[r][c] = v0[r] * u0[c] + v1[r] * u1[c] + v2[r] * u2[c];
+}
+
 // One instance of the pose solve.  P = predicted cuboid [32][3] (root dropped).
 //   euler_xyz[3]: rotation about x, y, z (reference egonet.py:265-277)
 //   returns the observation angle alpha (egonet.py:203-236)
@@ -134,42 +173,9 @@ EGN_HD inline double egn_pose_solve_one(const double* P, double kpt_x, double fx
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) Hm[r][c] += (T[i][r] - mx[r]) * (P[3 * i + c] - my[c]);
 
-  // H = U S V^T.  v_k (prediction space) = eigenvectors of H^T H for the two
-  // largest eigenvalues, u_k = H v_k / |H v_k| (template space).  R = V U^T with
-  // the third pair replaced by cross products equals the reference's
-  // det-corrected V diag(1,1,d) U^T (transformation.py:121-132) and needs no
-  // third singular value.
-  double A[3][3], V[3][3], ev[3];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c)
-      A[r][c] = Hm[0][r] * Hm[0][c] + Hm[1][r] * Hm[1][c] + Hm[2][r] * Hm[2][c];
-  egn_jacobi3(A, V, ev);
-  int i0 = 0;
-  if (ev[1] > ev[i0]) i0 = 1;
-  if (ev[2] > ev[i0]) i0 = 2;
-  int i1 = (i0 == 0) ? 1 : 0;
-  for (int k = 0; k < 3; ++k)
-    if (k != i0 && ev[k] > ev[i1]) i1 = k;
-  double v0[3], v1[3], v2[3], u0[3], u1[3], u2[3];
-  for (int d = 0; d < 3; ++d) {
-    v0[d] = V[d][i0];
-    v1[d] = V[d][i1];
-  }
-  for (int r = 0; r < 3; ++r) {
-    u0[r] = Hm[r][0] * v0[0] + Hm[r][1] * v0[1] + Hm[r][2] * v0[2];
-    u1[r] = Hm[r][0] * v1[0] + Hm[r][1] * v1[1] + Hm[r][2] * v1[2];
-  }
-  const double n0 = sqrt(u0[0] * u0[0] + u0[1] * u0[1] + u0[2] * u0[2]);
-  for (int d = 0; d < 3; ++d) u0[d] /= n0;
-  const double dot = u0[0] * u1[0] + u0[1] * u1[1] + u0[2] * u1[2];
-  for (int d = 0; d < 3; ++d) u1[d] -= dot * u0[d];
-  const double n1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
-  for (int d = 0; d < 3; ++d) u1[d] /= n1;
-  egn_cross3(u0, u1, u2);
-  egn_cross3(v0, v1, v2);
+  // R = V U^T of H = U S V^T with the reflection fix (transformation.py:121-132)
   double R[3][3];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) R[r][c] = v0[r] * u0[c] + v1[r] * u1[c] + v2[r] * u2[c];
+  egn_kabsch_rotation(Hm, R);
 
   // Rotation.from_matrix(R).as_euler('yxz') (extrinsic): R = Rz(c) Rx(b) Ry(a);
   // reference re-orders to (x, y, z) = (b, a, c)  (egonet.py:273-276)

@@ -7,6 +7,20 @@ The heat-map decode inside ``get_distance_src`` runs on the GPU (csrc/decode.hip
 wavefront per map: hard arg-max, soft-arg-max, or the numpy-style soft-arg-max); the
 rest -- 33 points per instance through a 2x3 inverse crop affine, distances, PCK
 counts -- is per-instance host arithmetic in float64 like the reference's.
+
+The lifter's 3-D metrics (``RError3D`` :390-449, ``RTError3D`` :451-538, ``JointDistance3D`` :343-388,
+``RotationError3D`` :303-341, ``Evaluator`` :540-573; helpers :223-301) keep the reference's constructor arguments,
+attribute names (``mean_rT``, ``max_R``, ``count_R``, ... as numpy arrays) and ``report()`` text.  ``update`` takes
+two kinds of input:
+  CUDA tensors   csrc/lifter_metrics.hip (``egn_lifter_metrics_update_f32``): the rows stay on the device and are
+                 folded into one device accumulator per metric object; with ``statistics=`` (or after
+                 ``set_statistics``) the unnormalise of trainer.py:474-481 is fused into the kernel.  Nothing is read
+                 back until ``report()`` or the first attribute access.
+  numpy arrays   host arithmetic in float64 (the reference runs the same formulas in the arrays' float32), so the
+                 classes also work without a GPU.
+Out of scope, each a ``NotImplementedError``: ``T_style`` / ``style`` 'procrustes' (the reference aligns the
+prediction IN PLACE, criterions.py:285-292, so the rotation error after it is that of the aligned points),
+``R_style`` other than 'euler' (:266-267) and ``3d_kpt_sample_style`` other than 'bbox9' (:399-402).
 """
 import numpy as np
 import torch
@@ -129,3 +143,355 @@ class JointDistance2DSIP(object):
         logger.info('Error type: {:s}\tMPJPE: {}\t'.format(self.name, self.mean))
         for thres, value in zip(PCK_THRES, self.PCK_counts):
             logger.info('PCK at threshold {:.2f}: {:.3f}'.format(thres, value / self.count))
+
+
+# ---- the lifter's 3-D metrics -----------------------------------------------------------------------------------
+_LAYOUT_COLS = {0: 35, 1: 39}                       # csrc/metric_math.h: 'R3d' / 'R3d+T' result columns
+_ACC_SUM, _ACC_MAX, _ACC_MIN = 8, 48, 88            # include/egonet_hip.h: the accumulator's float64 slots
+_ACC_DOUBLES = 128
+
+
+def _euler_xyz_abs_deg(R):
+    """|Rotation.from_matrix(R).as_euler('xyz', degrees=True)| for R [n,3,3] float64: extrinsic x-y-z,
+    R = Rz(c) Ry(b) Rx(a); at gimbal lock the third angle is zero like scipy's (csrc/metric_math.h)."""
+    cb = np.sqrt(R[:, 0, 0] ** 2 + R[:, 1, 0] ** 2)
+    lock = cb <= 1e-7
+    a = np.where(lock, np.arctan2(-R[:, 1, 2], R[:, 1, 1]), np.arctan2(R[:, 2, 1], R[:, 2, 2]))
+    c = np.where(lock, 0.0, np.arctan2(R[:, 1, 0], R[:, 0, 0]))
+    return np.abs(np.stack([a, np.arctan2(-R[:, 2, 0], cb), c], axis=1) * (180.0 / np.pi))
+
+
+def _rotation_errors(prediction, ground_truth):
+    """update_rotation_error style 'euler' (criterions.py:241-269, transformation.py:99-134) for all rows at once."""
+    n = len(prediction)
+    X = np.asarray(prediction, dtype=np.float64).reshape(n, -1, 3)
+    Y = np.asarray(ground_truth, dtype=np.float64).reshape(n, -1, 3)
+    Xm = X - X.mean(axis=1, keepdims=True)
+    Ym = Y - Y.mean(axis=1, keepdims=True)
+    H = np.einsum('nir,nic->nrc', Xm, Ym)
+    U, _, Vt = np.linalg.svd(H)
+    R = np.einsum('nkr,nck->nrc', Vt, U)                            # Vt.T @ U.T
+    flip = np.linalg.det(R) < 0
+    Vt[flip, 2, :] *= -1                                            # the reflection fix, transformation.py:125-132
+    R[flip] = np.einsum('nkr,nck->nrc', Vt[flip], U[flip])
+    return _euler_xyz_abs_deg(R)
+
+
+def _joint_distances(prediction, ground_truth):
+    n = len(prediction)
+    p = np.asarray(prediction, dtype=np.float64).reshape(n, -1, 3)
+    g = np.asarray(ground_truth, dtype=np.float64).reshape(n, -1, 3)
+    return np.sqrt(((g - p) ** 2).sum(axis=2))
+
+
+class _Stats3D(object):
+    """count / mean / max / min per group of error columns (update_statistics, criterions.py:223-239) with a host
+    and a device accumulator.  ``_groups``: (name_str, first column, end column) in the kernel's column order."""
+    _groups = ()
+    device_update = True
+
+    def _init_stats(self, layout):
+        self._layout = layout
+        self._host = {}
+        for name, a, b in self._groups:
+            self._host['count' + name] = 0
+            self._host['mean' + name] = np.zeros(b - a)
+            self._host['max' + name] = -np.ones(b - a)
+            self._host['min' + name] = np.ones(b - a) * 1e16
+        self._acc = self._ws = self._stats_host = self._stats_dev = None
+        self._pending = False
+
+    def __getattr__(self, key):                     # only reached for names that are not ordinary attributes
+        host = self.__dict__.get('_host')
+        if host is not None and key in host:
+            self._sync()
+            return host[key]
+        raise AttributeError(key)
+
+    def _fold(self, name, update):
+        """update_statistics for one group; ``update`` [n, columns] float64."""
+        h, n = self._host, len(update)
+        h['mean' + name] = (h['count' + name] * h['mean' + name] + np.sum(update, axis=0)) / (h['count' + name] + n)
+        h['count' + name] = h['count' + name] + n
+        h['max' + name] = np.maximum(h['max' + name], update.max(axis=0))
+        h['min' + name] = np.minimum(h['min' + name], update.min(axis=0))
+
+    def set_statistics(self, mean_out, std_out):
+        """The fused unnormalise of the device path (and the float32 one of the host path): ``x * std + mean``."""
+        self._stats_host = (np.ascontiguousarray(mean_out, dtype=np.float32).reshape(-1),
+                            np.ascontiguousarray(std_out, dtype=np.float32).reshape(-1))
+        self._stats_dev = None
+
+    def _use_statistics(self, statistics):
+        if statistics is not None:
+            cur = self._stats_host
+            m = np.ascontiguousarray(statistics['mean_out'], dtype=np.float32).reshape(-1)
+            s = np.ascontiguousarray(statistics['std_out'], dtype=np.float32).reshape(-1)
+            if cur is None or not (np.array_equal(cur[0], m) and np.array_equal(cur[1], s)):
+                self.set_statistics(m, s)
+        return self._stats_host
+
+    def _update_device(self, prediction, ground_truth, statistics=None, rows_out=None):
+        from .. import _lib
+        pred, gt = prediction.detach(), ground_truth.detach()
+        if pred.dtype != torch.float32 or gt.dtype != torch.float32 or pred.dim() != 2 or pred.shape != gt.shape:
+            raise ValueError('%s: float32 [n, D] prediction and ground truth of one shape' % self.name)
+        D = 99 if self._layout else 96
+        if pred.shape[1] != D:
+            raise ValueError('%s: rows of %d values, the device path takes %d' % (self.name, pred.shape[1], D))
+        if pred.stride(1) != 1 or pred.stride(0) != gt.stride(0) or gt.stride(1) != 1 or pred.stride(0) < D:
+            pred, gt = pred.contiguous(), gt.contiguous()
+        dev, n = pred.device, pred.shape[0]
+        if n == 0:
+            return
+        L = _lib.lib()
+        stats = self._use_statistics(statistics)
+        with torch.cuda.device(dev):
+            st = _lib.current_stream(dev)
+            if self._acc is None or self._acc.device != dev:
+                self._sync()
+                self._acc = torch.empty(_ACC_DOUBLES, dtype=torch.float64, device=dev)
+                _lib.check(L.egn_lifter_metrics_reset(_lib.ptr(self._acc), self._layout, st), 'metrics reset')
+            nb = L.egn_lifter_metrics_ws_bytes(n)
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nb:
+                self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            mean = std = None
+            if stats is not None:
+                if stats[0].size != D or stats[1].size != D:
+                    raise ValueError('%s: statistics of %d values for rows of %d' % (self.name, stats[0].size, D))
+                if self._stats_dev is None or self._stats_dev[0].device != dev:
+                    self._stats_dev = tuple(torch.from_numpy(a).to(dev) for a in stats)
+                mean, std = self._stats_dev
+            if rows_out is not None and (rows_out.dtype != torch.float64 or not rows_out.is_contiguous() or
+                                         tuple(rows_out.shape) != (n, _LAYOUT_COLS[self._layout])):
+                raise ValueError('rows_out must be contiguous float64 [%d, %d]' % (n, _LAYOUT_COLS[self._layout]))
+            _lib.check(L.egn_lifter_metrics_update_f32(
+                _lib.ptr(pred), _lib.ptr(gt), n, D, pred.stride(0) if n else D, _lib.ptr(mean), _lib.ptr(std),
+                self._layout, _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._acc), _lib.ptr(rows_out), st),
+                'metrics update')
+        self._pending = True
+
+    def _sync(self):
+        """The one read-back: the device accumulator is merged into the host attributes and reset."""
+        if not self.__dict__.get('_pending'):
+            return
+        from .. import _lib
+        self._pending = False
+        acc = self._acc.cpu().numpy()
+        with torch.cuda.device(self._acc.device):
+            _lib.check(_lib.lib().egn_lifter_metrics_reset(_lib.ptr(self._acc), self._layout,
+                                                           _lib.current_stream(self._acc.device)), 'metrics reset')
+        n = int(acc[0])
+        if n == 0:
+            return
+        h = self._host
+        for name, a, b in self._groups:
+            shape = (1, 3) if name.endswith('_xyz') else (b - a,)      # the reference's [1, 3] arrays, see RTError3D
+            h['mean' + name] = (h['count' + name] * h['mean' + name] +
+                                acc[_ACC_SUM + a:_ACC_SUM + b].reshape(shape)) / (h['count' + name] + n)
+            h['count' + name] = h['count' + name] + n
+            h['max' + name] = np.maximum(h['max' + name], acc[_ACC_MAX + a:_ACC_MAX + b].reshape(shape))
+            h['min' + name] = np.minimum(h['min' + name], acc[_ACC_MIN + a:_ACC_MIN + b].reshape(shape))
+
+    def _host_arrays(self, prediction, ground_truth, statistics):
+        prediction, ground_truth = np.asarray(prediction), np.asarray(ground_truth)
+        stats = self._use_statistics(statistics)
+        if stats is not None:                       # operations.py:50-52 on float32 arrays
+            m, s = stats[0].reshape(1, -1), stats[1].reshape(1, -1)
+            prediction = prediction.astype(np.float32) * s + m
+            ground_truth = ground_truth.astype(np.float32) * s + m
+        return prediction, ground_truth
+
+    def _is_device(self, prediction):
+        return torch.is_tensor(prediction) and prediction.is_cuda
+
+
+def _check_styles(name, T_style, R_style, sample_style):
+    if sample_style != 'bbox9':
+        raise NotImplementedError('%s: 3d_kpt_sample_style %r (criterions.py:399-402 knows bbox9 only)'
+                                  % (name, sample_style))
+    if T_style == 'procrustes':
+        raise NotImplementedError("%s: T_style 'procrustes' (criterions.py:285-292 aligns the prediction in place, "
+                                  'the rotation error that follows is that of the aligned points)' % name)
+    if T_style != 'direct':
+        raise NotImplementedError('%s: T_style %r (criterions.py:352-357, 465-479)' % (name, T_style))
+    if R_style != 'euler':
+        raise NotImplementedError('%s: R_style %r (criterions.py:266-267 knows euler only)' % (name, R_style))
+
+
+class RError3D(_Stats3D):
+    """Relative shape error; rows [shape relative to the root] (criterions.py:390-449)."""
+    _groups = (('_rT', 0, 32), ('_R', 32, 35))
+
+    def __init__(self, cfgs, num_joints):
+        self.name = 'RError3D'
+        self.T_style = cfgs['metrics']['R3D']['T_style']
+        self.R_style = cfgs['metrics']['R3D']['R_style']
+        _check_styles(self.name, self.T_style, self.R_style, cfgs['dataset']['3d_kpt_sample_style'])
+        self.num_joints = num_joints - 1            # discount the root joint
+        self._groups = (('_rT', 0, self.num_joints), ('_R', 32, 35))
+        self._init_stats(0)
+
+    def update(self, prediction, ground_truth=None, meta_data=None, logger=None, statistics=None):
+        if self._is_device(prediction):
+            if self.num_joints != 32:
+                raise NotImplementedError('RError3D on the device: 33-point cuboids (32 points + root)')
+            return self._update_device(prediction, ground_truth, statistics)
+        prediction, ground_truth = self._host_arrays(prediction, ground_truth, statistics)
+        self._fold('_rT', _joint_distances(prediction, ground_truth))
+        self._fold('_R', _rotation_errors(prediction, ground_truth))
+
+    def report(self, logger):
+        MPJPE = self.mean_rT.sum() / self.num_joints
+        logger.info('Error type: {error_type:s}\t'
+                    'MPJPE of the shape relative to the root:\t'
+                    'MPJPE: {MPJPE}\t'
+                    'Rotation error of the shape relative to the root:\t'
+                    'Mean error: {mean_R}\t'
+                    'Max error: {max_R}\t'
+                    'Min error: {min_R}\t'.format(error_type=self.name, MPJPE=MPJPE, mean_R=self.mean_R,
+                                                 max_R=self.max_R, min_R=self.min_R))
+
+
+class RTError3D(_Stats3D):
+    """Rotation and translation error combined; rows [root, shape relative to the root] (criterions.py:451-538)."""
+
+    def __init__(self, cfgs, num_joints):
+        self.name = 'RTError3D'
+        self.T_style = cfgs['metrics']['RTError3D']['T_style']
+        self.R_style = cfgs['metrics']['RTError3D']['R_style']
+        _check_styles(self.name, self.T_style, self.R_style, cfgs['dataset']['3d_kpt_sample_style'])
+        self.num_joints = num_joints - 1
+        self._groups = (('_T', 35, 36), ('_T_xyz', 36, 39), ('_rT', 0, self.num_joints), ('_R', 32, 35))
+        self._init_stats(1)
+
+    def update(self, prediction, ground_truth=None, meta_data=None, logger=None, statistics=None):
+        if self._is_device(prediction):
+            if self.num_joints != 32:
+                raise NotImplementedError('RTError3D on the device: 33-point cuboids (root + 32 points)')
+            return self._update_device(prediction, ground_truth, statistics)
+        prediction, ground_truth = self._host_arrays(prediction, ground_truth, statistics)
+        self._fold('_T', _joint_distances(prediction[:, :3], ground_truth[:, :3]))
+        # [n, 1, 3] like the reference's reshape(n, -1, 3): its _T_xyz attributes are [1, 3] after the first update
+        self._fold('_T_xyz', np.abs(ground_truth[:, :3].astype(np.float64) -
+                                    prediction[:, :3].astype(np.float64)).reshape(-1, 1, 3))
+        self._fold('_rT', _joint_distances(prediction[:, 3:], ground_truth[:, 3:]))
+        self._fold('_R', _rotation_errors(prediction[:, 3:], ground_truth[:, 3:]))
+
+    def report(self, logger):
+        MPJPE = self.mean_rT.sum() / self.num_joints
+        logger.info('Error type: {error_type:s}\t'
+                    'Translation error of the root:\t'
+                    'Mean error: {mean_T}\t'
+                    'Max error: {max_T}\t'
+                    'Min error: {min_T}\t'
+                    'Translation error of the root in three directions:\t'
+                    'Mean error (L1): {mean_T_xyz}\t'
+                    'MPJPE of the shape relative to the root:\t'
+                    'MPJPE: {MPJPE}\t'
+                    'Rotation error of the shape relative to the root:\t'
+                    'Mean error: {mean_R}\t'
+                    'Max error: {max_R}\t'
+                    'Min error: {min_R}\t'.format(error_type=self.name, MPJPE=MPJPE, mean_T=self.mean_T,
+                                                 max_T=self.max_T, min_T=self.min_T, mean_T_xyz=self.mean_T_xyz,
+                                                 mean_R=self.mean_R, max_R=self.max_R, min_R=self.min_R))
+
+
+class JointDistance3D(_Stats3D):
+    """Joint distance error (criterions.py:343-388); the device path takes the 96-column rows."""
+
+    def __init__(self, cfgs):
+        self.name = 'Joint distance'
+        self.style = cfgs['metrics']['JD3D']['style']
+        if self.style == 'procrustes':
+            raise NotImplementedError("JointDistance3D: style 'procrustes' (criterions.py:285-292)")
+        if self.style != 'direct':
+            raise NotImplementedError('JointDistance3D: style %r (criterions.py:352-357)' % (self.style,))
+        self.num_joints = int(cfgs['FCModel']['output_size'] / 3)
+        self._groups = (('', 0, self.num_joints),)
+        self._init_stats(0)
+
+    def update(self, prediction, ground_truth=None, meta_data=None, logger=None, statistics=None):
+        if self._is_device(prediction):
+            if self.num_joints != 32:
+                raise NotImplementedError('JointDistance3D on the device: 96-column rows (32 points)')
+            return self._update_device(prediction, ground_truth, statistics)
+        prediction, ground_truth = self._host_arrays(prediction, ground_truth, statistics)
+        self._fold('', _joint_distances(prediction, ground_truth))
+
+    def report(self, logger):
+        MPJPE = self.mean.sum() / self.num_joints
+        logger.info('Error type: {error_type:s}\t'
+                    'MPJPE: {MPJPE}\t'
+                    'Mean error for each joint: {mean_error}\t'
+                    'Max error for each joint: {max_error}\t'
+                    'Min error for each joint: {min_error}\t'.format(error_type=self.name, MPJPE=MPJPE,
+                                                                    mean_error=self.mean, max_error=self.max,
+                                                                    min_error=self.min))
+
+
+class RotationError3D(_Stats3D):
+    """Rotation estimation error (criterions.py:303-341); the device path takes the 96-column rows."""
+    _groups = (('', 32, 35),)
+
+    def __init__(self, cfgs):
+        self.name = 'Rotation error'
+        self.style = cfgs['metrics']['R3D']['style']
+        if self.style != 'euler':
+            raise NotImplementedError('RotationError3D: style %r (criterions.py:266-267 knows euler only)'
+                                      % (self.style,))
+        self._init_stats(0)
+
+    def update(self, prediction, ground_truth=None, meta_data=None, logger=None, statistics=None):
+        if self._is_device(prediction):
+            return self._update_device(prediction, ground_truth, statistics)
+        prediction, ground_truth = self._host_arrays(prediction, ground_truth, statistics)
+        self._fold('', _rotation_errors(prediction, ground_truth))
+
+    def report(self, logger):
+        logger.info('Error type: {error_type:s}\t'
+                    'Mean error: {mean_error}\t'
+                    'Max error: {max_error}\t'
+                    'Min error: {min_error}\t'.format(error_type=self.name, mean_error=self.mean,
+                                                     max_error=self.max, min_error=self.min))
+
+
+def _make_metric(cls):
+    import inspect
+    takes_joints = 'num_joints' in inspect.signature(cls.__init__).parameters
+    return (lambda cfgs, num_joints: cls(cfgs, num_joints)) if takes_joints else (lambda cfgs, num_joints: cls(cfgs))
+
+
+# the names ``Evaluator`` resolves (the reference evaluates the string, criterions.py:549-550)
+METRICS = {c.__name__: _make_metric(c) for c in (RError3D, RTError3D, JointDistance3D, RotationError3D,
+                                                 JointDistance2DSIP, AngleError)}
+
+
+class Evaluator(object):
+    """A list of metrics by name (criterions.py:540-573).  ``device_update``: ``trainer.evaluate`` may hand CUDA
+    tensors and the set's statistics to ``update`` instead of unnormalised host arrays; it holds when every metric
+    of the list has the device path."""
+
+    def __init__(self, metrics, cfgs=None, num_joints=9):
+        self.metrics = []
+        for metric in metrics:
+            if metric not in METRICS:
+                raise NotImplementedError('metric %r (known: %s)' % (metric, ', '.join(sorted(METRICS))))
+            self.metrics.append(METRICS[metric](cfgs, num_joints))
+        self.device_update = bool(self.metrics) and all(isinstance(m, _Stats3D) for m in self.metrics)
+
+    def set_statistics(self, mean_out, std_out):
+        for metric in self.metrics:
+            metric.set_statistics(mean_out, std_out)
+
+    def update(self, prediction, ground_truth=None, meta_data=None, logger=None, statistics=None):
+        for metric in self.metrics:
+            if statistics is not None:
+                metric.update(prediction, ground_truth=ground_truth, meta_data=meta_data, logger=logger,
+                              statistics=statistics)
+            else:
+                metric.update(prediction, ground_truth=ground_truth, meta_data=meta_data, logger=logger)
+
+    def report(self, logger):
+        for metric in self.metrics:
+            metric.report(logger)

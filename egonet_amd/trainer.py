@@ -216,10 +216,14 @@ def evaluate(eval_dataset, model, loss_func, cfgs, logger, evaluator, save=False
     ``forward``).  ``loss_func`` (the caller's criterion, optional) and ``evaluator``
     (``update(prediction, ground_truth=, meta_data=)`` / ``report(logger)``) are called like the
     reference calls them; 3D plotting (``vis_epoch``) is outside the hot path and skipped.
+    An evaluator with ``device_update = True`` (``metric.criterions.Evaluator`` over the lifter's 3-D metrics) gets
+    the CUDA prediction / target as they are -- with ``testing_settings.unnormalize`` also the set's ``statistics``,
+    its kernel unnormalises -- instead of the ``.cpu().numpy()`` copies and the host unnormalise.
     Returns the mean validation loss (None without ``loss_func``)."""
     ts = cfgs['testing_settings']
     unnorm = bool(ts.get('unnormalize', False))
     stats = eval_dataset.statistics if unnorm else None
+    dev_eval = evaluator is not None and bool(getattr(evaluator, 'device_update', False))
     model.eval()
     if ts.get('apply_dropout', False):
         # trainer.py:424-428: dropout layers back in train mode ("a loss similar to the training loss"); the model's
@@ -242,10 +246,17 @@ def evaluate(eval_dataset, model, loss_func, cfgs, logger, evaluator, save=False
                 loss = loss_func(prediction, target, weights, meta)
             loss_sum += float(loss.item()) * data.size(0)
             seen += data.size(0)
-        if unnorm:
+        fused = unnorm and dev_eval and torch.is_tensor(prediction) and prediction.is_cuda
+        if fused:                                   # both stay in HBM: the evaluator's kernel unnormalises
+            evaluator.update(prediction, ground_truth=target, meta_data=meta, statistics=stats)
+            if save:
+                target = eval_dataset.unnormalize(target.data.cpu().numpy(), stats['mean_out'], stats['std_out'])
+                prediction = eval_dataset.unnormalize(prediction.data.cpu().numpy(), stats['mean_out'],
+                                                      stats['std_out'])
+        elif unnorm:
             target = eval_dataset.unnormalize(target.data.cpu().numpy(), stats['mean_out'], stats['std_out'])
             prediction = eval_dataset.unnormalize(prediction.data.cpu().numpy(), stats['mean_out'], stats['std_out'])
-        if evaluator is not None:
+        if evaluator is not None and not fused:
             evaluator.update(prediction, ground_truth=target, meta_data=meta)
         if save:
             preds.append(prediction if isinstance(prediction, np.ndarray) else
@@ -267,14 +278,18 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
           valid_dataset=None, collate_fn=None, save_debug=False, evaluate_fn=None, evaluator=None,
           sample_builder=None):
     """trainer.py:127-263.  Validation during training (``eval_during``): ``evaluate_fn(valid_dataset,
-    model, epoch)`` if given, else this module's ``evaluate`` with ``evaluator`` (the reference builds
-    its ``Evaluator`` from libs/metric, which is outside this package: pass one in).
+    model, epoch)`` if given, else this module's ``evaluate`` with ``evaluator``; with neither, an
+    ``Evaluator(training_settings.eval_metrics, cfgs, train_dataset.num_joints)`` is built like the reference's
+    (trainer.py:151-156) -- one object for the whole run, so its statistics run over every validation pass, as there.
     ``sample_builder``: a callable (``common.train_samples.TrainSampleBuilder``) that turns each loader item
     -- e.g. the list of decoded frame records ``common.train_samples.collate_frames`` yields -- into the
     ``(data, target, weights, meta)`` batch; None: the loader yields that batch itself."""
     ts = cfgs['training_settings']
     total_epochs, report_every = ts['total_epochs'], ts['report_every']
     eval_during = bool(ts.get('eval_during', False)) and valid_dataset is not None
+    if eval_during and evaluate_fn is None and evaluator is None and ts.get('eval_metrics'):
+        from .metric.criterions import Evaluator
+        evaluator = Evaluator(ts['eval_metrics'], cfgs, train_dataset.num_joints)
     if eval_during and evaluate_fn is None and evaluator is None:
         logger.warning('training_settings.eval_during is set but neither evaluate_fn nor evaluator was given: '
                        'no validation during training')

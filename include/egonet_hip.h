@@ -649,6 +649,36 @@ int egn_normalize_rows_f32(float* x, long N, int C, const float* mean, const flo
 /* dst[i][:] = src[idx[i]][:], i < n; idx int64 on the device; an index outside [0, nrows) yields zeros */
 int egn_gather_rows_f32(const float* src, long nrows, int C, const int64_t* idx, int n, float* dst, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The lifter's 3-D validation metrics on the device (csrc/lifter_metrics.hip, per-row math in csrc/metric_math.h).
+ * Replaces the host loops of libs/metric/criterions.py:223-301 (update_statistics, update_joints_3d_error style
+ * 'direct', update_rotation_error style 'euler') behind RError3D / RTError3D (:390-538) and the per-batch
+ * .cpu().numpy() + unnormalise of libs/trainer/trainer.py:474-481.  Every launch is added to egn_launch_count().
+ *
+ * layout 0 = 'R3d': rows of D = 96 float32 (32 points relative to the root); result columns [0,32) _rT point
+ *   distances, [32,35) _R |Euler 'xyz' angles| in degrees of the Kabsch rotation prediction -> target: 35 columns.
+ * layout 1 = 'R3d+T': D = 99, the root first; the same 35 columns, then [35] _T root distance and [36,39) _T_xyz
+ *   |root difference|: 39 columns.
+ * Accumulator: EGN_LIFTER_METRICS_ACC_DOUBLES float64 on the device: [0] row count, [1] layout, [8 + c] column sums,
+ *   [48 + c] maxima, [88 + c] minima (c < 40; columns past the layout's keep the initial values).  The mean of a column
+ *   is sum / count.  egn_lifter_metrics_reset sets count and sums to 0, maxima to -1 and minima to 1e16, the
+ *   reference's initial values (criterions.py:403-411); it must run once before the first update.
+ * egn_lifter_metrics_update_f32 folds n rows in: pred / gt [n][ld] float32 (ld >= D floats between rows), mean_out /
+ *   std_out [D] float32 or both NULL: x * std + mean first, in float32, product and sum rounded separately
+ *   (operations.py:50-52 on float32 arrays); everything after it is float64.  ws: egn_lifter_metrics_ws_bytes(n)
+ *   bytes (grows with n up to 2048 rows, constant beyond), contents irrelevant between calls.  rows_out [n][35 | 39]
+ *   float64 or NULL: the per-row columns.  Two launches: the block partials (plain stores, no atomics) and their fold
+ *   into acc in block order, so equal inputs give equal bits.  n == 0 is a no-op; n < 0, a NULL pred / gt / ws / acc,
+ *   a D other than 96 (layout 0) / 99 (layout 1), ld < D, one of mean_out / std_out alone or a short ws: EGN_E_BADARG.
+ *   A row whose predicted (or target) points coincide has rotation error 0 like the reference; see metric_math.h for
+ *   rank-1 rows.  Non-finite inputs reach the sums like they reach the reference's distances, never max / min. */
+#define EGN_LIFTER_METRICS_ACC_DOUBLES 128
+long egn_lifter_metrics_ws_bytes(long n);
+int egn_lifter_metrics_reset(double* acc, int layout, void* stream);
+int egn_lifter_metrics_update_f32(const float* pred, const float* gt, long n, int D, int ld, const float* mean_out,
+                                  const float* std_out, int layout, void* ws, long ws_bytes, double* acc,
+                                  double* rows_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

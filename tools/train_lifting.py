@@ -3,13 +3,19 @@
 
     python tools/train_lifting.py --label-dir <label_2> --calib-dir <calib> --train-list train.txt \
         --valid-list val.txt --out <dir> [--size 1242 375] [--epochs 300] [--batch-size 2048]
+        [--eval-every 500 --eval-start-epoch 250 --metrics RError3D]
     python tools/train_lifting.py --synthetic 2000 --out <dir>       # seeded synthetic labels, no KITTI tree
 
 Pairs are built on the device (egonet_amd.common.lifter_pairs), normalised with the train set's statistics, fed to
 ``trainer.train_cascade`` from HBM, and ``L.pth`` + ``LS.npy`` are written like train_lifting.py:51-54.  A split
 list holds one frame name per line ('000123'); the image size is taken from ``--size`` (the reference opens every
 image for it; KITTI frames differ by a few pixels -- pass records with their own sizes through the Python API
-where that matters)."""
+where that matters).
+
+``--eval-every N`` validates every N batches after ``--eval-start-epoch`` like the reference's ``eval_during``
+(configs/KITTI_train_lifting.yml: eval_every 500, eval_start_epoch 250) with the metrics of ``--metrics``
+(``RError3D``; ``RTError3D`` for ``--out-rep R3d+T``): rotation error and MPJPE of the unnormalised cuboids, computed
+on the device (egonet_amd.metric.criterions).  The run ends with one more pass over the valid pairs."""
 import argparse
 import logging
 import os
@@ -21,23 +27,30 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from egonet_amd import configs, synth, trainer          # noqa: E402
 from egonet_amd.common import lifter_pairs as lp        # noqa: E402
+from egonet_amd.metric.criterions import Evaluator      # noqa: E402
 
 
 def lifting_cfgs(args):
     """The keys of configs/KITTI_train_lifting.yml that the builder and the trainer read."""
     cfg = configs.clone(configs.w48_config())
+    metrics = args.metrics or ['RTError3D' if args.out_rep == 'R3d+T' else 'RError3D']
+    eval_during = args.eval_every > 0
     cfg['FCModel'].update(num_neurons=args.neurons, num_blocks=args.blocks, dropout=args.dropout)
     cfg.update(use_gpu=True, exp_type='2dto3d', cascade={'num_stages': 1},
+               metrics={'R3D': {'T_style': 'direct', 'R_style': 'euler', 'style': 'euler'},
+                        'RTError3D': {'T_style': 'direct', 'R_style': 'euler'}, 'JD3D': {'style': 'direct'}},
                dataset={'detect_classes': ['Car'], '3d_kpt_sample_style': 'bbox9',
                         'interpolate': {'flag': True, 'style': 'bbox12', 'coef': [0.332, 0.667]},
                         'lft_in_rep': 'coordinates2d', 'lft_out_rep': args.out_rep},
                optimizer={'optim_type': 'adam', 'lr': args.lr, 'weight_decay': 0.0, 'momentum': 0.9,
                           'milestones': [int(0.5 * args.epochs) or 1, int(0.75 * args.epochs) or 1], 'gamma': 0.1},
                training_settings={'total_epochs': args.epochs, 'batch_size': args.batch_size, 'num_threads': 4,
-                                  'shuffle': True, 'report_every': args.report_every, 'eval_during': False,
-                                  'plot_loss': False, 'lft_aug': True, 'lft_aug_times': args.aug_times},
+                                  'shuffle': True, 'report_every': args.report_every, 'eval_during': eval_during,
+                                  'eval_every': args.eval_every, 'eval_start_epoch': args.eval_start_epoch,
+                                  'eval_metrics': metrics, 'plot_loss': False, 'lft_aug': True,
+                                  'lft_aug_times': args.aug_times},
                testing_settings={'batch_size': args.batch_size, 'num_threads': 4, 'shuffle': False,
-                                 'unnormalize': False})
+                                 'unnormalize': True})
     return cfg
 
 
@@ -72,6 +85,11 @@ def main():
     ap.add_argument('--dropout', type=float, default=0.5)
     ap.add_argument('--report-every', type=int, default=100)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--eval-every', type=int, default=0, metavar='N',
+                    help='validate every N batches during training (0 = off)')
+    ap.add_argument('--eval-start-epoch', type=int, default=0, help='validate only after this epoch')
+    ap.add_argument('--metrics', nargs='+', default=None,
+                    help='metrics of the validation (default RError3D, RTError3D for --out-rep R3d+T)')
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format='%(message)s')
     logger = logging.getLogger('train_lifting')
@@ -96,7 +114,8 @@ def main():
         logger.info('valid: %d pairs' % len(valid_set))
     record = trainer.train_cascade(train_set, valid_set, cfgs, logger)
     if valid_set is not None:                               # trainer.py:395-513 over the valid pairs, from HBM too
-        trainer.evaluate(valid_set, record['cascade'][0].cuda(), _mse, cfgs, logger, None)
+        evaluator = Evaluator(cfgs['training_settings']['eval_metrics'], cfgs, train_set.num_joints)
+        trainer.evaluate(valid_set, record['cascade'][0].cuda(), _mse, cfgs, logger, evaluator)
     os.makedirs(args.out, exist_ok=True)
     torch.save(record['cascade'][0].cpu().state_dict(), os.path.join(args.out, 'L.pth'))
     np.save(os.path.join(args.out, 'LS.npy'), train_set.statistics)
