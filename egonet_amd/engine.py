@@ -23,7 +23,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, tuner
 from ._lib import Ref, NULL_REF, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_LEAKY
 
 CK = 16                 # input channels per K chunk (EGN_CK in csrc/egn_internal.h)
@@ -112,7 +112,7 @@ def pack_wino4_weight(w):
 
 
 def pack_for_kind(w, kind):
-    """The filter in the layout the kernels of a tile-configuration KIND read (egn_conv_config_kind):
+    """The filter in the layout the kernels of a tile-configuration KIND read (tuner.kind_of):
     0 direct, 1 Winograd F(2x2,3x3), 2 / 3 Winograd F(4x4,3x3) (conv_wino43_kernel / conv_wino4_kernel)."""
     if kind == 3:
         return pack_wino4_weight(w)
@@ -407,19 +407,21 @@ class Program(object):
         return (x.n, x.h, x.w, op['cin'], x.cs, op['cout'], cs_out, op['kh'], op['kw'], op['stride'],
                 op['pad'], op['res'] is not None, bool(op['out_nchw']))
 
+    @staticmethod
+    def _conv_kinds(op):
+        """The filter kinds the program feeds this conv (tuner.usable): Winograd only behind a plain epilogue."""
+        plain_act = (op['act'] & 0xf) in (ACT_NONE, ACT_RELU) and not (op['act'] & ACT_RES_AFTER)
+        return tuner.ALL_KINDS if plain_act else tuner.DIRECT
+
     def _choose_and_pack(self, rec, device):
         """Tile configuration per conv (measured table / autotune) and the filter in the layout
         that configuration's kernel stages through LDS."""
-        from . import tuner
-        L = self.lib
         for kind, op in rec.ops:
             if kind != 'conv' or op.get('w') is not None:
                 continue
             if 'cfg' not in op:
-                plain_act = (op['act'] & 0xf) in (ACT_NONE, ACT_RELU) and not (op['act'] & ACT_RES_AFTER)
-                op['cfg'] = tuner.choose(device, self._conv_key(op), allow_wino=plain_act, allow_f43=plain_act)
-            kind = L.egn_conv_config_kind(op['cfg']) if op['cfg'] > 0 else 0
-            op['w'] = rec.weight(pack_for_kind(op['w_src'], kind))
+                op['cfg'] = tuner.choose(device, self._conv_key(op), self._conv_kinds(op))
+            op['w'] = rec.weight(pack_for_kind(op['w_src'], tuner.kind_of(op['cfg'])))
 
     def _emit(self, kind, op):
         L, h = self.lib, self.handle

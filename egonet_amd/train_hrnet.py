@@ -164,7 +164,7 @@ class PackedFilters(object):
 
     def get(self, weight, dgrad, stream, wino=False):
         """``wino``: the Winograd-transformed filter instead of the direct pack -- True / 1: F(2x2,3x3) (conv_wino.hip,
-        egn_conv_config_kind 1), 3: F(4x4,3x3) in conv_wino4.hip's register-feed layout (kind 3)."""
+        tuner.kind_of 1), 3: F(4x4,3x3) in conv_wino4.hip's register-feed layout (kind 3)."""
         wino = int(wino)
         code = int(dgrad) | (4 if wino == 3 else (2 if wino else 0))
         ent = self.entries.get((id(weight), code))
@@ -303,24 +303,13 @@ class _Tape(object):
         # with all the others (PackedFilters), BatchNorm statistics come from conv_wino4s_kernel's item end, the K-split
         # configurations get the owner's ticket words (one stream: launches that share them are ordered)
         can_f43 = can_wino and f43_ok and self.o.allow_f43 in (('all',) if dgrad else ('all', 'fwd'))
-        cfg = tuner.choose(self.dev, key, allow_wino=can_wino, allow_f43=can_f43)
-        kind = self.L.egn_conv_config_kind(cfg) if cfg > 0 else 0
-        if kind == 2:
-            # conv_wino43_kernel's filter layout (kind 2) is not one the tape packs: never launch it on a direct-packed
-            # filter -- take the best configuration of the kinds the tape feeds instead
-            cfg = tuner.choose(self.dev, key, allow_wino=can_wino, allow_f43=False)
-            kind = self.L.egn_conv_config_kind(cfg) if cfg > 0 else 0
-        ntk = 0
-        if kind == 3:
-            ntk = self.L.egn_conv2d_ticket_words(n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, cfg)
-            if ntk > 0 and (ntk > self.o.tickets.numel() or (res is not None and res.data_ptr() == y.data_ptr())):
-                # (the K split writes a raw share into y before the residual is read: not for the in-place gradient add)
-                cfg = tuner.choose(self.dev, key, allow_wino=can_wino, allow_f43=False)
-                kind = self.L.egn_conv_config_kind(cfg) if cfg > 0 else 0
-                ntk = 0
+        kinds = tuner.TAPE_F43 if can_f43 else tuner.TAPE_WINO if can_wino else tuner.DIRECT
+        cfg = tuner.choose(self.dev, key, kinds, ticket_cap=self.o.tickets.numel(),
+                           inplace_res=res is not None and res.data_ptr() == y.data_ptr())
+        kind = tuner.kind_of(cfg)
         if kind == 3:
             wp = self.o.packs.get(weight, dgrad, self.st, wino=3)
-        elif can_wino and kind == 1:
+        elif kind == 1:
             wp = self.o.packs.get(weight, dgrad, self.st, wino=True)
         elif wp is None:
             wp = self._pack(weight, dgrad)
@@ -340,8 +329,8 @@ class _Tape(object):
                                                 _lib.ptr(res), _lib.ptr(y), n, h, w, cin, cs_in, cout, cs_out, kh, kw,
                                                 stride, pad, act, cfg, None if stats is None else _lib.ptr(stats[0]),
                                                 0 if stats is None else stats[1],
-                                                _lib.ptr(self.o.tickets) if ntk > 0 else None, self.o.tickets.numel(),
-                                                self.st), 'conv (F(4x4,3x3))')
+                                                _lib.ptr(self.o.tickets) if tuner.ticket_words(key, cfg) > 0 else None,
+                                                self.o.tickets.numel(), self.st), 'conv (F(4x4,3x3))')
         elif stats is not None:
             _lib.check(self.L.egn_conv2d_bnstats_f32(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(self.o.ones), _lib.ptr(shift),
                                                      _lib.ptr(y), n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride,

@@ -1,9 +1,9 @@
 """The convolution requests the product makes, and every tile configuration the tuner could answer each with.
 
 Helper module of tests/test_gpu_conv_sweep.py and tests/test_conv_sweep_cpu.py (imported, not a conftest).
-``tuner.choose`` keeps whichever configuration MEASURED fastest among all that ``egn_conv_plan_query`` accepts,
-so every accepted configuration has to compute its convolution correctly -- not only the ones the shipped table
-names.  There is no hand-written shape list: the requests come from the recordings the product makes.
+``tuner.choose`` keeps whichever of ``tuner.candidates`` MEASURED fastest, so every one of them has to compute its
+convolution correctly -- not only the ones the shipped table names.  No hand-written shape list, no rule restated:
+the requests are the product's recordings, each with what its caller told the tuner; the tuner's predicate does the rest.
 
 A request is a dict:
   key      the ``tuner.shape_key`` arguments (n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, has_res, nchw)
@@ -12,12 +12,13 @@ A request is a dict:
            egn_conv2d_ex_f32 / egn_conv2d_bnstats_f32 / egn_conv2d_f32 by configuration) or 'conv2d'
            (egn_conv2d_f32 with a tuner-chosen configuration: the 4x3 GEMM of the pedestrian data gradient, the
            lifter's row GEMMs)
-  kinds    the filter kinds (egn_conv_config_kind) the caller can feed
-  res      a residual is read; ``alias``: it is y itself (the tape's in-place data-gradient add)
+  kinds, ticket_cap, inplace_res: as the caller passed them to ``tuner.choose`` (the filter kinds it packs, the
+           ticket words it owns, whether it said that the residual is y)
+  alias    the launch reads its residual from y itself (the tape's in-place data-gradient add)
   stats    the caller asks for fused BatchNorm statistics (the tape's BatchNorm layers without a bias)
   src      where it was seen (model / batch / layer tag)
 """
-import ctypes as C
+import inspect
 import os
 
 import numpy as np
@@ -36,19 +37,12 @@ U = 2.0 ** -24      # unit roundoff of fp32
 # layers: every constant stays below it.
 C_BOUND = {0: 18.0, 1: 60.0, 3: 1500.0}
 KIND_NAMES = {0: 'direct', 1: 'F(2x2,3x3)', 3: 'F(4x4,3x3)'}
-K_SPLIT = (83, 84)
-TAPE_TICKET_WORDS = 1 << 16      # train_hrnet.TapeOwner.tickets
-
-_ALL_KINDS = frozenset((0, 1, 2, 3))
 
 
-def kind_of(cfg):
-    return _lib.lib().egn_conv_config_kind(cfg) if cfg > 0 else 0
-
-
-def _request(key, act, entry, kinds, alias=False, stats=False, src=''):
+def _request(key, act, entry, kinds, ticket_cap=None, inplace_res=False, alias=False, stats=False, src=''):
     return dict(key=tuple(int(v) if not isinstance(v, bool) else v for v in key), act=int(act), entry=entry,
-                kinds=frozenset(kinds), alias=bool(alias), stats=bool(stats), src=src)
+                kinds=frozenset(kinds), ticket_cap=ticket_cap, inplace_res=bool(inplace_res), alias=bool(alias),
+                stats=bool(stats), src=src)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -78,9 +72,8 @@ def _program_requests(rec, src):
     for kind, op in rec.ops:
         if kind != 'conv':
             continue
-        # engine.Program._choose_and_pack: Winograd kinds only for a plain epilogue
-        plain = (op['act'] & 0xf) in (engine.ACT_NONE, engine.ACT_RELU) and not (op['act'] & engine.ACT_RES_AFTER)
-        out.append(_request(engine.Program._conv_key(op), op['act'], 'program', _ALL_KINDS if plain else (0,),
+        # (what engine.Program._choose_and_pack passes to tuner.choose)
+        out.append(_request(engine.Program._conv_key(op), op['act'], 'program', engine.Program._conv_kinds(op),
                             alias=op['res'] is not None and op['res'] is op['y'], src='%s:%s' % (src, op['tag'])))
     return out
 
@@ -110,14 +103,15 @@ def inference_requests():
 # training tape (GPU): the requests of real steps
 # ---------------------------------------------------------------------------------------------------------------
 class TapeRecorder(object):
-    """Context manager: wraps ``_Tape._conv_launch`` (forward and data-gradient convolutions of the HRNet tape) and
-    ``tuner.choose`` (everything else that asks the tuner: the pedestrian 4x3 data-gradient GEMM, the lifter's row
-    GEMMs) and records each call as a request."""
+    """Context manager: records every ``tuner.choose`` call of a training step as a request.  ``_Tape._conv_launch``
+    (forward and data-gradient convolutions of the HRNet tape) is wrapped only for what the tuner never sees: the
+    activation, fused statistics, a residual, forward or data gradient.  A call from anywhere else (the pedestrian
+    4x3 data-gradient GEMM, the lifter's row GEMMs) is a plain egn_conv2d_f32."""
 
     def __init__(self, src=''):
         self.src = src
         self.reqs = []
-        self._inside = 0
+        self._launch = None
 
     def __enter__(self):
         from egonet_amd import train_hrnet as T
@@ -126,30 +120,30 @@ class TapeRecorder(object):
         orig_launch, orig_choose = self._orig
         me = self
 
-        def conv_launch(tape, x, wp, shift, y, n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, act,
-                        weight=None, dgrad=0, want_stats=False, res=None, f43_ok=True):
-            # the same outcome as the tape's own test (train_hrnet._Tape._conv_launch)
-            can_wino = weight is not None and act in (engine.ACT_NONE, engine.ACT_RELU) and tape.o.allow_wino
-            can_f43 = can_wino and f43_ok and tape.o.allow_f43 in (('all',) if dgrad else ('all', 'fwd'))
-            kinds = {0} | ({1} if can_wino else set()) | ({3} if can_f43 else set())     # (never kind 2)
-            alias = res is not None and res.data_ptr() == y.data_ptr()
-            if res is not None and not alias:
-                raise AssertionError('the tape passes a residual only as the in-place gradient add')
-            me.reqs.append(_request((n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, res is not None, False),
-                                    act, 'tape', kinds, alias=alias, stats=want_stats and tape.o.fuse_bn_stats,
-                                    src='%s:%s' % (me.src, 'dgrad' if dgrad else 'fwd')))
-            me._inside += 1
-            try:
-                return orig_launch(tape, x, wp, shift, y, n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, act,
-                                   weight=weight, dgrad=dgrad, want_stats=want_stats, res=res, f43_ok=f43_ok)
-            finally:
-                me._inside -= 1
+        def named(fn, args, kw):
+            call = inspect.signature(fn).bind(*args, **kw)
+            call.apply_defaults()
+            return call.arguments
 
-        def choose(device, args, allow_wino=False, allow_f43=False):
-            if not me._inside:
-                kinds = {0} | ({1} if allow_wino else set()) | ({2, 3} if allow_f43 else set())
-                me.reqs.append(_request(args, engine.ACT_NONE, 'conv2d', kinds, src='%s:choose' % me.src))
-            return orig_choose(device, args, allow_wino=allow_wino, allow_f43=allow_f43)
+        def conv_launch(*args, **kw):
+            c = named(orig_launch, args, kw)
+            if c['res'] is not None and c['res'].data_ptr() != c['y'].data_ptr():
+                raise AssertionError('the tape passes a residual only as the in-place gradient add')
+            me._launch = dict(act=c['act'], entry='tape', has_res=c['res'] is not None,
+                              stats=c['want_stats'] and c['self'].o.fuse_bn_stats, src='dgrad' if c['dgrad'] else 'fwd')
+            try:
+                return orig_launch(*args, **kw)
+            finally:
+                me._launch = None
+
+        def choose(*args, **kw):
+            c = named(orig_choose, args, kw)
+            key = tuple(c['key'])
+            at = me._launch or dict(act=engine.ACT_NONE, entry='conv2d', has_res=key[11], stats=False, src='choose')
+            me.reqs.append(_request(key[:11] + (at['has_res'], key[12]), at['act'], at['entry'], c['kinds'],
+                                    c['ticket_cap'], c['inplace_res'], alias=c['inplace_res'], stats=at['stats'],
+                                    src='%s:%s' % (me.src, at['src'])))
+            return orig_choose(*args, **kw)
 
         T._Tape._conv_launch = conv_launch
         tuner.choose = choose
@@ -210,46 +204,16 @@ def _tape_steps(device, g):
 # ---------------------------------------------------------------------------------------------------------------
 # candidates
 # ---------------------------------------------------------------------------------------------------------------
-def plans(key, cfg):
-    n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, has_res, nchw = key
-    out = (C.c_int * 12)()
-    return _lib.lib().egn_conv_plan_query(n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, int(nchw), cfg,
-                                          out) == 0
-
-
-def ticket_words(key, cfg):
-    n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, has_res, nchw = key
-    return _lib.lib().egn_conv2d_ticket_words(n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, cfg)
-
-
 def bnstats_rows(key, cfg):
     n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, has_res, nchw = key
     return _lib.lib().egn_conv2d_bnstats_rows(n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, cfg)
-
-
-def candidates(req):
-    """cfg 0 (the cost model) plus every selectable configuration that plans the key and whose filter kind the caller
-    feeds -- the rules of tuner.tune / tuner._pick and of the tape: the tape never feeds kind 2 and takes no K-split
-    configuration for the in-place residual or when its ticket words are too few."""
-    L = _lib.lib()
-    out = [0]
-    for cfg in range(1, L.egn_conv_num_configs() + 1):
-        kind = L.egn_conv_config_kind(cfg)
-        if kind < 0 or kind not in req['kinds'] or not plans(req['key'], cfg):
-            continue
-        if req['entry'] == 'tape':
-            ntk = ticket_words(req['key'], cfg) if kind == 3 else 0
-            if ntk > 0 and (req['alias'] or ntk > TAPE_TICKET_WORDS):
-                continue
-        out.append(cfg)
-    return out
 
 
 def pairs(reqs):
     """[(request, cfg)] without duplicate (key, act, entry, aliasing, statistics, candidate) tuples."""
     seen, out = {}, []
     for r in reqs:
-        for cfg in candidates(r):
+        for cfg in tuner.candidates(r['key'], r['kinds'], r['ticket_cap'], r['inplace_res']):
             t = (r['key'], r['act'], r['entry'], r['alias'], r['stats'], cfg)
             if t in seen:
                 seen[t]['srcs'].append(r['src'])

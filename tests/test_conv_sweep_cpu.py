@@ -106,15 +106,14 @@ def test_corpus_is_real_and_without_duplicates():
     assert any((r['key'][7], r['key'][8]) in ((4, 4), (4, 3)) for r in reqs)     # the valid head convolutions
     assert {70, 20} <= {r['key'][0] for r in reqs}
     for p in prs:                     # a candidate's filter is one the caller can feed, and the planner takes the key
-        assert p['cfg'] == 0 or (S.kind_of(p['cfg']) in p['kinds'] and S.plans(p['key'], p['cfg']))
+        assert tuner.kind_of(p['cfg']) in p['kinds'] and tuner.usable(p['key'], p['cfg'], p['kinds']), p
 
 
 _KEY = re.compile(r'n(\d+)_h(\d+)_w(\d+)_ci(\d+)\.(\d+)_co(\d+)\.(\d+)_k(\d+)x(\d+)_s(\d+)_p(\d+)_r(\d+)_o(\d+)$')
 
 
-def test_every_tabled_config_is_a_candidate():
-    """Whatever the shipped table can hand out for a shape is a candidate the sweep runs for it (tuner.tune times
-    exactly the selectable configurations the planner accepts; tuner._pick falls back to any of them)."""
+def _table():
+    """(shape_key arguments, entry) of every shape of the shipped table."""
     tab = tuner._load()
     assert tab
     for key, ent in tab.items():
@@ -123,19 +122,49 @@ def test_every_tabled_config_is_a_candidate():
         v = [int(t) for t in m.groups()]
         args = tuple(v[:11]) + (bool(v[11]), bool(v[12]))
         assert tuner.shape_key(*args) == key
-        cand = set(S.candidates(S._request(args, 0, 'program', (0, 1, 2, 3))))
+        yield args, ent
+
+
+def test_every_tabled_config_is_a_candidate():
+    """Whatever the shipped table can hand out for a shape is a candidate the sweep runs for it (tuner.tune times
+    exactly tuner.candidates; tuner._pick falls back to any of them)."""
+    for args, ent in _table():
+        cand = set(tuner.candidates(args, tuner.ALL_KINDS))
         # (ids retired since the table was measured have kind -1: tuner._pick never returns them)
-        ids = {c for c in {int(k) for k in ent.get('ms', {})} | {int(ent['cfg'])} if S.kind_of(c) >= 0}
-        assert ids and ids <= cand, (key, sorted(ids - cand))
+        ids = {c for c in {int(k) for k in ent.get('ms', {})} | {int(ent['cfg'])} if tuner.kind_of(c) >= 0}
+        assert ids and ids <= cand, (args, sorted(ids - cand))
 
 
 def test_tape_candidates_follow_the_tape_rules():
-    """No kind 2 for the tape, no K split for the in-place residual: the tape's own fall-backs
-    (train_hrnet._Tape._conv_launch)."""
-    L = _lib.lib()
+    """What train_hrnet._Tape._conv_launch tells the tuner: no kind 2, no K split for the in-place residual."""
     key = (8, 16, 16, 192, 192, 192, 192, 3, 3, 1, 1, True, False)
-    free = S.candidates(S._request(key, 0, 'tape', (0, 1, 3)))
-    alias = S.candidates(S._request(key, 0, 'tape', (0, 1, 3), alias=True))
+    free = tuner.candidates(key, tuner.TAPE_F43, 1 << 16)
+    alias = tuner.candidates(key, tuner.TAPE_F43, 1 << 16, inplace_res=True)
     assert 84 in free and 84 not in alias and set(alias) < set(free)
-    assert all(L.egn_conv_config_kind(c) != 2 for c in free if c)
-    assert set(S.candidates(S._request(key, 0, 'tape', (0,)))) == {c for c in free if S.kind_of(c) == 0}
+    assert 84 not in tuner.candidates(key, tuner.TAPE_F43, tuner.ticket_words(key, 84) - 1)     # too few ticket words
+    assert all(_lib.lib().egn_conv_config_kind(c) != 2 for c in free if c)
+    assert set(tuner.candidates(key, tuner.DIRECT, 1 << 16)) == {c for c in free if tuner.kind_of(c) == 0}
+
+
+PROFILES = {                                    # what each caller passes to tuner.choose
+    'program, plain epilogue': dict(kinds=tuner.ALL_KINDS),
+    'program, other epilogue': dict(kinds=tuner.DIRECT),
+    'tape forward': dict(kinds=tuner.TAPE_F43, ticket_cap=1 << 16),
+    'tape aliased data gradient': dict(kinds=tuner.TAPE_F43, ticket_cap=1 << 16, inplace_res=True),
+    'direct only': dict(kinds=tuner.DIRECT),
+}
+
+
+def test_choose_answers_with_a_candidate(monkeypatch):
+    """With autotuning off, what ``choose`` hands each kind of caller for each tabled shape is one of ``candidates``
+    for that caller -- the set the sweep runs."""
+    monkeypatch.setenv('EGONET_AMD_AUTOTUNE', '0')
+    for name in ('EGONET_AMD_WINO', 'EGONET_AMD_F43', 'EGONET_AMD_F43_MATCH', 'EGONET_AMD_SKIP_CFG'):
+        monkeypatch.delenv(name, raising=False)
+    picked = set()
+    for args, _ in _table():
+        for who, prof in PROFILES.items():
+            cfg = tuner.choose('cpu', args, **prof)
+            assert cfg in tuner.candidates(args, **prof), (who, args, cfg)
+            picked.add((who, tuner.kind_of(cfg)))
+    assert ('tape forward', 3) in picked and ('program, plain epilogue', 3) in picked       # (not vacuous)

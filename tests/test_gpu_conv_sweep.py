@@ -26,7 +26,7 @@ import pytest
 import torch
 
 import conv_sweep as S
-from egonet_amd import _lib, engine
+from egonet_amd import _lib, engine, tuner
 from train_checks import conv_ref64
 
 pytestmark = pytest.mark.gpu
@@ -109,7 +109,8 @@ class _Case(object):
 
 def _modes(req, cfg):
     """The launches of one (request, candidate) pair: (entry, with statistics, with ticket words)."""
-    kind = S.kind_of(cfg)
+    kind = tuner.kind_of(cfg)
+    k_split = tuner.ticket_words(req['key'], cfg) > 0
     entry = req['entry']
     if entry == 'program':
         out = [('program', False, False)]
@@ -117,12 +118,12 @@ def _modes(req, cfg):
         rows = S.bnstats_rows(req['key'], cfg) if cfg > 0 else 0
         stats = req['stats'] and cfg > 0 and rows > 0
         if kind == 3:
-            out = [('ex', stats, S.ticket_words(req['key'], cfg) > 0)]
+            out = [('ex', stats, k_split)]
         else:
             out = [('bnstats' if stats else 'conv2d', stats, False)]
     else:
         out = [('conv2d', False, False)]
-    if cfg in S.K_SPLIT and not req['alias'] and out[0] != ('conv2d', False, False):
+    if k_split and not req['alias'] and out[0] != ('conv2d', False, False):
         out.append(('conv2d', False, False))          # the three-launch form (egonet_hip.h: egn_conv_config_kind)
     return out
 
@@ -133,7 +134,7 @@ def _run_pair(case, cfg, mode, stats, tickets):
     req = case.req
     n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, has_res, nchw = req['key']
     key = req['key']
-    wp = case.packed(S.kind_of(cfg))
+    wp = case.packed(tuner.kind_of(cfg))
     stream = _lib.current_stream()
     fails = []
     ywhole, y = _guarded(case.ny, torch.float32, None if req['alias'] else float('nan'))
@@ -145,7 +146,7 @@ def _run_pair(case, cfg, mode, stats, tickets):
     pwhole = part = None
     if stats:
         pwhole, part = _guarded(rows * 2 * cout, torch.float64, float('nan'))
-    ntk = S.ticket_words(key, cfg) if tickets else 0
+    ntk = tuner.ticket_words(key, cfg) if tickets else 0
     twhole = tk = None
     if tickets:
         twhole, tk = _guarded(ntk, torch.int32, 0)
@@ -209,11 +210,11 @@ def _run_pair(case, cfg, mode, stats, tickets):
                     fails.append('pad channels not 0')
                 r = S.ratio(got, case.y64, case.A)
                 worst = float(r.max())
-                if not worst <= S.C_BOUND[S.kind_of(cfg)]:
-                    fails.append('error %.1f x 2^-24 A > %g' % (worst, S.C_BOUND[S.kind_of(cfg)]))
+                if not worst <= S.C_BOUND[tuner.kind_of(cfg)]:
+                    fails.append('error %.1f x 2^-24 A > %g' % (worst, S.C_BOUND[tuner.kind_of(cfg)]))
                 if stats:
                     tot = part.view(rows, 2, cout).sum(0)
-                    c = S.C_BOUND[S.kind_of(cfg)] * S.U
+                    c = S.C_BOUND[tuner.kind_of(cfg)] * S.U
                     if not bool(((tot[0] - case.sum64).abs() <= c * case.sumA).all()) or \
                             not bool(((tot[1] - case.sq64).abs() <= c * case.sqA).all()):
                         fails.append('fused BatchNorm statistics off')
@@ -226,7 +227,7 @@ def _run_pair(case, cfg, mode, stats, tickets):
                     # statistics, so WHICH block's row holds them follows arrival order (csrc/conv_wino4.hip, ST):
                     # the rows may differ in bits, their float64 totals must still meet the bound
                     tot = part.view(rows, 2, cout).sum(0)
-                    c = S.C_BOUND[S.kind_of(cfg)] * S.U
+                    c = S.C_BOUND[tuner.kind_of(cfg)] * S.U
                     if not bool(((tot[0] - case.sum64).abs() <= c * case.sumA).all()) or \
                             not bool(((tot[1] - case.sq64).abs() <= c * case.sqA).all()):
                         fails.append('second launch: fused BatchNorm statistics off')
@@ -264,14 +265,15 @@ def test_every_candidate_config_matches_float64(sweep_pairs):
             for mode, stats, tickets in _modes(p, cfg):
                 worst, f = _run_pair(case, cfg, mode, stats, tickets)
                 n_launch += 1
+                k_split = tuner.ticket_words(p['key'], cfg) > 0
                 name = mode + ('+stats' if stats else '') + ('+tickets' if tickets else '') + \
-                    ('(3 launches)' if cfg in S.K_SPLIT and mode == 'conv2d' else '')
+                    ('(3 launches)' if k_split and mode == 'conv2d' else '')
                 per_entry[name] = per_entry.get(name, 0) + 1
                 ent['launches'] += 1
                 if worst >= ent['worst']:
                     ent['worst'], ent['where'] = worst, '%s %s act %d %s' % (name, p['srcs'][0], p['act'],
                                                                              'alias' if p['alias'] else '')
-                k = S.kind_of(cfg)
+                k = tuner.kind_of(cfg)
                 kinds_worst[k] = max(kinds_worst.get(k, 0.0), worst)
                 for msg in f:
                     fails.append('cfg %d %s key %s act %d alias %d (%s): %s'

@@ -87,7 +87,7 @@ def test_every_table_entry_plans_for_its_shape():
         n70 += cfg == 70
         n79 += cfg == 79
         # a caller that cannot feed Winograd filters still gets a configuration it can run
-        alt = tuner._pick(ent, allow_wino=False, allow_f43=False)
+        alt = tuner._pick(ent, (n, h, w, cin, cs_in, cout, cs_out, kh, kw, s, p, r, o), tuner.DIRECT)
         assert alt == 0 or L.egn_conv_config_kind(alt) == 0, (key, alt)
     assert n70 >= 8 and n79 >= 15, (n70, n79)
 

@@ -10,7 +10,6 @@ words, the way the engine runs it.
     python tools/retune_f43.py --out gpurun_out/gfx950.json [--rounds 3]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import re
@@ -19,7 +18,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from egonet_amd import _lib, tuner  # noqa: E402
+from egonet_amd import tuner  # noqa: E402
 
 F43 = (70, 80, 82, 83, 84)
 KEY = re.compile(r'n(\d+)_h(\d+)_w(\d+)_ci(\d+)\.(\d+)_co(\d+)\.(\d+)_k(\d+)x(\d+)_s(\d+)_p(\d+)_r(\d+)_o(\d+)$')
@@ -30,11 +29,9 @@ def main():
     ap.add_argument('--out', required=True)
     ap.add_argument('--rounds', type=int, default=3)
     a = ap.parse_args()
-    L = _lib.lib()
     dev = torch.device('cuda:0')
     torch.cuda.set_device(dev)
     table = dict(tuner._load())
-    out = (C.c_int * 12)()
     changed = 0
     for key in sorted(table):
         m = KEY.match(key)
@@ -42,13 +39,12 @@ def main():
             continue
         v = [int(g) for g in m.groups()]
         args = tuple(v[:11]) + (bool(v[11]), bool(v[12]))
-        cands = [c for c in F43 if L.egn_conv_config_kind(c) == 3 and
-                 L.egn_conv_plan_query(*v[:11], v[12], c, out) == 0]
+        cands = [c for c in F43 if tuner.usable(args, c, {3})]
         if not cands:
             continue
         entry = table[key]
         ms = {int(k): float(t) for k, t in entry.get('ms', {}).items()}
-        others = {c: t for c, t in ms.items() if c not in F43 and L.egn_conv_config_kind(c) >= 0}
+        others = {c: t for c, t in ms.items() if c not in F43 and tuner.kind_of(c) >= 0}
         ref = min(others, key=others.get) if others else 0
         only = set(cands) | ({ref} if ref else set())
         best = {}
@@ -57,7 +53,7 @@ def main():
             for c, t in times.items():
                 best[c] = min(t, best.get(c, t))
         ms.update(best)
-        pick = min((c for c in ms if L.egn_conv_config_kind(c) >= 0), key=lambda c: ms[c])
+        pick = min((c for c in ms if tuner.kind_of(c) >= 0), key=lambda c: ms[c])
         if pick != entry['cfg']:
             changed += 1
         print('%-58s %2d -> %2d   %s' % (key, entry['cfg'], pick, '  '.join('%d: %.1f us' % (c, 1e3 * best[c]) for c in sorted(best))),
