@@ -61,6 +61,8 @@ SIGNATURES = {
     'egn_crop_frames_warp_normalize_u8': (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     'egn_conv2d_wgrad_ws_bytes': (C.c_long, [_i] * 11),
     'egn_conv2d_wgrad_f32': (_i, [_p, _p, _p] + [_i] * 11 + [_p, C.c_long, _p]),
+    'egn_conv2d_wgrad_num_variants': (_i, []),
+    'egn_conv2d_wgrad_plan_query': (_i, [_i] * 11 + [C.POINTER(_i)]),
     'egn_pack_matrix_f32': (_i, [_p, _i, _i, _i, _i, _p, _p]),
     'egn_transpose_f32': (_i, [_p, _i, _i, _i, _p, _i, _p]),
     'egn_colreduce_ws_bytes': (C.c_long, [_i]),

@@ -309,7 +309,9 @@ static int pick_j(int cout, int cin, int wm, int wn, bool prefer3 = false) {
   return (c3 < c4 || (prefer3 && c3 == c4)) ? 3 : 4;
 }
 
-static int wgrad_plan(WgradArgs& a, WgradVariant& v, size_t& lds) {
+// shrink (optional): how often the tile-shrinking loop halved TNB / TH / TW
+static int wgrad_plan(WgradArgs& a, WgradVariant& v, size_t& lds, int* shrink = nullptr) {
+  if (shrink) shrink[0] = shrink[1] = shrink[2] = 0;
   if (a.N <= 0 || a.H <= 0 || a.W <= 0 || a.Cin <= 0 || a.Cout <= 0 || a.KH <= 0 || a.KW <= 0 || a.stride <= 0 ||
       a.pad < 0 || a.cs_in % 4 || a.cs_out % 4 || a.cs_in < a.Cin || a.cs_out < a.Cout)
     return EGN_E_BADARG;
@@ -381,9 +383,9 @@ static int wgrad_plan(WgradArgs& a, WgradVariant& v, size_t& lds) {
     lds = ((size_t)a.TP * (CW + 4) + (size_t)a.NHP * (IW + 4)) * sizeof(float);
     const bool regs_ok = a.TP * (CW / 4) <= v.a_it * NT && a.NHP * (IW / 4) <= v.b_it * NT;
     if (lds <= budget && regs_ok) break;
-    if (a.TNB > 1 && a.TNB * a.TH * a.TW > 4) a.TNB /= 2;
-    else if (a.TH > 1 && a.TH >= a.TW) a.TH /= 2;
-    else if (a.TW > 1) a.TW /= 2;
+    if (a.TNB > 1 && a.TNB * a.TH * a.TW > 4) { a.TNB /= 2; if (shrink) ++shrink[0]; }
+    else if (a.TH > 1 && a.TH >= a.TW) { a.TH /= 2; if (shrink) ++shrink[1]; }
+    else if (a.TW > 1) { a.TW /= 2; if (shrink) ++shrink[2]; }
     else if (lds <= 150 * 1024 && regs_ok) break;
     else return EGN_E_BADARG;
   }
@@ -421,15 +423,91 @@ static int wgrad_launch(const WgradArgs& a, size_t lds, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
-extern "C" long egn_conv2d_wgrad_ws_bytes(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int KH,
-                                          int KW, int stride, int pad) {
+template <int VARIANT>
+static int wgrad_launch_wino(const WgradArgs& a, size_t, hipStream_t stream) {
+  return egn_wgrad_wino_launch(a, VARIANT, stream);
+}
+
+// Every kernel the dispatch can launch: the variant as wgrad_plan leaves it (a_it / b_it after the 128-pixel-tile
+// adjustment) and its launcher.  egn_conv2d_wgrad_plan_query reports the row index.
+struct WgradRow {
+  WgradVariant v;
+  int (*launch)(const WgradArgs&, size_t, hipStream_t);
+};
+#define EGN_WG_ROW(NTAPW, TPW, WM, WN, J, A_IT, B_IT, KS) \
+  {WgradVariant{NTAPW, TPW, WM, WN, J, A_IT, B_IT, (KS) > 1 ? (KS) : 0, 0}, wgrad_launch<NTAPW, TPW, WM, WN, J, A_IT, B_IT, KS>}
+static const WgradRow kWgradTable[] = {
+    {WgradVariant{0, 0, 0, 0, 0, 0, 0, 0, 1}, wgrad_launch_wino<1>},  // Winograd, 8 x 16 tiles of one image
+    {WgradVariant{0, 0, 0, 0, 0, 0, 0, 0, 2}, wgrad_launch_wino<2>},  // Winograd, 8 x 8 tiles of an image pair
+    EGN_WG_ROW(3, 3, 1, 1, 3, 2, 3, 4),   // 3x3, 48-wide, K-sliced, 128-pixel tiles (stride 1)
+    EGN_WG_ROW(3, 3, 1, 1, 3, 2, 5, 4),   // 3x3, 48-wide, K-sliced, 64-pixel tiles
+    EGN_WG_ROW(9, 1, 1, 1, 3, 3, 5, 1),   // <= 9 taps, 48-wide, 128-pixel tiles (stride 1)
+    EGN_WG_ROW(9, 1, 1, 1, 3, 2, 5, 1),   // <= 9 taps, 48-wide, 64-pixel tiles
+    EGN_WG_ROW(9, 1, 1, 1, 4, 2, 5, 1),   // <= 9 taps, 64-wide
+    EGN_WG_ROW(8, 2, 1, 1, 3, 2, 5, 1),   // 10..16 taps, 48-wide
+    EGN_WG_ROW(8, 2, 1, 1, 4, 2, 5, 1),   // 10..16 taps, 64-wide
+    EGN_WG_ROW(1, 1, 2, 2, 4, 4, 4, 1),   // 1x1, 128 x 128
+    EGN_WG_ROW(1, 1, 2, 1, 4, 8, 4, 1),   // 1x1, 128 x 64
+    EGN_WG_ROW(1, 1, 1, 2, 4, 4, 8, 1),   // 1x1, 64 x 128
+    EGN_WG_ROW(1, 1, 1, 1, 3, 8, 8, 1),   // 1x1, 48 x 48
+    EGN_WG_ROW(1, 1, 1, 1, 4, 8, 8, 1),   // 1x1, 64 x 64
+};
+#undef EGN_WG_ROW
+constexpr int kWgradRows = (int)(sizeof(kWgradTable) / sizeof(kWgradTable[0]));
+
+static int wgrad_row_of(const WgradVariant& v) {
+  for (int i = 0; i < kWgradRows; ++i) {
+    const WgradVariant& r = kWgradTable[i].v;
+    if (r.wino != v.wino) continue;
+    if (v.wino || (r.ntapw == v.ntapw && r.tpw == v.tpw && r.wm == v.wm && r.wn == v.wn && r.j == v.j &&
+                   r.a_it == v.a_it && r.b_it == v.b_it && r.ks == v.ks))
+      return i;
+  }
+  return -1;
+}
+
+// split lanes of the reduce kernel
+static int wgrad_reduce_lanes(int nsplit) { return nsplit > 64 ? 32 : nsplit > 4 ? 8 : 2; }
+
+static WgradArgs wgrad_args(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int KH, int KW, int stride,
+                            int pad) {
   WgradArgs a = {};
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.cs_in = cs_in; a.Cout = Cout; a.cs_out = cs_out;
   a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
+  return a;
+}
+
+extern "C" long egn_conv2d_wgrad_ws_bytes(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int KH,
+                                          int KW, int stride, int pad) {
+  WgradArgs a = wgrad_args(N, H, W, Cin, cs_in, Cout, cs_out, KH, KW, stride, pad);
   WgradVariant v;
   size_t lds;
-  if (wgrad_plan(a, v, lds) != 0) return -1;
+  if (wgrad_plan(a, v, lds) != 0 || wgrad_row_of(v) < 0) return -1;
   return (long)((size_t)a.nsplit * a.taps * a.CoP * a.CiP * sizeof(float));
+}
+
+extern "C" int egn_conv2d_wgrad_num_variants(void) { return kWgradRows; }
+
+extern "C" int egn_conv2d_wgrad_plan_query(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int KH,
+                                           int KW, int stride, int pad, int* out) {
+  if (!out) return EGN_E_BADARG;
+  WgradArgs a = wgrad_args(N, H, W, Cin, cs_in, Cout, cs_out, KH, KW, stride, pad);
+  WgradVariant v;
+  size_t lds;
+  int shrink[3];
+  const int rc = wgrad_plan(a, v, lds, shrink);
+  if (rc != 0) return rc;
+  const int row = wgrad_row_of(v);
+  if (row < 0) return EGN_E_BADARG;
+  out[0] = row; out[1] = v.wino;
+  out[2] = a.TH; out[3] = a.TW; out[4] = a.TNB;
+  out[5] = a.co_tiles; out[6] = a.ci_tiles;
+  out[7] = a.ntiles; out[8] = a.tiles_per_split; out[9] = a.nsplit;
+  out[10] = wgrad_reduce_lanes(a.nsplit);
+  out[11] = v.wino ? 1 : 0;
+  out[12] = (int)lds;
+  out[13] = shrink[0]; out[14] = shrink[1]; out[15] = shrink[2];
+  return 0;
 }
 
 extern "C" int egn_conv2d_wgrad_f32(const float* x, const float* dy, float* dw, int N, int H, int W, int Cin,
@@ -437,35 +515,33 @@ extern "C" int egn_conv2d_wgrad_f32(const float* x, const float* dy, float* dw, 
                                     long ws_bytes, void* stream) {
   if (!x || !dy || !dw || !ws) return EGN_E_BADARG;
   g_egn_direct_convs.fetch_add(1, std::memory_order_relaxed);
-  WgradArgs a = {};
+  WgradArgs a = wgrad_args(N, H, W, Cin, cs_in, Cout, cs_out, KH, KW, stride, pad);
   a.x = x; a.dy = dy; a.part = (float*)ws;
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.cs_in = cs_in; a.Cout = Cout; a.cs_out = cs_out;
-  a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
   WgradVariant v;
   size_t lds;
   int rc = wgrad_plan(a, v, lds);
   if (rc != 0) return rc;
   if ((size_t)ws_bytes < (size_t)a.nsplit * a.taps * a.CoP * a.CiP * sizeof(float)) return EGN_E_BADARG;
+  const int row = wgrad_row_of(v);
+  if (row < 0) return EGN_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
-  if (v.wino) rc = egn_wgrad_wino_launch(a, v.wino, st);
-  else if (v.ks == 4) rc = v.b_it == 3 ? wgrad_launch<3, 3, 1, 1, 3, 2, 3, 4>(a, lds, st) : wgrad_launch<3, 3, 1, 1, 3, 2, 5, 4>(a, lds, st);
-  else if (v.ntapw == 9 && v.j == 3) rc = v.a_it == 3 ? wgrad_launch<9, 1, 1, 1, 3, 3, 5>(a, lds, st) : wgrad_launch<9, 1, 1, 1, 3, 2, 5>(a, lds, st);
-  else if (v.ntapw == 9) rc = wgrad_launch<9, 1, 1, 1, 4, 2, 5>(a, lds, st);
-  else if (v.ntapw == 8) rc = v.j == 3 ? wgrad_launch<8, 2, 1, 1, 3, 2, 5>(a, lds, st) : wgrad_launch<8, 2, 1, 1, 4, 2, 5>(a, lds, st);
-  else if (v.wm == 2 && v.wn == 2) rc = wgrad_launch<1, 1, 2, 2, 4, 4, 4>(a, lds, st);
-  else if (v.wm == 2) rc = wgrad_launch<1, 1, 2, 1, 4, 8, 4>(a, lds, st);
-  else if (v.wn == 2) rc = wgrad_launch<1, 1, 1, 2, 4, 4, 8>(a, lds, st);
-  else rc = v.j == 3 ? wgrad_launch<1, 1, 1, 1, 3, 8, 8>(a, lds, st) : wgrad_launch<1, 1, 1, 1, 4, 8, 8>(a, lds, st);
+  rc = kWgradTable[row].launch(a, lds, st);
   if (rc != 0) return rc;
   const size_t total4 = (size_t)a.taps * a.CoP * (a.CiP / 4);
-  if (a.nsplit > 64)
-    hipLaunchKernelGGL(wgrad_reduce_kernel<32>, dim3((unsigned)((total4 + 31) / 32)), dim3(1024), 0, st, a.part, dw,
-                       a.nsplit, a.taps, Cout, Cin, a.CoP, a.CiP, v.wino ? a.co_tiles : 0);
-  else if (a.nsplit > 4)
-    hipLaunchKernelGGL(wgrad_reduce_kernel<8>, dim3((unsigned)((total4 + 31) / 32)), dim3(256), 0, st, a.part, dw,
-                       a.nsplit, a.taps, Cout, Cin, a.CoP, a.CiP, v.wino ? a.co_tiles : 0);
-  else
-    hipLaunchKernelGGL(wgrad_reduce_kernel<2>, dim3((unsigned)((total4 + 31) / 32)), dim3(64), 0, st, a.part, dw,
-                       a.nsplit, a.taps, Cout, Cin, a.CoP, a.CiP, v.wino ? a.co_tiles : 0);
+  const dim3 grid((unsigned)((total4 + 31) / 32));
+  const int frag_co_tiles = v.wino ? a.co_tiles : 0;
+  switch (wgrad_reduce_lanes(a.nsplit)) {
+    case 32:
+      hipLaunchKernelGGL(wgrad_reduce_kernel<32>, grid, dim3(1024), 0, st, a.part, dw, a.nsplit, a.taps, Cout, Cin,
+                         a.CoP, a.CiP, frag_co_tiles);
+      break;
+    case 8:
+      hipLaunchKernelGGL(wgrad_reduce_kernel<8>, grid, dim3(256), 0, st, a.part, dw, a.nsplit, a.taps, Cout, Cin,
+                         a.CoP, a.CiP, frag_co_tiles);
+      break;
+    default:
+      hipLaunchKernelGGL(wgrad_reduce_kernel<2>, grid, dim3(64), 0, st, a.part, dw, a.nsplit, a.taps, Cout, Cin,
+                         a.CoP, a.CiP, frag_co_tiles);
+  }
   return (int)hipGetLastError();
 }

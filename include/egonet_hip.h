@@ -280,6 +280,20 @@ int egn_conv2d_wgrad_f32(const float* x, const float* dy, float* dw, int N, int 
                          int W, int Cin, int cs_in, int Cout, int cs_out, int KH,
                          int KW, int stride, int pad, void* ws, long ws_bytes,
                          void* stream);
+/* Host-only introspection of the weight-gradient planner (no GPU needed, like
+ * egn_conv_plan_query).  egn_conv2d_wgrad_num_variants(): rows of the dispatch
+ * table = kernels egn_conv2d_wgrad_f32 can launch.  The query returns non-zero
+ * exactly where egn_conv2d_wgrad_ws_bytes() returns < 0, else fills
+ * out[0..15] = table row, form (0 direct, 1 Winograd 8 x 16 tiles, 2 Winograd
+ *              8 x 8 tiles of image pairs), TH, TW, TNB, co_tiles, ci_tiles,
+ *              ntiles, tiles_per_split, nsplit, reduce lanes (2, 8 or 32),
+ *              slab order (0 dense [tap][CoP][CiP], 1 MFMA-fragment order),
+ *              lds_bytes, and how often the tile-shrinking loop halved TNB,
+ *              TH, TW. */
+int egn_conv2d_wgrad_num_variants(void);
+int egn_conv2d_wgrad_plan_query(int N, int H, int W, int Cin, int cs_in, int Cout,
+                                int cs_out, int KH, int KW, int stride, int pad,
+                                int* out);
 /* conv weights [nchunk][1][4][CoutP][4] from a row-major matrix:
  * transpose 0: W[co][ci] = src[co*ld+ci]; 1: W[co][ci] = src[ci*ld+co] */
 int egn_pack_matrix_f32(const float* src, int ld, int cout, int cin,

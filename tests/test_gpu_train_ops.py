@@ -229,6 +229,13 @@ def _nhwc(t, cs):
     (2, 35, 66, 8, 8, 1, 2, 0),          # 1x1 stride-2 projection (head2)
     (6, 66, 66, 4, 4, 4, 1, 0),          # 4x4 valid conv of the coordinate head
     (3, 10, 10, 4, 3, (4, 3), 1, 0),     # 4x3 valid conv (Pedestrian 64x48 maps)
+    # instantiations the list above never selected (tests/wgrad_sweep.py names the table row of each):
+    (3, 48, 48, 9, 13, (1, 3), 1, 0),    # <9,1,1,1,3,3,5>: at most 9 taps, not 3x3, 48-wide
+    (3, 48, 48, 10, 14, 2, 2, 0),        # <9,1,1,1,3,2,5>: the same with stride 2 (64-pixel tiles)
+    (3, 64, 64, 6, 5, 4, 1, 0),          # <8,2,1,1,4,2,5>: 10..16 taps, 64-wide
+    (2, 48, 33, 8, 8, 1, 1, 0),          # <1,1,1,1,3,8,8>: single-wave 1x1, 48-wide (33 <- 48)
+    (2, 64, 64, 8, 8, 1, 1, 0),          # <1,1,1,1,4,8,8>: single-wave 1x1, 64-wide (64 <- 64)
+    (3, 48, 48, 64, 64, 3, 1, 1),        # Winograd, 96 tiles: the fragment-order reduce at 32 lanes
 ])
 def test_conv_wgrad(n, cin, cout, h, w, k, stride, pad):
     L = _lib.lib()
