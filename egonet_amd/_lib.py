@@ -144,7 +144,11 @@ SIGNATURES = {
     'egn_lifter_metrics_ws_bytes': (C.c_long, [C.c_long]),
     'egn_lifter_metrics_reset': (_i, [_p, _i, _p]),
     'egn_lifter_metrics_update_f32': (_i, [_p, _p, C.c_long, _i, _i, _p, _p, _i, _p, C.c_long, _p, _p, _p]),
-    'egn_program_op_info': (_i, [_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), C.c_char_p, _i]),
+    'egn_kpt_metrics_ws_bytes': (C.c_long, [_i, _i]),
+    'egn_kpt_metrics_reset': (_i, [_p, _p]),
+    'egn_kpt_metrics_update_f32': (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _d, _d, _p, C.c_long, _p, _p, _p,
+                                        _p, _p]),
+    'egn_program_op_info': (_i,[_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), C.c_char_p, _i]),
 }
 
 _LIB = None

@@ -7,6 +7,9 @@ The heat-map decode inside ``get_distance_src`` runs on the GPU (csrc/decode.hip
 wavefront per map: hard arg-max, soft-arg-max, or the numpy-style soft-arg-max); the
 rest -- 33 points per instance through a 2x3 inverse crop affine, distances, PCK
 counts -- is per-instance host arithmetic in float64 like the reference's.
+``JointDistance2DSIP`` with CUDA predictions and ``DistanceSrcMeter`` (the training loop's
+``metric_func``) run all of it on the device instead (csrc/kpt_metrics.hip: decode, rescale,
+closed-form inverse affine, distances, PCK counts, a device accumulator) and read back once.
 
 The lifter's 3-D metrics (``RError3D`` :390-449, ``RTError3D`` :451-538, ``JointDistance3D`` :343-388,
 ``RotationError3D`` :303-341, ``Evaluator`` :540-573; helpers :223-301) keep the reference's constructor arguments,
@@ -122,17 +125,246 @@ class AngleError(object):
         logger.info('Error type: {:s}\tError: {}\t'.format(self.name, self.mean))
 
 
+# ---- get_distance_src on the device -----------------------------------------------------------------------------
+_KPT_ACC_DOUBLES = 8                                # include/egonet_hip.h: count, sum of distances, pck[3]
+_KPT_MODES = {'hard': 0, 'soft': 1, 'soft-np': 2}   # the decode modes a CUDA heat-map can take
+_KPT_META = ('center', 'scale', 'rotation', 'original_joints')
+
+
+def _kpt_on_device(prediction):
+    """CUDA heat-maps, or a (maps, coordinates) tuple whose coordinates are CUDA: the device path."""
+    if type(prediction) is tuple:
+        return torch.is_tensor(prediction[1]) and prediction[1].is_cuda
+    return torch.is_tensor(prediction) and prediction.is_cuda
+
+
+class _KptMetricsDevice(object):
+    """The device side of get_distance_src (csrc/kpt_metrics.hip): one accumulator in HBM, two launches per batch,
+    nothing read back before ``read()``.  Host ``meta`` arrays travel in ONE pinned buffer and one non-blocking copy on
+    the current stream; the buffer is double-buffered and each half is guarded by an event, so a copy in flight is
+    never overwritten (the scheme of common/train_samples.py)."""
+
+    def __init__(self):
+        self._acc = self._ws = None
+        self._pinned, self._events, self._turn = [None, None], [None, None], 0
+        self.pending = False
+
+    def _staging(self, nbytes):
+        k = self._turn
+        self._turn ^= 1
+        if self._events[k] is not None:
+            self._events[k].synchronize()           # the copy that last read buffer k has finished
+        buf = self._pinned[k]
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
+            self._pinned[k] = buf
+        return k, buf
+
+    def _labels(self, meta, K, dev):
+        """center [n,2], scale [n,2], rotation [n], original_joints [n,K,3] as float64 device tensors."""
+        n = len(meta['center'])
+        fields = {}
+        for key, shape in zip(_KPT_META, ((n, 2), (n, 2), (n,), (n, K, 3))):
+            v = meta[key] if key in meta else None          # a missing 'rotation' means zeros
+            if torch.is_tensor(v) and v.is_cuda:
+                v = v.detach().to(device=dev, dtype=torch.float64)
+                if key == 'original_joints' and v.shape[-1] == 2:
+                    v = torch.cat([v, torch.ones_like(v[..., :1])], dim=-1)
+                fields[key] = v.reshape(shape).contiguous()
+                continue
+            a = np.zeros(shape) if v is None else np.asarray(v.numpy() if torch.is_tensor(v) else v, dtype=np.float64)
+            if key == 'original_joints':
+                if a.ndim != 3 or a.shape[:2] != (n, K) or a.shape[2] not in (2, 3):
+                    raise ValueError('Array shape not supported.')
+                if a.shape[2] == 2:                           # no visibility column: every joint counts
+                    a = np.concatenate([a, np.ones((n, K, 1))], axis=2)
+            fields[key] = a.reshape(shape)
+        host = [k for k in _KPT_META if isinstance(fields[k], np.ndarray)]
+        if host and n:
+            total = sum(fields[k].size for k in host)
+            turn, pinned = self._staging(total * 8)
+            view = pinned[:total * 8].view(torch.float64).numpy()
+            off = 0
+            for k in host:
+                view[off:off + fields[k].size] = fields[k].reshape(-1)
+                off += fields[k].size
+            staged = torch.empty(total, dtype=torch.float64, device=dev)
+            staged.copy_(pinned[:total * 8].view(torch.float64), non_blocking=True)
+            if self._events[turn] is None:
+                self._events[turn] = torch.cuda.Event()
+            self._events[turn].record(torch.cuda.current_stream(dev))
+            off = 0
+            for k in host:
+                size = fields[k].size
+                fields[k] = staged[off:off + size].view(fields[k].shape)
+                off += size
+        elif host:
+            for k in host:
+                fields[k] = None
+        return n, fields
+
+    def update(self, prediction, meta, image_size, arg_max, want=()):
+        """Launch only.  ``want``: any of 'src_coord', 'joints_pred', 'max_vals' -> dict of device tensors."""
+        from .. import _lib
+        if type(prediction) is tuple:
+            hm, coords, mode = None, prediction[1].detach().float().contiguous(), 0
+            if coords.dim() != 3 or coords.shape[2] != 2:
+                raise ValueError('coordinates must be [N, K, 2]')
+            N, K, H, W = coords.shape[0], coords.shape[1], 0, 0
+            dev = coords.device
+        else:
+            if arg_max not in _KPT_MODES:
+                raise NotImplementedError
+            hm, coords, mode = prediction.detach().float().contiguous(), None, _KPT_MODES[arg_max]
+            assert hm.dim() == 4, 'batch_images should be 4-ndim'
+            N, K, H, W = hm.shape
+            dev = hm.device
+        L = _lib.lib()
+        out = {}
+        with torch.cuda.device(dev):
+            n, f = self._labels(meta, K, dev)
+            if n > N:
+                raise ValueError('%d labelled instances for %d predictions' % (n, N))
+            st = _lib.current_stream(dev)
+            if self._acc is None or self._acc.device != dev:
+                if self.pending:
+                    raise RuntimeError('the accumulator holds unread updates of another device')
+                self._acc = torch.empty(_KPT_ACC_DOUBLES, dtype=torch.float64, device=dev)
+                _lib.check(L.egn_kpt_metrics_reset(_lib.ptr(self._acc), st), 'key-point metrics reset')
+            nb = L.egn_kpt_metrics_ws_bytes(N, K)
+            if nb < 0:
+                raise ValueError('key-point metrics: %d x %d maps' % (N, K))
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nb:
+                self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            if 'src_coord' in want:
+                out['src_coord'] = torch.empty(n, K, 2, dtype=torch.float64, device=dev)
+            if 'joints_pred' in want:
+                out['joints_pred'] = torch.empty(N, K, 2, dtype=torch.float32, device=dev)
+            if 'max_vals' in want and hm is not None:
+                out['max_vals'] = torch.empty(N, K, 1, dtype=torch.float32, device=dev)
+            _lib.check(L.egn_kpt_metrics_update_f32(
+                _lib.ptr(hm), _lib.ptr(coords), N, K, H, W, mode, _lib.ptr(f['center']), _lib.ptr(f['scale']),
+                _lib.ptr(f['rotation']), _lib.ptr(f['original_joints']), n, float(image_size[0]), float(image_size[1]),
+                _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._acc), _lib.ptr(out.get('src_coord')),
+                _lib.ptr(out.get('joints_pred')), _lib.ptr(out.get('max_vals')), st), 'key-point metrics update')
+        self.pending = self.pending or N > 0
+        return out
+
+    def peek(self):
+        """The accumulator's 8 float64 on the host (synchronises); zeros before the first update."""
+        if self._acc is None:
+            return np.zeros(_KPT_ACC_DOUBLES)
+        return self._acc.cpu().numpy()
+
+    def reset(self):
+        """Zero the accumulator (a launch, no synchronisation)."""
+        self.pending = False
+        if self._acc is None:
+            return
+        from .. import _lib
+        with torch.cuda.device(self._acc.device):
+            _lib.check(_lib.lib().egn_kpt_metrics_reset(_lib.ptr(self._acc), _lib.current_stream(self._acc.device)),
+                       'key-point metrics reset')
+
+    def take(self):
+        """The one read-back: the accumulator's values, and the accumulator zeroed."""
+        acc = self.peek()
+        self.reset()
+        return acc
+
+
+class DistanceSrcMeter(object):
+    """get_distance_src as the training loop's ``metric_func`` with the whole metric on the device
+    (csrc/kpt_metrics.hip).  ``meter(prediction, meta, cfgs)`` returns ``(avg, cnt, others)`` like get_distance_src
+    and synchronises like it: a drop-in replacement.  ``accumulate(prediction, meta, cfgs=None)`` only launches;
+    ``read()`` -> (running mean, count, PCK_counts) since the last ``reset()`` is the read-back.  ``trainer.train``
+    uses the three when it finds ``accumulate``.  Predictions must be CUDA: heat-maps [N,K,H,W] with ``arg_max``
+    'hard' / 'soft' / 'soft-np', or a (maps, coordinates) tuple."""
+
+    def __init__(self, cfgs=None, image_size=(256., 256.), arg_max='hard'):
+        self.image_size = image_size if cfgs is None else cfgs['heatmapModel']['input_size']
+        self.arg_max = arg_max
+        self._dev = _KptMetricsDevice()
+        self._call = _KptMetricsDevice()            # the per-batch figures of __call__: an accumulator of its own
+
+    def _size(self, cfgs):
+        return self.image_size if cfgs is None else cfgs['heatmapModel']['input_size']
+
+    def _check(self, prediction):
+        if not _kpt_on_device(prediction):
+            raise TypeError('DistanceSrcMeter needs a CUDA prediction; get_distance_src takes host arrays')
+
+    def accumulate(self, prediction, meta, cfgs=None):
+        self._check(prediction)
+        self._dev.update(prediction, meta, self._size(cfgs), self.arg_max)
+
+    def read(self):
+        acc = self._dev.peek()
+        cnt = int(acc[0])
+        return (acc[1] / cnt if cnt else 0.0), cnt, acc[2:5].copy()
+
+    def reset(self):
+        self._dev.reset()
+
+    def __call__(self, prediction, meta, cfgs=None):
+        self._check(prediction)
+        out = self._call.update(prediction, meta, self._size(cfgs), self.arg_max,
+                                want=('src_coord', 'joints_pred', 'max_vals'))
+        acc = self._call.take()
+        cnt = int(acc[0])
+        correct = acc[2:5].copy()
+        others = {'src_coord': out['src_coord'].cpu().numpy(), 'joints_pred': out['joints_pred'].cpu().numpy(),
+                  'max_vals': out['max_vals'].cpu().numpy() if 'max_vals' in out else None,
+                  'correct_cnt': correct, 'PCK_batch': correct / cnt if cnt else np.zeros(len(PCK_THRES))}
+        return (acc[1] / cnt if cnt else 0.0), cnt, others
+
+
 class JointDistance2DSIP(object):
-    """Running mean of get_distance_src + PCK over an evaluation pass."""
+    """Running mean of get_distance_src + PCK over an evaluation pass.  CUDA predictions (heat-maps, or a tuple whose
+    coordinates are CUDA) are folded into a device accumulator (csrc/kpt_metrics.hip) and read back once, at
+    ``report()`` or at the first access of ``count`` / ``mean`` / ``PCK_counts``; numpy inputs and CPU tensors take
+    the host path of get_distance_src.  Both kinds of update merge in one object.  ``device_update = False`` sends
+    CUDA predictions down the host path too (decode on the device, the rest on the host): the comparison of
+    tools/kpt_metrics_bench.py."""
+    device_update = True
 
     def __init__(self, cfgs, num_joints=None):
         self.name = 'Joint distance in the source image plane'
         self.num_joints = num_joints if num_joints is not None else cfgs['heatmapModel']['num_joints']
         self.image_size = cfgs['heatmapModel']['input_size']
         self.arg_max = cfgs['testing_settings'].get('arg_max')
-        self.count, self.mean, self.PCK_counts = 0, 0., np.zeros(len(PCK_THRES))
+        self._count, self._mean, self._pck = 0, 0., np.zeros(len(PCK_THRES))
+        self._dev = _KptMetricsDevice()
+
+    def _sync(self):
+        """The one read-back: the device accumulator is merged into the host attributes and reset."""
+        if not self._dev.pending:
+            return
+        acc = self._dev.take()
+        cnt = int(acc[0])
+        if cnt == 0:
+            return
+        self._mean = (self._mean * self._count + acc[1]) / (self._count + cnt)
+        self._count += cnt
+        self._pck = self._pck + acc[2:5]
+
+    def _synced(name):
+        def get(self):
+            self._sync()
+            return getattr(self, name)
+
+        def put(self, value):
+            self._sync()
+            setattr(self, name, value)
+        return property(get, put)
+
+    count, mean, PCK_counts = _synced('_count'), _synced('_mean'), _synced('_pck')
+    del _synced
 
     def update(self, prediction, meta_data, ground_truth=None, logger=None):
+        if self.device_update and _kpt_on_device(prediction):
+            self._dev.update(prediction, meta_data, self.image_size, self.arg_max)
+            return
         avg, cnt, others = get_distance_src(prediction, meta_data, arg_max=self.arg_max, image_size=self.image_size)
         self.mean = (self.mean * self.count + cnt * avg) / (self.count + cnt)
         self.count += cnt

@@ -281,6 +281,10 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
     model, epoch)`` if given, else this module's ``evaluate`` with ``evaluator``; with neither, an
     ``Evaluator(training_settings.eval_metrics, cfgs, train_dataset.num_joints)`` is built like the reference's
     (trainer.py:151-156) -- one object for the whole run, so its statistics run over every validation pass, as there.
+    ``metric_func``: a callable ``(prediction, meta, cfgs) -> (avg, cnt, others)`` run on every batch, or an object
+    with ``accumulate(prediction, meta, cfgs)`` / ``read() -> (running mean, count, ...)`` / ``reset()``
+    (``metric.criterions.DistanceSrcMeter``): accumulated on every batch without a read-back, reset at the start of an
+    epoch, read only on report batches.
     ``sample_builder``: a callable (``common.train_samples.TrainSampleBuilder``) that turns each loader item
     -- e.g. the list of decoded frame records ``common.train_samples.collate_frames`` yields -- into the
     ``(data, target, weights, meta)`` batch; None: the loader yields that batch itself."""
@@ -303,6 +307,8 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
     step = make_step(model, cfgs, loss_func, optim)
     is_hc = isinstance(step, HRNetTrainStep)
     dev = step.dev
+    # a metric with accumulate / read / reset (metric.criterions.DistanceSrcMeter) keeps its running sums on the device
+    metric_on_device = metric_func is not None and hasattr(metric_func, 'accumulate')
     x_buffer, y_buffer = [], []
     frozen = False
     if eval_during:
@@ -319,6 +325,8 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
             loader = get_loader(train_dataset, cfgs, 'training', collate_fn)
             total_batches, t_epoch = len(loader), time.time()
             acc = _Acc()
+            if metric_on_device:
+                metric_func.reset()
             for batch_idx, batch in enumerate(loader):
                 if sample_builder is not None:
                     batch = sample_builder(batch)
@@ -334,10 +342,14 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
                     loss = step.step(data, target)
                     prediction = None
                 # the optional metric runs on EVERY batch and accumulates, like the reference
-                # (trainer.py:200-205); its decode is on the device, its result is a host number
+                # (trainer.py:200-205); a plain callable decodes on the device and returns a host number, a meter
+                # only launches and is read back where the loss is
                 if metric_func is not None and prediction is not None:
-                    avg_acc, cnt, others = metric_func(prediction, meta, cfgs)
-                    acc.update(avg_acc, n=cnt, others=others)
+                    if metric_on_device:
+                        metric_func.accumulate(prediction, meta, cfgs)
+                    else:
+                        avg_acc, cnt, others = metric_func(prediction, meta, cfgs)
+                        acc.update(avg_acc, n=cnt, others=others)
                 if not frozen:
                     # everything built so far (model, datasets, the step's packed filters, torch's module
                     # tables: millions of objects) moves to the permanent generation: the full collections
@@ -351,7 +363,11 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
                     logger.info('Epoch: [%d][%d/%d]  loss %.6f  lr %.2e  %.1f samples/s' % (
                         epoch, batch_idx, total_batches, lv, step.lr,
                         (batch_idx + 1) * data.size(0) / max(time.time() - t_epoch, 1e-9)))
-                    if acc.count:
+                    if metric_on_device and prediction is not None:
+                        run_mean, run_cnt = metric_func.read()[:2]         # the meter's one read-back
+                        if run_cnt:
+                            logger.info('          metric %.6f (running mean over %d)' % (run_mean, run_cnt))
+                    elif acc.count:
                         logger.info('          metric %.6f (running mean over %d)' % (acc.avg, acc.count))
                     x_buffer.append(total_batches * (epoch - 1) + batch_idx)
                     y_buffer.append(lv)

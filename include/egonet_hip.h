@@ -693,6 +693,40 @@ int egn_lifter_metrics_update_f32(const float* pred, const float* gt, long n, in
                                   const float* std_out, int layout, void* ws, long ws_bytes, double* acc,
                                   double* rows_out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The key-point model's source-image metric on the device (csrc/kpt_metrics.hip, per-instance math in
+ * csrc/kpt_metric_math.h).  Replaces the host loop of libs/metric/criterions.py:68-143 (get_distance_src: rescale,
+ * inverse crop affine, get_distance :17-37, get_PCK :57-66) behind JointDistance2DSIP (:173-224) and the metric_func of
+ * the training loop (libs/trainer/trainer.py:200-205).  Every launch is added to the launch counter.
+ *
+ * Accumulator: EGN_KPT_METRICS_ACC_DOUBLES float64 on the device: [0] joints counted, [1] sum of their distances,
+ *   [2..4] joints closer than 0.1 / 0.2 / 0.3 of the instance's PCK denominator, the rest zero.  The mean distance is
+ *   [1] / [0].  The reset zeroes it; it must run once before the first update.
+ * The update folds one batch in.  Prediction, exactly one of
+ *   hm      [N][K][H][W] float32 heat-maps, decoded like the decode entry point above does with the same `mode`
+ *           (0 hard, 1 soft, 2 soft-np; bit-identical, one decoder) and multiplied by float32(img_w / W);
+ *   coords  [N][K][2] float32 in [0, 1] (the coordinate head), multiplied by float32 (img_w, img_h).
+ *   Labels of the first n <= N predictions, float64: center [n][2], scale [n][2] (x 200 px), rotation [n] in degrees
+ *   (NULL = zeros), original_joints [n][K][3] (x, y, visibility; a joint counts when visibility != 0).  The crop window
+ *   is img_w x img_h.  Per labelled instance the inverse crop affine is built in float64 from the reference's three
+ *   point pairs held in float32 (img_proc.py:26-64, inv=1); the PCK denominator is (max y - min y) / 3 over ALL K
+ *   annotated joints.
+ *   ws: the ws_bytes query's size for (N, K), contents irrelevant between calls.  Optional outputs, each may be NULL:
+ *   src_coord [n][K][2] float64 (predictions in the source image), joints_pred [N][K][2] float32 (rescaled
+ *   predictions), max_vals [N][K] float32 (raw maxima; heat-maps only, untouched with coords).
+ *   Two launches: one wavefront per map writes block partials (plain stores, no atomics), a single block folds them
+ *   into acc in block order, so equal inputs give equal bits.  N == 0 is a no-op.  Both or neither of hm / coords,
+ *   n > N, N * K or H * W past 2^31 - 1, a mode outside 0..2, a NULL label array with n > 0, a NULL ws / acc, a
+ *   non-positive window or a short ws: EGN_E_BADARG. */
+#define EGN_KPT_METRICS_ACC_DOUBLES 8
+long egn_kpt_metrics_ws_bytes(int N, int K);
+int egn_kpt_metrics_reset(double* acc, void* stream);
+int egn_kpt_metrics_update_f32(const float* hm, const float* coords, int N, int K, int H, int W, int mode,
+                               const double* center, const double* scale, const double* rotation,
+                               const double* original_joints, int n, double img_w, double img_h, void* ws,
+                               long ws_bytes, double* acc, double* src_coord, float* joints_pred, float* max_vals,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif
