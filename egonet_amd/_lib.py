@@ -57,6 +57,16 @@ SIGNATURES = {
     'egn_pose_solve_host_f64': (_i, [_p, _i, _p, _d, _d, _i, _p, _p]),
     'egn_kitti_eval_image': (_i, [C.c_char_p, C.c_char_p, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                                   C.POINTER(_d), C.POINTER(_d)]),
+    'egn_kitti_eval_dirs_host': (_i, [C.c_char_p, C.c_char_p, _i] + [C.POINTER(_i)] * 3 + [C.POINTER(_d)] * 2 +
+                                 [C.POINTER(_i)] * 2),
+    'egn_kitti_eval_dirs_dev': (_i, [C.c_char_p, C.c_char_p, _i] + [C.POINTER(_i)] * 3 + [C.POINTER(_d)] * 2 +
+                                [C.POINTER(_i)] * 2 + [_p]),
+    'egn_kitti_eval_packed_host': (_i, [_i] + [_p] * 9 + [_i] + [C.POINTER(_i)] * 2 + [C.POINTER(_d)] * 2 +
+                                   [C.POINTER(_i)] * 2),
+    'egn_kitti_eval_packed_dev': (_i, [_i] + [_p] * 9 + [_i] + [C.POINTER(_i)] * 2 + [C.POINTER(_d)] * 2 +
+                                  [C.POINTER(_i)] * 2 + [_p]),
+    'egn_kitti_overlap_host_f64': (_i, [_p, _p, C.c_long, _i, _p]),
+    'egn_kitti_overlap_dev_f64': (_i, [_p, _p, C.c_long, _i, _p, _p]),
     'egn_crop_warp_normalize_u8': (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p]),
     'egn_crop_frames_warp_normalize_u8': (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     'egn_conv2d_wgrad_ws_bytes': (C.c_long, [_i] * 11),

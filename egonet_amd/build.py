@@ -2,6 +2,8 @@
 
     python -m egonet_amd.build [--force]
 
+also builds ``tools/_build/kitti_eval_cli``, the KITTI evaluator as a stand-alone host program.
+
 hipcc cross-compiles without a GPU.  The shared object is git-ignored but
 travels with the repo snapshot to the GPU box.  The library is linked to a
 temporary name, dlopen'ed (catches undefined symbols such as a kernel stub the
@@ -66,6 +68,24 @@ def _compile_objects(hipcc, flags, probes, force, verbose):
 
 
 PROBES_OUT = os.path.join(os.path.dirname(HERE), 'tools', '_build', 'libegonet_hip_probes.so')
+CLI_SRC = os.path.join(os.path.dirname(HERE), 'tools', 'kitti_eval_cli.cpp')
+CLI_OUT = os.path.join(os.path.dirname(HERE), 'tools', '_build', 'kitti_eval_cli')
+
+
+def build_cli(force=False, verbose=True):
+    """tools/kitti_eval_cli.cpp + csrc/kitti_eval.cpp -> tools/_build/kitti_eval_cli: the KITTI evaluator as a host
+    program (no HIP, no GPU), compiled by the host C++ compiler ($CXX, default c++)."""
+    srcs = [CLI_SRC, os.path.join(CSRC, 'kitti_eval.cpp')]
+    deps = srcs + [os.path.join(CSRC, h) for h in ('kitti_eval_core.h', 'kitti_overlap_math.h', 'pose_math.h')] + \
+        [os.path.join(os.path.dirname(HERE), 'include', 'egonet_hip.h')]
+    if not force and os.path.isfile(CLI_OUT) and all(os.path.getmtime(d) <= os.path.getmtime(CLI_OUT) for d in deps):
+        return CLI_OUT
+    os.makedirs(os.path.dirname(CLI_OUT), exist_ok=True)
+    cmd = [os.environ.get('CXX', 'c++'), '-O2', '-std=c++17', '-o', CLI_OUT] + srcs
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return CLI_OUT
 
 
 def build(force=False, verbose=True, probes=False):
@@ -104,3 +124,5 @@ def build(force=False, verbose=True, probes=False):
 
 if __name__ == '__main__':
     print(build(force='--force' in sys.argv, probes='--probes' in sys.argv))
+    if '--probes' not in sys.argv:
+        print(build_cli(force='--force' in sys.argv))

@@ -1,24 +1,27 @@
-// kitti_eval.cpp -- KITTI 2D-detection AP and Average Orientation Similarity
-// (AOS), the IMAGE-metric path of the reference's offline evaluator, without
-// Boost.  Host code.
+// kitti_eval.cpp -- the KITTI object evaluator on the host: 2D AP and Average Orientation Similarity (IMAGE),
+// bird's-eye-view AP (GROUND) and 3D AP (BOX3D), all three blocks of the reference's offline evaluator, without Boost
+// (SURVEY section 8f rank 4).  Host code: it runs without a GPU and is also what tools/kitti_eval_cli.cpp links; the
+// device path (kitti_eval.hip) shares the parsing, the thresholds and the curves defined here.
 //
 // Reference: tools/kitti-eval/evaluate_object_3d_offline.cpp
-//   loadDetections :131-176, loadGroundtruth :178-202, imageBoxOverlap :227-265,
-//   getThresholds :346-379, cleanData :381-454, computeStatistics :456-615,
-//   eval_class :622-706, 11-point summary in saveAndPlotPlots :720-724,
-//   eval :791-850 (the IMAGE block; the ground / 3D blocks need Boost.Geometry
-//   and are out of scope).
-// The reference file cannot be compiled in this image (Boost headers absent), so
-// this restatement is checked against an independent Python restatement
-// (oracle/kitti_eval_oracle.py) and hand-computed cases: PARITY UNPINNED against
-// the reference binary.
+//   loadDetections :131-176, loadGroundtruth :178-202, imageBoxOverlap :227-265, toPolygon / groundBoxOverlap /
+//   box3DOverlap :268-344 (kitti_overlap_math.h: the one Boost operation, the intersection of two rotated rectangles,
+//   is a four-side clip), getThresholds :346-379, cleanData :381-454, computeStatistics :456-615 (kitti_eval_core.h),
+//   eval_class :622-706, 11-point summary in saveAndPlotPlots :720-724, eval :795-915.
+// The reference file cannot be compiled here (Boost headers absent): PARITY UNPINNED against the reference binary.
+// What pins this file instead: an independent Python restatement (oracle/kitti_eval_oracle.py for IMAGE,
+// tests/kitti_eval3d_ref.py for GROUND / BOX3D, whose overlaps come from scipy's half-plane intersection), closed-form
+// overlaps and hand-computed cases.
 //
-// Semantics kept on purpose: the class-overlap table as overwritten in the
-// reference (0.7 / 0.5 / 0.5 for car / pedestrian / cyclist, :54), detection
-// heights truncated to int (:441), "Van" / "Person_sitting" neighbours ignored,
-// DontCare areas absorb unassigned detections (criterion = detection area),
-// recall sampled at 41 points with the left/right-closest rule, precision and
-// AOS made monotone from the right.
+// Where the reference recomputes an overlap inside the matching loops (recall pass + up to 41 threshold passes, times
+// 3 levels, per metric), the overlaps of all (detection, ground truth) pairs of a frame are computed once here.
+//
+// Semantics kept on purpose: the class-overlap table as overwritten in the reference (0.7 / 0.5 / 0.5 for car /
+// pedestrian / cyclist in every metric, :55), difficulty by the 2D box height in every metric, detection heights
+// truncated to int (:444), "Van" / "Person_sitting" neighbours ignored, DontCare areas absorb unassigned detections by
+// the metric's own overlap over the detection (:582), AOS only for IMAGE (:877), a class scored in GROUND / BOX3D only
+// when one of its detections has t1 / t2 != -1000 (:164-167), recall sampled at 41 points with the left/right-closest
+// rule, precision and AOS made monotone from the right.
 #include <dirent.h>
 #include <math.h>
 #include <stdint.h>
@@ -31,49 +34,14 @@
 #include <string>
 #include <vector>
 
+#include "../../include/egonet_hip.h"
+#include "kitti_eval_core.h"
+
+namespace egn_kitti {
+
 namespace {
 
-constexpr int kClasses = 3, kLevels = 3, kSamples = 41;
-const char* const kClassName[kClasses] = {"car", "pedestrian", "cyclist"};
-const int kMinHeight[kLevels] = {40, 25, 25};
-const int kMaxOcclusion[kLevels] = {0, 1, 2};
-const double kMaxTruncation[kLevels] = {0.15, 0.3, 0.5};
-const double kMinOverlap[kClasses] = {0.7, 0.5, 0.5};  // MIN_OVERLAP[IMAGE][class]
-
-struct Box {
-  std::string type;
-  double x1, y1, x2, y2, alpha;
-};
-struct Truth {
-  Box box;
-  double truncation;
-  int occlusion;
-};
-struct Det {
-  Box box;
-  double score;
-};
-struct Frame {
-  std::vector<Truth> gt;
-  std::vector<Det> det;
-};
-struct Counts {
-  std::vector<double> tp_scores;
-  double similarity = 0;
-  int tp = 0, fp = 0, fn = 0;
-};
-
-bool same(const std::string& a, const char* b) { return strcasecmp(a.c_str(), b) == 0; }
-
-// mode -1: intersection over union; 0: over the first box's area
-double overlap(const Box& a, const Box& b, int mode) {
-  const double w = std::min(a.x2, b.x2) - std::max(a.x1, b.x1);
-  const double h = std::min(a.y2, b.y2) - std::max(a.y1, b.y1);
-  if (w <= 0 || h <= 0) return 0;
-  const double inter = w * h;
-  const double area_a = (a.x2 - a.x1) * (a.y2 - a.y1), area_b = (b.x2 - b.x1) * (b.y2 - b.y1);
-  return mode == -1 ? inter / (area_a + area_b - inter) : inter / area_a;
-}
+constexpr int kSamples = EGN_KITTI_SAMPLES;
 
 bool read_lines(const std::string& path, std::vector<std::vector<std::string>>& rows) {
   FILE* f = fopen(path.c_str(), "r");
@@ -88,102 +56,153 @@ bool read_lines(const std::string& path, std::vector<std::vector<std::string>>& 
   return true;
 }
 
-// gt flags: 0 counted, 1 ignored (neighbour class / too hard), -1 other class
-// det flags: 0 evaluated, 1 too small, -1 other class
-void classify(int cls, int level, const Frame& fr, std::vector<int>& gt_flag, std::vector<int>& det_flag,
-              std::vector<Box>& dontcare, int& n_gt) {
-  for (const Truth& g : fr.gt) {
-    int valid = -1;
-    if (same(g.box.type, kClassName[cls])) valid = 1;
-    else if (cls == 1 && same(g.box.type, "Person_sitting")) valid = 0;
-    else if (cls == 0 && same(g.box.type, "Van")) valid = 0;
-    const bool hard = g.occlusion > kMaxOcclusion[level] || g.truncation > kMaxTruncation[level] ||
-                      (g.box.y2 - g.box.y1) < kMinHeight[level];
-    if (valid == 1 && !hard) {
-      gt_flag.push_back(0);
-      ++n_gt;
-    } else if (valid == 0 || (hard && valid == 1)) {
-      gt_flag.push_back(1);
-    } else {
-      gt_flag.push_back(-1);
-    }
-    if (same(g.box.type, "DontCare")) dontcare.push_back(g.box);
-  }
-  for (const Det& d : fr.det) {
-    const int height = (int)fabs(d.box.y1 - d.box.y2);  // truncated to an integer, as the reference does
-    if (height < kMinHeight[level]) det_flag.push_back(1);
-    else det_flag.push_back(same(d.box.type, kClassName[cls]) ? 0 : -1);
-  }
+// fields 3 (alpha), 4-7 (2D box), 8-14 (h w l t1 t2 t3 ry) of a row -> EGN_KITTI_BOX doubles
+void push_box(const std::vector<std::string>& r, std::vector<double>& out) {
+  for (int k = 4; k < 8; ++k) out.push_back(atof(r[k].c_str()));
+  out.push_back(atof(r[3].c_str()));
+  for (int k = 8; k < 15; ++k) out.push_back(atof(r[k].c_str()));
 }
 
-Counts match(int cls, const Frame& fr, const std::vector<Box>& dontcare, const std::vector<int>& gt_flag,
-             const std::vector<int>& det_flag, bool with_fp, bool with_aos, double thresh) {
-  Counts out;
-  const double kNone = -10000000;
-  const size_t nd = fr.det.size();
-  std::vector<char> taken(nd, 0), below(nd, 0);
-  std::vector<double> delta;
-  if (with_fp)
-    for (size_t j = 0; j < nd; ++j) below[j] = fr.det[j].score < thresh;
-  for (size_t i = 0; i < fr.gt.size(); ++i) {
-    if (gt_flag[i] == -1) continue;
-    int pick = -1;
-    double valid = kNone, best = 0;
-    bool picked_small = false;
-    for (size_t j = 0; j < nd; ++j) {
-      if (det_flag[j] == -1 || taken[j] || below[j]) continue;
-      const double o = overlap(fr.det[j].box, fr.gt[i].box, -1);
-      if (!(o > kMinOverlap[cls])) continue;
-      if (!with_fp) {                       // recall pass: the most confident candidate
-        if (fr.det[j].score > valid) {
-          pick = (int)j;
-          valid = fr.det[j].score;
-        }
-      } else if ((o > best || picked_small) && det_flag[j] == 0) {  // pr pass: the best-overlapping one
-        best = o;
-        pick = (int)j;
-        valid = 1;
-        picked_small = false;
-      } else if (valid == kNone && det_flag[j] == 1) {
-        pick = (int)j;
-        valid = 1;
-        picked_small = true;
-      }
+}  // namespace
+
+int type_code(const char* name) {
+  static const char* const kNames[] = {"car", "pedestrian", "cyclist", "van", "person_sitting", "dontcare"};
+  for (int k = 0; k < 6; ++k)
+    if (strcasecmp(name, kNames[k]) == 0) return k;
+  return EGN_KT_OTHER;
+}
+
+void Packed::end_frame() {
+  const long long ng = (long long)gt_type.size() - gt_off.back(), nd = (long long)det_type.size() - det_off.back();
+  gt_off.push_back((int)gt_type.size());
+  det_off.push_back((int)det_type.size());
+  pair_off.push_back(pair_off.back() + ng * nd);
+  word_off.push_back(word_off.back() + (int)((nd + 31) / 32));
+}
+
+EgnKittiView Packed::view(const double* ov, const double* sim) const {
+  EgnKittiView v;
+  v.nf = nf();
+  v.gt_off = gt_off.data();
+  v.det_off = det_off.data();
+  v.pair_off = pair_off.data();
+  v.word_off = word_off.data();
+  v.gt_box = gt_box.data();
+  v.gt_trunc = gt_trunc.data();
+  v.gt_type = gt_type.data();
+  v.gt_occ = gt_occ.data();
+  v.det_box = det_box.data();
+  v.det_score = det_score.data();
+  v.det_type = det_type.data();
+  v.ov = ov;
+  v.sim = sim;
+  v.pairs = pair_off.back();
+  return v;
+}
+
+int load_dirs(const char* gt_dir, const char* result_dir, Packed& p) {
+  const std::string data_dir = std::string(result_dir) + "/data/";
+  std::vector<int> ids;
+  if (DIR* d = opendir(data_dir.c_str())) {
+    while (dirent* e = readdir(d)) {
+      const std::string name = e->d_name;
+      if (name.size() < 10) continue;
+      ids.push_back(atoi(name.substr(name.size() - 10).c_str()));
     }
-    if (valid == kNone) {
-      if (gt_flag[i] == 0) ++out.fn;
-    } else if (gt_flag[i] == 1 || det_flag[pick] == 1) {
-      taken[pick] = 1;                      // matched, but one side is ignored: neither TP nor FP
-    } else {
-      ++out.tp;
-      out.tp_scores.push_back(fr.det[pick].score);
-      if (with_aos) delta.push_back(fr.gt[i].box.alpha - fr.det[pick].box.alpha);
-      taken[pick] = 1;
+    closedir(d);
+  }
+  if (ids.empty()) return -3;
+  std::sort(ids.begin(), ids.end());
+  for (size_t f = 0; f < ids.size(); ++f) {
+    char name[32];
+    snprintf(name, sizeof name, "%06d.txt", ids[f]);
+    std::vector<std::vector<std::string>> rows;
+    if (!read_lines(std::string(gt_dir) + "/" + name, rows)) return -2;
+    for (const auto& r : rows) {
+      if (r.size() < 15) continue;
+      push_box(r, p.gt_box);
+      p.gt_type.push_back(type_code(r[0].c_str()));
+      p.gt_trunc.push_back(atof(r[1].c_str()));
+      p.gt_occ.push_back(atoi(r[2].c_str()));
+    }
+    rows.clear();
+    if (!read_lines(data_dir + name, rows)) return -3;
+    for (const auto& r : rows) {
+      if (r.size() < 16) continue;
+      push_box(r, p.det_box);
+      p.det_type.push_back(type_code(r[0].c_str()));
+      p.det_score.push_back(atof(r[15].c_str()));
+    }
+    if (p.gt_type.size() > 0x7ffffff || p.det_type.size() > 0x7ffffff) return -1;
+    p.end_frame();
+  }
+  return 0;
+}
+
+int from_arrays(int nf, const int* gt_off, const int* det_off, const double* gt_box, const int* gt_type,
+                const double* gt_trunc, const int* gt_occ, const double* det_box, const int* det_type,
+                const double* det_score, Packed& p) {
+  if (nf < 0 || !gt_off || !det_off || gt_off[0] != 0 || det_off[0] != 0) return -1;
+  for (int f = 0; f < nf; ++f)
+    if (gt_off[f + 1] < gt_off[f] || det_off[f + 1] < det_off[f]) return -1;
+  const int ng = gt_off[nf], nd = det_off[nf];
+  if (ng > 0x7ffffff || nd > 0x7ffffff) return -1;
+  if (ng > 0 && (!gt_box || !gt_type || !gt_trunc || !gt_occ)) return -1;
+  if (nd > 0 && (!det_box || !det_type || !det_score)) return -1;
+  for (int i = 0; i < ng; ++i)
+    if (gt_type[i] < 0 || gt_type[i] > EGN_KT_OTHER) return -1;
+  for (int j = 0; j < nd; ++j)
+    if (det_type[j] < 0 || det_type[j] > EGN_KT_OTHER) return -1;
+  p.gt_box.assign(gt_box, gt_box + (size_t)ng * EGN_KITTI_BOX);
+  p.gt_type.assign(gt_type, gt_type + ng);
+  p.gt_trunc.assign(gt_trunc, gt_trunc + ng);
+  p.gt_occ.assign(gt_occ, gt_occ + ng);
+  p.det_box.assign(det_box, det_box + (size_t)nd * EGN_KITTI_BOX);
+  p.det_type.assign(det_type, det_type + nd);
+  p.det_score.assign(det_score, det_score + nd);
+  for (int f = 0; f < nf; ++f) {
+    const long long g = gt_off[f + 1] - gt_off[f], d = det_off[f + 1] - det_off[f];
+    p.gt_off.push_back(gt_off[f + 1]);
+    p.det_off.push_back(det_off[f + 1]);
+    p.pair_off.push_back(p.pair_off.back() + g * d);
+    p.word_off.push_back(p.word_off.back() + (int)((d + 31) / 32));
+  }
+  if (p.pair_off.back() > (1LL << 36)) return -1;
+  return 0;
+}
+
+void scored(const Packed& p, int metrics, Result& r) {
+  r.n_frames = p.nf();
+  r.aos_valid = 1;
+  for (int k = 0; k < 9; ++k) r.evaluated[k] = 0;
+  for (size_t j = 0; j < p.det_type.size(); ++j) {
+    const double* b = p.det_box.data() + j * EGN_KITTI_BOX;
+    if (b[EGN_KB_ALPHA] == -10) r.aos_valid = 0;
+    const int c = p.det_type[j];
+    if (c > EGN_KT_CYCLIST) continue;
+    if (b[EGN_KB_X1] >= 0) r.evaluated[c] = 1;
+    if (b[EGN_KB_T1] != -1000) r.evaluated[3 + c] = 1;
+    if (b[EGN_KB_T2] != -1000) r.evaluated[6 + c] = 1;
+  }
+  for (int m = 0; m < 3; ++m)
+    if (!(metrics >> m & 1))
+      for (int c = 0; c < 3; ++c) r.evaluated[m * 3 + c] = 0;
+}
+
+std::vector<double> similarity_table(const Packed& p) {
+  std::vector<double> sim((size_t)p.pair_off.back(), 0.0);
+  for (int f = 0; f < p.nf(); ++f) {
+    const int g0 = p.gt_off[f], ng = p.gt_off[f + 1] - g0, d0 = p.det_off[f], nd = p.det_off[f + 1] - d0;
+    double* s = sim.data() + p.pair_off[f];
+    for (int i = 0; i < ng; ++i) {
+      if (p.gt_type[g0 + i] > EGN_KT_CYCLIST) continue;          // only a pair of one class can be a true positive
+      const double ag = p.gt_box[(size_t)(g0 + i) * EGN_KITTI_BOX + EGN_KB_ALPHA];
+      for (int j = 0; j < nd; ++j)
+        if (p.det_type[d0 + j] == p.gt_type[g0 + i])
+          s[(size_t)i * nd + j] = (1.0 + cos(ag - p.det_box[(size_t)(d0 + j) * EGN_KITTI_BOX + EGN_KB_ALPHA])) / 2.0;
     }
   }
-  if (!with_fp) return out;
-  for (size_t j = 0; j < nd; ++j)
-    if (!(taken[j] || det_flag[j] != 0 || below[j])) ++out.fp;
-  int stuff = 0;
-  for (const Box& dc : dontcare)
-    for (size_t j = 0; j < nd; ++j) {
-      if (taken[j] || det_flag[j] != 0 || below[j]) continue;
-      if (overlap(fr.det[j].box, dc, 0) > kMinOverlap[cls]) {
-        taken[j] = 1;
-        ++stuff;
-      }
-    }
-  out.fp -= stuff;
-  if (with_aos) {
-    if (out.tp > 0 || out.fp > 0) {
-      double s = 0.0;                       // FPs contribute 0
-      for (double d : delta) s += (1.0 + cos(d)) / 2.0;
-      out.similarity = s;
-    } else {
-      out.similarity = -1;
-    }
-  }
-  return out;
+  return sim;
 }
 
 std::vector<double> recall_thresholds(std::vector<double> v, double n_gt) {
@@ -200,39 +219,107 @@ std::vector<double> recall_thresholds(std::vector<double> v, double n_gt) {
   return t;
 }
 
-void evaluate(int cls, int level, const std::vector<Frame>& frames, bool with_aos, double* precision, double* aos) {
-  const size_t nf = frames.size();
-  std::vector<std::vector<int>> gt_flag(nf), det_flag(nf);
-  std::vector<std::vector<Box>> dontcare(nf);
-  std::vector<double> scores;
-  int n_gt = 0;
-  for (size_t f = 0; f < nf; ++f) {
-    classify(cls, level, frames[f], gt_flag[f], det_flag[f], dontcare[f], n_gt);
-    const Counts c = match(cls, frames[f], dontcare[f], gt_flag[f], det_flag[f], false, false, 0);
-    scores.insert(scores.end(), c.tp_scores.begin(), c.tp_scores.end());
+void curves(const int* counts, const double* similarity, int n_thr, bool with_aos, double* precision, double* aos) {
+  for (int i = 0; i < kSamples; ++i) {
+    precision[i] = 0;
+    if (aos) aos[i] = 0;
   }
-  const std::vector<double> thr = recall_thresholds(scores, n_gt);
-  std::vector<Counts> pr(thr.size());
-  for (size_t f = 0; f < nf; ++f)
-    for (size_t t = 0; t < thr.size(); ++t) {
-      const Counts c = match(cls, frames[f], dontcare[f], gt_flag[f], det_flag[f], true, with_aos, thr[t]);
-      pr[t].tp += c.tp;
-      pr[t].fp += c.fp;
-      pr[t].fn += c.fn;
-      if (c.similarity != -1) pr[t].similarity += c.similarity;
-    }
-  for (int i = 0; i < kSamples; ++i) precision[i] = aos[i] = 0;
-  for (size_t i = 0; i < thr.size() && i < (size_t)kSamples; ++i) {
-    precision[i] = pr[i].tp / (double)(pr[i].tp + pr[i].fp);
-    if (with_aos) aos[i] = pr[i].similarity / (double)(pr[i].tp + pr[i].fp);
+  for (int i = 0; i < n_thr && i < kSamples; ++i) {
+    const int tp = counts[3 * i], fp = counts[3 * i + 1];
+    precision[i] = tp / (double)(tp + fp);
+    if (with_aos) aos[i] = similarity[i] / (double)(tp + fp);
   }
-  for (size_t i = 0; i < thr.size() && i < (size_t)kSamples; ++i) {  // monotone from the right, over all 41 samples
+  for (int i = 0; i < n_thr && i < kSamples; ++i) {   // monotone from the right, over all 41 samples
     precision[i] = *std::max_element(precision + i, precision + kSamples);
     if (with_aos) aos[i] = *std::max_element(aos + i, aos + kSamples);
   }
 }
 
+namespace {
+
+// the three overlap tables of every frame, once
+std::vector<double> overlap_tables(const Packed& p) {
+  const size_t pairs = (size_t)p.pair_off.back();
+  std::vector<double> ov(3 * pairs);
+  for (int f = 0; f < p.nf(); ++f) {
+    const int g0 = p.gt_off[f], ng = p.gt_off[f + 1] - g0, d0 = p.det_off[f], nd = p.det_off[f + 1] - d0;
+    for (int i = 0; i < ng; ++i) {
+      const double* g = p.gt_box.data() + (size_t)(g0 + i) * EGN_KITTI_BOX;
+      const int criterion = p.gt_type[g0 + i] == EGN_KT_DONTCARE ? 0 : -1;
+      for (int j = 0; j < nd; ++j) {
+        double o[4];
+        egn_kitti_overlaps(p.det_box.data() + (size_t)(d0 + j) * EGN_KITTI_BOX, g, criterion, o);
+        const size_t at = (size_t)p.pair_off[f] + (size_t)i * nd + j;
+        for (int m = 0; m < 3; ++m) ov[m * pairs + at] = o[m];
+      }
+    }
+  }
+  return ov;
+}
+
+// eval_class for one (metric, class, level)
+void evaluate(const EgnKittiView& v, int metric, int cls, int level, bool with_aos, Result& r) {
+  const int combo = (metric * 3 + cls) * 3 + level;
+  int max_words = 1, max_gt = 1;
+  for (int f = 0; f < v.nf; ++f) {
+    max_words = std::max(max_words, v.word_off[f + 1] - v.word_off[f]);
+    max_gt = std::max(max_gt, v.gt_off[f + 1] - v.gt_off[f]);
+  }
+  std::vector<unsigned> taken(max_words);
+  std::vector<double> frame_scores(max_gt), scores;
+  EgnKittiCounts c;
+  int n_gt = 0;
+  for (int f = 0; f < v.nf; ++f) {
+    egn_kitti_match<false>(v, f, cls, level, metric, false, 0.0, taken.data(), 1, frame_scores.data(), c);
+    n_gt += c.n_gt;
+    scores.insert(scores.end(), frame_scores.begin(), frame_scores.begin() + c.tp);
+  }
+  std::vector<double> thr = recall_thresholds(scores, n_gt);
+  if (thr.size() > (size_t)kSamples) thr.resize(kSamples);
+  const int nt = (int)thr.size();
+  int* counts = r.counts + combo * kSamples * 3;
+  double similarity[kSamples] = {0};
+  for (int f = 0; f < v.nf; ++f)
+    for (int t = 0; t < nt; ++t) {
+      egn_kitti_match<true>(v, f, cls, level, metric, with_aos, thr[t], taken.data(), 1, nullptr, c);
+      counts[3 * t] += c.tp;
+      counts[3 * t + 1] += c.fp;
+      counts[3 * t + 2] += c.fn;
+      if (c.similarity != -1) similarity[t] += c.similarity;
+    }
+  r.n_thresholds[combo] = nt;
+  r.n_gt[combo] = n_gt;
+  curves(counts, similarity, nt, with_aos, r.precision + combo * kSamples,
+         metric == 0 ? r.aos + (cls * 3 + level) * kSamples : nullptr);
+}
+
 }  // namespace
+
+void evaluate_host(const Packed& p, int metrics, Result& r) {
+  scored(p, metrics, r);
+  const std::vector<double> ov = overlap_tables(p);
+  const bool with_aos = r.aos_valid && (r.evaluated[0] || r.evaluated[1] || r.evaluated[2]);
+  std::vector<double> sim;
+  if (with_aos) sim = similarity_table(p);
+  const EgnKittiView v = p.view(ov.data(), with_aos ? sim.data() : nullptr);
+  for (int m = 0; m < 3; ++m)
+    for (int c = 0; c < 3; ++c)
+      for (int l = 0; l < 3; ++l)
+        if (r.evaluated[m * 3 + c]) evaluate(v, m, c, l, m == 0 && with_aos, r);
+}
+
+void copy_out(const Result& r, int* n_frames, int* evaluated, int* aos_valid, double* precision, double* aos,
+              int* counts, int* n_thresholds) {
+  if (n_frames) *n_frames = r.n_frames;
+  *aos_valid = r.aos_valid;
+  memcpy(evaluated, r.evaluated, sizeof r.evaluated);
+  memcpy(precision, r.precision, sizeof r.precision);
+  memcpy(aos, r.aos, sizeof r.aos);
+  if (counts) memcpy(counts, r.counts, sizeof r.counts);
+  if (n_thresholds) memcpy(n_thresholds, r.n_thresholds, sizeof r.n_thresholds);
+}
+
+}  // namespace egn_kitti
 
 // precision / aos: [3 classes][3 difficulty levels][41 recall samples] doubles.
 // evaluated[c] = 1 when class c has at least one detection (with x1 >= 0);
@@ -242,58 +329,50 @@ void evaluate(int cls, int level, const std::vector<Frame>& frames, bool with_ao
 extern "C" int egn_kitti_eval_image(const char* gt_dir, const char* result_dir, int* n_frames, int* evaluated,
                                     int* aos_valid, double* precision, double* aos) {
   if (!gt_dir || !result_dir || !evaluated || !aos_valid || !precision || !aos) return -1;
-  const std::string data_dir = std::string(result_dir) + "/data/";
-  std::vector<int> ids;
-  if (DIR* d = opendir(data_dir.c_str())) {
-    while (dirent* e = readdir(d)) {
-      const std::string name = e->d_name;
-      if (name.size() < 10) continue;
-      ids.push_back(atoi(name.substr(name.size() - 10).c_str()));
-    }
-    closedir(d);
-  }
-  if (ids.empty()) return -3;
-  std::sort(ids.begin(), ids.end());
-  std::vector<Frame> frames(ids.size());
-  bool with_aos = true;
-  for (int c = 0; c < kClasses; ++c) evaluated[c] = 0;
-  for (size_t f = 0; f < ids.size(); ++f) {
-    char name[32];
-    snprintf(name, sizeof name, "%06d.txt", ids[f]);
-    std::vector<std::vector<std::string>> rows;
-    if (!read_lines(std::string(gt_dir) + "/" + name, rows)) return -2;
-    for (const auto& r : rows) {
-      if (r.size() < 15) continue;
-      Truth g;
-      g.box = Box{r[0], atof(r[4].c_str()), atof(r[5].c_str()), atof(r[6].c_str()), atof(r[7].c_str()), atof(r[3].c_str())};
-      g.truncation = atof(r[1].c_str());
-      g.occlusion = atoi(r[2].c_str());
-      frames[f].gt.push_back(g);
-    }
-    rows.clear();
-    if (!read_lines(data_dir + name, rows)) return -3;
-    for (const auto& r : rows) {
-      if (r.size() < 16) continue;
-      Det d;
-      d.box = Box{r[0], atof(r[4].c_str()), atof(r[5].c_str()), atof(r[6].c_str()), atof(r[7].c_str()), atof(r[3].c_str())};
-      d.score = atof(r[15].c_str());
-      frames[f].det.push_back(d);
-      if (d.box.alpha == -10) with_aos = false;
-      for (int c = 0; c < kClasses; ++c)
-        if (same(d.box.type, kClassName[c])) {
-          if (d.box.x1 >= 0) evaluated[c] = 1;
-          break;
-        }
-    }
-  }
-  if (n_frames) *n_frames = (int)frames.size();
-  *aos_valid = with_aos ? 1 : 0;
-  for (int c = 0; c < kClasses; ++c)
-    for (int l = 0; l < kLevels; ++l) {
-      double* p = precision + (c * kLevels + l) * kSamples;
-      double* a = aos + (c * kLevels + l) * kSamples;
-      for (int i = 0; i < kSamples; ++i) p[i] = a[i] = 0;
-      if (evaluated[c]) evaluate(c, l, frames, with_aos, p, a);
-    }
+  egn_kitti::Packed p;
+  if (const int rc = egn_kitti::load_dirs(gt_dir, result_dir, p)) return rc;
+  egn_kitti::Result r;
+  egn_kitti::evaluate_host(p, 1, r);
+  if (n_frames) *n_frames = r.n_frames;
+  *aos_valid = r.aos_valid;
+  for (int c = 0; c < 3; ++c) evaluated[c] = r.evaluated[c];
+  memcpy(precision, r.precision, sizeof(double) * 9 * EGN_KITTI_SAMPLES);
+  memcpy(aos, r.aos, sizeof(double) * 9 * EGN_KITTI_SAMPLES);
+  return 0;
+}
+
+extern "C" int egn_kitti_eval_dirs_host(const char* gt_dir, const char* result_dir, int metrics, int* n_frames,
+                                        int* evaluated, int* aos_valid, double* precision, double* aos, int* counts,
+                                        int* n_thresholds) {
+  if (!gt_dir || !result_dir || !evaluated || !aos_valid || !precision || !aos || (metrics & ~7)) return -1;
+  egn_kitti::Packed p;
+  if (const int rc = egn_kitti::load_dirs(gt_dir, result_dir, p)) return rc;
+  egn_kitti::Result r;
+  egn_kitti::evaluate_host(p, metrics, r);
+  egn_kitti::copy_out(r, n_frames, evaluated, aos_valid, precision, aos, counts, n_thresholds);
+  return 0;
+}
+
+extern "C" int egn_kitti_eval_packed_host(int n_frames, const int* gt_off, const int* det_off, const double* gt_box,
+                                          const int* gt_type, const double* gt_trunc, const int* gt_occ,
+                                          const double* det_box, const int* det_type, const double* det_score,
+                                          int metrics, int* evaluated, int* aos_valid, double* precision, double* aos,
+                                          int* counts, int* n_thresholds) {
+  if (!evaluated || !aos_valid || !precision || !aos || (metrics & ~7)) return -1;
+  egn_kitti::Packed p;
+  if (egn_kitti::from_arrays(n_frames, gt_off, det_off, gt_box, gt_type, gt_trunc, gt_occ, det_box, det_type,
+                             det_score, p))
+    return -1;
+  egn_kitti::Result r;
+  egn_kitti::evaluate_host(p, metrics, r);
+  egn_kitti::copy_out(r, nullptr, evaluated, aos_valid, precision, aos, counts, n_thresholds);
+  return 0;
+}
+
+extern "C" int egn_kitti_overlap_host_f64(const double* det_box, const double* gt_box, long n, int criterion,
+                                          double* out) {
+  if (n < 0 || criterion < -1 || criterion > 1 || (n > 0 && (!det_box || !gt_box || !out))) return -1;
+  for (long k = 0; k < n; ++k)
+    egn_kitti_overlaps(det_box + k * EGN_KITTI_BOX, gt_box + k * EGN_KITTI_BOX, criterion, out + 4 * k);
   return 0;
 }

@@ -231,6 +231,58 @@ int egn_kitti_eval_image(const char* gt_dir, const char* result_dir, int* n_fram
                          double* aos);
 
 /* ------------------------------------------------------------------------
+ * The whole KITTI object evaluator: IMAGE (2D AP + AOS), GROUND (bird's-eye-view AP) and BOX3D (3D AP), the three
+ * blocks of evaluate_object_3d_offline.cpp:853-911, without Boost.  Per-pair math in csrc/kitti_overlap_math.h, the
+ * matching loop in csrc/kitti_eval_core.h (one function for host and device), the host path in csrc/kitti_eval.cpp,
+ * the device path in csrc/kitti_eval.hip.
+ *
+ * A box is 12 doubles: x1 y1 x2 y2 alpha h w l t1 t2 t3 ry.  Type codes: 0 car, 1 pedestrian, 2 cyclist, 3 van,
+ * 4 person_sitting, 5 dontcare, 6 anything else.  metrics: bit 0 IMAGE, bit 1 GROUND, bit 2 BOX3D.
+ *   evaluated    [3 metrics][3 classes]: the class is scored in the metric (a detection of it has x1 >= 0 /
+ *                t1 != -1000 / t2 != -1000) and the metric was asked for
+ *   aos_valid    0 if any detection carries alpha == -10
+ *   precision    [3 metrics][3 classes][3 levels][41 recall samples]
+ *   aos          [3 classes][3 levels][41], IMAGE only
+ *   counts       [3 metrics][3 classes][3 levels][41][3]: tp, fp, fn at each score threshold; may be NULL
+ *   n_thresholds [3 metrics][3 classes][3 levels]: recall steps reached; may be NULL
+ * Rows of combinations that are not scored stay 0.
+ *
+ * egn_kitti_eval_dirs_host / _dev read gt_dir/%06d.txt and result_dir/data/%06d.txt like egn_kitti_eval_image (same
+ * return codes).  egn_kitti_eval_packed_host / _dev take the frames as arrays: frame f owns ground truths
+ * gt_off[f] .. gt_off[f + 1] and detections det_off[f] .. det_off[f + 1]; all pointers are HOST pointers.  Offsets
+ * that do not start at 0 or decrease, a type code outside the table, more than 2^27 - 1 rows: -1.
+ *
+ * The _dev entries run on the current device: one packed copy up, four launches on `stream` (overlap table of all
+ * (detection, ground truth) pairs; recall pass, one thread per (frame, metric, class, level); precision pass, one
+ * wavefront per (frame, metric, class, level) with lane = score threshold; fixed-order fold of the similarity), two
+ * synchronisations (the true-positive scores come back once for getThresholds), independent of the number of frames.
+ * No capacity per frame.  Integer totals and a fixed-order similarity sum: equal inputs give equal bits, and the
+ * results equal the _host entries'.  The workspace is allocated and freed inside the call (hipMalloc / hipFree).
+ * Every launch is added to the launch counter; the _host entries launch nothing.
+ *
+ * egn_kitti_overlap_host_f64 / _dev_f64: pair k is det_box[k] against gt_box[k]; criterion -1 over the union, 0 over
+ * the detection, 1 over the ground truth; out [n][4] = image overlap, ground overlap, 3D overlap, bird's-eye-view
+ * intersection area.  _dev takes device pointers and is one launch on `stream`.
+ * ---------------------------------------------------------------------- */
+int egn_kitti_eval_dirs_host(const char* gt_dir, const char* result_dir, int metrics, int* n_frames, int* evaluated,
+                             int* aos_valid, double* precision, double* aos, int* counts, int* n_thresholds);
+int egn_kitti_eval_dirs_dev(const char* gt_dir, const char* result_dir, int metrics, int* n_frames, int* evaluated,
+                            int* aos_valid, double* precision, double* aos, int* counts, int* n_thresholds,
+                            void* stream);
+int egn_kitti_eval_packed_host(int n_frames, const int* gt_off, const int* det_off, const double* gt_box,
+                               const int* gt_type, const double* gt_trunc, const int* gt_occ, const double* det_box,
+                               const int* det_type, const double* det_score, int metrics, int* evaluated,
+                               int* aos_valid, double* precision, double* aos, int* counts, int* n_thresholds);
+int egn_kitti_eval_packed_dev(int n_frames, const int* gt_off, const int* det_off, const double* gt_box,
+                              const int* gt_type, const double* gt_trunc, const int* gt_occ, const double* det_box,
+                              const int* det_type, const double* det_score, int metrics, int* evaluated,
+                              int* aos_valid, double* precision, double* aos, int* counts, int* n_thresholds,
+                              void* stream);
+int egn_kitti_overlap_host_f64(const double* det_box, const double* gt_box, long n, int criterion, double* out);
+int egn_kitti_overlap_dev_f64(const double* det_box, const double* gt_box, long n, int criterion, double* out,
+                              void* stream);
+
+/* ------------------------------------------------------------------------
  * Crop front end: all boxes of one image in one launch (egonet.py:68-96:
  * get_affine_transform + cv2.warpAffine(INTER_LINEAR, border 0) + ToTensor +
  * Normalize).  img [H,W,3] uint8 RGB (row pitch in bytes); M [n,6] f64 forward

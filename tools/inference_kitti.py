@@ -1,7 +1,7 @@
 """End-to-end inference on a KITTI-style directory (the flow of the reference's
 ``tools/inference.py:main/inference`` for BASELINE config 5): frames + 2D boxes ->
 GPU crops -> HRNet key-points -> lifter -> pose solve -> KITTI result files ->
-(optionally) 2D AP / AOS against labels.
+(optionally) 2D AP / AOS, bird's-eye-view AP and 3D AP against labels.
 
     python tools/inference_kitti.py --images <dir of png> --boxes <dir of KITTI label/detection txt>
         [--calib <dir>] --out <result dir> [--ckpt <dir with HC.pth L.pth LS.npy> | --synthetic]
@@ -151,8 +151,13 @@ def main(argv=None):
     if dist is not None:
         dist.destroy_process_group()
     if a.gt:
-        res = evaluate.evaluate_aos(a.gt, a.out)
-        out['eval'] = {k: {'AP': v['AP'], 'AOS': v['AOS']} for k, v in res.items() if isinstance(v, dict)}
+        res = evaluate.evaluate_kitti(a.gt, a.out)
+        out['eval'] = {k: {s: v[s] for s in ('AP', 'AOS', 'AP_bev', 'AP_3d') if s in v}
+                       for k, v in res.items() if isinstance(v, dict)}
+        for k, v in out['eval'].items():
+            for s, vals in v.items():
+                if vals is not None:
+                    print('%s %s: %.4f %.4f %.4f' % (k, s, vals[0], vals[1], vals[2]), file=sys.stderr)
     print(json.dumps(out))
     return out
 
