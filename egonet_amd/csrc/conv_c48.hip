@@ -643,7 +643,7 @@ static int c48_launch(const ConvArgs& a, size_t lds, int grid, hipStream_t strea
   return (int)hipGetLastError();
 }
 
-int egn_conv_launch_c48(const ConvArgs& a, size_t lds, int waves, hipStream_t stream) {
+int egn_conv_launch_c48(const ConvArgs& a, size_t lds, C48Kernel k, hipStream_t stream) {
   static int cus = 0;
   if (!cus) {
     int dev = 0;
@@ -654,26 +654,32 @@ int egn_conv_launch_c48(const ConvArgs& a, size_t lds, int waves, hipStream_t st
   }
   const int ntiles = a.tiles_x * a.tiles_y * a.N;
   const int grid = ntiles < cus ? ntiles : cus;
-  if (waves == -1) {  // 16 x 16 tile, halo as a ring of chunks
-    static bool raised_t[EGN_MAX_DEVICES];
-    if (egn_first_use_on_device(raised_t)) {
-      EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_c48t_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
+  switch (k) {
+    case C48_Ring: {  // 16 x 16 tile, halo as a ring of chunks
+      static bool raised_t[EGN_MAX_DEVICES];
+      if (egn_first_use_on_device(raised_t)) {
+        EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_c48t_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
+      }
+      hipLaunchKernelGGL(conv_c48t_kernel, dim3(grid), dim3(512), lds, stream, a);
+      return (int)hipGetLastError();
     }
-    hipLaunchKernelGGL(conv_c48t_kernel, dim3(grid), dim3(512), lds, stream, a);
-    return (int)hipGetLastError();
-  }
+    case C48_Waves8: return c48_launch<8>(a, lds, grid, stream);
 #ifdef EGN_PROBES
-  if (waves == 0) {  // register-resident filter
-    static bool raised[EGN_MAX_DEVICES];
-    if (egn_first_use_on_device(raised)) {
-      EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_c48r_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
+    case C48_RegFilter: {  // register-resident filter
+      static bool raised[EGN_MAX_DEVICES];
+      if (egn_first_use_on_device(raised)) {
+        EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_c48r_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
+      }
+      hipLaunchKernelGGL(conv_c48r_kernel, dim3(grid), dim3(256), lds, stream, a);
+      return (int)hipGetLastError();
     }
-    hipLaunchKernelGGL(conv_c48r_kernel, dim3(grid), dim3(256), lds, stream, a);
-    return (int)hipGetLastError();
-  }
-  if (waves == 4) return c48_launch<4>(a, lds, grid, stream);       // cfg 41: never selected either
+    case C48_Waves4: return c48_launch<4>(a, lds, grid, stream);       // cfg 41: never selected either
+#else
+    case C48_RegFilter:
+    case C48_Waves4: return EGN_E_BADARG;     // probe builds only
 #endif
-  return waves == 8 ? c48_launch<8>(a, lds, grid, stream) : EGN_E_BADARG;
+  }
+  return EGN_E_BADARG;
 }

@@ -300,35 +300,34 @@ static int launch_one(const ConvArgs& a, size_t lds, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
-// dma family: local ids 1..10 = config ids 11..20 (table in conv_plan.hip)
-int egn_conv_launch_dma(const ConvArgs& a, int local_id, size_t lds, hipStream_t stream) {
+// dma family: config ids 11..20 and 21..30 (table in conv_plan.hip)
+int egn_conv_launch_dma(const ConvArgs& a, DirectTile tile, size_t lds, hipStream_t stream) {
 #ifdef EGN_PROBES
   // timing ablations of the 128x48 / 128x96 tiles (tools/conv_probe.py): probe builds only (-DEGN_PROBES) -- the product
   // library neither contains these kernels nor reads the variable
   static const int abl = getenv("EGN_CONV_ABLATE") ? atoi(getenv("EGN_CONV_ABLATE")) : 0;
-  if (abl && (local_id == 2 || local_id == 6)) {
-    if (local_id == 2) {
-      if (abl == 1) return launch_abl<2, 2, 4, 3, 1>(a, lds, stream);
-      if (abl == 2) return launch_abl<2, 2, 4, 3, 2>(a, lds, stream);
-      if (abl == 3) return launch_abl<2, 2, 4, 3, 3>(a, lds, stream);
-    } else {
-      if (abl == 1) return launch_abl<4, 1, 2, 3, 1>(a, lds, stream);
-      if (abl == 2) return launch_abl<4, 1, 2, 3, 2>(a, lds, stream);
-      if (abl == 3) return launch_abl<4, 1, 2, 3, 3>(a, lds, stream);
-    }
+  if (abl && tile == T128x96) {
+    if (abl == 1) return launch_abl<2, 2, 4, 3, 1>(a, lds, stream);
+    if (abl == 2) return launch_abl<2, 2, 4, 3, 2>(a, lds, stream);
+    if (abl == 3) return launch_abl<2, 2, 4, 3, 3>(a, lds, stream);
+  }
+  if (abl && tile == T128x48) {
+    if (abl == 1) return launch_abl<4, 1, 2, 3, 1>(a, lds, stream);
+    if (abl == 2) return launch_abl<4, 1, 2, 3, 2>(a, lds, stream);
+    if (abl == 3) return launch_abl<4, 1, 2, 3, 3>(a, lds, stream);
   }
 #endif
-  switch (local_id) {
-    case 1: return launch_one<4, 1, 4, 3>(a, lds, stream);
-    case 2: return launch_one<2, 2, 4, 3>(a, lds, stream);
-    case 3: return launch_one<2, 2, 4, 2>(a, lds, stream);
-    case 4: return launch_one<4, 1, 4, 1>(a, lds, stream);
-    case 5: return launch_one<4, 1, 4, 2>(a, lds, stream);
-    case 6: return launch_one<4, 1, 2, 3>(a, lds, stream);
-    case 7: return launch_one<2, 2, 2, 3>(a, lds, stream);
-    case 8: return launch_one<2, 2, 2, 2>(a, lds, stream);
-    case 9: return launch_one<1, 4, 4, 1>(a, lds, stream);
-    case 10: return launch_one<1, 4, 2, 3>(a, lds, stream);
-    default: return EGN_E_BADARG;
+  switch (tile) {
+    case T256x48: return launch_one<4, 1, 4, 3>(a, lds, stream);
+    case T128x96: return launch_one<2, 2, 4, 3>(a, lds, stream);
+    case T128x64: return launch_one<2, 2, 4, 2>(a, lds, stream);
+    case T256x16: return launch_one<4, 1, 4, 1>(a, lds, stream);
+    case T256x32: return launch_one<4, 1, 4, 2>(a, lds, stream);
+    case T128x48: return launch_one<4, 1, 2, 3>(a, lds, stream);
+    case T64x96: return launch_one<2, 2, 2, 3>(a, lds, stream);
+    case T64x64: return launch_one<2, 2, 2, 2>(a, lds, stream);
+    case T64x64_NWaves: return launch_one<1, 4, 4, 1>(a, lds, stream);
+    case T32x192: return launch_one<1, 4, 2, 3>(a, lds, stream);
   }
+  return EGN_E_BADARG;
 }

@@ -214,18 +214,18 @@ static int launch_one(const ConvArgs& a, size_t lds, hipStream_t stream) {
 }
 
 // staged family: config ids 1..10 (table in conv_plan.hip)
-int egn_conv_launch_staged(const ConvArgs& a, int cfg_id, size_t lds, hipStream_t stream) {
-  switch (cfg_id) {
-    case 1: return launch_one<4, 1, 4, 3, 6, 7>(a, lds, stream);
-    case 2: return launch_one<2, 2, 4, 3, 6, 8>(a, lds, stream);
-    case 3: return launch_one<2, 2, 4, 2, 8, 8>(a, lds, stream);
-    case 4: return launch_one<4, 1, 4, 1, 8, 8>(a, lds, stream);
-    case 5: return launch_one<4, 1, 4, 2, 8, 8>(a, lds, stream);
-    case 6: return launch_one<4, 1, 2, 3, 8, 8>(a, lds, stream);
-    case 7: return launch_one<2, 2, 2, 3, 8, 8>(a, lds, stream);
-    case 8: return launch_one<2, 2, 2, 2, 8, 8>(a, lds, stream);
-    case 9: return launch_one<1, 4, 4, 1, 8, 8>(a, lds, stream);
-    case 10: return launch_one<1, 4, 2, 3, 8, 8>(a, lds, stream);
-    default: return EGN_E_BADARG;
+int egn_conv_launch_staged(const ConvArgs& a, DirectTile tile, size_t lds, hipStream_t stream) {
+  switch (tile) {
+    case T256x48: return launch_one<4, 1, 4, 3, 6, 7>(a, lds, stream);
+    case T128x96: return launch_one<2, 2, 4, 3, 6, 8>(a, lds, stream);
+    case T128x64: return launch_one<2, 2, 4, 2, 8, 8>(a, lds, stream);
+    case T256x16: return launch_one<4, 1, 4, 1, 8, 8>(a, lds, stream);
+    case T256x32: return launch_one<4, 1, 4, 2, 8, 8>(a, lds, stream);
+    case T128x48: return launch_one<4, 1, 2, 3, 8, 8>(a, lds, stream);
+    case T64x96: return launch_one<2, 2, 2, 3, 8, 8>(a, lds, stream);
+    case T64x64: return launch_one<2, 2, 2, 2, 8, 8>(a, lds, stream);
+    case T64x64_NWaves: return launch_one<1, 4, 4, 1, 8, 8>(a, lds, stream);
+    case T32x192: return launch_one<1, 4, 2, 3, 8, 8>(a, lds, stream);
   }
+  return EGN_E_BADARG;
 }

@@ -1844,74 +1844,140 @@ static int wino43_launch(ConvArgs a, size_t lds, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
-// rows of the BatchNorm partial table a launch writes (0 = this variant has no fused statistics)
-int egn_conv_wino_stats_rows(const ConvArgs& a, int variant) {
-  int v = variant & 15;
-  if ((variant >> 4) || v < 2 || v == 10 || v > 12) return 0;      // (10: the F(4x4,3x3) kernel has no fused statistics)
-  const int per_cu = v >= 11 ? 2 : 1;
-  if (v >= 11) v = v == 11 ? 5 : 4;   // 11 / 12: conv_wino9_kernel with 8-channel stages on the tiles of 5 / 4
-  if (v >= 6) v -= 4;              // variants 6..9 = conv_wino9_kernel on the geometries of 2..5
-  const int tnb = v == 3 ? 4 : (v == 4 ? 2 : 1);
-  return wino8_grid(a, tnb, per_cu);       // one partial row per block
+constexpr int W8_ABL_STAMPS = 32;     // conv_wino8_kernel's stamp build (its ABL & 32)
+
+// rows of the BatchNorm partial table a launch writes (0 = this kernel has no fused statistics); a: planned
+int egn_conv_wino_stats_rows(const ConvArgs& a, WinoKernel k, int abl) {
+  if (abl) return 0;
+  switch (k) {
+    case Wino_16x16:
+    case Wino_8x8x4:
+    case Wino43: return 0;
+    case Wino8_16x16:
+    case Wino8_8x8x4:
+    case Wino8_8x8x2:
+    case Wino8_8x16:
+    case Wino9_16x16:
+    case Wino9_8x8x4:
+    case Wino9_8x8x2:
+    case Wino9_8x16: return wino8_grid(a, a.TNB, 1);       // one partial row per block
+    case Wino9h_8x16:
+    case Wino9h_8x8x2: return wino8_grid(a, a.TNB, 2);     // two blocks per CU
+  }
+  return 0;
 }
 
-// variant 0: 16 x 16 pixel tile of one image; variant 1: four 8 x 8 images (the 8 x 8 maps);
-// variants 2 / 3: the same two geometries on the 8-wave kernel; variant 4: two 8 x 8 images, 4 waves
-size_t egn_conv_wino_lds_bytes(int variant, int cout) {
-  if ((variant & 15) == 10) return egn_conv_wino43_lds_bytes(variant >> 4);
-  int v = variant & 15;
-  if (v == 11 || v == 12) {        // 8-channel stages, 4 waves: half the filter stage and half the halo planes
-    const int cot = egn_wino_cot(cout) ? egn_wino_cot(cout) : WN_CO;
-    const size_t halo2 = 2 * (size_t)(v == 11 ? WinoGeom<8, 16, 1>::PLANE : WinoGeom<8, 8, 2>::PLANE);
-    return (2 * (size_t)(16 * 2 * cot) + 2 * halo2) * 16 + (size_t)4 * 2 * cot * sizeof(double) +
-           ((variant >> 4) == 4 ? 4 * 48 * sizeof(unsigned long long) : 0);     // stamp build
-  }
-  if (v >= 6) v -= 4;              // conv_wino9_kernel: the LDS image of conv_wino8_kernel
-  size_t halo = (v & 1) ? WinoDims<8, 8, 4>::BUF : WinoDims<16, 16, 1>::BUF;
-  if (v >= 2) halo = (v & 1) ? EGN_CKQ * WinoGeom<8, 8, 4>::PLANE : EGN_CKQ * WinoGeom<16, 16, 1>::PLANE;
-  if (v == 4) halo = EGN_CKQ * WinoGeom<8, 8, 2>::PLANE;
-  if (v == 5) halo = EGN_CKQ * WinoGeom<8, 16, 1>::PLANE;
-  const int cot = v >= 2 && egn_wino_cot(cout) ? egn_wino_cot(cout) : WN_CO;   // the 4-wave kernel: 48 only
-  const size_t stats = v >= 2 ? (size_t)((v == 4 || v == 5) ? 4 : 8) * 2 * cot * sizeof(double) : 0;
-  const size_t stamps = (variant >> 4) == 4 && v >= 2 ? 8 * 48 * sizeof(unsigned long long) : 0;   // stamp builds
-  return (2 * (size_t)(16 * EGN_CKQ * cot) + 2 * halo) * 16 + stats + stamps;
+// conv_wino8_kernel / conv_wino9_kernel: two U slabs and two halo buffers of kq float4 planes, the [waves][2][cot]
+// double table of the BatchNorm partial sums, and the stamp area of the stamp builds
+template <int TH, int TW, int TNB>
+static size_t wino8_lds_bytes(int kq, int nw, int cot, bool stamps) {
+  return (2 * (size_t)(16 * kq * cot) + 2 * (size_t)kq * WinoGeom<TH, TW, TNB>::PLANE) * 16 +
+         (size_t)nw * 2 * cot * sizeof(double) + (stamps ? nw * 48 * sizeof(unsigned long long) : 0);
 }
-int egn_conv_launch_wino(const ConvArgs& a, size_t lds, int variant, hipStream_t stream) {
+// conv_wino_kernel: 48-channel co-tiles only, halo buffers padded to whole 256-thread pieces, no statistics
+template <int TH, int TW, int TNB>
+static size_t wino_lds_bytes() {
+  return (2 * (size_t)(16 * EGN_CKQ * WN_CO) + 2 * (size_t)WinoDims<TH, TW, TNB>::BUF) * 16;
+}
+size_t egn_conv_wino_lds_bytes(WinoKernel k, int abl, int cout) {
+  const int cot = egn_wino_cot(cout) ? egn_wino_cot(cout) : WN_CO;
+  switch (k) {
+    case Wino_16x16: return wino_lds_bytes<16, 16, 1>();
+    case Wino_8x8x4: return wino_lds_bytes<8, 8, 4>();
+    case Wino8_16x16: return wino8_lds_bytes<16, 16, 1>(EGN_CKQ, 8, cot, abl == W8_ABL_STAMPS);
+    case Wino8_8x8x4: return wino8_lds_bytes<8, 8, 4>(EGN_CKQ, 8, cot, abl == W8_ABL_STAMPS);
+    case Wino8_8x8x2: return wino8_lds_bytes<8, 8, 2>(EGN_CKQ, 4, cot, abl == W8_ABL_STAMPS);
+    case Wino8_8x16: return wino8_lds_bytes<8, 16, 1>(EGN_CKQ, 4, cot, abl == W8_ABL_STAMPS);
+    case Wino9_16x16: return wino8_lds_bytes<16, 16, 1>(EGN_CKQ, 8, cot, abl != 0);      // (abl = its CLK)
+    case Wino9_8x8x4: return wino8_lds_bytes<8, 8, 4>(EGN_CKQ, 8, cot, abl != 0);
+    case Wino9_8x8x2: return wino8_lds_bytes<8, 8, 2>(EGN_CKQ, 4, cot, abl != 0);
+    case Wino9_8x16: return wino8_lds_bytes<8, 16, 1>(EGN_CKQ, 4, cot, abl != 0);
+    case Wino9h_8x16: return wino8_lds_bytes<8, 16, 1>(2, 4, cot, abl != 0);             // 8-channel stages
+    case Wino9h_8x8x2: return wino8_lds_bytes<8, 8, 2>(2, 4, cot, abl != 0);
+    case Wino43: return egn_conv_wino43_lds_bytes(abl);
+  }
+  return 0;
+}
+// abl: the kernel's ABL (conv_wino_kernel, conv_wino8_kernel) or CLK (conv_wino9_kernel, conv_wino43_kernel) argument
+int egn_conv_launch_wino(const ConvArgs& a, size_t lds, WinoKernel k, int abl, hipStream_t stream) {
   const int act = a.act & EGN_ACT_MASK;
   if ((act != EGN_ACT_NONE && act != EGN_ACT_RELU) || (a.act & EGN_ACT_RES_AFTER)) return EGN_E_BADARG;
-  switch (variant) {
-    // what the shipped table / the tuner can select (egn_conv_config_kind >= 0 in the product build)
-    case 2: return wino8_launch<16, 16, 1>(a, lds, stream);
-    case 3: return wino8_launch<8, 8, 4>(a, lds, stream);
-    case 4: return wino8_launch<8, 8, 2, 0, 4>(a, lds, stream);
-    case 5: return wino8_launch<8, 16, 1, 0, 4>(a, lds, stream);
-    case 6: return wino9_launch<16, 16, 1>(a, lds, stream);
-    case 7: return wino9_launch<8, 8, 4>(a, lds, stream);
-    case 8: return wino9_launch<8, 8, 2, 4>(a, lds, stream);
-    case 9: return wino9_launch<8, 16, 1, 4>(a, lds, stream);
 #ifdef EGN_PROBES
-    // -DEGN_PROBES (python -m egonet_amd.build --probes; tools/ only): the families measured and retired -- the
-    // 4-wave kernel (cfg 45 / 46), the first F(4x4,3x3) kernel (65), two 4-wave blocks per CU (67 / 68) -- and the
-    // timing-ablation / s_memtime-stamp builds (WRONG RESULTS; 47-50, 53-55, 58, 63, 66, 69)
-    case 0: return wino_launch<16, 16, 1>(a, lds, stream);
-    case 1: return wino_launch<8, 8, 4>(a, lds, stream);
-    case 10: return a.stats ? EGN_E_BADARG : wino43_launch<0>(a, lds, stream);
-    case 0x1a: return wino43_launch<1>(a, lds, stream);           // s_memtime stamps (tools/wino_clk.py)
-    case 11: return wino9_launch<8, 16, 1, 4, 2>(a, lds, stream);   // 8-channel stages, two blocks per CU
-    case 12: return wino9_launch<8, 8, 2, 4, 2>(a, lds, stream);
-    case 0x12: return wino8_launch<16, 16, 1, 16>(a, lds, stream);
-    case 0x22: return wino8_launch<16, 16, 1, 7>(a, lds, stream);
-    case 0x32: return wino8_launch<16, 16, 1, 3>(a, lds, stream);
-    case 0x42: return wino8_launch<16, 16, 1, 32>(a, lds, stream);   // timeline stamps (tools/wino_clk.py)
-    case 0x46: return egn_wino_cot(a.Cout) == 48 ? wino9_launch_nt<16, 16, 1, 8, 3, 1>(a, lds, stream) : EGN_E_BADARG;
-    case 0x4b: return egn_wino_cot(a.Cout) == 48 ? wino9_launch_nt<8, 16, 1, 4, 3, 1, 2>(a, lds, stream) : EGN_E_BADARG;
-    case 0x10: return wino_launch<16, 16, 1, 15>(a, lds, stream);
-    case 0x20: return wino_launch<16, 16, 1, 7>(a, lds, stream);
-    case 0x30: return wino_launch<16, 16, 1, 3>(a, lds, stream);
-    case 0x40: return wino_launch<16, 16, 1, 11>(a, lds, stream);
-#endif
-    default: return EGN_E_BADARG;
+  // -DEGN_PROBES (python -m egonet_amd.build --probes; tools/ only): the timing-ablation / s_memtime-stamp builds
+  // (WRONG RESULTS; cfg 47-50, 53-55, 58, 63, 66, 69)
+  if (abl) {
+    switch (k) {
+      case Wino_16x16:
+        switch (abl) {
+          case 15: return wino_launch<16, 16, 1, 15>(a, lds, stream);
+          case 7: return wino_launch<16, 16, 1, 7>(a, lds, stream);
+          case 3: return wino_launch<16, 16, 1, 3>(a, lds, stream);
+          case 11: return wino_launch<16, 16, 1, 11>(a, lds, stream);
+          default: return EGN_E_BADARG;
+        }
+      case Wino8_16x16:
+        switch (abl) {
+          case 16: return wino8_launch<16, 16, 1, 16>(a, lds, stream);
+          case 7: return wino8_launch<16, 16, 1, 7>(a, lds, stream);
+          case 3: return wino8_launch<16, 16, 1, 3>(a, lds, stream);
+          case W8_ABL_STAMPS: return wino8_launch<16, 16, 1, 32>(a, lds, stream);   // timeline stamps (tools/wino_clk.py)
+          default: return EGN_E_BADARG;
+        }
+      // s_memtime stamps (tools/wino_clk.py): CLK = 1; conv_wino9_kernel's on 48-channel co-tiles only
+      case Wino9_16x16:
+        switch (abl) {
+          case 1: return egn_wino_cot(a.Cout) == 48 ? wino9_launch_nt<16, 16, 1, 8, 3, 1>(a, lds, stream) : EGN_E_BADARG;
+          default: return EGN_E_BADARG;
+        }
+      case Wino9h_8x16:
+        switch (abl) {
+          case 1: return egn_wino_cot(a.Cout) == 48 ? wino9_launch_nt<8, 16, 1, 4, 3, 1, 2>(a, lds, stream) : EGN_E_BADARG;
+          default: return EGN_E_BADARG;
+        }
+      case Wino43:
+        switch (abl) {
+          case 1: return wino43_launch<1>(a, lds, stream);
+          default: return EGN_E_BADARG;
+        }
+      case Wino_8x8x4:
+      case Wino8_8x8x4:
+      case Wino8_8x8x2:
+      case Wino8_8x16:
+      case Wino9_8x8x4:
+      case Wino9_8x8x2:
+      case Wino9_8x16:
+      case Wino9h_8x8x2: return EGN_E_BADARG;      // no ablation build
+    }
   }
+#endif
+  if (abl) return EGN_E_BADARG;
+  switch (k) {
+    // what the shipped table / the tuner can select (egn_conv_config_kind >= 0 in the product build)
+    case Wino8_16x16: return wino8_launch<16, 16, 1>(a, lds, stream);
+    case Wino8_8x8x4: return wino8_launch<8, 8, 4>(a, lds, stream);
+    case Wino8_8x8x2: return wino8_launch<8, 8, 2, 0, 4>(a, lds, stream);
+    case Wino8_8x16: return wino8_launch<8, 16, 1, 0, 4>(a, lds, stream);
+    case Wino9_16x16: return wino9_launch<16, 16, 1>(a, lds, stream);
+    case Wino9_8x8x4: return wino9_launch<8, 8, 4>(a, lds, stream);
+    case Wino9_8x8x2: return wino9_launch<8, 8, 2, 4>(a, lds, stream);
+    case Wino9_8x16: return wino9_launch<8, 16, 1, 4>(a, lds, stream);
+#ifdef EGN_PROBES
+    // the families measured and retired: the 4-wave kernel (cfg 45 / 46), the first F(4x4,3x3) kernel (65), two
+    // 4-wave blocks per CU (67 / 68)
+    case Wino_16x16: return wino_launch<16, 16, 1>(a, lds, stream);
+    case Wino_8x8x4: return wino_launch<8, 8, 4>(a, lds, stream);
+    case Wino43: return a.stats ? EGN_E_BADARG : wino43_launch<0>(a, lds, stream);
+    case Wino9h_8x16: return wino9_launch<8, 16, 1, 4, 2>(a, lds, stream);   // 8-channel stages, two blocks per CU
+    case Wino9h_8x8x2: return wino9_launch<8, 8, 2, 4, 2>(a, lds, stream);
+#else
+    case Wino_16x16:
+    case Wino_8x8x4:
+    case Wino43:
+    case Wino9h_8x16:
+    case Wino9h_8x8x2: return EGN_E_BADARG;      // probe builds only
+#endif
+  }
+  return EGN_E_BADARG;
 }
 
 // ---------------------------------------------------------------------------------------------

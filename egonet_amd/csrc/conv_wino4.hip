@@ -593,46 +593,62 @@ __global__ __launch_bounds__(256) void conv_wino4_finish_kernel(float* __restric
   reinterpret_cast<float4*>(y)[i] = v;
 }
 
-// geo: bits 0-1 the geometry (0: 16 x 32 regions, 1: 16 x 16 regions, 2: four 8 x 8 images), bit 2: input channels split
-// over two items (geometries 1 and 2: one exchange round per item)
-// bit 3 (geo 9) [round 6]: 96 output channels per item on geometry 1 -- conv_wino4w.hip
+// Wino4w [round 6]: 96 output channels per item on 16 x 16 regions -- conv_wino4w.hip
 bool egn_conv_wino4w_applies(const ConvArgs& a);
 int egn_conv_launch_wino4w(ConvArgs a, size_t lds, int abl, hipStream_t stream);
-// bit 4 (geo 17) [round 6]: half-size blocks (6 waves, 16 tiles), two per CU -- conv_wino4h.hip
+// Wino4h [round 6]: half-size blocks (6 waves, 16 tiles), two per CU -- conv_wino4h.hip
 bool egn_conv_wino4h_applies(const ConvArgs& a);
-// bit 5 (geo 49): the two blocks of a CU as the halves of ONE 12-wave workgroup (conv_wino4d_kernel)
+// Wino4d (dual): the two blocks of a CU as the halves of ONE 12-wave workgroup (conv_wino4d_kernel)
 size_t egn_conv_wino4h_lds_bytes(int dual);
 int egn_conv_launch_wino4h(ConvArgs a, size_t lds, int abl, int dual, hipStream_t stream);
-// bit 6 (geo 64) [round 6]: row-owner waves, one exchange round per item, 16 x 32 regions -- conv_wino4r.hip
+// Wino4r [round 6]: row-owner waves, one exchange round per item, 16 x 32 regions -- conv_wino4r.hip
 bool egn_conv_wino4r_applies(const ConvArgs& a);
 size_t egn_conv_wino4r_lds_bytes();
 int egn_conv_launch_wino4r(ConvArgs a, size_t lds, int abl, hipStream_t stream);
-bool egn_conv_wino4_applies(const ConvArgs& a, int geo) {
-  if (geo & 64) return geo == 64 && egn_conv_wino4r_applies(a);
-  if (geo & 16) return (geo == 17 || geo == 49) && egn_conv_wino4h_applies(a);
-  if (geo & 8) return geo == 9 && egn_conv_wino4w_applies(a);
-  const int g = geo & 3, ks = (geo & 4) ? 2 : 1;
-  if (g > 2 || (ks > 1 && g == 0)) return false;
-  const bool map_ok = g == 2 ? (a.Ho == 8 && a.Wo == 8) : (a.Ho % 16 == 0 && a.Wo % (g ? 16 : 32) == 0);
+
+// the input channels of an item split over two items (one exchange round per item)
+static bool w4_ksplit(Wino4Kernel k) { return k == Wino4b_KSplit || k == Wino4c_KSplit; }
+
+bool egn_conv_wino4_applies(const ConvArgs& a, Wino4Kernel k) {
+  bool map_ok = false;
+  switch (k) {
+    case Wino4: map_ok = a.Ho % 16 == 0 && a.Wo % 32 == 0; break;
+    case Wino4b:
+    case Wino4b_KSplit: map_ok = a.Ho % 16 == 0 && a.Wo % 16 == 0; break;
+    case Wino4c:
+    case Wino4c_KSplit: map_ok = a.Ho == 8 && a.Wo == 8; break;
+    case Wino4w: return egn_conv_wino4w_applies(a);
+    case Wino4h:
+    case Wino4d: return egn_conv_wino4h_applies(a);
+    case Wino4r: return egn_conv_wino4r_applies(a);
+  }
   // (K split: whole 16-channel stages per half; the residual is read after y was zeroed -- it must be another buffer)
-  if (ks > 1 && (a.Cin % 32 || (a.res && a.res == a.y))) return false;
+  if (w4_ksplit(k) && (a.Cin % 32 || (a.res && a.res == a.y))) return false;
   return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin % 16 == 0 && a.cs_in == a.Cin &&
          a.Cout % W4_CO == 0 && a.cs_out == a.Cout && !a.out_nchw && map_ok && !(a.act & EGN_ACT_RES_AFTER) &&
          ((a.act & EGN_ACT_MASK) == EGN_ACT_NONE || (a.act & EGN_ACT_MASK) == EGN_ACT_RELU);
 }
 // ticket words a K-split launch wants (zeroed once; every launch leaves them zero): the error word (index 0) + one per
 // (region, co-tile); 0 = none
-// (a: planned -- tiles_x / tiles_y are the regions of an image)
-int egn_conv_wino4_tickets(const ConvArgs& a, int geo) {
-  if (!(geo & 4) || !egn_conv_wino4_applies(a, geo)) return 0;
-  const int nimg = (geo & 3) == 2 ? 4 : 1;
+// (a: planned -- tiles_x / tiles_y are the regions of an image, TNB its images)
+int egn_conv_wino4_tickets(const ConvArgs& a, Wino4Kernel k) {
+  if (!w4_ksplit(k) || !egn_conv_wino4_applies(a, k)) return 0;
   // the error word (raised by a block whose wait ran out) + one word per (region, co-tile)
-  return a.tiles_x * a.tiles_y * ((a.N + nimg - 1) / nimg) * (a.Cout / W4_CO) + 1;
+  return a.tiles_x * a.tiles_y * ((a.N + a.TNB - 1) / a.TNB) * (a.Cout / W4_CO) + 1;
 }
-size_t egn_conv_wino4_lds_bytes(int geo) {      // (+ the stamp area of the ABL & 64 build)
-  if (geo & 64) return egn_conv_wino4r_lds_bytes();
-  if (geo & 16) return egn_conv_wino4h_lds_bytes(geo & 32);
-  return ((geo & 3) == 2 ? w4_lds_bytes<2>() : w4_lds_bytes<0>()) + 12 * 96 * 8;
+size_t egn_conv_wino4_lds_bytes(Wino4Kernel k) {      // (+ the stamp area of the ABL & 64 build)
+  switch (k) {
+    case Wino4:
+    case Wino4b:
+    case Wino4b_KSplit:
+    case Wino4w: return w4_lds_bytes<0>() + 12 * 96 * 8;
+    case Wino4c:
+    case Wino4c_KSplit: return w4_lds_bytes<2>() + 12 * 96 * 8;
+    case Wino4h: return egn_conv_wino4h_lds_bytes(0);
+    case Wino4d: return egn_conv_wino4h_lds_bytes(1);
+    case Wino4r: return egn_conv_wino4r_lds_bytes();
+  }
+  return 0;
 }
 // floats of the packed filter (engine.pack_wino4_weight): [co-tile][k-group = Cin / 4][wave][9 of 12][64]
 extern "C" long long egn_wino4_weight_floats(int cout, int cin) {
@@ -684,11 +700,22 @@ static int w4_grid(int nwork, int nck) {
   return nwork < cap ? nwork : cap;
 }
 // rows of the BatchNorm partial table a launch with ConvArgs::stats writes (a: planned): one per block; 0 = none
-int egn_conv_wino4_stats_rows(const ConvArgs& a, int geo) {
-  if ((geo & (24 | 64)) || !egn_conv_wino4_applies(a, geo)) return 0;      // (the wide items / half blocks have no training build)
-  const int g = geo & 3, ks = (geo & 4) ? 2 : 1, nimg = g == 2 ? 4 : 1;
+int egn_conv_wino4_stats_rows(const ConvArgs& a, Wino4Kernel k) {
+  switch (k) {
+    case Wino4w:
+    case Wino4h:
+    case Wino4d:
+    case Wino4r: return 0;      // (the wide items / half blocks / row owners have no training build)
+    case Wino4:
+    case Wino4b:
+    case Wino4b_KSplit:
+    case Wino4c:
+    case Wino4c_KSplit: break;
+  }
+  if (!egn_conv_wino4_applies(a, k)) return 0;
+  const int ks = w4_ksplit(k) ? 2 : 1;
   const int nct = a.Cout / W4_CO;
-  const int nreg = a.tiles_x * a.tiles_y * ((a.N + nimg - 1) / nimg);
+  const int nreg = a.tiles_x * a.tiles_y * ((a.N + a.TNB - 1) / a.TNB);
   return w4_grid(w4_item_count(w4_item_mode(nct), nreg, nct, ks), nct * ks);
 }
 
@@ -727,48 +754,55 @@ static int wino4_launch(ConvArgs a, size_t lds, hipStream_t stream) {
   }
   return (int)hipGetLastError();
 }
-int egn_conv_launch_wino4(ConvArgs a, size_t lds, int abl, int geo, hipStream_t stream) {
-  if (!egn_conv_wino4_applies(a, geo)) return EGN_E_BADARG;
-  if (geo & 64) return a.stats ? EGN_E_BADARG : egn_conv_launch_wino4r(a, lds, abl, stream);
-  if (geo & 16) return a.stats ? EGN_E_BADARG : egn_conv_launch_wino4h(a, lds, abl, geo & 32, stream);
-  if (geo & 8) return a.stats ? EGN_E_BADARG : egn_conv_launch_wino4w(a, lds, abl, stream);
+// abl: the kernel's ABL argument (0 = the real kernel)
+int egn_conv_launch_wino4(ConvArgs a, size_t lds, Wino4Kernel k, int abl, hipStream_t stream) {
+  if (!egn_conv_wino4_applies(a, k)) return EGN_E_BADARG;
   if (a.stats) {                       // the training tape: BatchNorm statistics in the item end
     if (abl) return EGN_E_BADARG;
-    switch (geo) {
-      case 0: return wino4_launch<0, 0, 1, true>(a, lds, stream);
-      case 1: return wino4_launch<0, 1, 1, true>(a, lds, stream);
-      case 5: return wino4_launch<0, 1, 2, true>(a, lds, stream);
-      case 2: return wino4_launch<0, 2, 1, true>(a, lds, stream);
-      case 6: return wino4_launch<0, 2, 2, true>(a, lds, stream);
-      default: return EGN_E_BADARG;
+    switch (k) {
+      case Wino4: return wino4_launch<0, 0, 1, true>(a, lds, stream);
+      case Wino4b: return wino4_launch<0, 1, 1, true>(a, lds, stream);
+      case Wino4b_KSplit: return wino4_launch<0, 1, 2, true>(a, lds, stream);
+      case Wino4c: return wino4_launch<0, 2, 1, true>(a, lds, stream);
+      case Wino4c_KSplit: return wino4_launch<0, 2, 2, true>(a, lds, stream);
+      case Wino4w:
+      case Wino4h:
+      case Wino4d:
+      case Wino4r: return EGN_E_BADARG;      // no training build
     }
+    return EGN_E_BADARG;
   }
-  if ((geo & 3) == 2) {
-    if (abl) return EGN_E_BADARG;
-    return (geo & 4) ? wino4_launch<0, 2, 2>(a, lds, stream) : wino4_launch<0, 2, 1>(a, lds, stream);
-  }
-  if (geo == 5) return abl ? EGN_E_BADARG : wino4_launch<0, 1, 2>(a, lds, stream);
-  if (geo) {
-    switch (abl) {
-      case 0: return wino4_launch<0, 1, 1>(a, lds, stream);
+  switch (k) {
+    case Wino4r: return egn_conv_launch_wino4r(a, lds, abl, stream);
+    case Wino4h: return egn_conv_launch_wino4h(a, lds, abl, 0, stream);
+    case Wino4d: return egn_conv_launch_wino4h(a, lds, abl, 1, stream);
+    case Wino4w: return egn_conv_launch_wino4w(a, lds, abl, stream);
+    case Wino4c: return abl ? EGN_E_BADARG : wino4_launch<0, 2, 1>(a, lds, stream);
+    case Wino4c_KSplit: return abl ? EGN_E_BADARG : wino4_launch<0, 2, 2>(a, lds, stream);
+    case Wino4b_KSplit: return abl ? EGN_E_BADARG : wino4_launch<0, 1, 2>(a, lds, stream);
+    case Wino4b:
+      switch (abl) {
+        case 0: return wino4_launch<0, 1, 1>(a, lds, stream);
 #ifdef EGN_PROBES
-      case 64: return wino4_launch<64, 1, 1>(a, lds, stream);
+        case 64: return wino4_launch<64, 1, 1>(a, lds, stream);
 #endif
-      default: return EGN_E_BADARG;
-    }
-  }
-  switch (abl) {
-    case 0: return wino4_launch<0, 0, 1>(a, lds, stream);
+        default: return EGN_E_BADARG;
+      }
+    case Wino4:
+      switch (abl) {
+        case 0: return wino4_launch<0, 0, 1>(a, lds, stream);
 #ifdef EGN_PROBES       // timing ablations / stamp builds: tools/ only (python -m egonet_amd.build --probes)
-    case 1: return wino4_launch<1, 0, 1>(a, lds, stream);
-    case 2: return wino4_launch<2, 0, 1>(a, lds, stream);
-    case 4: return wino4_launch<4, 0, 1>(a, lds, stream);
-    case 8: return wino4_launch<8, 0, 1>(a, lds, stream);
-    case 16: return wino4_launch<16, 0, 1>(a, lds, stream);
-    case 7: return wino4_launch<7, 0, 1>(a, lds, stream);
-    case 32: return wino4_launch<32, 0, 1>(a, lds, stream);
-    case 64: return wino4_launch<64, 0, 1>(a, lds, stream);
+        case 1: return wino4_launch<1, 0, 1>(a, lds, stream);
+        case 2: return wino4_launch<2, 0, 1>(a, lds, stream);
+        case 4: return wino4_launch<4, 0, 1>(a, lds, stream);
+        case 8: return wino4_launch<8, 0, 1>(a, lds, stream);
+        case 16: return wino4_launch<16, 0, 1>(a, lds, stream);
+        case 7: return wino4_launch<7, 0, 1>(a, lds, stream);
+        case 32: return wino4_launch<32, 0, 1>(a, lds, stream);
+        case 64: return wino4_launch<64, 0, 1>(a, lds, stream);
 #endif
-    default: return EGN_E_BADARG;
+        default: return EGN_E_BADARG;
+      }
   }
+  return EGN_E_BADARG;
 }

@@ -54,14 +54,73 @@ struct ConvArgs {
   unsigned* tickets;
 };
 
+// One row of kConfigs (conv_plan.hip) says everything about a config id: which family launches it, which of the
+// family's kernels, on which tile, with which filter packing, in which build.  Nothing is decoded from it elsewhere.
+enum class ConvFamily {
+  Staged,   // global -> registers -> LDS, searched tile (conv_mfma.hip)
+  Dma,      // LDS-DMA double-buffered pipeline, searched tile (conv_dma.hip)
+  Retired,  // reserved ids: never planned, never launched
+  C48,      // filter-resident persistent kernels of the 48 -> 48 3x3 layers (conv_c48.hip)
+  Wino,     // fused Winograd F(2x2,3x3) and the first F(4x4,3x3) kernel (conv_wino.hip)
+  Stem,     // 3x3 s2, 3 -> 64 channels (conv_stem.hip)
+  Wino4,    // fused Winograd F(4x4,3x3) (conv_wino4.hip, conv_wino4w/h/r.hip)
+  Fc,       // 1x1 row GEMM (conv_fc.hip)
+  S2r,      // 3x3 s2 from the 48-channel branch (conv_s2r.hip)
+};
+// the kernel within its family; the geometry suffix is TH x TW [x TNB images]
+enum DirectTile {   // Staged / Dma: block tile M x N (output pixels x output channels)
+  T256x48, T128x96, T128x64, T256x16, T256x32, T128x48, T64x96, T64x64, T64x64_NWaves, T32x192
+};
+enum C48Kernel { C48_Waves4, C48_Waves8, C48_RegFilter, C48_Ring };
+enum WinoKernel {
+  Wino_16x16, Wino_8x8x4,                                  // conv_wino_kernel (4 waves)
+  Wino8_16x16, Wino8_8x8x4, Wino8_8x8x2, Wino8_8x16,       // conv_wino8_kernel (8 waves; 8x8x2 / 8x16: 4 waves)
+  Wino9_16x16, Wino9_8x8x4, Wino9_8x8x2, Wino9_8x16,       // conv_wino9_kernel on the same tiles
+  Wino9h_8x16, Wino9h_8x8x2,                               // conv_wino9_kernel with 8-channel stages, two blocks per CU
+  Wino43,                                                  // conv_wino43_kernel: F(4x4,3x3)
+};
+enum Wino4Kernel {
+  Wino4,                    // conv_wino4_kernel: 16 x 32 regions
+  Wino4b, Wino4b_KSplit,    // conv_wino4b_kernel / conv_wino4bk_kernel: 16 x 16 regions
+  Wino4c, Wino4c_KSplit,    // conv_wino4c_kernel<., 1 / 2>: four 8 x 8 images per region
+  Wino4w,                   // conv_wino4w_kernel: 16 x 16 regions x 96 output channels per item
+  Wino4h, Wino4d,           // conv_wino4h_kernel / conv_wino4d_kernel: half-size blocks
+  Wino4r,                   // conv_wino4r_kernel: row-owner waves, 16 x 32 regions
+};
+union ConvKernel {          // the member ConvConfig::family names; families with one kernel leave it empty
+  int none;
+  DirectTile direct;
+  C48Kernel c48;
+  WinoKernel wino;
+  Wino4Kernel wino4;
+  constexpr ConvKernel() : none(0) {}
+  constexpr ConvKernel(DirectTile k) : direct(k) {}
+  constexpr ConvKernel(C48Kernel k) : c48(k) {}
+  constexpr ConvKernel(WinoKernel k) : wino(k) {}
+  constexpr ConvKernel(Wino4Kernel k) : wino4(k) {}
+};
+
 struct ConvConfig {
   int id;
-  int wm, wn, mt, nt;  // waves in M/N, 16x16 sub-tiles per wave in M/N
-  int ai, bi;          // dwordx4 staging loads per lane: halo tile / weights of a stage
-  int dma;             // 1 = LDS-DMA double-buffered pipeline (conv_dma.hip)
+  // Staged / Dma: waves in M / N, 16x16 sub-tiles per wave in M / N.  Other families: wm = waves of a block and a
+  // nominal tile; egn_conv_plan_query exports the four for every id
+  int wm, wn, mt, nt;
+  ConvFamily family;
+  ConvKernel kernel;
+  int abl;           // the kernel's ABL / CLK template argument: 0 = the real kernel, else a timing-ablation or stamp build
+  int kind;          // filter packing as egn_conv_config_kind returns it; -1 = not selectable (ablation / stamp / retired)
+  bool probe_only;   // compiled, planned and launched by -DEGN_PROBES builds only
+  struct {           // Staged / Dma (searched tile): dwordx4 staging loads per lane for the halo tile / the weights of a
+    int ai, bi;      // stage, and the LDS budget in KiB the search keeps a block within
+    int lds_kb;
+  } staging;
+  struct {           // every other family: the fixed output tile (TNB images x TH rows x TW cols), taps per stage, and
+    int TH, TW, TNB, tps;   // the input (halo) tile where it is not (TH + 2) x (TW + 2)
+    int HH, HW;
+  } tile;
+  const char* name;  // kernel symbol as rocprofv3 prints it (Staged / Dma: formatted from wm..nt, egn_conv_config_name)
   int tile_m() const { return wm * mt * 16; }
   int tile_n() const { return wn * nt * 16; }
-  int threads() const { return 64 * wm * wn; }
 };
 
 // co-tile of the Winograd kernels (conv_wino.hip): 48 where Cout allows, else 32, 0 = not supported
