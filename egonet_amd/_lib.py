@@ -151,6 +151,8 @@ SIGNATURES = {
     'egn_col_mean_std_f32': (_i, [_p, C.c_long, _i, _p, C.c_long, _p, _p, _p]),
     'egn_normalize_rows_f32': (_i, [_p, C.c_long, _i, _p, _p, _p]),
     'egn_gather_rows_f32': (_i, [_p, C.c_long, _i, _p, _i, _p, _p]),
+    'egn_pose2d_annot_ws_bytes': (C.c_long, [_i]),
+    'egn_pose2d_annot_f64': (_i, [_p, _p, _p, _i, _p, _i, _d, _d, _i, _d, _i, _d, _p, C.c_long] + [_p] * 9),
     'egn_lifter_metrics_ws_bytes': (C.c_long, [C.c_long]),
     'egn_lifter_metrics_reset': (_i, [_p, _i, _p]),
     'egn_lifter_metrics_update_f32': (_i, [_p, _p, C.c_long, _i, _i, _p, _p, _i, _p, C.c_long, _p, _p, _p]),

@@ -31,16 +31,20 @@ _COL = {k: i for i, k in enumerate(FIELDNAMES)}
 LABEL_COLUMNS = ('dl', 'dh', 'dw', 'lx', 'ly', 'lz', 'ry')      # -> l h w x y z rot_y, the order of a label row
 
 
-def parse_label_text(text, classes):
+def parse_label_text(text, classes, with_alpha=False):
     """Label rows [n,7] float64 (l, h, w, x, y, z, rot_y) of the lines whose type is in ``classes``
-    (csv_read_annot, car_instance.py:792-829: space separated, other classes skipped)."""
-    rows = []
+    (csv_read_annot, car_instance.py:792-829: space separated, other classes skipped).  ``with_alpha``: the pair
+    (rows, alpha [n] float64), for ``common.pose_annot``."""
+    rows, alpha = [], []
     for line in text.splitlines():
         f = line.split(' ')
         if not f or f[0] not in classes:
             continue
         rows.append([float(f[_COL[k]]) for k in LABEL_COLUMNS])
-    return np.array(rows, dtype=np.float64).reshape(-1, 7)
+        if with_alpha:
+            alpha.append(float(f[_COL['alpha']]))
+    rows = np.array(rows, dtype=np.float64).reshape(-1, 7)
+    return (rows, np.array(alpha, dtype=np.float64)) if with_alpha else rows
 
 
 def parse_calib_text(text):

@@ -15,6 +15,8 @@
 // last float64 bit).  No fast-math: the float32 division of normalize_rows must be the IEEE one.
 #include "egn_internal.h"
 #include "pose_math.h"
+#include "cuboid_math.h"       // canon_point
+#include "compact_scan.h"      // pairs_scan_kernel
 #pragma clang fp contract(off)
 
 namespace {
@@ -40,28 +42,6 @@ struct PairArgs {
   float* out3d;              // [N][3(J-1) | 3J]
   double* roots;             // [N][3]
 };
-
-// canonical cuboid point j (car_instance.py:730-747): centre, 8 corners, 12 edges x ncoef interpolated points;
-// the centring offsets are float32-rounded, so the centre is not exactly zero
-__device__ inline void canon_corner(int k, double l, double h, double w, double* p) {   // k = 0..8
-  const double ox = -(double)((float)l / 2.0f), oy = -(double)(float)h, oz = -(double)((float)w / 2.0f);
-  const int c = k - 1;
-  p[0] = (k == 0 ? 0.5 * l : (c < 4 ? l : 0.0)) + ox;
-  p[1] = (k == 0 ? 0.5 * h : ((c & 1) ? h : 0.0)) + oy;
-  p[2] = (k == 0 ? 0.5 * w : (((c >> 1) & 1) ? 0.0 : w)) + oz;
-}
-
-__device__ inline void canon_point(int j, double l, double h, double w, const double* coef, double* p) {
-  if (j < 9) {
-    canon_corner(j, l, h, w, p);
-    return;
-  }
-  const int e = (j - 9) % 12, k = (j - 9) / 12;
-  double a[3], b[3];
-  canon_corner(1 + egn_edge_parent(e), l, h, w, a);
-  canon_corner(1 + egn_edge_child(e), l, h, w, b);
-  for (int d = 0; d < 3; ++d) p[d] = a[d] + coef[k] * (b[d] - a[d]);
-}
 
 template <bool WRITE>
 __global__ __launch_bounds__(PT) void pairs_kernel(PairArgs a) {
@@ -204,35 +184,6 @@ __global__ __launch_bounds__(PT) void pairs_kernel(PairArgs a) {
   {
     double* dst = a.roots + row0 * 3;
     for (int e = tid; e < cnt * 3; e += PT) dst[e] = s_root[e];
-  }
-}
-
-// one block: counts -> exclusive offsets, total -> *total.  Thread t owns a contiguous chunk; the chunk sums are
-// scanned by thread 0, so the result does not depend on scheduling.
-__global__ __launch_bounds__(1024) void pairs_scan_kernel(int* counts, int n, long long* total) {
-  __shared__ long long s_sum[1024];
-  const int t = threadIdx.x;
-  const int per = (n + 1023) / 1024;
-  const int b = min(t * per, n), e = min(b + per, n);
-  long long sum = 0;
-  for (int i = b; i < e; ++i) sum += counts[i];
-  s_sum[t] = sum;
-  __syncthreads();
-  if (t == 0) {
-    long long run = 0;
-    for (int i = 0; i < 1024; ++i) {
-      const long long v = s_sum[i];
-      s_sum[i] = run;
-      run += v;
-    }
-    *total = run;
-  }
-  __syncthreads();
-  long long run = s_sum[t];
-  for (int i = b; i < e; ++i) {
-    const int v = counts[i];
-    counts[i] = (int)run;
-    run += v;
   }
 }
 

@@ -716,6 +716,32 @@ int egn_normalize_rows_f32(float* x, long N, int C, const float* mean, const flo
 int egn_gather_rows_f32(const float* src, long nrows, int C, const int64_t* idx, int n, float* dst, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The 2-D pose annotations the key-point model trains on, built on the device (csrc/pose_annot.hip; the cuboid is
+ * the lifter pairs' own, csrc/cuboid_math.h).  Replaces the host loops of libs/dataset/KITTI/car_instance.py:221-262
+ * (_prepare_key_points_custom -> get_2d_3d_pair without augmentation) and :304-346 (_prepare_2d_pose_annot ->
+ * kpts2cs method 'boundary', cs2bbox, int()).  Every launch is added to egn_launch_count().
+ *
+ * egn_pose2d_annot_f64: per label the J-point cuboid, posed and projected with the frame's intrinsics; a point is
+ * visible when 0 < u < width and 0 < v < height.  Level 1 ("raw") keeps a label when visible / J >= inlier_share,
+ * level 2 ("kept") when it also has >= min_visible visible points.  Both levels are compacted in label order.
+ *   labels [A][7] f64 (l h w x y z rot_y), alpha [A] f64, label_frame [A] i32 in [0, F) (the caller checks it; an
+ *   index outside is clamped into the table, never read out of bounds), frames [F][14] f64 (K row major, shift,
+ *   width, height), coef0 / coef1: the edge interpolation coefficients, J = 33 (both) or 21 (coef0 only).
+ *   ws: egn_pose2d_annot_ws_bytes(A) bytes of scratch.
+ *   raw_kpts [A][J][3] f64 (u, v, visible): the first totals[0] rows are written;
+ *   kpts [A][J][2] f64, boxes [A][4] i32, rots [A][2] f64 (alpha, rot_y), src [A] i32 (the label's index): the
+ *   first totals[1] rows are written.  A box is centre -/+ half-size with centre = (min + max) / 2 and half-size =
+ *   (max - min) * enlarge / 2 over all J points, each corner truncated toward zero (saturated to the int32 range).
+ *   frame_raw / frame_kept [F] i32: instances of each frame at the two levels; totals [2] i64.
+ *   A = 0 is allowed (the pointers sized by A may then be NULL): the counts and totals are zeroed. */
+long egn_pose2d_annot_ws_bytes(int A);
+int egn_pose2d_annot_f64(const double* labels, const double* alpha, const int* label_frame, int A,
+                         const double* frames, int F, double coef0, double coef1, int J, double inlier_share,
+                         int min_visible, double enlarge, void* ws, long ws_bytes, double* raw_kpts, double* kpts,
+                         int* boxes, double* rots, int* src, int* frame_raw, int* frame_kept, int64_t* totals,
+                         void* stream);
+
+/* ------------------------------------------------------------------------
  * The lifter's 3-D validation metrics on the device (csrc/lifter_metrics.hip, per-row math in csrc/metric_math.h).
  * Replaces the host loops of libs/metric/criterions.py:223-301 (update_statistics, update_joints_3d_error style
  * 'direct', update_rotation_error style 'euler') behind RError3D / RTError3D (:390-538) and the per-batch

@@ -1,0 +1,189 @@
+#!/usr/bin/env python
+"""Train the key-point sub-model HC from a KITTI tree: the counterpart of the reference's tools/train_IGRs.py:49-106.
+
+    python tools/train_IGRs.py --kitti <dir with image_2 label_2 calib> [--split-file <stems>]
+        [--valid-split-file <stems>] --out <dir> [--epochs 45] [--batch-frames 8] [--eval-every N] [--seed S]
+        [--tiny] [--max-steps N] [--workers 4] [--report-every 30] [--lr 1e-3]
+
+Labels + calibration -> ``PoseAnnotBuilder`` (the 2-D pose annotations, built on the device:
+egonet_amd.common.pose_annot) -> ``PoseFrames`` -> ``DataLoader(collate_fn=collate_frames)`` (frames decoded in the
+workers) -> ``trainer.train(sample_builder=TrainSampleBuilder(...))`` (crops and targets on the device, the native
+tape), with the settings of configs/KITTI_train_IGRs.yml.  ``HC.pth`` (a flat ``state_dict`` with the reference's
+keys, what ``EgoNet(cfgs, pre_trained=True)`` loads) is written into ``--out``.
+
+A split file holds one frame name per line ('000123'); without one every label file of the tree is used.  A batch is
+``--batch-frames`` frames with all their kept cars.  ``--eval-every N`` scores the validation split (the training
+frames without ``--valid-split-file``) every N batches with ``JointDistance2DSIP`` on the device; with a validation
+split the run also ends with one pass over it.  ``--max-steps N`` ends the run after N steps; ``--tiny`` trains the
+small network of tools/inference_kitti.py --tiny (tests).  One JSON line is printed: frames, the instances kept and
+dropped at each of the two filters, steps, ``last_loss``, the output path.  ``last_loss`` is the last loss the trainer
+REPORTED (every ``--report-every`` batches of an epoch, starting with batch 0), not the last step's: with
+``--report-every 30 --max-steps 2`` it is step 0's.
+"""
+import argparse
+import json
+import logging
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from egonet_amd import configs, trainer                                  # noqa: E402
+from egonet_amd.common import crop_gpu, pose_annot, train_samples          # noqa: E402
+from egonet_amd.metric.criterions import DistanceSrcMeter, Evaluator       # noqa: E402
+from egonet_amd.model.heatmapModel import hrnet                            # noqa: E402
+
+
+def igr_cfgs(a):
+    """The keys of configs/KITTI_train_IGRs.yml that the builders, the model and the trainer read."""
+    cfg = configs.clone(configs.hrnet_config(8, (64, 64), 33, 'coordinates', modules=(1, 1, 1), num_blocks=1)
+                        if a.tiny else configs.w48_config('coordinates'))
+    cfg['heatmapModel'].update(jitter_bbox=True, jitter_params={'shift': [0.1, 0.1], 'scaling': [0.4, 0.4]},
+                               loss_type='JointsCompositeLoss', loss_spec_list=['mse', 'l1', 'sl1'],
+                               loss_weight_list=[1.0, 0.1, 'None'], cr_loss_threshold=0.15, target_type='gaussian',
+                               sigma=1)
+    cfg.update(train=True, use_gpu=True, exp_type='instanceto2d',
+               dataset={'name': 'KITTI', 'detect_classes': ['Car'], '3d_kpt_sample_style': 'bbox9',
+                        'interpolate': {'flag': True, 'style': 'bbox12', 'coef': [0.332, 0.667]},
+                        '2d_kpt_style': 'bbox9',
+                        'pth_transform': {'mean': list(crop_gpu.IMAGENET_MEAN), 'std': list(crop_gpu.IMAGENET_STD)}},
+               optimizer={'optim_type': 'adam', 'lr': a.lr, 'weight_decay': 0.0, 'momentum': 0.9,
+                          'milestones': [10, 20, 30, 40], 'gamma': 0.5},
+               training_settings={'total_epochs': a.epochs, 'batch_size': a.batch_frames, 'num_threads': a.workers,
+                                  'shuffle': True, 'use_target_weight': False, 'report_every': a.report_every,
+                                  'eval_every': a.eval_every, 'eval_during': a.eval_every > 0,
+                                  'eval_metrics': ['JointDistance2DSIP'], 'plot_loss': False},
+               # the validation batches are built by a device front end inside collate_fn: no worker processes
+               testing_settings={'batch_size': a.batch_frames, 'num_threads': 0, 'shuffle': False,
+                                 'apply_dropout': False, 'unnormalize': False, 'arg_max': 'hard',
+                                 'eval_metrics': ['JointDistance2DSIP'], 'alpha_mode': 'proj'})
+    return cfg
+
+
+def build_model(cfgs, seed):
+    """Seeds numpy and torch, then makes the network: the same seed gives the same initial weights and, from there,
+    the same shuffles and box jitter."""
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    return hrnet.get_pose_net(cfgs, is_train=True).cuda()
+
+
+def read_stems(path):
+    with open(path) as fh:
+        return [ln.strip() for ln in fh if ln.strip()]
+
+
+class _BudgetLoader(object):
+    """The ``DataLoader`` ``trainer.get_loader`` would make, ended when the run's step budget is used up."""
+
+    def __init__(self, owner, batch_size, shuffle):
+        self.owner = owner
+        self.loader = torch.utils.data.DataLoader(owner.frames, batch_size=batch_size, shuffle=shuffle,
+                                                  num_workers=owner.workers,
+                                                  collate_fn=train_samples.collate_frames)
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        if self.owner.left == 0:
+            return
+        for batch in self.loader:
+            self.owner.steps += 1
+            if self.owner.left is not None:
+                self.owner.left -= 1
+            yield batch
+            if self.owner.left == 0:
+                return
+
+
+class _Budgeted(object):
+    """``PoseFrames`` behind the loader hook of ``trainer.get_loader``: counts the steps, stops after ``max_steps``.
+
+    A workaround, named as one: ``device_loader`` is the hook ``get_loader`` keeps for row sets that live on the
+    device (``LifterPairs``); nothing here does.  It is used because ``trainer.train`` has no step limit and a loader
+    is the only place a caller can end an epoch early without the trainer's cooperation.  Once the budget is used up
+    the remaining epochs still run their ``sche.step()`` over an empty loader; the weights no longer change.  A
+    ``max_steps`` argument of ``trainer.train`` would replace this class."""
+
+    def __init__(self, frames, workers, max_steps):
+        self.frames, self.workers = frames, workers
+        self.left = max_steps if max_steps and max_steps > 0 else None
+        self.steps = 0
+        self.num_joints = frames.num_joints
+
+    def __len__(self):
+        return len(self.frames)
+
+    def device_loader(self, batch_size, shuffle):
+        return _BudgetLoader(self, batch_size, shuffle)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--kitti', required=True, help='directory with image_2, label_2 and calib')
+    ap.add_argument('--split-file', default=None)
+    ap.add_argument('--valid-split-file', default=None)
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--epochs', type=int, default=45)
+    ap.add_argument('--batch-frames', type=int, default=8)
+    ap.add_argument('--eval-every', type=int, default=0, metavar='N', help='validate every N batches (0 = off)')
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--tiny', action='store_true', help='tiny HC (tests)')
+    ap.add_argument('--max-steps', type=int, default=0, metavar='N', help='end the run after N steps (0 = no limit)')
+    ap.add_argument('--workers', type=int, default=4)
+    ap.add_argument('--report-every', type=int, default=30)
+    ap.add_argument('--lr', type=float, default=1e-3)
+    a = ap.parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format='%(message)s')
+    logger = logging.getLogger('train_IGRs')
+    cfgs = igr_cfgs(a)
+    model = build_model(cfgs, a.seed)
+
+    annot_builder = pose_annot.PoseAnnotBuilder(cfgs, 'train')
+    annot = annot_builder(pose_annot.kitti_records(a.kitti, read_stems(a.split_file) if a.split_file else None))
+    counts = annot_builder.last_counts
+    logger.info('train: %(frames_kept)d of %(frames)d frames, %(kept_visible)d of %(labels)d cars '
+                '(%(dropped_inlier)d outside the image, %(dropped_visible)d with too few visible points)' % counts)
+    if not annot['paths']:
+        ap.error('no car of %s passed the visibility filters' % a.kitti)
+    train_set = _Budgeted(pose_annot.PoseFrames(annot), a.workers, a.max_steps)
+
+    valid_frames, evaluator, evaluate_fn = None, None, None
+    if a.valid_split_file or a.eval_every > 0:
+        valid_annot = annot if not a.valid_split_file else pose_annot.PoseAnnotBuilder(cfgs, 'valid')(
+            pose_annot.kitti_records(a.kitti, read_stems(a.valid_split_file)))
+        valid_frames = pose_annot.PoseFrames(valid_annot)
+        valid_builder = train_samples.TrainSampleBuilder(cfgs, split='valid')      # no jitter (img_proc.py:217)
+        evaluator = Evaluator(['JointDistance2DSIP'], cfgs)
+
+        def valid_collate(batch):
+            return valid_builder(train_samples.collate_frames(batch))
+
+        def evaluate_fn(dataset, mdl, epoch):
+            return trainer.evaluate(dataset, mdl, None, cfgs, logger, evaluator, collate_fn=valid_collate, epoch=epoch)
+
+    optim, sche = trainer.prepare_optim(model, cfgs)
+    record = trainer.train(train_set, model, None, optim, sche, cfgs, logger, metric_func=DistanceSrcMeter(cfgs),
+                           valid_dataset=valid_frames, evaluate_fn=evaluate_fn,
+                           sample_builder=train_samples.TrainSampleBuilder(cfgs, split='train'))
+    if a.valid_split_file:                                  # trainer.py:395-513 over the validation split
+        evaluate_fn(valid_frames, model, None)
+        model.train()
+
+    os.makedirs(a.out, exist_ok=True)
+    path = os.path.join(a.out, 'HC.pth')
+    logger.info('=> saving final model state to {}'.format(path))
+    torch.save({k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, path)
+    out = dict(counts, steps=train_set.steps, last_loss=record['loss'][-1] if record['loss'] else None, out=path)
+    if evaluator is not None and evaluator.metrics[0].count:
+        m = evaluator.metrics[0]
+        out['eval'] = {'metric': 'JointDistance2DSIP', 'mean': float(m.mean), 'count': int(m.count)}
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == '__main__':
+    main()
