@@ -160,6 +160,9 @@ SIGNATURES = {
     'egn_kpt_metrics_reset': (_i, [_p, _p]),
     'egn_kpt_metrics_update_f32': (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _d, _d, _p, C.c_long, _p, _p, _p,
                                         _p, _p]),
+    'egn_angle_metrics_ws_bytes': (C.c_long, [C.c_long]),
+    'egn_angle_metrics_reset': (_i, [_p, _p]),
+    'egn_angle_metrics_update_f32': (_i, [_p, C.c_long, _i, _p, _p, C.c_long, _p, _p]),
     'egn_program_op_info': (_i,[_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), C.c_char_p, _i]),
 }
 

@@ -17,8 +17,9 @@ gradient buffer, overlapped all-reduce) stay the faster path; this is the drop-i
 
 Every head of ``PoseHighResolutionNet`` trains here: 'coordinates', 'heatmap' (plain or with the pixel-shuffle
 upsampler: the maps' gradient is unshuffled into the pre-shuffle activations, csrc/heads.hip) and 'angleregression'
-(AvgPool2d + Linear/BatchNorm1d/ReLU + Linear on the tape; the reference defines no loss for it, so the caller's
-criterion on the returned [N, 2] is the only way to train it).
+(AvgPool2d + Linear/BatchNorm1d/ReLU + Linear on the tape; the caller's criterion -- the reference's ``MSELoss1D`` /
+``SmoothL1Loss1D``, function.py:204-228 -- runs on the returned [N, 2]; ``HRNetTrainStep(angle_type=...)`` is the native
+form of the same iteration).
 
 Limits (raise or fall back loudly, never silently): the input must not require a gradient (the modules
 route such calls to the torch graph).

@@ -255,14 +255,18 @@ class PoseAnnotBuilder(object):
 class PoseFrames(torch.utils.data.Dataset):
     """One record per kept frame of ``annotations`` in the form ``TrainSampleBuilder`` documents: ``image`` decoded
     here (in the ``DataLoader`` worker) by ``crop_gpu.load_rgb``, ``boxes [n,4]``, ``joints [n,J,2]`` (no visibility
-    column: all visible, car_instance.py:1278-1279), ``path``.  Use it with ``train_samples.collate_frames``."""
+    column: all visible, car_instance.py:1278-1279), ``path``, and -- when the annotations hold them -- ``rots [n,2]``
+    (``alpha``, ``rot_y``: the angle baselines' targets, car_instance.py:1250).  Use it with
+    ``train_samples.collate_frames``."""
 
     def __init__(self, annotations):
         self.paths = list(annotations['paths'])
         self.boxes = list(annotations['boxes'])
         self.joints = list(annotations['kpts'])
-        if not (len(self.paths) == len(self.boxes) == len(self.joints)):
-            raise ValueError('paths, boxes and kpts must have one entry per frame')
+        self.rots = list(annotations['rots']) if 'rots' in annotations else None
+        if not (len(self.paths) == len(self.boxes) == len(self.joints)) or \
+                (self.rots is not None and len(self.rots) != len(self.paths)):
+            raise ValueError('paths, boxes, kpts and rots must have one entry per frame')
         self.num_joints = int(self.joints[0].shape[1]) if self.joints else 0
 
     def __len__(self):
@@ -270,8 +274,11 @@ class PoseFrames(torch.utils.data.Dataset):
 
     def __getitem__(self, i):
         from . import crop_gpu
-        return {'image': crop_gpu.load_rgb(self.paths[i]), 'boxes': self.boxes[i], 'joints': self.joints[i],
-                'path': self.paths[i]}
+        rec = {'image': crop_gpu.load_rgb(self.paths[i]), 'boxes': self.boxes[i], 'joints': self.joints[i],
+               'path': self.paths[i]}
+        if self.rots is not None:
+            rec['rots'] = self.rots[i]
+        return rec
 
 
 def kitti_records(root, stems=None):

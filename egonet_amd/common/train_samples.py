@@ -33,6 +33,8 @@ from .. import _lib
 from . import crop_gpu
 
 MAX_INS_CNT = 140              # car_instance.py:33
+TARGETS = {'heatmap': None, 'alpha': 0, 'theta': 1}       # the column of a record's ``rots`` an angle mode regresses
+EXP_TARGETS = {'baselinealpha': 'alpha', 'baselinetheta': 'theta'}      # cfgs['exp_type'], car_instance.py:1248
 SIZE = 200.0
 _ALIGN = 256                   # byte alignment of every section of the staging buffer
 
@@ -51,10 +53,21 @@ class TrainSampleBuilder(object):
     meta)``, the first three CUDA fp32, ``meta`` host numpy with the reference's keys.
 
     A record is ``{'image': [H,W,3] uint8 RGB, 'boxes': [n,4], 'joints': [n,K,2|3], 'path': str}`` (the fields
-    ``annot_2dpose`` holds for ``instanceto2d``); a missing visibility column means 1 (car_instance.py:1278-1279)."""
+    ``annot_2dpose`` holds for ``instanceto2d``); a missing visibility column means 1 (car_instance.py:1278-1279).
 
-    def __init__(self, cfgs, split='train', device=None):
+    ``target``: 'heatmap' (the above), or 'alpha' / 'theta' -- the direct-regression baselines (car_instance.py:
+    1248-1271, ``generate_hm=False``); None reads ``cfgs['exp_type']`` ('baselinealpha' / 'baselinetheta', anything else
+    means 'heatmap').  In the angle modes every record also holds ``'rots': [n,2]`` (``alpha``, ``rot_y``) and the batch
+    is ``(images, targets [N,2] = float32([cos r, sin r]) on the device, torch.ones(1), meta)`` with
+    ``meta['angles_gt'] [N]`` float64; no heat-map launch is made."""
+
+    def __init__(self, cfgs, split='train', device=None, target=None):
         hm = cfgs['heatmapModel']
+        if target is None:
+            target = EXP_TARGETS.get(cfgs.get('exp_type'), 'heatmap')
+        if target not in TARGETS:
+            raise ValueError('target %r (one of %s)' % (target, ', '.join(sorted(TARGETS))))
+        self.target, self.rot_col = target, TARGETS[target]
         if _hm_value(hm, 'target_type', 'gaussian') != 'gaussian':
             raise NotImplementedError('target_type %r: the reference draws gaussian targets only '
                                       '(img_proc.py:368)' % hm['target_type'])
@@ -107,6 +120,19 @@ class TrainSampleBuilder(object):
             raise ValueError('joints have %d key points, heatmapModel.num_joints is %d'
                              % (joints.shape[1], self.num_joints))
         return np.concatenate(boxes), joints, np.concatenate(frame)
+
+    def gather_rots(self, records, n_all):
+        """The regressed angle [N] f64 of all boxes in record order (column ``rot_col`` of every record's ``rots``)."""
+        rots = []
+        for f, rec in enumerate(records):
+            if 'rots' not in rec:
+                raise ValueError("record %d has no 'rots': target %r needs [n,2] (alpha, rot_y) per frame"
+                                 % (f, self.target))
+            rots.append(np.asarray(rec['rots'], dtype=np.float64).reshape(-1, 2)[:, self.rot_col])
+        rots = np.concatenate(rots)
+        if len(rots) != n_all:
+            raise ValueError('%d rots for %d boxes' % (len(rots), n_all))
+        return rots
 
     def jitter_boxes(self, boxes, draws):
         """jitter_bbox_with_kpts_no_occlu (img_proc.py:174-191); draws [N,4] = the four rand() of each box."""
@@ -171,7 +197,8 @@ class TrainSampleBuilder(object):
     def plan(self, records, rng=np.random):
         """All host work of a batch, in the reference's draw order (per frame, per box: 4 draws; then the
         length_limit choice).  Returns a dict: 'kept' [n] (indices into the batch's boxes), 'frame' [n],
-        'trans' [n,2,3], 'draws' [N,4] or None, and 'meta' (the reference's keys)."""
+        'trans' [n,2,3], 'draws' [N,4] or None, and 'meta' (the reference's keys); in the angle modes also 'targets'
+        [n,2] float32 and meta['angles_gt'] [n]."""
         boxes, joints, frame = self.gather(records)
         n_all = len(boxes)
         draws = None
@@ -187,7 +214,17 @@ class TrainSampleBuilder(object):
         meta = {'path': [r.get('path', '') for r in records],
                 'original_joints': joints[kept], 'transformed_joints': tj[kept],
                 'center': c[kept], 'scale': s[kept], 'joints_vis': tj[kept][:, :, 2]}
-        return {'kept': kept, 'frame': frame[kept], 'trans': trans[kept], 'draws': draws, 'meta': meta}
+        p = {'kept': kept, 'frame': frame[kept], 'trans': trans[kept], 'draws': draws, 'meta': meta}
+        if self.rot_col is not None:
+            # car_instance.py:1264-1270: [cos r, sin r] in float64, rounded to float32 once; ``chosen`` indexes them
+            # like every other meta array (length_limit :1344-1352)
+            r = self.gather_rots(records, n_all)[kept]
+            meta['angles_gt'] = r
+            # (one scalar call per angle, as there: at most MAX_INS_CNT of them, and no array loop of numpy's can
+            # round differently)
+            p['targets'] = np.array([[np.cos(v), np.sin(v)] for v in r], dtype=np.float64).reshape(-1, 2) \
+                .astype(np.float32)
+        return p
 
     # -- device work ---------------------------------------------------------------------------------------------
     def _staging(self, nbytes):
@@ -226,8 +263,10 @@ class TrainSampleBuilder(object):
         for img in frames:
             offs.append(total)
             total += up(img.nbytes)
-        sections = [('tab', (len(frames), 4), np.int64), ('box_frame', (n,), np.int32), ('M', (n, 6), np.float64),
-                    ('joints', (n, K, 3), np.float64), ('vis', (n, K), np.float32)]
+        angle = self.rot_col is not None
+        sections = [('tab', (len(frames), 4), np.int64), ('box_frame', (n,), np.int32), ('M', (n, 6), np.float64)]
+        sections += [('angles', (n, 2), np.float32)] if angle else \
+            [('joints', (n, K, 3), np.float64), ('vis', (n, K), np.float32)]
         where = {}
         for name, shape, dt in sections:
             where[name] = total
@@ -238,8 +277,11 @@ class TrainSampleBuilder(object):
             host[off:off + img.nbytes] = np.ascontiguousarray(img).reshape(-1)
         tab = np.array([[off, img.shape[0], img.shape[1], 3 * img.shape[1]] for img, off in zip(frames, offs)],
                        dtype=np.int64)
-        values = {'tab': tab, 'box_frame': remap[p['frame']].astype(np.int32), 'M': p['trans'].reshape(n, 6),
-                  'joints': meta['transformed_joints'], 'vis': meta['joints_vis'].astype(np.float32)}
+        values = {'tab': tab, 'box_frame': remap[p['frame']].astype(np.int32), 'M': p['trans'].reshape(n, 6)}
+        if angle:
+            values['angles'] = p['targets']
+        else:
+            values.update(joints=meta['transformed_joints'], vis=meta['joints_vis'].astype(np.float32))
         for name, shape, dt in sections:
             a = np.ascontiguousarray(values[name], dtype=dt).reshape(-1)
             host[where[name]:where[name] + a.nbytes] = a.view(np.uint8)
@@ -264,12 +306,8 @@ class TrainSampleBuilder(object):
             tab_d = view('tab', (len(frames), 4), torch.int64)
             frame_d = view('box_frame', (n,), torch.int32)
             M_d = view('M', (n, 6), torch.float64)
-            joints_d = view('joints', (n, K, 3), torch.float64)
-            vis_d = view('vis', (n, K), torch.float32)
             mean_t, std_t = crop_gpu._norm_consts(self.mean, self.std, dev)
             images = torch.empty(n, 3, h, w, dtype=torch.float32, device=dev)
-            targets = torch.empty(n, K, hm_h, hm_w, dtype=torch.float32, device=dev)
-            weights = torch.empty(n, K, 1, dtype=torch.float32, device=dev)
             L = _lib.lib()
             st = _lib.current_stream(dev)
             _lib.check(L.egn_crop_frames_warp_normalize_u8(_lib.ptr(staged), _lib.ptr(tab_d), len(frames),
@@ -278,6 +316,16 @@ class TrainSampleBuilder(object):
                        'crop frames')
             if ev:
                 ev[2].record(stream)
+            if angle:
+                # the targets came up with the staging copy; the dummy weight of my_collate_fn (car_instance.py:1388-1390)
+                if ev:
+                    ev[3].record(stream)
+                    self.last_timings = {'host_ms': host_ms, 'events': ev}
+                return images, view('angles', (n, 2), torch.float32), torch.ones(1), meta
+            joints_d = view('joints', (n, K, 3), torch.float64)
+            vis_d = view('vis', (n, K), torch.float32)
+            targets = torch.empty(n, K, hm_h, hm_w, dtype=torch.float32, device=dev)
+            weights = torch.empty(n, K, 1, dtype=torch.float32, device=dev)
             # the reference's stride quirk (img_proc.py:376-378): input_size / heatmap_size in (h, w) order, the
             # first of them divides x -- egn_gaussian_targets_f32 takes the two strides in that order
             _lib.check(L.egn_gaussian_targets_f32(_lib.ptr(joints_d), _lib.ptr(vis_d), n, K, hm_h, hm_w,

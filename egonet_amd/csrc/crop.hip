@@ -186,5 +186,6 @@ extern "C" int egn_crop_frames_warp_normalize_u8(const uint8_t* frames, const lo
   const dim3 grid((unsigned)((out_h + kCropRows - 1) / kCropRows), (unsigned)n);
   hipLaunchKernelGGL(crop_frames_warp_normalize_kernel, grid, dim3(256), 2 * out_w * sizeof(int), (hipStream_t)stream,
                      a);
+  egn_count_launches(1);
   return (int)hipGetLastError();
 }

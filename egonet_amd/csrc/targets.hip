@@ -57,5 +57,6 @@ extern "C" int egn_gaussian_targets_f32(const double* joints, const float* vis, 
   if (g > 8192) g = 8192;
   hipLaunchKernelGGL(gaussian_targets_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, joints, vis, N, K,
                      H, W, stride_x, stride_y, sigma, target, weight);
+  egn_count_launches(1);            // provable from outside: the sample front end's angle modes make no such launch
   return (int)hipGetLastError();
 }

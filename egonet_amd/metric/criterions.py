@@ -11,6 +11,9 @@ counts -- is per-instance host arithmetic in float64 like the reference's.
 ``metric_func``) run all of it on the device instead (csrc/kpt_metrics.hip: decode, rescale,
 closed-form inverse affine, distances, PCK counts, a device accumulator) and read back once.
 
+``get_angle_error`` / ``AngleError`` with CUDA predictions and ``AngleErrorMeter`` (the angle baselines' ``metric_func``)
+run on the device too (csrc/angle_metrics.hip: atan2 in float64, the wrapped difference, a {count, sum} accumulator).
+
 The lifter's 3-D metrics (``RError3D`` :390-449, ``RTError3D`` :451-538, ``JointDistance3D`` :343-388,
 ``RotationError3D`` :303-341, ``Evaluator`` :540-573; helpers :223-301) keep the reference's constructor arguments,
 attribute names (``mean_rT``, ``max_R``, ``count_R``, ... as numpy arrays) and ``report()`` text.  ``update`` takes
@@ -31,6 +34,7 @@ import torch
 from ..common import img_proc as lip
 
 PCK_THRES = np.array([0.1, 0.2, 0.3])
+_ANGLE_CALL = None                                  # get_angle_error's device accumulator for CUDA predictions
 
 
 def get_distance(gt, pred):
@@ -54,6 +58,16 @@ def get_PCK(pred, gt):
 
 
 def get_angle_error(pred, meta_data, cfgs=None):
+    """Mean error in degrees of predicted [cos, sin] rows against ``meta_data['angles_gt']`` (radians), the row count,
+    None.  numpy arrays and CPU tensors: host arithmetic like the reference's; a CUDA prediction: csrc/angle_metrics.hip
+    and one read-back of the {count, sum} pair."""
+    if torch.is_tensor(pred) and pred.is_cuda:
+        global _ANGLE_CALL
+        if _ANGLE_CALL is None or (_ANGLE_CALL._acc is not None and _ANGLE_CALL._acc.device != pred.device):
+            _ANGLE_CALL = _AngleMetricsDevice()     # an accumulator of its own (and its pinned staging), kept
+        _ANGLE_CALL.update(pred, meta_data)
+        acc = _ANGLE_CALL.take()
+        return acc[1] / len(pred), len(pred), None
     if not isinstance(pred, np.ndarray):
         pred = pred.data.cpu().numpy()
     dif = np.abs(meta_data['angles_gt'] - np.arctan2(pred[:, 1], pred[:, 0])) * 180 / np.pi
@@ -112,12 +126,46 @@ def get_distance_src(output, meta_data, cfgs=None, image_size=(256.0, 256.0), ar
 
 
 class AngleError(object):
+    """Running mean of get_angle_error over an evaluation pass (criterions.py:145-171).  CUDA predictions are folded
+    into a device accumulator (csrc/angle_metrics.hip): ``update`` only launches, the one read-back is in ``report()``
+    or at the first access of ``count`` / ``mean``; numpy inputs and CPU tensors take the host path.  Both kinds of
+    update merge in one object.  ``device_update = False`` sends CUDA predictions down the host path too."""
+    device_update = True
+
     def __init__(self, cfgs, num_joints=None):
         self.name = 'Angle error in degrees'
-        self.num_joints, self.count, self.mean = num_joints, 0, 0.
+        self.num_joints, self._count, self._mean = num_joints, 0, 0.
+        self._dev = _AngleMetricsDevice()
+
+    def _sync(self):
+        """The one read-back: the device accumulator is merged into the host attributes and reset."""
+        if not self._dev.pending:
+            return
+        acc = self._dev.take()
+        cnt = int(acc[0])
+        if cnt == 0:
+            return
+        self._mean = (self._mean * self._count + acc[1]) / (self._count + cnt)
+        self._count += cnt
+
+    def _synced(name):
+        def get(self):
+            self._sync()
+            return getattr(self, name)
+
+        def put(self, value):
+            self._sync()
+            setattr(self, name, value)
+        return property(get, put)
+
+    count, mean = _synced('_count'), _synced('_mean')
+    del _synced
 
     def update(self, prediction, meta_data, ground_truth=None, logger=None):
-        avg, cnt, _ = get_angle_error(prediction, meta_data)
+        if self.device_update and torch.is_tensor(prediction) and prediction.is_cuda:
+            self._dev.update(prediction, meta_data)
+            return
+        avg, cnt, _ = get_angle_error(prediction.cpu() if torch.is_tensor(prediction) else prediction, meta_data)
         self.mean = (self.mean * self.count + cnt * avg) / (self.count + cnt)
         self.count += cnt
 
@@ -138,16 +186,27 @@ def _kpt_on_device(prediction):
     return torch.is_tensor(prediction) and prediction.is_cuda
 
 
-class _KptMetricsDevice(object):
-    """The device side of get_distance_src (csrc/kpt_metrics.hip): one accumulator in HBM, two launches per batch,
-    nothing read back before ``read()``.  Host ``meta`` arrays travel in ONE pinned buffer and one non-blocking copy on
-    the current stream; the buffer is double-buffered and each half is guarded by an event, so a copy in flight is
-    never overwritten (the scheme of common/train_samples.py)."""
+class _PinnedStaging(object):
+    """Host ``meta`` arrays travel in ONE pinned buffer and one non-blocking copy on the current stream; the buffer is
+    double-buffered and each half is guarded by an event, so a copy in flight is never overwritten (the scheme of
+    common/train_samples.py)."""
 
     def __init__(self):
         self._acc = self._ws = None
         self._pinned, self._events, self._turn = [None, None], [None, None], 0
         self.pending = False
+
+    def _upload_f64(self, flat, dev):
+        """``flat`` (host float64, 1-D) -> a device tensor, by one non-blocking copy out of the pinned buffer."""
+        total = flat.size
+        turn, pinned = self._staging(total * 8)
+        pinned[:total * 8].view(torch.float64).numpy()[:] = flat
+        staged = torch.empty(total, dtype=torch.float64, device=dev)
+        staged.copy_(pinned[:total * 8].view(torch.float64), non_blocking=True)
+        if self._events[turn] is None:
+            self._events[turn] = torch.cuda.Event()
+        self._events[turn].record(torch.cuda.current_stream(dev))
+        return staged
 
     def _staging(self, nbytes):
         k = self._turn
@@ -159,6 +218,11 @@ class _KptMetricsDevice(object):
             buf = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
             self._pinned[k] = buf
         return k, buf
+
+
+class _KptMetricsDevice(_PinnedStaging):
+    """The device side of get_distance_src (csrc/kpt_metrics.hip): one accumulator in HBM, two launches per batch,
+    nothing read back before ``read()``."""
 
     def _labels(self, meta, K, dev):
         """center [n,2], scale [n,2], rotation [n], original_joints [n,K,3] as float64 device tensors."""
@@ -317,6 +381,104 @@ class DistanceSrcMeter(object):
                   'max_vals': out['max_vals'].cpu().numpy() if 'max_vals' in out else None,
                   'correct_cnt': correct, 'PCK_batch': correct / cnt if cnt else np.zeros(len(PCK_THRES))}
         return (acc[1] / cnt if cnt else 0.0), cnt, others
+
+
+# ---- get_angle_error on the device ------------------------------------------------------------------------------
+_ANGLE_ACC_DOUBLES = 2                              # include/egonet_hip.h: rows counted, sum of errors in degrees
+
+
+class _AngleMetricsDevice(_PinnedStaging):
+    """The device side of get_angle_error (csrc/angle_metrics.hip): a {count, sum} accumulator in HBM, two launches
+    per batch, nothing read back before ``peek()``.  A host ``meta['angles_gt']`` travels in one pinned non-blocking
+    copy."""
+
+    def update(self, prediction, meta):
+        """Launch only.  ``prediction`` [N, >= 2] float32 CUDA, any row pitch (only [cos, sin] are read)."""
+        from .. import _lib
+        pred = prediction.detach()
+        if pred.dim() != 2 or pred.shape[1] < 2:
+            raise ValueError('angle predictions must be [N, 2] rows of [cos, sin], got %s' % (tuple(pred.shape),))
+        if pred.dtype != torch.float32 or pred.stride(1) != 1 or (pred.shape[0] > 1 and pred.stride(0) < 2):
+            pred = pred.float().contiguous()
+        N, dev = pred.shape[0], pred.device
+        gt = meta['angles_gt']
+        if len(gt) != N:
+            raise ValueError('%d angles_gt for %d predictions' % (len(gt), N))
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            st = _lib.current_stream(dev)
+            if self._acc is None or self._acc.device != dev:
+                if self.pending:
+                    raise RuntimeError('the accumulator holds unread updates of another device')
+                self._acc = torch.empty(_ANGLE_ACC_DOUBLES, dtype=torch.float64, device=dev)
+                _lib.check(L.egn_angle_metrics_reset(_lib.ptr(self._acc), st), 'angle metrics reset')
+            if N == 0:
+                return
+            if torch.is_tensor(gt) and gt.is_cuda:
+                gt = gt.detach().to(device=dev, dtype=torch.float64).reshape(N).contiguous()
+            else:
+                gt = self._upload_f64(np.asarray(gt.numpy() if torch.is_tensor(gt) else gt,
+                                                 dtype=np.float64).reshape(N), dev)
+            nb = L.egn_angle_metrics_ws_bytes(N)
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nb:
+                self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            _lib.check(L.egn_angle_metrics_update_f32(_lib.ptr(pred), N, pred.stride(0) if N > 1 else 2, _lib.ptr(gt),
+                                                      _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._acc), st),
+                       'angle metrics update')
+        self.pending = True
+
+    def peek(self):
+        """The accumulator's two float64 on the host (synchronises); zeros before the first update."""
+        if self._acc is None:
+            return np.zeros(_ANGLE_ACC_DOUBLES)
+        return self._acc.cpu().numpy()
+
+    def reset(self):
+        """Zero the accumulator (a launch, no synchronisation)."""
+        self.pending = False
+        if self._acc is None:
+            return
+        from .. import _lib
+        with torch.cuda.device(self._acc.device):
+            _lib.check(_lib.lib().egn_angle_metrics_reset(_lib.ptr(self._acc), _lib.current_stream(self._acc.device)),
+                       'angle metrics reset')
+
+    def take(self):
+        """The one read-back: the accumulator's values, and the accumulator zeroed."""
+        acc = self.peek()
+        self.reset()
+        return acc
+
+
+class AngleErrorMeter(object):
+    """get_angle_error as the training loop's ``metric_func`` with the metric on the device (csrc/angle_metrics.hip),
+    the contract of ``DistanceSrcMeter``: ``accumulate(prediction, meta, cfgs=None)`` only launches; ``read()`` ->
+    (running mean in degrees, count) since the last ``reset()`` is the read-back; ``meter(prediction, meta, cfgs)``
+    returns ``(avg, cnt, None)`` like get_angle_error and synchronises like it.  Predictions must be CUDA [N, 2]."""
+
+    def __init__(self, cfgs=None):
+        self._dev = _AngleMetricsDevice()
+
+    @staticmethod
+    def _check(prediction):
+        if not (torch.is_tensor(prediction) and prediction.is_cuda):
+            raise TypeError('AngleErrorMeter needs a CUDA prediction; get_angle_error takes host arrays')
+
+    def accumulate(self, prediction, meta, cfgs=None):
+        self._check(prediction)
+        self._dev.update(prediction, meta)
+
+    def read(self):
+        acc = self._dev.peek()
+        cnt = int(acc[0])
+        return (acc[1] / cnt if cnt else 0.0), cnt
+
+    def reset(self):
+        self._dev.reset()
+
+    def __call__(self, prediction, meta, cfgs=None):
+        self._check(prediction)
+        return get_angle_error(prediction, meta, cfgs)
 
 
 class JointDistance2DSIP(object):

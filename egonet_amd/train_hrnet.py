@@ -711,21 +711,40 @@ class TapeOwner(object):
         return self._wgrad_ws
 
 class HRNetTrainStep(TapeOwner):
-    """``step(images, target, joints_xy)`` = one iteration of trainer.py:183-209."""
+    """``step(images, target, joints_xy)`` = one iteration of trainer.py:183-209.  ``angle_type`` ('mse' | 'sl1'): the
+    criterion of the 'angleregression' head (MSELoss1D / SmoothL1Loss1D, function.py:204-228); ``step(images, target
+    [N,2])`` then, and ``last_angles`` holds the [N,2] prediction."""
 
     CR_CRITERIA = {'mse': 0, 'l1': 1, 'sl1': 2}      # loss_dict, function.py:17-20
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, w_hm=1.0, w_coor=0.1, grad_sync=None,
                  sigma=1, w_cr=None, cr_type='sl1', cr_indices=None, target_cr=4.0 / 3.0, cr_loss_thres=0.15,
                  hm_type='mse', coor_type='l1', optim_type='adam', momentum=0.0, weight_decay=0.0,
-                 use_target_weight=False):
+                 use_target_weight=False, angle_type=None):
         self._init_tape_owner(model)
         p0 = next(model.parameters())
+        self.angle_crit = None
         if model.head_type == 'angleregression':
-            raise NotImplementedError(
-                "the 'angleregression' head has no loss in the reference (libs/loss defines none for it), so its "
-                "training loop cannot train it and neither can this step; train it through the autograd bridge: "
-                "model.train(); loss = criterion(model(x), target); loss.backward() runs the native tape")
+            if angle_type is None:
+                raise NotImplementedError(
+                    "the 'angleregression' head trains with MSELoss1D or SmoothL1Loss1D (function.py:204-228), not with "
+                    "the heat-map / coordinate terms: pass angle_type='mse' or 'sl1' (trainer.make_step reads it from "
+                    "the criterion); without it this head has no loss in the reference's composite criterion for the "
+                    "step to run")
+            if angle_type not in ('mse', 'sl1'):
+                raise NotImplementedError("angle_type %r (function.py:204-228 defines 'mse' = MSELoss1D and 'sl1' = "
+                                          "SmoothL1Loss1D)" % (angle_type,))
+            given = dict(w_hm=(w_hm, 1.0), w_coor=(w_coor, 0.1), w_cr=(w_cr, None), cr_indices=(cr_indices, None),
+                         hm_type=(hm_type, 'mse'), coor_type=(coor_type, 'l1'), use_target_weight=(use_target_weight, False))
+            bad = sorted(k for k, (v, default) in given.items() if v is not default and v != default)
+            if bad:
+                raise ValueError("the angle head has one term, angle_type; %s belong to the heat-map, coordinate and "
+                                 "cross-ratio terms of the other heads" % ', '.join(bad))
+            self.angle_crit = self.CR_CRITERIA[angle_type]
+            w_hm = w_coor = 0.0                   # the heat-map / coordinate terms do not exist for this head
+        elif angle_type is not None:
+            raise ValueError('angle_type is the criterion of the angle head; this model has head_type %r'
+                             % (model.head_type,))
         if model.head_type == 'heatmap' and w_coor:
             raise NotImplementedError("the 'heatmap' head trains with the heat-map term only (w_coor=0)")
         # JointsMSELoss(use_target_weight) (function.py:22-46, the heat-map head's criterion): both maps are multiplied
@@ -765,7 +784,22 @@ class HRNetTrainStep(TapeOwner):
         self.flat = FlatParams(model.parameters())
         self.loss_dev = torch.zeros(1, dtype=torch.float64, device=self.dev)
         self.counters = StepCounters()
-        self.last_maps = self.last_coords = None
+        self.last_maps = self.last_coords = self.last_angles = None
+
+    def _angle_loss(self, tape, target, n, st):
+        """MSELoss1D / SmoothL1Loss1D (function.py:204-228: nn.MSELoss / nn.SmoothL1Loss, 'mean' over the 2N elements)
+        and the gradient seed at final_fc.3 in one launch of egn_elem_loss_f32: rows of the padded activations against
+        the compact [N, 2] target; the padding columns of the gradient stay zero."""
+        out = tape.named['final_fc.3']
+        self.last_angles = tape.user['final_fc.3'].view(n, out.c)
+        if target is None or tuple(target.shape) != (n, out.c):
+            raise ValueError('target must be [%d, %d] rows of [cos, sin], got %s'
+                             % (n, out.c, None if target is None else tuple(target.shape)))
+        dpad = torch.zeros(n * out.cs, dtype=torch.float32, device=self.dev)
+        _lib.check(self.L.egn_elem_loss_f32(_lib.ptr(tape.data[id(out)]), _lib.ptr(target), n, out.c, out.cs, out.c,
+                                            self.angle_crit, 1.0, 0, _lib.ptr(dpad), _lib.ptr(self.loss_dev), st),
+                   'angle loss')
+        tape.grad[id(out)] = [dpad, True]
 
     def _pixshuf_loss(self, tape, target, joints_xy, joints_vis, target_weight, n, h, w, st):
         """The pixel-shuffle head's JointsMSELoss-style term (hrnet.py:373-383, 598-600; function.py:22-46) as ONE
@@ -820,6 +854,9 @@ class HRNetTrainStep(TapeOwner):
         m, L = self.model, self.L
         if not m.training:
             raise RuntimeError('HRNetTrainStep.step needs model.train()')
+        if self.angle_crit is not None and not (joints_xy is None and joints_vis is None and target_weight is None):
+            raise ValueError("the angle head's step takes (images, target [N,2]) only: joints_xy, joints_vis and "
+                             'target_weight belong to the heat-map and coordinate heads')
         images = images.contiguous().float()
         if target is not None:
             target = target.contiguous().float()
@@ -834,7 +871,10 @@ class HRNetTrainStep(TapeOwner):
             self.walker._record(n, cin, h, w, None, r=tape)
             J = m.num_joints
             self.counters.tick(tape.bns, self.loss_dev, st)       # num_batches_tracked += 1, loss = 0: one launch
-            if m.head_type == 'coordinates':
+            if m.head_type == 'angleregression':
+                aug = None
+                self._angle_loss(tape, target, n, st)             # loss and gradient seed in one launch
+            elif m.head_type == 'coordinates':
                 aug, coords = tape.named['head1'], tape.named['head2.4']
                 cd = tape.user['head2.4'].view(n, 2 * J)          # compact [N, 2K] = coords [N,K,2]
                 self.last_coords = cd.view(n, J, 2)
@@ -870,7 +910,9 @@ class HRNetTrainStep(TapeOwner):
             else:
                 aug = tape.named['final_layer']
                 self.last_maps = tape.user['final_layer']
-            if aug is None:
+            if self.angle_crit is not None:
+                pass                                              # no map term for the angle head
+            elif aug is None:
                 self._pixshuf_loss(tape, target, joints_xy, joints_vis, target_weight, n, h, w, st)
             else:
                 if target is None:

@@ -16,7 +16,9 @@ ignore the autograd mode in eval mode) -- then the caller's loss / evaluator obj
 executed: the loss weights come from ``loss_func.comp_dict`` when it has one
 (JointsCompositeLoss, function.py:61-93) else from
 ``cfgs['heatmapModel']['loss_weight_list']``; the learning rate of every epoch is
-read from ``optim.param_groups`` after ``sche.step()``.  Plotting and debug-image
+read from ``optim.param_groups`` after ``sche.step()``.  For the 'angleregression' head
+(exp_type baselinealpha / baselinetheta) the criterion's class name -- ``MSELoss1D`` / ``SmoothL1Loss1D``,
+function.py:204-228 -- or ``cfgs['heatmapModel']['loss_type']`` selects the native step's ``angle_type``.  Plotting and debug-image
 dumps of the reference are not reproduced.
 """
 import gc
@@ -170,12 +172,38 @@ def _loss_weights(loss_func, cfgs):
     return w_hm, w_coor, cr
 
 
+_ANGLE_CRITERIA = {'MSELoss1D': 'mse', 'MSELoss': 'mse', 'SmoothL1Loss1D': 'sl1', 'SmoothL1Loss': 'sl1'}
+
+
+def _angle_type(loss_func, cfgs):
+    """'mse' / 'sl1' for the angle head: from the criterion object's class name, then from
+    cfgs['heatmapModel']['loss_type'] (train_IGRs.py:42 evaluates that name in libs/loss/function.py)."""
+    name = type(loss_func).__name__ if loss_func is not None else None
+    if name in _ANGLE_CRITERIA:
+        reduction = getattr(getattr(loss_func, 'criterion', loss_func), 'reduction', 'mean')
+        if reduction != 'mean':
+            raise NotImplementedError("%s(reduction=%r): the native angle step averages over the 2N elements "
+                                      "('mean')" % (name, reduction))
+        return _ANGLE_CRITERIA[name]
+    cfg_name = cfgs.get('heatmapModel', {}).get('loss_type')
+    if cfg_name in _ANGLE_CRITERIA:
+        return _ANGLE_CRITERIA[cfg_name]
+    raise NotImplementedError("the 'angleregression' head trains with MSELoss1D or SmoothL1Loss1D "
+                              '(libs/loss/function.py:204-228); got loss_func %s and heatmapModel.loss_type %r'
+                              % (name, cfg_name))
+
+
 def make_step(model, cfgs, loss_func=None, optim=None):
     """The native step object for ``model`` (HC or L), configured like the reference's loss / optimizer."""
     lr = optim.param_groups[0]['lr'] if optim is not None else cfgs['optimizer']['lr']
     sync = parallel.FlatGradSync() if torch.distributed.is_available() and torch.distributed.is_initialized() \
         and torch.distributed.get_world_size() > 1 else None
     inner = model.module if hasattr(model, 'module') else model          # DataParallel / DDP wrappers
+    if isinstance(inner, PoseHighResolutionNet) and inner.head_type == 'angleregression':
+        step = HRNetTrainStep(inner, lr=lr, grad_sync=sync, angle_type=_angle_type(loss_func, cfgs),
+                              **_optim_kwargs(optim, cfgs))
+        step.apply_cr_loss = False
+        return step
     if isinstance(inner, PoseHighResolutionNet):
         w_hm, w_coor, cr = _loss_weights(loss_func, cfgs)
         sigma = cfgs.get('heatmapModel', {}).get('sigma', 1)
@@ -306,6 +334,7 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
     eval_start = ts.get('eval_start_epoch', 0)
     step = make_step(model, cfgs, loss_func, optim)
     is_hc = isinstance(step, HRNetTrainStep)
+    is_angle = is_hc and step.angle_crit is not None           # baselinealpha / baselinetheta: one term, no L_cr
     dev = step.dev
     # a metric with accumulate / read / reset (metric.criterions.DistanceSrcMeter) keeps its running sums on the device
     metric_on_device = metric_func is not None and hasattr(metric_func, 'accumulate')
@@ -315,7 +344,7 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
         _make_host_group()      # all ranks are here together: the group exists before anyone has to wait in it
     try:
         for epoch in range(1, total_epochs + 1):
-            if epoch > 1 and is_hc:
+            if epoch > 1 and is_hc and not is_angle:
                 step.apply_cr_loss = True                       # trainer.py:168-169: L_cr from the second epoch on
             model.train()
             if sche is not None:
@@ -333,7 +362,10 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
                 data, target, weights, meta = batch
                 data = data.to(dev, non_blocking=True)
                 target = target.to(dev, non_blocking=True)
-                if is_hc:
+                if is_angle:
+                    loss = step.step(data, target)
+                    prediction = step.last_angles
+                elif is_hc:
                     joints = meta['transformed_joints'] if step.w_coor else None
                     loss = step.step(data, target, joints,
                                      target_weight=weights if step.use_target_weight else None)

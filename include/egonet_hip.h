@@ -300,7 +300,8 @@ int egn_crop_warp_normalize_u8(const uint8_t* img, int H, int W, int pitch,
  *   frame_tab  [n_frames][4] int64: byte offset into `frames`, H, W, row pitch (bytes)
  *   box_frame  [n] int32 frame index of each box (outside [0, n_frames): border only)
  *   M          [n,6] f64 forward affines image -> crop; out [n,3,out_h,out_w] f32
- * Per-pixel semantics are exactly those of egn_crop_warp_normalize_u8.  n <= 65535, out_w <= 4096. */
+ * Per-pixel semantics are exactly those of egn_crop_warp_normalize_u8.  n <= 65535, out_w <= 4096.
+ * The launch is added to the launch counter. */
 int egn_crop_frames_warp_normalize_u8(const uint8_t* frames, const long long* frame_tab,
                                       int n_frames, const int* box_frame, const double* M,
                                       int n, int out_h, int out_w, const float* mean,
@@ -569,7 +570,8 @@ int egn_fuse_bwd_f32(const float* dy, const float* y, float* g, int N, int H,
  *   joints [N,K,3] f64 (x, y, unused) in input pixels; vis [N,K] f32 or NULL
  *   target [N,K,H,W] f32 out; weight [N,K] f32 out (vis, zeroed where the dot
  *   is completely out of bounds), may be NULL
- *   stride_x = input_size[0]/heatmap_size[0], stride_y = input_size[1]/heatmap_size[1] */
+ *   stride_x = input_size[0]/heatmap_size[0], stride_y = input_size[1]/heatmap_size[1]
+ * The launch is added to the launch counter. */
 int egn_gaussian_targets_f32(const double* joints, const float* vis, int N, int K,
                              int H, int W, double stride_x, double stride_y,
                              double sigma, float* target, float* weight,
@@ -804,6 +806,27 @@ int egn_kpt_metrics_update_f32(const float* hm, const float* coords, int N, int 
                                const double* original_joints, int n, double img_w, double img_h, void* ws,
                                long ws_bytes, double* acc, double* src_coord, float* joints_pred, float* max_vals,
                                void* stream);
+
+/* ------------------------------------------------------------------------
+ * The angle-regression baselines' metric on the device (csrc/angle_metrics.hip).  Replaces the per-batch
+ * .cpu().numpy() of libs/metric/criterions.py:40-55 (get_angle_error) behind AngleError (:145-171) and the metric_func
+ * of the training loop (libs/trainer/trainer.py:200-205).  Every launch is added to the launch counter.
+ *
+ * Accumulator: EGN_ANGLE_METRICS_ACC_DOUBLES float64 on the device: [0] rows counted, [1] sum of their errors in
+ *   degrees; the mean error is [1] / [0].  The reset zeroes it; it must run once before the first update.
+ * The update folds one batch in: row i of pred (float32, row pitch ld >= 2 floats, only columns 0 and 1 are read:
+ *   [cos, sin]) against angles_gt[i] (float64, radians): d = |gt - atan2(sin, cos)| * 180 / pi with the atan2 in
+ *   float64, and 360 - d where d > 180.
+ *   ws: the ws_bytes query's size for N, contents irrelevant between calls.
+ *   Two launches: one thread per row, one {count, sum} partial per block (plain stores, no atomics); a single wave
+ *   folds the partials into acc in a fixed order, so equal inputs give equal bits.  N == 0 is a no-op (no launch).
+ *   N < 0 or past 2^31 - 1, ld < 2, a NULL acc, and with N > 0 a NULL pred / angles_gt / ws or a short ws:
+ *   EGN_E_BADARG. */
+#define EGN_ANGLE_METRICS_ACC_DOUBLES 2
+long egn_angle_metrics_ws_bytes(long N);
+int egn_angle_metrics_reset(double* acc, void* stream);
+int egn_angle_metrics_update_f32(const float* pred, long N, int ld, const double* angles_gt, void* ws, long ws_bytes,
+                                 double* acc, void* stream);
 
 #ifdef __cplusplus
 }

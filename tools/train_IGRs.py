@@ -4,6 +4,7 @@
     python tools/train_IGRs.py --kitti <dir with image_2 label_2 calib> [--split-file <stems>]
         [--valid-split-file <stems>] --out <dir> [--epochs 45] [--batch-frames 8] [--eval-every N] [--seed S]
         [--tiny] [--max-steps N] [--workers 4] [--report-every 30] [--lr 1e-3]
+        [--exp-type instanceto2d|baselinealpha|baselinetheta] [--loss-type MSELoss1D|SmoothL1Loss1D]
 
 Labels + calibration -> ``PoseAnnotBuilder`` (the 2-D pose annotations, built on the device:
 egonet_amd.common.pose_annot) -> ``PoseFrames`` -> ``DataLoader(collate_fn=collate_frames)`` (frames decoded in the
@@ -19,6 +20,12 @@ small network of tools/inference_kitti.py --tiny (tests).  One JSON line is prin
 dropped at each of the two filters, steps, ``last_loss``, the output path.  ``last_loss`` is the last loss the trainer
 REPORTED (every ``--report-every`` batches of an epoch, starting with batch 0), not the last step's: with
 ``--report-every 30 --max-steps 2`` it is step 0's.
+
+``--exp-type baselinealpha | baselinetheta`` trains the paper's direct-regression baselines instead: the same backbone
+with the 'angleregression' head on targets ``[cos r, sin r]`` of ``alpha`` / ``rot_y`` (``PoseFrames`` carries the
+annotations' ``rots``, ``TrainSampleBuilder(target=...)`` emits them), the criterion ``--loss-type`` on the native step,
+``AngleErrorMeter`` as the training metric and ``AngleError`` for validation; the state dict goes to
+``<exp-type>.pth``.
 """
 import argparse
 import json
@@ -32,19 +39,32 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from egonet_amd import configs, trainer                                  # noqa: E402
 from egonet_amd.common import crop_gpu, pose_annot, train_samples          # noqa: E402
-from egonet_amd.metric.criterions import DistanceSrcMeter, Evaluator       # noqa: E402
+from egonet_amd.loss import function as loss_function                      # noqa: E402
+from egonet_amd.metric.criterions import AngleErrorMeter, DistanceSrcMeter, Evaluator       # noqa: E402
 from egonet_amd.model.heatmapModel import hrnet                            # noqa: E402
 
 
 def igr_cfgs(a):
     """The keys of configs/KITTI_train_IGRs.yml that the builders, the model and the trainer read."""
-    cfg = configs.clone(configs.hrnet_config(8, (64, 64), 33, 'coordinates', modules=(1, 1, 1), num_blocks=1)
-                        if a.tiny else configs.w48_config('coordinates'))
+    exp_type = getattr(a, 'exp_type', 'instanceto2d')
+    angle = exp_type in train_samples.EXP_TARGETS
+    if angle:
+        # the angle head pools a 4 x 4 map behind four stride-2 blocks (hrnet.py:384-422): 256 x 256 crops, tiny or not
+        cfg = configs.clone(configs.hrnet_config(8, (256, 256), 33, 'angleregression', modules=(1, 1, 1), num_blocks=1)
+                            if a.tiny else configs.w48_config('angleregression'))
+    else:
+        cfg = configs.clone(configs.hrnet_config(8, (64, 64), 33, 'coordinates', modules=(1, 1, 1), num_blocks=1)
+                            if a.tiny else configs.w48_config('coordinates'))
+    metric = 'AngleError' if angle else 'JointDistance2DSIP'
     cfg['heatmapModel'].update(jitter_bbox=True, jitter_params={'shift': [0.1, 0.1], 'scaling': [0.4, 0.4]},
                                loss_type='JointsCompositeLoss', loss_spec_list=['mse', 'l1', 'sl1'],
                                loss_weight_list=[1.0, 0.1, 'None'], cr_loss_threshold=0.15, target_type='gaussian',
                                sigma=1)
-    cfg.update(train=True, use_gpu=True, exp_type='instanceto2d',
+    if angle:
+        cfg['heatmapModel']['loss_type'] = a.loss_type          # one criterion: no spec / weight lists
+        for key in ('loss_spec_list', 'loss_weight_list', 'cr_loss_threshold'):
+            del cfg['heatmapModel'][key]
+    cfg.update(train=True, use_gpu=True, exp_type=exp_type,
                dataset={'name': 'KITTI', 'detect_classes': ['Car'], '3d_kpt_sample_style': 'bbox9',
                         'interpolate': {'flag': True, 'style': 'bbox12', 'coef': [0.332, 0.667]},
                         '2d_kpt_style': 'bbox9',
@@ -54,11 +74,11 @@ def igr_cfgs(a):
                training_settings={'total_epochs': a.epochs, 'batch_size': a.batch_frames, 'num_threads': a.workers,
                                   'shuffle': True, 'use_target_weight': False, 'report_every': a.report_every,
                                   'eval_every': a.eval_every, 'eval_during': a.eval_every > 0,
-                                  'eval_metrics': ['JointDistance2DSIP'], 'plot_loss': False},
+                                  'eval_metrics': [metric], 'plot_loss': False},
                # the validation batches are built by a device front end inside collate_fn: no worker processes
                testing_settings={'batch_size': a.batch_frames, 'num_threads': 0, 'shuffle': False,
                                  'apply_dropout': False, 'unnormalize': False, 'arg_max': 'hard',
-                                 'eval_metrics': ['JointDistance2DSIP'], 'alpha_mode': 'proj'})
+                                 'eval_metrics': [metric], 'alpha_mode': 'proj'})
     return cfg
 
 
@@ -136,11 +156,19 @@ def main(argv=None):
     ap.add_argument('--workers', type=int, default=4)
     ap.add_argument('--report-every', type=int, default=30)
     ap.add_argument('--lr', type=float, default=1e-3)
+    ap.add_argument('--exp-type', default='instanceto2d', choices=['instanceto2d'] + sorted(train_samples.EXP_TARGETS))
+    ap.add_argument('--loss-type', default='MSELoss1D', choices=['MSELoss1D', 'SmoothL1Loss1D'],
+                    help='criterion of the angle baselines (libs/loss/function.py:204-228)')
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format='%(message)s')
     logger = logging.getLogger('train_IGRs')
     cfgs = igr_cfgs(a)
+    angle = a.exp_type in train_samples.EXP_TARGETS
+    metric = cfgs['testing_settings']['eval_metrics'][0]
     model = build_model(cfgs, a.seed)
+    # train_IGRs.py:42: the criterion named by the config; the native step reads which one it is
+    loss_func = getattr(loss_function, a.loss_type)() if angle else None
+    target = train_samples.EXP_TARGETS.get(a.exp_type, 'heatmap')
 
     annot_builder = pose_annot.PoseAnnotBuilder(cfgs, 'train')
     annot = annot_builder(pose_annot.kitti_records(a.kitti, read_stems(a.split_file) if a.split_file else None))
@@ -156,31 +184,33 @@ def main(argv=None):
         valid_annot = annot if not a.valid_split_file else pose_annot.PoseAnnotBuilder(cfgs, 'valid')(
             pose_annot.kitti_records(a.kitti, read_stems(a.valid_split_file)))
         valid_frames = pose_annot.PoseFrames(valid_annot)
-        valid_builder = train_samples.TrainSampleBuilder(cfgs, split='valid')      # no jitter (img_proc.py:217)
-        evaluator = Evaluator(['JointDistance2DSIP'], cfgs)
+        valid_builder = train_samples.TrainSampleBuilder(cfgs, split='valid', target=target)      # no jitter (img_proc.py:217)
+        evaluator = Evaluator([metric], cfgs)
 
         def valid_collate(batch):
             return valid_builder(train_samples.collate_frames(batch))
 
         def evaluate_fn(dataset, mdl, epoch):
-            return trainer.evaluate(dataset, mdl, None, cfgs, logger, evaluator, collate_fn=valid_collate, epoch=epoch)
+            return trainer.evaluate(dataset, mdl, loss_func, cfgs, logger, evaluator, collate_fn=valid_collate,
+                                    epoch=epoch)
 
     optim, sche = trainer.prepare_optim(model, cfgs)
-    record = trainer.train(train_set, model, None, optim, sche, cfgs, logger, metric_func=DistanceSrcMeter(cfgs),
+    record = trainer.train(train_set, model, loss_func, optim, sche, cfgs, logger,
+                           metric_func=AngleErrorMeter(cfgs) if angle else DistanceSrcMeter(cfgs),
                            valid_dataset=valid_frames, evaluate_fn=evaluate_fn,
-                           sample_builder=train_samples.TrainSampleBuilder(cfgs, split='train'))
+                           sample_builder=train_samples.TrainSampleBuilder(cfgs, split='train', target=target))
     if a.valid_split_file:                                  # trainer.py:395-513 over the validation split
         evaluate_fn(valid_frames, model, None)
         model.train()
 
     os.makedirs(a.out, exist_ok=True)
-    path = os.path.join(a.out, 'HC.pth')
+    path = os.path.join(a.out, a.exp_type + '.pth' if angle else 'HC.pth')
     logger.info('=> saving final model state to {}'.format(path))
     torch.save({k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, path)
     out = dict(counts, steps=train_set.steps, last_loss=record['loss'][-1] if record['loss'] else None, out=path)
     if evaluator is not None and evaluator.metrics[0].count:
         m = evaluator.metrics[0]
-        out['eval'] = {'metric': 'JointDistance2DSIP', 'mean': float(m.mean), 'count': int(m.count)}
+        out['eval'] = {'metric': metric, 'mean': float(m.mean), 'count': int(m.count)}
     print(json.dumps(out))
     return out
 
