@@ -15,11 +15,9 @@ boxes, affines and subset.  What is heavy runs on the device: the uint8 frames g
 ``egn_gaussian_targets_f32`` draws all maps.  ``meta`` is host numpy, computed before the upload, so reading it
 needs no device synchronisation.
 
-Upload.  Frames, the frame table, the per-box frame index, the affines, joints and visibilities are packed into
-one pinned staging buffer and sent by ONE ``non_blocking`` copy on the current stream; the kernels and the
-training step that follow run on that stream, so their ordering needs nothing more.  The staging buffers are
-double-buffered and each is guarded by an event recorded after its copy: a call refills buffer ``k`` only after
-waiting on ``k``'s event (the copy two calls back), so a copy still in flight is never overwritten.
+Upload.  Frames, the frame table, the per-box frame index, the affines, joints and visibilities go up as the
+sections of ONE pinned, double-buffered, event-guarded ``non_blocking`` copy on the current stream
+(common/staging.py); the kernels and the training step that follow run on that stream.
 
 Decode stays in the ``DataLoader`` workers: a Dataset returns records (see ``INTEGRATION.md``), ``collate_frames``
 keeps them as a list, ``TrainSampleBuilder`` turns the list into the batch.
@@ -30,13 +28,12 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import crop_gpu
+from . import crop_gpu, staging
 
 MAX_INS_CNT = 140              # car_instance.py:33
 TARGETS = {'heatmap': None, 'alpha': 0, 'theta': 1}       # the column of a record's ``rots`` an angle mode regresses
 EXP_TARGETS = {'baselinealpha': 'alpha', 'baselinetheta': 'theta'}      # cfgs['exp_type'], car_instance.py:1248
 SIZE = 200.0
-_ALIGN = 256                   # byte alignment of every section of the staging buffer
 
 
 def collate_frames(batch):
@@ -90,9 +87,7 @@ class TrainSampleBuilder(object):
         self.jitter = bool(hm.get('jitter_bbox', False)) and split == 'train' and bool(cfgs.get('train', False))
         self.scaling = tuple(hm['jitter_params']['scaling']) if self.jitter else None
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        self._pinned = [None, None]
-        self._events = [None, None]
-        self._turn = 0
+        self._staging = staging.PinnedStaging(1 << 20)
         # True: every call keeps {'host_ms', 'events'} in last_timings -- four timing events: before the upload,
         # after it, after the crop launch, after the targets launch (tools/train_samples_bench.py reads them after a synchronise)
         self.record_timings = False
@@ -227,17 +222,33 @@ class TrainSampleBuilder(object):
         return p
 
     # -- device work ---------------------------------------------------------------------------------------------
-    def _staging(self, nbytes):
-        """The pinned buffer of this call (double-buffered, event-guarded: see the module docstring)."""
-        k = self._turn
-        self._turn ^= 1
-        if self._events[k] is not None:
-            self._events[k].synchronize()           # the copy that last read buffer k has finished
-        buf = self._pinned[k]
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
-            self._pinned[k] = buf
-        return k, buf
+    def pack(self, records, p):
+        """The host arrays of a batch's one upload, in staging order (host only): the frames that keep a box as
+        ('frame', f), the frame table [offset in the block, rows, columns, row pitch], the per-box frame index, the
+        affines, then the targets' inputs."""
+        n = len(p['kept'])
+        used = np.unique(p['frame'])
+        remap = np.full(len(records), -1, dtype=np.int64)
+        remap[used] = np.arange(len(used))
+        arrays = {}
+        for f in used:
+            img = records[f]['image']
+            img = img.numpy() if torch.is_tensor(img) else np.asarray(img)
+            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+                raise ValueError('record %d: image must be [H,W,3] uint8 RGB, got %s %s' % (f, img.dtype, img.shape))
+            arrays['frame', f] = img
+        tab = arrays['tab'] = np.empty((len(used), 4), dtype=np.int64)
+        arrays['box_frame'] = remap[p['frame']].astype(np.int32)
+        arrays['M'] = np.asarray(p['trans'], dtype=np.float64).reshape(n, 6)
+        if self.rot_col is not None:
+            arrays['angles'] = np.asarray(p['targets'], dtype=np.float32).reshape(n, 2)
+        else:
+            arrays['joints'] = np.asarray(p['meta']['transformed_joints'], dtype=np.float64)
+            arrays['vis'] = p['meta']['joints_vis'].astype(np.float32)
+        where, _ = staging.layout([(name, a.nbytes) for name, a in arrays.items()], staging.ALIGN)
+        tab[:] = [[where['frame', f], arrays['frame', f].shape[0], arrays['frame', f].shape[1],
+                   3 * arrays['frame', f].shape[1]] for f in used]
+        return arrays
 
     def __call__(self, records, rng=np.random):
         t0 = time.perf_counter()
@@ -246,92 +257,40 @@ class TrainSampleBuilder(object):
         K = self.num_joints
         h, w = self.input_hw
         hm_h, hm_w = self.heatmap_hw
-        used = np.unique(p['frame'])
-        remap = np.full(len(records), -1, dtype=np.int64)
-        remap[used] = np.arange(len(used))
-        frames = []
-        for f in used:
-            img = records[f]['image']
-            img = img.numpy() if torch.is_tensor(img) else np.asarray(img)
-            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
-                raise ValueError('record %d: image must be [H,W,3] uint8 RGB, got %s %s' % (f, img.dtype, img.shape))
-            frames.append(img)
-
-        def up(nbytes):
-            return (nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
-        offs, total = [], 0
-        for img in frames:
-            offs.append(total)
-            total += up(img.nbytes)
-        angle = self.rot_col is not None
-        sections = [('tab', (len(frames), 4), np.int64), ('box_frame', (n,), np.int32), ('M', (n, 6), np.float64)]
-        sections += [('angles', (n, 2), np.float32)] if angle else \
-            [('joints', (n, K, 3), np.float64), ('vis', (n, K), np.float32)]
-        where = {}
-        for name, shape, dt in sections:
-            where[name] = total
-            total += up(int(np.prod(shape)) * np.dtype(dt).itemsize)
-        k, pinned = self._staging(total)
-        host = pinned.numpy()
-        for img, off in zip(frames, offs):
-            host[off:off + img.nbytes] = np.ascontiguousarray(img).reshape(-1)
-        tab = np.array([[off, img.shape[0], img.shape[1], 3 * img.shape[1]] for img, off in zip(frames, offs)],
-                       dtype=np.int64)
-        values = {'tab': tab, 'box_frame': remap[p['frame']].astype(np.int32), 'M': p['trans'].reshape(n, 6)}
-        if angle:
-            values['angles'] = p['targets']
-        else:
-            values.update(joints=meta['transformed_joints'], vis=meta['joints_vis'].astype(np.float32))
-        for name, shape, dt in sections:
-            a = np.ascontiguousarray(values[name], dtype=dt).reshape(-1)
-            host[where[name]:where[name] + a.nbytes] = a.view(np.uint8)
+        arrays = self.pack(records, p)
         dev = self.device
-        host_ms = (time.perf_counter() - t0) * 1e3
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if self.record_timings else None
+
+        def host_part_ends(stream):
+            self.last_timings = {'host_ms': (time.perf_counter() - t0) * 1e3, 'events': ev}
+            ev[0].record(stream)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
-            staged = torch.empty(total, dtype=torch.uint8, device=dev)
-            if ev:
-                ev[0].record(stream)
-            staged.copy_(pinned[:total], non_blocking=True)
-            if self._events[k] is None:
-                self._events[k] = torch.cuda.Event()
-            self._events[k].record(stream)
-            if ev:
-                ev[1].record(stream)
-
-            def view(name, shape, dt):
-                nb = int(np.prod(shape)) * torch.empty(0, dtype=dt).element_size()
-                return staged[where[name]:where[name] + nb].view(dt).view(*shape)
-            tab_d = view('tab', (len(frames), 4), torch.int64)
-            frame_d = view('box_frame', (n,), torch.int32)
-            M_d = view('M', (n, 6), torch.float64)
+            d, staged = self._staging.upload(arrays, dev, views=[k for k in arrays if type(k) is str],
+                                             before_copy=host_part_ends if ev else None,
+                                             after_copy=ev[1].record if ev else None)
             mean_t, std_t = crop_gpu._norm_consts(self.mean, self.std, dev)
             images = torch.empty(n, 3, h, w, dtype=torch.float32, device=dev)
             L = _lib.lib()
             st = _lib.current_stream(dev)
-            _lib.check(L.egn_crop_frames_warp_normalize_u8(_lib.ptr(staged), _lib.ptr(tab_d), len(frames),
-                                                           _lib.ptr(frame_d), _lib.ptr(M_d), n, h, w,
+            _lib.check(L.egn_crop_frames_warp_normalize_u8(_lib.ptr(staged), _lib.ptr(d['tab']), len(arrays['tab']),
+                                                           _lib.ptr(d['box_frame']), _lib.ptr(d['M']), n, h, w,
                                                            _lib.ptr(mean_t), _lib.ptr(std_t), _lib.ptr(images), st),
                        'crop frames')
             if ev:
                 ev[2].record(stream)
-            if angle:
+            if self.rot_col is not None:
                 # the targets came up with the staging copy; the dummy weight of my_collate_fn (car_instance.py:1388-1390)
                 if ev:
                     ev[3].record(stream)
-                    self.last_timings = {'host_ms': host_ms, 'events': ev}
-                return images, view('angles', (n, 2), torch.float32), torch.ones(1), meta
-            joints_d = view('joints', (n, K, 3), torch.float64)
-            vis_d = view('vis', (n, K), torch.float32)
+                return images, d['angles'], torch.ones(1), meta
             targets = torch.empty(n, K, hm_h, hm_w, dtype=torch.float32, device=dev)
             weights = torch.empty(n, K, 1, dtype=torch.float32, device=dev)
             # the reference's stride quirk (img_proc.py:376-378): input_size / heatmap_size in (h, w) order, the
             # first of them divides x -- egn_gaussian_targets_f32 takes the two strides in that order
-            _lib.check(L.egn_gaussian_targets_f32(_lib.ptr(joints_d), _lib.ptr(vis_d), n, K, hm_h, hm_w,
+            _lib.check(L.egn_gaussian_targets_f32(_lib.ptr(d['joints']), _lib.ptr(d['vis']), n, K, hm_h, hm_w,
                                                   float(h) / float(hm_h), float(w) / float(hm_w), self.sigma,
                                                   _lib.ptr(targets), _lib.ptr(weights), st), 'gaussian targets')
             if ev:
                 ev[3].record(stream)
-                self.last_timings = {'host_ms': host_ms, 'events': ev}
         return images, targets, weights, meta

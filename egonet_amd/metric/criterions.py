@@ -10,6 +10,7 @@ counts -- is per-instance host arithmetic in float64 like the reference's.
 ``JointDistance2DSIP`` with CUDA predictions and ``DistanceSrcMeter`` (the training loop's
 ``metric_func``) run all of it on the device instead (csrc/kpt_metrics.hip: decode, rescale,
 closed-form inverse affine, distances, PCK counts, a device accumulator) and read back once.
+Host ``meta`` arrays go up through common/staging.py; every device accumulator is a ``_DeviceAcc``.
 
 ``get_angle_error`` / ``AngleError`` with CUDA predictions and ``AngleErrorMeter`` (the angle baselines' ``metric_func``)
 run on the device too (csrc/angle_metrics.hip: atan2 in float64, the wrapped difference, a {count, sum} accumulator).
@@ -28,13 +29,16 @@ Out of scope, each a ``NotImplementedError``: ``T_style`` / ``style`` 'procruste
 prediction IN PLACE, criterions.py:285-292, so the rotation error after it is that of the aligned points),
 ``R_style`` other than 'euler' (:266-267) and ``3d_kpt_sample_style`` other than 'bbox9' (:399-402).
 """
+import functools
+
 import numpy as np
 import torch
 
+from .. import _lib
 from ..common import img_proc as lip
+from ..common.staging import PinnedStaging
 
 PCK_THRES = np.array([0.1, 0.2, 0.3])
-_ANGLE_CALL = None                                  # get_angle_error's device accumulator for CUDA predictions
 
 
 def get_distance(gt, pred):
@@ -62,17 +66,21 @@ def get_angle_error(pred, meta_data, cfgs=None):
     None.  numpy arrays and CPU tensors: host arithmetic like the reference's; a CUDA prediction: csrc/angle_metrics.hip
     and one read-back of the {count, sum} pair."""
     if torch.is_tensor(pred) and pred.is_cuda:
-        global _ANGLE_CALL
-        if _ANGLE_CALL is None or (_ANGLE_CALL._acc is not None and _ANGLE_CALL._acc.device != pred.device):
-            _ANGLE_CALL = _AngleMetricsDevice()     # an accumulator of its own (and its pinned staging), kept
-        _ANGLE_CALL.update(pred, meta_data)
-        acc = _ANGLE_CALL.take()
-        return acc[1] / len(pred), len(pred), None
+        call = _angle_call(pred.device)
+        call.update(pred, meta_data)
+        return call.take()[1] / len(pred), len(pred), None
     if not isinstance(pred, np.ndarray):
         pred = pred.data.cpu().numpy()
     dif = np.abs(meta_data['angles_gt'] - np.arctan2(pred[:, 1], pred[:, 0])) * 180 / np.pi
     dif = np.where(dif > 180, 360 - dif, dif)
     return dif.sum() / len(pred), len(pred), None
+
+
+@functools.lru_cache(maxsize=None)
+def _angle_call(device):
+    """get_angle_error's device side for CUDA predictions on ``device``: an accumulator (and a pinned staging) of its
+    own, kept."""
+    return _AngleMetricsDevice()
 
 
 def _decode(output, arg_max):
@@ -125,7 +133,123 @@ def get_distance_src(output, meta_data, cfgs=None, image_size=(256.0, 256.0), ar
     return sum(distances) / cnt, cnt, others
 
 
-class AngleError(object):
+# ---- what the device paths share ---------------------------------------------------------------------------------
+class _DeviceAcc(object):
+    """``n_doubles`` float64 in HBM that a metric's kernels fold into, and the kernels' workspace.
+    ``reset_fn(accumulator pointer, stream)`` launches the metric's reset and returns its status; ``what`` names the
+    metric in errors.  ``pending``: updates were launched since the last read-back (the owner sets it)."""
+
+    def __init__(self, n_doubles, reset_fn, what):
+        self.n_doubles, self._reset_fn, self.what = n_doubles, reset_fn, what
+        self.tensor = self._ws = None
+        self.pending = False
+
+    def _launch_reset(self, stream):
+        _lib.check(self._reset_fn(_lib.ptr(self.tensor), stream), self.what + ' reset')
+
+    def ensure(self, dev, stream):
+        """The accumulator on ``dev``, allocated and reset at the first use."""
+        if self.tensor is None or self.tensor.device != dev:
+            if self.pending:
+                raise RuntimeError('the accumulator holds unread updates of another device')
+            self.tensor = torch.empty(self.n_doubles, dtype=torch.float64, device=dev)
+            self._launch_reset(stream)
+        return self.tensor
+
+    def workspace(self, nbytes, dev):
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return self._ws
+
+    def peek(self):
+        """The accumulator's float64 on the host (synchronises); zeros before the first update."""
+        if self.tensor is None:
+            return np.zeros(self.n_doubles)
+        return self.tensor.cpu().numpy()
+
+    def reset(self):
+        """Reset the accumulator (a launch, no synchronisation)."""
+        self.pending = False
+        if self.tensor is None:
+            return
+        with torch.cuda.device(self.tensor.device):
+            self._launch_reset(_lib.current_stream(self.tensor.device))
+
+    def take(self):
+        """The one read-back: the accumulator's values, and the accumulator reset."""
+        acc = self.peek()
+        self.reset()
+        return acc
+
+
+class _MetricsDevice(object):
+    """The device side of a 2-D metric: one accumulator, whose ``peek`` / ``reset`` / ``take`` / ``pending`` it
+    hands out, and the pinned staging of the host ``meta`` arrays."""
+
+    def __init__(self, n_doubles, reset_fn, what):
+        acc = self._acc = _DeviceAcc(n_doubles, reset_fn, what)
+        self.peek, self.reset, self.take = acc.peek, acc.reset, acc.take
+        self._staging = PinnedStaging(1 << 16)
+
+    pending = property(lambda self: self._acc.pending)
+
+
+def _synced(name):
+    """The host attribute ``name`` behind ``self._sync()``: the first access reads the device accumulator back."""
+    def get(self):
+        self._sync()
+        return getattr(self, name)
+
+    def put(self, value):
+        self._sync()
+        setattr(self, name, value)
+    return property(get, put)
+
+
+class _RunningMean(object):
+    """``count`` / ``mean`` of a 2-D metric: host updates, and the updates ``_dev`` folded on the device, merged at the
+    first access."""
+    count, mean = _synced('_count'), _synced('_mean')
+
+    def _sync(self):
+        """The one read-back: the device accumulator is merged into the host attributes and reset.  Returns what was
+        merged, None if nothing was counted."""
+        if not self._dev.pending:
+            return None
+        acc = self._dev.take()
+        cnt = int(acc[0])
+        if cnt == 0:
+            return None
+        self._mean = (self._mean * self._count + acc[1]) / (self._count + cnt)
+        self._count += cnt
+        return acc
+
+
+class _Meter(object):
+    """The meter contract of ``trainer.train``: ``accumulate(prediction, meta, cfgs=None)`` only launches; ``read()`` ->
+    (running mean, count, ...) since the last ``reset()`` is the read-back.  A subclass holds ``_dev`` and says when a
+    prediction is on the device (``_on_device``), what to raise otherwise (``_needs_cuda``) and how to launch
+    (``_update``)."""
+    _more = staticmethod(lambda acc: ())            # what read() returns after (mean, count)
+
+    def _check(self, prediction):
+        if not self._on_device(prediction):
+            raise TypeError(self._needs_cuda)
+
+    def accumulate(self, prediction, meta, cfgs=None):
+        self._check(prediction)
+        self._update(prediction, meta, cfgs)
+
+    def read(self):
+        acc = self._dev.peek()
+        cnt = int(acc[0])
+        return ((acc[1] / cnt if cnt else 0.0), cnt) + self._more(acc)
+
+    def reset(self):
+        self._dev.reset()
+
+
+class AngleError(_RunningMean):
     """Running mean of get_angle_error over an evaluation pass (criterions.py:145-171).  CUDA predictions are folded
     into a device accumulator (csrc/angle_metrics.hip): ``update`` only launches, the one read-back is in ``report()``
     or at the first access of ``count`` / ``mean``; numpy inputs and CPU tensors take the host path.  Both kinds of
@@ -136,30 +260,6 @@ class AngleError(object):
         self.name = 'Angle error in degrees'
         self.num_joints, self._count, self._mean = num_joints, 0, 0.
         self._dev = _AngleMetricsDevice()
-
-    def _sync(self):
-        """The one read-back: the device accumulator is merged into the host attributes and reset."""
-        if not self._dev.pending:
-            return
-        acc = self._dev.take()
-        cnt = int(acc[0])
-        if cnt == 0:
-            return
-        self._mean = (self._mean * self._count + acc[1]) / (self._count + cnt)
-        self._count += cnt
-
-    def _synced(name):
-        def get(self):
-            self._sync()
-            return getattr(self, name)
-
-        def put(self, value):
-            self._sync()
-            setattr(self, name, value)
-        return property(get, put)
-
-    count, mean = _synced('_count'), _synced('_mean')
-    del _synced
 
     def update(self, prediction, meta_data, ground_truth=None, logger=None):
         if self.device_update and torch.is_tensor(prediction) and prediction.is_cuda:
@@ -186,43 +286,13 @@ def _kpt_on_device(prediction):
     return torch.is_tensor(prediction) and prediction.is_cuda
 
 
-class _PinnedStaging(object):
-    """Host ``meta`` arrays travel in ONE pinned buffer and one non-blocking copy on the current stream; the buffer is
-    double-buffered and each half is guarded by an event, so a copy in flight is never overwritten (the scheme of
-    common/train_samples.py)."""
+class _KptMetricsDevice(_MetricsDevice):
+    """The device side of get_distance_src (csrc/kpt_metrics.hip): one accumulator in HBM, two launches per batch,
+    nothing read back before ``peek()``."""
 
     def __init__(self):
-        self._acc = self._ws = None
-        self._pinned, self._events, self._turn = [None, None], [None, None], 0
-        self.pending = False
-
-    def _upload_f64(self, flat, dev):
-        """``flat`` (host float64, 1-D) -> a device tensor, by one non-blocking copy out of the pinned buffer."""
-        total = flat.size
-        turn, pinned = self._staging(total * 8)
-        pinned[:total * 8].view(torch.float64).numpy()[:] = flat
-        staged = torch.empty(total, dtype=torch.float64, device=dev)
-        staged.copy_(pinned[:total * 8].view(torch.float64), non_blocking=True)
-        if self._events[turn] is None:
-            self._events[turn] = torch.cuda.Event()
-        self._events[turn].record(torch.cuda.current_stream(dev))
-        return staged
-
-    def _staging(self, nbytes):
-        k = self._turn
-        self._turn ^= 1
-        if self._events[k] is not None:
-            self._events[k].synchronize()           # the copy that last read buffer k has finished
-        buf = self._pinned[k]
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
-            self._pinned[k] = buf
-        return k, buf
-
-
-class _KptMetricsDevice(_PinnedStaging):
-    """The device side of get_distance_src (csrc/kpt_metrics.hip): one accumulator in HBM, two launches per batch,
-    nothing read back before ``read()``."""
+        super().__init__(_KPT_ACC_DOUBLES, lambda acc, st: _lib.lib().egn_kpt_metrics_reset(acc, st),
+                         'key-point metrics')
 
     def _labels(self, meta, K, dev):
         """center [n,2], scale [n,2], rotation [n], original_joints [n,K,3] as float64 device tensors."""
@@ -243,33 +313,12 @@ class _KptMetricsDevice(_PinnedStaging):
                 if a.shape[2] == 2:                           # no visibility column: every joint counts
                     a = np.concatenate([a, np.ones((n, K, 1))], axis=2)
             fields[key] = a.reshape(shape)
-        host = [k for k in _KPT_META if isinstance(fields[k], np.ndarray)]
-        if host and n:
-            total = sum(fields[k].size for k in host)
-            turn, pinned = self._staging(total * 8)
-            view = pinned[:total * 8].view(torch.float64).numpy()
-            off = 0
-            for k in host:
-                view[off:off + fields[k].size] = fields[k].reshape(-1)
-                off += fields[k].size
-            staged = torch.empty(total, dtype=torch.float64, device=dev)
-            staged.copy_(pinned[:total * 8].view(torch.float64), non_blocking=True)
-            if self._events[turn] is None:
-                self._events[turn] = torch.cuda.Event()
-            self._events[turn].record(torch.cuda.current_stream(dev))
-            off = 0
-            for k in host:
-                size = fields[k].size
-                fields[k] = staged[off:off + size].view(fields[k].shape)
-                off += size
-        elif host:
-            for k in host:
-                fields[k] = None
+        host = {k: fields[k] for k in _KPT_META if isinstance(fields[k], np.ndarray)}
+        fields.update(self._staging.upload(host, dev)[0] if host and n else dict.fromkeys(host))
         return n, fields
 
     def update(self, prediction, meta, image_size, arg_max, want=()):
         """Launch only.  ``want``: any of 'src_coord', 'joints_pred', 'max_vals' -> dict of device tensors."""
-        from .. import _lib
         if type(prediction) is tuple:
             hm, coords, mode = None, prediction[1].detach().float().contiguous(), 0
             if coords.dim() != 3 or coords.shape[2] != 2:
@@ -290,16 +339,11 @@ class _KptMetricsDevice(_PinnedStaging):
             if n > N:
                 raise ValueError('%d labelled instances for %d predictions' % (n, N))
             st = _lib.current_stream(dev)
-            if self._acc is None or self._acc.device != dev:
-                if self.pending:
-                    raise RuntimeError('the accumulator holds unread updates of another device')
-                self._acc = torch.empty(_KPT_ACC_DOUBLES, dtype=torch.float64, device=dev)
-                _lib.check(L.egn_kpt_metrics_reset(_lib.ptr(self._acc), st), 'key-point metrics reset')
+            acc = self._acc.ensure(dev, st)
             nb = L.egn_kpt_metrics_ws_bytes(N, K)
             if nb < 0:
                 raise ValueError('key-point metrics: %d x %d maps' % (N, K))
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nb:
-                self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            ws = self._acc.workspace(nb, dev)
             if 'src_coord' in want:
                 out['src_coord'] = torch.empty(n, K, 2, dtype=torch.float64, device=dev)
             if 'joints_pred' in want:
@@ -309,41 +353,22 @@ class _KptMetricsDevice(_PinnedStaging):
             _lib.check(L.egn_kpt_metrics_update_f32(
                 _lib.ptr(hm), _lib.ptr(coords), N, K, H, W, mode, _lib.ptr(f['center']), _lib.ptr(f['scale']),
                 _lib.ptr(f['rotation']), _lib.ptr(f['original_joints']), n, float(image_size[0]), float(image_size[1]),
-                _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._acc), _lib.ptr(out.get('src_coord')),
+                _lib.ptr(ws), ws.numel(), _lib.ptr(acc), _lib.ptr(out.get('src_coord')),
                 _lib.ptr(out.get('joints_pred')), _lib.ptr(out.get('max_vals')), st), 'key-point metrics update')
-        self.pending = self.pending or N > 0
+        self._acc.pending = self._acc.pending or N > 0
         return out
 
-    def peek(self):
-        """The accumulator's 8 float64 on the host (synchronises); zeros before the first update."""
-        if self._acc is None:
-            return np.zeros(_KPT_ACC_DOUBLES)
-        return self._acc.cpu().numpy()
 
-    def reset(self):
-        """Zero the accumulator (a launch, no synchronisation)."""
-        self.pending = False
-        if self._acc is None:
-            return
-        from .. import _lib
-        with torch.cuda.device(self._acc.device):
-            _lib.check(_lib.lib().egn_kpt_metrics_reset(_lib.ptr(self._acc), _lib.current_stream(self._acc.device)),
-                       'key-point metrics reset')
-
-    def take(self):
-        """The one read-back: the accumulator's values, and the accumulator zeroed."""
-        acc = self.peek()
-        self.reset()
-        return acc
-
-
-class DistanceSrcMeter(object):
+class DistanceSrcMeter(_Meter):
     """get_distance_src as the training loop's ``metric_func`` with the whole metric on the device
     (csrc/kpt_metrics.hip).  ``meter(prediction, meta, cfgs)`` returns ``(avg, cnt, others)`` like get_distance_src
     and synchronises like it: a drop-in replacement.  ``accumulate(prediction, meta, cfgs=None)`` only launches;
     ``read()`` -> (running mean, count, PCK_counts) since the last ``reset()`` is the read-back.  ``trainer.train``
     uses the three when it finds ``accumulate``.  Predictions must be CUDA: heat-maps [N,K,H,W] with ``arg_max``
     'hard' / 'soft' / 'soft-np', or a (maps, coordinates) tuple."""
+    _on_device = staticmethod(_kpt_on_device)
+    _needs_cuda = 'DistanceSrcMeter needs a CUDA prediction; get_distance_src takes host arrays'
+    _more = staticmethod(lambda acc: (acc[2:5].copy(),))         # the PCK counts
 
     def __init__(self, cfgs=None, image_size=(256., 256.), arg_max='hard'):
         self.image_size = image_size if cfgs is None else cfgs['heatmapModel']['input_size']
@@ -354,21 +379,8 @@ class DistanceSrcMeter(object):
     def _size(self, cfgs):
         return self.image_size if cfgs is None else cfgs['heatmapModel']['input_size']
 
-    def _check(self, prediction):
-        if not _kpt_on_device(prediction):
-            raise TypeError('DistanceSrcMeter needs a CUDA prediction; get_distance_src takes host arrays')
-
-    def accumulate(self, prediction, meta, cfgs=None):
-        self._check(prediction)
+    def _update(self, prediction, meta, cfgs):
         self._dev.update(prediction, meta, self._size(cfgs), self.arg_max)
-
-    def read(self):
-        acc = self._dev.peek()
-        cnt = int(acc[0])
-        return (acc[1] / cnt if cnt else 0.0), cnt, acc[2:5].copy()
-
-    def reset(self):
-        self._dev.reset()
 
     def __call__(self, prediction, meta, cfgs=None):
         self._check(prediction)
@@ -387,14 +399,17 @@ class DistanceSrcMeter(object):
 _ANGLE_ACC_DOUBLES = 2                              # include/egonet_hip.h: rows counted, sum of errors in degrees
 
 
-class _AngleMetricsDevice(_PinnedStaging):
+class _AngleMetricsDevice(_MetricsDevice):
     """The device side of get_angle_error (csrc/angle_metrics.hip): a {count, sum} accumulator in HBM, two launches
     per batch, nothing read back before ``peek()``.  A host ``meta['angles_gt']`` travels in one pinned non-blocking
     copy."""
 
+    def __init__(self):
+        super().__init__(_ANGLE_ACC_DOUBLES, lambda acc, st: _lib.lib().egn_angle_metrics_reset(acc, st),
+                         'angle metrics')
+
     def update(self, prediction, meta):
         """Launch only.  ``prediction`` [N, >= 2] float32 CUDA, any row pitch (only [cos, sin] are read)."""
-        from .. import _lib
         pred = prediction.detach()
         if pred.dim() != 2 or pred.shape[1] < 2:
             raise ValueError('angle predictions must be [N, 2] rows of [cos, sin], got %s' % (tuple(pred.shape),))
@@ -407,81 +422,41 @@ class _AngleMetricsDevice(_PinnedStaging):
         L = _lib.lib()
         with torch.cuda.device(dev):
             st = _lib.current_stream(dev)
-            if self._acc is None or self._acc.device != dev:
-                if self.pending:
-                    raise RuntimeError('the accumulator holds unread updates of another device')
-                self._acc = torch.empty(_ANGLE_ACC_DOUBLES, dtype=torch.float64, device=dev)
-                _lib.check(L.egn_angle_metrics_reset(_lib.ptr(self._acc), st), 'angle metrics reset')
+            acc = self._acc.ensure(dev, st)
             if N == 0:
                 return
             if torch.is_tensor(gt) and gt.is_cuda:
                 gt = gt.detach().to(device=dev, dtype=torch.float64).reshape(N).contiguous()
             else:
-                gt = self._upload_f64(np.asarray(gt.numpy() if torch.is_tensor(gt) else gt,
-                                                 dtype=np.float64).reshape(N), dev)
-            nb = L.egn_angle_metrics_ws_bytes(N)
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nb:
-                self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+                gt = np.asarray(gt.numpy() if torch.is_tensor(gt) else gt, dtype=np.float64).reshape(N)
+                gt = self._staging.upload({'angles_gt': gt}, dev)[0]['angles_gt']
+            ws = self._acc.workspace(L.egn_angle_metrics_ws_bytes(N), dev)
             _lib.check(L.egn_angle_metrics_update_f32(_lib.ptr(pred), N, pred.stride(0) if N > 1 else 2, _lib.ptr(gt),
-                                                      _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._acc), st),
+                                                      _lib.ptr(ws), ws.numel(), _lib.ptr(acc), st),
                        'angle metrics update')
-        self.pending = True
-
-    def peek(self):
-        """The accumulator's two float64 on the host (synchronises); zeros before the first update."""
-        if self._acc is None:
-            return np.zeros(_ANGLE_ACC_DOUBLES)
-        return self._acc.cpu().numpy()
-
-    def reset(self):
-        """Zero the accumulator (a launch, no synchronisation)."""
-        self.pending = False
-        if self._acc is None:
-            return
-        from .. import _lib
-        with torch.cuda.device(self._acc.device):
-            _lib.check(_lib.lib().egn_angle_metrics_reset(_lib.ptr(self._acc), _lib.current_stream(self._acc.device)),
-                       'angle metrics reset')
-
-    def take(self):
-        """The one read-back: the accumulator's values, and the accumulator zeroed."""
-        acc = self.peek()
-        self.reset()
-        return acc
+        self._acc.pending = True
 
 
-class AngleErrorMeter(object):
+class AngleErrorMeter(_Meter):
     """get_angle_error as the training loop's ``metric_func`` with the metric on the device (csrc/angle_metrics.hip),
     the contract of ``DistanceSrcMeter``: ``accumulate(prediction, meta, cfgs=None)`` only launches; ``read()`` ->
     (running mean in degrees, count) since the last ``reset()`` is the read-back; ``meter(prediction, meta, cfgs)``
     returns ``(avg, cnt, None)`` like get_angle_error and synchronises like it.  Predictions must be CUDA [N, 2]."""
+    _on_device = staticmethod(lambda prediction: torch.is_tensor(prediction) and prediction.is_cuda)
+    _needs_cuda = 'AngleErrorMeter needs a CUDA prediction; get_angle_error takes host arrays'
 
     def __init__(self, cfgs=None):
         self._dev = _AngleMetricsDevice()
 
-    @staticmethod
-    def _check(prediction):
-        if not (torch.is_tensor(prediction) and prediction.is_cuda):
-            raise TypeError('AngleErrorMeter needs a CUDA prediction; get_angle_error takes host arrays')
-
-    def accumulate(self, prediction, meta, cfgs=None):
-        self._check(prediction)
+    def _update(self, prediction, meta, cfgs):
         self._dev.update(prediction, meta)
-
-    def read(self):
-        acc = self._dev.peek()
-        cnt = int(acc[0])
-        return (acc[1] / cnt if cnt else 0.0), cnt
-
-    def reset(self):
-        self._dev.reset()
 
     def __call__(self, prediction, meta, cfgs=None):
         self._check(prediction)
         return get_angle_error(prediction, meta, cfgs)
 
 
-class JointDistance2DSIP(object):
+class JointDistance2DSIP(_RunningMean):
     """Running mean of get_distance_src + PCK over an evaluation pass.  CUDA predictions (heat-maps, or a tuple whose
     coordinates are CUDA) are folded into a device accumulator (csrc/kpt_metrics.hip) and read back once, at
     ``report()`` or at the first access of ``count`` / ``mean`` / ``PCK_counts``; numpy inputs and CPU tensors take
@@ -498,30 +473,12 @@ class JointDistance2DSIP(object):
         self._count, self._mean, self._pck = 0, 0., np.zeros(len(PCK_THRES))
         self._dev = _KptMetricsDevice()
 
+    PCK_counts = _synced('_pck')
+
     def _sync(self):
-        """The one read-back: the device accumulator is merged into the host attributes and reset."""
-        if not self._dev.pending:
-            return
-        acc = self._dev.take()
-        cnt = int(acc[0])
-        if cnt == 0:
-            return
-        self._mean = (self._mean * self._count + acc[1]) / (self._count + cnt)
-        self._count += cnt
-        self._pck = self._pck + acc[2:5]
-
-    def _synced(name):
-        def get(self):
-            self._sync()
-            return getattr(self, name)
-
-        def put(self, value):
-            self._sync()
-            setattr(self, name, value)
-        return property(get, put)
-
-    count, mean, PCK_counts = _synced('_count'), _synced('_mean'), _synced('_pck')
-    del _synced
+        acc = _RunningMean._sync(self)
+        if acc is not None:
+            self._pck = self._pck + acc[2:5]
 
     def update(self, prediction, meta_data, ground_truth=None, logger=None):
         if self.device_update and _kpt_on_device(prediction):
@@ -592,8 +549,9 @@ class _Stats3D(object):
             self._host['mean' + name] = np.zeros(b - a)
             self._host['max' + name] = -np.ones(b - a)
             self._host['min' + name] = np.ones(b - a) * 1e16
-        self._acc = self._ws = self._stats_host = self._stats_dev = None
-        self._pending = False
+        self._stats_host = self._stats_dev = None
+        self._acc = _DeviceAcc(_ACC_DOUBLES, lambda acc, st: _lib.lib().egn_lifter_metrics_reset(acc, layout, st),
+                               'metrics')
 
     def __getattr__(self, key):                     # only reached for names that are not ordinary attributes
         host = self.__dict__.get('_host')
@@ -626,7 +584,6 @@ class _Stats3D(object):
         return self._stats_host
 
     def _update_device(self, prediction, ground_truth, statistics=None, rows_out=None):
-        from .. import _lib
         pred, gt = prediction.detach(), ground_truth.detach()
         if pred.dtype != torch.float32 or gt.dtype != torch.float32 or pred.dim() != 2 or pred.shape != gt.shape:
             raise ValueError('%s: float32 [n, D] prediction and ground truth of one shape' % self.name)
@@ -642,13 +599,10 @@ class _Stats3D(object):
         stats = self._use_statistics(statistics)
         with torch.cuda.device(dev):
             st = _lib.current_stream(dev)
-            if self._acc is None or self._acc.device != dev:
-                self._sync()
-                self._acc = torch.empty(_ACC_DOUBLES, dtype=torch.float64, device=dev)
-                _lib.check(L.egn_lifter_metrics_reset(_lib.ptr(self._acc), self._layout, st), 'metrics reset')
-            nb = L.egn_lifter_metrics_ws_bytes(n)
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nb:
-                self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            if self._acc.pending and self._acc.tensor.device != dev:
+                self._sync()                        # what another device holds goes to the host statistics first
+            acc = self._acc.ensure(dev, st)
+            ws = self._acc.workspace(L.egn_lifter_metrics_ws_bytes(n), dev)
             mean = std = None
             if stats is not None:
                 if stats[0].size != D or stats[1].size != D:
@@ -661,20 +615,16 @@ class _Stats3D(object):
                 raise ValueError('rows_out must be contiguous float64 [%d, %d]' % (n, _LAYOUT_COLS[self._layout]))
             _lib.check(L.egn_lifter_metrics_update_f32(
                 _lib.ptr(pred), _lib.ptr(gt), n, D, pred.stride(0) if n else D, _lib.ptr(mean), _lib.ptr(std),
-                self._layout, _lib.ptr(self._ws), self._ws.numel(), _lib.ptr(self._acc), _lib.ptr(rows_out), st),
+                self._layout, _lib.ptr(ws), ws.numel(), _lib.ptr(acc), _lib.ptr(rows_out), st),
                 'metrics update')
-        self._pending = True
+        self._acc.pending = True
 
     def _sync(self):
         """The one read-back: the device accumulator is merged into the host attributes and reset."""
-        if not self.__dict__.get('_pending'):
+        dev = self.__dict__.get('_acc')             # __getattr__ may come here before _init_stats
+        if dev is None or not dev.pending:
             return
-        from .. import _lib
-        self._pending = False
-        acc = self._acc.cpu().numpy()
-        with torch.cuda.device(self._acc.device):
-            _lib.check(_lib.lib().egn_lifter_metrics_reset(_lib.ptr(self._acc), self._layout,
-                                                           _lib.current_stream(self._acc.device)), 'metrics reset')
+        acc = dev.take()
         n = int(acc[0])
         if n == 0:
             return
