@@ -21,7 +21,14 @@ sections of ONE pinned, double-buffered, event-guarded ``non_blocking`` copy on 
 
 Decode stays in the ``DataLoader`` workers: a Dataset returns records (see ``INTEGRATION.md``), ``collate_frames``
 keeps them as a list, ``TrainSampleBuilder`` turns the list into the batch.
+
+Mixed batches (``cfgs['ss']['flag']``, car_instance.py:1145-1169, 1292-1298, 1353-1380): every labelled frame with
+fewer than ``ss.max_per_img`` instances brings crops of one unlabelled frame -- same jitter, resize, affine, warp and
+normalisation, no targets and no meta.  The batch holds the ``n_fs`` labelled crops first, then the unlabelled ones;
+targets, weights and meta keep ``n_fs`` rows and ``meta['fs_instance_cnt'] = n_fs``.  The unlabelled frames join the
+frame table of the one upload and the one crop launch.  ``MixedFrames`` chooses and decodes them in the workers.
 """
+import os
 import time
 
 import numpy as np
@@ -56,7 +63,19 @@ class TrainSampleBuilder(object):
     1248-1271, ``generate_hm=False``); None reads ``cfgs['exp_type']`` ('baselinealpha' / 'baselinetheta', anything else
     means 'heatmap').  In the angle modes every record also holds ``'rots': [n,2]`` (``alpha``, ``rot_y``) and the batch
     is ``(images, targets [N,2] = float32([cos r, sin r]) on the device, torch.ones(1), meta)`` with
-    ``meta['angles_gt'] [N]`` float64; no heat-map launch is made."""
+    ``meta['angles_gt'] [N]`` float64; no heat-map launch is made.
+
+    ``cfgs['ss']`` (``flag``, ``max_per_img``) switches the mixed batches on for split 'train' in the heat-map mode (the
+    angle modes ignore it, like the reference's ``__getitem__``, car_instance.py:1248-1271).  The unlabelled frame of a
+    labelled record with fewer than ``max_per_img`` boxes is either the record's own ``'ss'`` entry ``{'image',
+    'boxes', 'path'}`` (chosen and decoded ahead, ``MixedFrames``: no draw here) or one of ``builder(records, rng,
+    unlabelled=pool)``, picked by ``rng.randint(0, len(pool))`` as ``extract_ss_sample`` does.  The batch is then
+    ``(images [N,3,h,w], targets [n_fs,K,hm_h,hm_w], target_weights [n_fs,K,1], meta)`` with ``n_fs <= N``.
+
+    Draw order on ``rng``, per frame of the batch (car_instance.py:1283-1294, img_proc.py:174-191, 302-308): four
+    ``rand()`` per labelled box (jitter on); then, where ``max_per_img`` exceeds the frame's box count, the ``randint``
+    (pool mode) and four ``rand()`` for EVERY box of the unlabelled frame -- it is cropped whole and cut to the first
+    ``max_per_img - n`` crops afterwards (img_proc.py:325-339).  After all frames the ``length_limit`` choice."""
 
     def __init__(self, cfgs, split='train', device=None, target=None):
         hm = cfgs['heatmapModel']
@@ -86,6 +105,9 @@ class TrainSampleBuilder(object):
         self.sigma = float(_hm_value(hm, 'sigma', 1))
         self.jitter = bool(hm.get('jitter_bbox', False)) and split == 'train' and bool(cfgs.get('train', False))
         self.scaling = tuple(hm['jitter_params']['scaling']) if self.jitter else None
+        ss = cfgs.get('ss') or {}
+        self.mix = bool(ss.get('flag', False)) and split == 'train' and self.rot_col is None
+        self.max_per_img = int(ss.get('max_per_img', 0)) if self.mix else 0
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self._staging = staging.PinnedStaging(1 << 20)
         # True: every call keeps {'host_ms', 'events'} in last_timings -- four timing events: before the upload,
@@ -189,27 +211,79 @@ class TrainSampleBuilder(object):
         out[..., 1] = np.where(vis, ty, y)
         return out
 
-    def plan(self, records, rng=np.random):
+    def plan(self, records, rng=np.random, unlabelled=None):
         """All host work of a batch, in the reference's draw order (per frame, per box: 4 draws; then the
         length_limit choice).  Returns a dict: 'kept' [n] (indices into the batch's boxes), 'frame' [n],
         'trans' [n,2,3], 'draws' [N,4] or None, and 'meta' (the reference's keys); in the angle modes also 'targets'
-        [n,2] float32 and meta['angles_gt'] [n]."""
-        boxes, joints, frame = self.gather(records)
+        [n,2] float32 and meta['angles_gt'] [n].
+
+        Mixed batches: the batch's boxes are the labelled ones in record order followed by the kept crops of the
+        unlabelled frames in frame order; 'kept', 'frame' and 'trans' cover all of them, 'n_fs' counts the labelled
+        prefix, 'frame' indexes 'sources' (the records followed by the unlabelled frames), 'draws' holds every draw in
+        stream order (dropped unlabelled boxes included), 'ss_idx' the ``randint`` draws and 'ss_boxes' (frame, crops
+        kept) of every labelled frame that drew."""
+        boxes_fs, joints, frame_fs = self.gather(records)
+        n_fs = len(boxes_fs)
+        counts = np.bincount(frame_fs, minlength=len(records))
+        sources, where = list(records), {}
+        draws_fs, draws_ss, stream, ss_idx, ss_boxes = [], [], [], [], []
+        boxes_ss, frame_ss = [], []
+        for f, rec in enumerate(records):
+            if self.jitter:
+                # (consecutive per-frame calls consume the stream exactly as one rand(n_all, 4) does)
+                draws_fs.append(rng.rand(counts[f], 4))
+                stream.append(draws_fs[-1])
+            want = self.max_per_img - int(counts[f])
+            if not self.mix or want <= 0:
+                continue                                    # extract_ss_sample :1150-1153: no draw at all
+            ss = rec.get('ss')
+            if ss is None:
+                if unlabelled is None or len(unlabelled) == 0:
+                    raise ValueError("record %d has %d boxes (< ss.max_per_img = %d) and no 'ss' entry: wrap the "
+                                     'frames in MixedFrames or pass unlabelled=pool' % (f, counts[f], self.max_per_img))
+                ss_idx.append(int(rng.randint(0, len(unlabelled))))
+                ss = unlabelled[ss_idx[-1]]
+            b = np.asarray(ss['boxes'], dtype=np.float64).reshape(-1, 4)
+            if self.jitter:
+                d = rng.rand(len(b), 4)                       # the frame is cropped whole: every box draws
+                stream.append(d)
+                draws_ss.append(d[:want])
+            b = b[:want]                                    # img_proc.py:325-339 (max_cnt)
+            ss_boxes.append((f, len(b)))
+            if not len(b):
+                continue
+            if id(ss) not in where:                         # a pool frame drawn twice goes up once
+                where[id(ss)] = len(sources)
+                sources.append(ss)
+            boxes_ss.append(b)
+            frame_ss.append(np.full(len(b), where[id(ss)], dtype=np.int64))
+        boxes = np.concatenate([boxes_fs] + boxes_ss)
+        frame = np.concatenate([frame_fs] + frame_ss)
         n_all = len(boxes)
-        draws = None
         if self.jitter:
-            draws = rng.rand(n_all, 4)
-            boxes = self.jitter_boxes(boxes, draws)
+            boxes = self.jitter_boxes(boxes, np.concatenate(draws_fs + draws_ss))
         c, s = self.resize_boxes(boxes)
         trans = self.affines(c, s)
-        tj = self.transform_joints(joints, trans)
-        kept = np.arange(n_all)
-        if n_all > MAX_INS_CNT:
-            kept = rng.choice(n_all, MAX_INS_CNT, replace=False)
+        tj = self.transform_joints(joints, trans[:n_fs])
+        # length_limit (car_instance.py:1344-1366)
+        kept, rows, counted = np.arange(n_all), np.arange(n_fs), self.mix
+        if n_all > MAX_INS_CNT and (n_fs == n_all or n_fs > MAX_INS_CNT):
+            # a choice among the labelled crops; in a mixed batch every unlabelled crop is dropped and the result has no
+            # 'fs_instance_cnt' (:1353-1360).  (With the mix on and n_fs == n_all the reference takes :1345-1352, which
+            # indexes the int 'fs_instance_cnt' and raises; the same choice is made here.)
+            kept = rows = rng.choice(n_fs, MAX_INS_CNT, replace=False)
+            counted = False
+        elif n_all > MAX_INS_CNT:
+            kept = kept[:MAX_INS_CNT]                       # :1361-1363: targets and meta untouched
         meta = {'path': [r.get('path', '') for r in records],
-                'original_joints': joints[kept], 'transformed_joints': tj[kept],
-                'center': c[kept], 'scale': s[kept], 'joints_vis': tj[kept][:, :, 2]}
-        p = {'kept': kept, 'frame': frame[kept], 'trans': trans[kept], 'draws': draws, 'meta': meta}
+                'original_joints': joints[rows], 'transformed_joints': tj[rows],
+                'center': c[rows], 'scale': s[rows], 'joints_vis': tj[rows][:, :, 2]}
+        p = {'kept': kept, 'frame': frame[kept], 'trans': trans[kept],
+             'draws': np.concatenate(stream) if stream else None, 'meta': meta}
+        if self.mix:
+            if counted:
+                meta['fs_instance_cnt'] = n_fs
+            p.update(n_fs=len(rows), sources=sources, ss_idx=ss_idx, ss_boxes=ss_boxes)
         if self.rot_col is not None:
             # car_instance.py:1264-1270: [cos r, sin r] in float64, rounded to float32 once; ``chosen`` indexes them
             # like every other meta array (length_limit :1344-1352)
@@ -227,6 +301,7 @@ class TrainSampleBuilder(object):
         ('frame', f), the frame table [offset in the block, rows, columns, row pitch], the per-box frame index, the
         affines, then the targets' inputs."""
         n = len(p['kept'])
+        records = p.get('sources', records)                 # mixed batches: the unlabelled frames follow the records
         used = np.unique(p['frame'])
         remap = np.full(len(records), -1, dtype=np.int64)
         remap[used] = np.arange(len(used))
@@ -250,10 +325,11 @@ class TrainSampleBuilder(object):
                    3 * arrays['frame', f].shape[1]] for f in used]
         return arrays
 
-    def __call__(self, records, rng=np.random):
+    def __call__(self, records, rng=np.random, unlabelled=None):
         t0 = time.perf_counter()
-        p = self.plan(records, rng)
+        p = self.plan(records, rng, unlabelled)
         meta, n = p['meta'], len(p['kept'])
+        n_fs = p.get('n_fs', n)                             # targets are drawn for the labelled prefix only
         K = self.num_joints
         h, w = self.input_hw
         hm_h, hm_w = self.heatmap_hw
@@ -284,13 +360,43 @@ class TrainSampleBuilder(object):
                 if ev:
                     ev[3].record(stream)
                 return images, d['angles'], torch.ones(1), meta
-            targets = torch.empty(n, K, hm_h, hm_w, dtype=torch.float32, device=dev)
-            weights = torch.empty(n, K, 1, dtype=torch.float32, device=dev)
+            targets = torch.empty(n_fs, K, hm_h, hm_w, dtype=torch.float32, device=dev)
+            weights = torch.empty(n_fs, K, 1, dtype=torch.float32, device=dev)
             # the reference's stride quirk (img_proc.py:376-378): input_size / heatmap_size in (h, w) order, the
             # first of them divides x -- egn_gaussian_targets_f32 takes the two strides in that order
-            _lib.check(L.egn_gaussian_targets_f32(_lib.ptr(d['joints']), _lib.ptr(d['vis']), n, K, hm_h, hm_w,
+            _lib.check(L.egn_gaussian_targets_f32(_lib.ptr(d['joints']), _lib.ptr(d['vis']), n_fs, K, hm_h, hm_w,
                                                   float(h) / float(hm_h), float(w) / float(hm_w), self.sigma,
                                                   _lib.ptr(targets), _lib.ptr(weights), st), 'gaussian targets')
             if ev:
                 ev[3].record(stream)
         return images, targets, weights, meta
+
+
+class MixedFrames(torch.utils.data.Dataset):
+    """``frames`` (``pose_annot.PoseFrames`` or any Dataset of the builder's records) with the unlabelled frame of the
+    mixed batches chosen and decoded in the ``DataLoader`` worker, as ``KITTI.extract_ss_sample`` does
+    (car_instance.py:1145-1169): a record with fewer than ``max_per_img`` boxes gets ``'ss': {'image', 'boxes',
+    'path'}`` -- index ``np.random.randint(0, len(paths))`` of ``ss_record``, the file with the basename of
+    ``ss_record['paths'][idx]`` under ``img_root``.  ``ss_record``: the reference's dictionary (``paths``, ``boxes``;
+    its ``kpts`` are not read) or the path of its ``.npy`` file."""
+
+    def __init__(self, frames, ss_record, img_root, max_per_img):
+        if isinstance(ss_record, (str, bytes, os.PathLike)):
+            ss_record = np.load(ss_record, allow_pickle=True).item()      # car_instance.py:180
+        self.frames, self.img_root, self.max_per_img = frames, img_root, int(max_per_img)
+        self.ss_paths, self.ss_boxes = list(ss_record['paths']), list(ss_record['boxes'])
+        if not self.ss_paths or len(self.ss_paths) != len(self.ss_boxes):
+            raise ValueError('the unlabelled record needs one boxes entry per path, and at least one frame')
+        if hasattr(frames, 'num_joints'):
+            self.num_joints = frames.num_joints
+
+    def __len__(self):
+        return len(self.frames)
+
+    def __getitem__(self, i):
+        rec = self.frames[i]
+        if self.max_per_img - len(rec['boxes']) <= 0:
+            return rec
+        idx = np.random.randint(0, len(self.ss_paths))
+        path = os.path.join(self.img_root, self.ss_paths[idx].split(os.sep)[-1])
+        return dict(rec, ss={'image': crop_gpu.load_rgb(path), 'boxes': self.ss_boxes[idx], 'path': path})

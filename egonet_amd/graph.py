@@ -35,6 +35,10 @@ class GraphedStep(object):
         for t in inputs:
             if t is not None and not (torch.is_tensor(t) and t.is_cuda):
                 raise ValueError('GraphedStep inputs must be CUDA tensors (they become the static graph inputs)')
+        if len(inputs) > 1 and inputs[0] is not None and inputs[1] is not None and len(inputs[1]) != len(inputs[0]):
+            raise ValueError('GraphedStep with a labelled prefix (%d target rows for %d inputs): a mixed batch changes '
+                             'its two row counts from step to step, a captured graph has static shapes'
+                             % (len(inputs[1]), len(inputs[0])))
         self.trainer = trainer
         # the trainer's side stream for weight gradients helps eager steps (-4 %); inside a graph the
         # forked branch replays slower than one chain (78.4 vs 76 ms measured), so capture one stream

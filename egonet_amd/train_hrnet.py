@@ -836,12 +836,44 @@ class HRNetTrainStep(TapeOwner):
                                           st), 'pixel-shuffle loss')
         tape._accum(u, du)
 
+    def _labelled_rows(self, n, target, joints_xy):
+        """``n_fs``: the rows of ``target`` when it holds fewer than the ``n`` images (a mixed batch: the labelled crops
+        first), else ``n``.  Raises where the reference has no labelled-prefix slice or this step has none."""
+        m = self.model
+        if target is None:
+            if joints_xy is not None and len(joints_xy) != n:
+                raise ValueError('a labelled prefix (%d joints_xy rows for %d images) with device-drawn targets '
+                                 '(target=None): pass the [n_fs,K,h,w] target of the labelled crops'
+                                 % (len(joints_xy), n))
+            return n
+        n_fs = int(target.shape[0])
+        if n_fs == n:
+            return n
+        if n_fs > n or n_fs < 1:
+            raise ValueError('target has %d rows for %d images' % (n_fs, n))
+        what = ('the angle head' if self.angle_crit is not None else
+                'the pixel-shuffle head' if m.head_type != 'coordinates' and m.pixel_shuffle else
+                'use_target_weight (JointsMSELoss has no slice, function.py:22-46)' if self.use_target_weight else None)
+        if what is not None:
+            raise ValueError('a labelled prefix (%d target rows for %d images) with %s: mixed batches train the '
+                             "'coordinates' head and the plain 'heatmap' head only" % (n_fs, n, what))
+        if joints_xy is not None and len(joints_xy) != n_fs:
+            raise ValueError('joints_xy must be [%d, %d, 2] like the target of the labelled crops, got %d rows'
+                             % (n_fs, m.num_joints, len(joints_xy)))
+        return n_fs
+
     @torch.no_grad()
     def step(self, images, target, joints_xy=None, update=True, joints_vis=None, target_weight=None):
         """images [N,3,H,W], target [N,K,h,w] heat-maps (None: drawn on the device from
         joints_xy / joints_vis with ``self.sigma``), joints_xy [N,K,2] in input pixels
         (``meta['transformed_joints'][:, :, :2]``).  Returns the loss as a 1-element
         float64 device tensor (no host sync).
+
+        Mixed batches (function.py:183-201): ``target`` and ``joints_xy`` may hold ``n_fs < N`` rows -- the labelled
+        crops are the first ``n_fs`` images, the others are unlabelled.  The heat-map and coordinate terms then run
+        over the labelled prefix (their means over ``n_fs`` rows, zero gradient for the rest), the cross-ratio term
+        and the BatchNorm statistics over all ``N``; ``last_maps`` / ``last_coords`` keep ``N`` rows.  For the
+        'coordinates' head and the plain 'heatmap' head with ``target`` given and ``use_target_weight`` off.
 
         The cyclic garbage collector is paused while the ~1 500 launches of the iteration are issued: a
         full collection in the middle (35 ms measured, every ~10 iterations) starves the GPU and doubles
@@ -863,6 +895,7 @@ class HRNetTrainStep(TapeOwner):
         n, cin, h, w = images.shape
         if h % 32 or w % 32:
             raise ValueError('HRNet input height/width must be multiples of 32, got %dx%d' % (h, w))
+        n_fs = self._labelled_rows(n, target, joints_xy)
         with torch.cuda.device(self.dev):
             st = _lib.current_stream(self.dev)
             self.flat.grad.zero_()
@@ -889,8 +922,11 @@ class HRNetTrainStep(TapeOwner):
                         gt[..., 0] /= w            # function.py:160-161 (img_size = (width, height))
                         gt[..., 1] /= h
                         gt = gt.contiguous()
-                        _lib.check(L.egn_elem_loss_f32(_lib.ptr(cd), _lib.ptr(gt), 1, cd.numel(), cd.numel(),
-                                                       cd.numel(), self.coor_crit, self.w_coor, 0, _lib.ptr(dc),
+                        if n_fs < n:
+                            dc.zero_()                            # the unlabelled rows: no coordinate gradient
+                        cnt = n_fs * 2 * J                        # the labelled rows come first (function.py:194-198)
+                        _lib.check(L.egn_elem_loss_f32(_lib.ptr(cd), _lib.ptr(gt), 1, cnt, cnt, cnt,
+                                                       self.coor_crit, self.w_coor, 0, _lib.ptr(dc),
                                                        _lib.ptr(self.loss_dev), st), 'coor loss')
                     else:
                         dc.zero_()
@@ -928,10 +964,12 @@ class HRNetTrainStep(TapeOwner):
                         joints_xy, torch.ones(n, J) if joints_vis is None else joints_vis,
                         dict(target_type='gaussian', input_size=(w, h), heatmap_size=(aug.h, aug.w), sigma=self.sigma),
                         device=self.dev)
-                if tuple(target.shape) != (n, J, aug.h, aug.w):
-                    raise ValueError('target must be %s, got %s' % ((n, J, aug.h, aug.w), tuple(target.shape)))
-                tg = tape._empty(n * aug.h * aug.w * aug.cs)
-                _lib.check(L.egn_nchw_to_nhwc_f32(_lib.ptr(target), _lib.ptr(tg), n, J, aug.h, aug.w, aug.cs, st))
+                if tuple(target.shape) != (n_fs, J, aug.h, aug.w):
+                    raise ValueError('target must be %s, got %s' % ((n_fs, J, aug.h, aug.w), tuple(target.shape)))
+                # the labelled crops are a contiguous prefix of the NHWC maps (function.py:183-186): the rows beyond
+                # n_fs * h * w are not read, and their gradient stays zero
+                tg = tape._empty(n_fs * aug.h * aug.w * aug.cs)
+                _lib.check(L.egn_nchw_to_nhwc_f32(_lib.ptr(target), _lib.ptr(tg), n_fs, J, aug.h, aug.w, aug.cs, st))
                 da = torch.zeros(n * aug.h * aug.w * aug.cs, dtype=torch.float32, device=self.dev)
                 pred_flat = tape.data[id(aug)]
                 wv = None
@@ -946,7 +984,7 @@ class HRNetTrainStep(TapeOwner):
                     pred_flat = (pred_flat.view(n, aug.h, aug.w, aug.cs) * wv).reshape(-1)
                     tg = (tg.view(n, aug.h, aug.w, aug.cs) * wv).reshape(-1)
                 # (1/K) sum_k 0.5*crit_k = 0.5 * crit over all joints (equal element counts), function.py:95-111
-                _lib.check(L.egn_elem_loss_f32(_lib.ptr(pred_flat), _lib.ptr(tg), n * aug.h * aug.w, J, aug.cs,
+                _lib.check(L.egn_elem_loss_f32(_lib.ptr(pred_flat), _lib.ptr(tg), n_fs * aug.h * aug.w, J, aug.cs,
                                                aug.cs, self.hm_crit, 0.5 * self.w_hm, 0, _lib.ptr(da),
                                                _lib.ptr(self.loss_dev), st), 'hm loss')
                 if wv is not None:

@@ -315,7 +315,11 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
     epoch, read only on report batches.
     ``sample_builder``: a callable (``common.train_samples.TrainSampleBuilder``) that turns each loader item
     -- e.g. the list of decoded frame records ``common.train_samples.collate_frames`` yields -- into the
-    ``(data, target, weights, meta)`` batch; None: the loader yields that batch itself."""
+    ``(data, target, weights, meta)`` batch; None: the loader yields that batch itself.
+    A mixed batch (``cfgs['ss']``, car_instance.py:1368-1380) passes through as it is: ``data`` holds ``N`` crops, the
+    labelled ones first, ``target`` and ``meta['transformed_joints']`` their ``n_fs <= N`` rows; the step takes the
+    heat-map and coordinate terms over the labelled prefix and the cross-ratio term over all crops, a metric sees the
+    ``N`` predictions and the ``n_fs`` meta rows, and the logged samples/s counts ``N``."""
     ts = cfgs['training_settings']
     total_epochs, report_every = ts['total_epochs'], ts['report_every']
     eval_during = bool(ts.get('eval_during', False)) and valid_dataset is not None

@@ -5,6 +5,7 @@
         [--valid-split-file <stems>] --out <dir> [--epochs 45] [--batch-frames 8] [--eval-every N] [--seed S]
         [--tiny] [--max-steps N] [--workers 4] [--report-every 30] [--lr 1e-3]
         [--exp-type instanceto2d|baselinealpha|baselinetheta] [--loss-type MSELoss1D|SmoothL1Loss1D]
+        [--cr-weight W] [--ss-record FILE --ss-img-root DIR [--ss-max-per-img 6]]
 
 Labels + calibration -> ``PoseAnnotBuilder`` (the 2-D pose annotations, built on the device:
 egonet_amd.common.pose_annot) -> ``PoseFrames`` -> ``DataLoader(collate_fn=collate_frames)`` (frames decoded in the
@@ -26,6 +27,13 @@ with the 'angleregression' head on targets ``[cos r, sin r]`` of ``alpha`` / ``r
 annotations' ``rots``, ``TrainSampleBuilder(target=...)`` emits them), the criterion ``--loss-type`` on the native step,
 ``AngleErrorMeter`` as the training metric and ``AngleError`` for validation; the state dict goes to
 ``<exp-type>.pth``.
+
+``--ss-record FILE --ss-img-root DIR`` switch on the self-supervised mix (the ``ss`` block of KITTI_train_IGRs.yml):
+``FILE`` is the reference's record of unlabelled frames (a ``.npy`` dictionary with ``paths`` and ``boxes``), ``DIR``
+holds the images under their basenames.  Every labelled frame with fewer than ``--ss-max-per-img`` cars then brings
+crops of one random unlabelled frame (``MixedFrames``); the heat-map and coordinate terms see the labelled crops, the
+cross-ratio term and BatchNorm all of them.  ``--cr-weight W`` is the third entry of ``loss_weight_list`` ('None' in the
+shipped file): the weight of the cross-ratio term, which counts from the second epoch on.  The mix needs it.
 """
 import argparse
 import json
@@ -58,8 +66,8 @@ def igr_cfgs(a):
     metric = 'AngleError' if angle else 'JointDistance2DSIP'
     cfg['heatmapModel'].update(jitter_bbox=True, jitter_params={'shift': [0.1, 0.1], 'scaling': [0.4, 0.4]},
                                loss_type='JointsCompositeLoss', loss_spec_list=['mse', 'l1', 'sl1'],
-                               loss_weight_list=[1.0, 0.1, 'None'], cr_loss_threshold=0.15, target_type='gaussian',
-                               sigma=1)
+                               loss_weight_list=[1.0, 0.1, _cr_weight(a)], cr_loss_threshold=0.15,
+                               target_type='gaussian', sigma=1)
     if angle:
         cfg['heatmapModel']['loss_type'] = a.loss_type          # one criterion: no spec / weight lists
         for key in ('loss_spec_list', 'loss_weight_list', 'cr_loss_threshold'):
@@ -79,7 +87,15 @@ def igr_cfgs(a):
                testing_settings={'batch_size': a.batch_frames, 'num_threads': 0, 'shuffle': False,
                                  'apply_dropout': False, 'unnormalize': False, 'arg_max': 'hard',
                                  'eval_metrics': [metric], 'alpha_mode': 'proj'})
+    if getattr(a, 'ss_record', None):
+        cfg['ss'] = {'flag': True, 'record_path': a.ss_record, 'img_root': a.ss_img_root,
+                     'max_per_img': a.ss_max_per_img}
     return cfg
+
+
+def _cr_weight(a):
+    w = getattr(a, 'cr_weight', None)
+    return 'None' if w is None or w == 0 else float(w)
 
 
 def build_model(cfgs, seed):
@@ -159,7 +175,23 @@ def main(argv=None):
     ap.add_argument('--exp-type', default='instanceto2d', choices=['instanceto2d'] + sorted(train_samples.EXP_TARGETS))
     ap.add_argument('--loss-type', default='MSELoss1D', choices=['MSELoss1D', 'SmoothL1Loss1D'],
                     help='criterion of the angle baselines (libs/loss/function.py:204-228)')
+    ap.add_argument('--cr-weight', type=float, default=None, metavar='W',
+                    help="weight of the cross-ratio term, from the second epoch on (default: off, the shipped 'None')")
+    ap.add_argument('--ss-record', default=None, metavar='FILE',
+                    help="the record of unlabelled frames (.npy dictionary with 'paths' and 'boxes'): mixed batches")
+    ap.add_argument('--ss-img-root', default=None, metavar='DIR', help='directory of the unlabelled images')
+    ap.add_argument('--ss-max-per-img', type=int, default=6,
+                    help='a labelled frame with fewer cars is filled up to this many crops from an unlabelled frame')
     a = ap.parse_args(argv)
+    if bool(a.ss_record) != bool(a.ss_img_root):
+        ap.error('--ss-record and --ss-img-root go together')
+    if a.ss_record and a.exp_type in train_samples.EXP_TARGETS:
+        ap.error('--ss-record: the angle baselines ignore the mix (car_instance.py:1248-1271)')
+    if a.ss_record and _cr_weight(a) == 'None':
+        ap.error('--ss-record without --cr-weight: the cross-ratio term is the only one that reads unlabelled crops; '
+                 'unlabelled crops then only change BatchNorm statistics')
+    if a.cr_weight is not None and a.exp_type in train_samples.EXP_TARGETS:
+        ap.error('--cr-weight belongs to the key-point model (instanceto2d)')
     logging.basicConfig(level=logging.INFO, format='%(message)s')
     logger = logging.getLogger('train_IGRs')
     cfgs = igr_cfgs(a)
@@ -177,7 +209,12 @@ def main(argv=None):
                 '(%(dropped_inlier)d outside the image, %(dropped_visible)d with too few visible points)' % counts)
     if not annot['paths']:
         ap.error('no car of %s passed the visibility filters' % a.kitti)
-    train_set = _Budgeted(pose_annot.PoseFrames(annot), a.workers, a.max_steps)
+    frames = pose_annot.PoseFrames(annot)
+    if a.ss_record:
+        frames = train_samples.MixedFrames(frames, a.ss_record, a.ss_img_root, a.ss_max_per_img)
+        logger.info('mixed batches: %d unlabelled frames, up to %d crops per labelled frame'
+                    % (len(frames.ss_paths), a.ss_max_per_img))
+    train_set = _Budgeted(frames, a.workers, a.max_steps)
 
     valid_frames, evaluator, evaluate_fn = None, None, None
     if a.valid_split_file or a.eval_every > 0:
