@@ -163,6 +163,8 @@ SIGNATURES = {
     'egn_angle_metrics_ws_bytes': (C.c_long, [C.c_long]),
     'egn_angle_metrics_reset': (_i, [_p, _p]),
     'egn_angle_metrics_update_f32': (_i, [_p, C.c_long, _i, _p, _p, C.c_long, _p, _p]),
+    'egn_pnp_refine_f64': (_i, [_p] * 5 + [_i, _i, _d] + [_p] * 6 + [_p]),
+    'egn_pnp_refine_host_f64': (_i, [_p] * 5 + [_i, _i, _d] + [_p] * 6),
     'egn_program_op_info': (_i,[_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), C.c_char_p, _i]),
 }
 

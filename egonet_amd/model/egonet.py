@@ -65,7 +65,7 @@ class EgoNet(nn.Module):
     # ------------------------------------------------------------------
     @torch.no_grad()
     def infer_crops(self, instances, centers, scales, K=None, kpts_x_for_alpha=None,
-                    alpha_mode='proj', decode='auto', to_host=True, slot=0):
+                    alpha_mode='proj', decode='auto', to_host=True, slot=0, refine=None, roots=None, max_shift=5.0):
         """instances [n,C,H,W] fp32 CUDA crops; centers/scales [n,2] float64
         (``modify_bbox`` outputs).  Returns a dict with
           kpts_2d [n,2J] f64 (screen), kpts_3d [n,J-1,3] f64, euler [n,3],
@@ -75,7 +75,16 @@ class EgoNet(nn.Module):
         'hard' (heat-map arg-max), 'auto' = by ``HC.head_type``.
         slot: which copy of the launch programs to use -- a serving loop that keeps two batches in flight on two
         streams alternates slot 0 / 1 (engine.HRNetEngine.program).
+        refine: None, or 'pnp' (needs K, [3,3] or [n,3,3]): one more launch between the un-normalisation and the pose
+        solve fits the lifted cuboid rigidly to its own key points (``refine_pnp``; ``roots`` [n,3] = initial roots,
+        default the weak-perspective start; ``max_shift`` as there).  The pose solve then runs on the refined relative
+        shape, ``translation`` is the refined root ('trans' alpha uses it), and the dict gains ``kpts_3d_refined``
+        [n,J,3], ``refine_status`` [n] and ``dims`` [n,3] = (l, h, w).
         """
+        if refine not in (None, 'pnp'):
+            raise ValueError("refine must be None or 'pnp', got %r" % (refine,))
+        if refine == 'pnp' and K is None:
+            raise ValueError("refine='pnp' needs the intrinsics K")
         if not instances.is_cuda:
             raise ValueError('infer_crops is the GPU pipeline; pass CUDA crops')
         if self.LS is None:
@@ -118,7 +127,33 @@ class EgoNet(nn.Module):
             _lib.check(L.egn_unnormalize_f64(_lib.ptr(y), n, D, D, _lib.ptr(ls['mean_out']),
                                              _lib.ptr(ls['std_out']), _lib.ptr(pred3d), stream))
             res = {'local': local, 'kpts_2d': screen, 'kpts_3d': pred3d.view(n, -1, 3)}
-            if D == 96:
+            if refine == 'pnp' and D != 96:
+                raise ValueError("refine='pnp' needs the 96-output lifter (a cuboid of 32 points + root)")
+            if D == 96 and refine == 'pnp':
+                # a host K is uploaded once, not per step: a copy from pageable memory makes the host wait for the
+                # stream, i.e. for HC and the lifter above
+                ikey = (K.tobytes(), K.shape, n, dev) if isinstance(K, np.ndarray) else None
+                if ikey is None or getattr(self, '_intr_dev_key', None) != ikey:
+                    self._intr_dev, self._intr_dev_key = self._intrinsics(K, n, dev), ikey
+                intr = self._intr_dev
+                ref = self._refine_device(pred3d.view(n, -1, 3), screen, intr, roots, None, max_shift)
+                refined = ref['kpts_3d_refined']
+                rel = (refined[:, 1:] - refined[:, :1]).contiguous()
+                euler = torch.empty(n, 3, dtype=torch.float64, device=dev)
+                alpha = torch.empty(n, dtype=torch.float64, device=dev)
+                kx = screen[:, 0] if kpts_x_for_alpha is None else _dev_f64(kpts_x_for_alpha, dev)
+                # the solve takes one (fx, cx); per-instance intrinsics go in through its argument instead:
+                # atan2(-fx, kx - cx) is the angle of atan2(-1, (kx - cx) / fx)
+                kx = ((kx - intr[:, 2]) / intr[:, 0]).contiguous()
+                amode = 0 if alpha_mode == 'proj' else 1
+                _lib.check(L.egn_pose_solve_f64(_lib.ptr(rel), n, _lib.ptr(kx), 1.0, 0.0, amode,
+                                                _lib.ptr(euler), _lib.ptr(alpha), stream), 'pose_solve')
+                if amode == 1:      # 'trans' on the refined root, not on the first relative point
+                    alpha = euler[:, 1] - torch.atan2(-refined[:, 0, 2], refined[:, 0, 0]) - 0.5 * math.pi
+                    alpha = torch.remainder(alpha + math.pi, 2 * math.pi) - math.pi
+                res.update(euler=euler, alpha=alpha, translation=refined[:, 0, :], kpts_3d_refined=refined,
+                           refine_status=ref['status'], dims=ref['dims'])
+            elif D == 96:
                 euler = torch.empty(n, 3, dtype=torch.float64, device=dev)
                 alpha = torch.empty(n, dtype=torch.float64, device=dev)
                 amode = 0 if (alpha_mode == 'proj' and K is not None) else 1
@@ -241,6 +276,126 @@ class EgoNet(nn.Module):
                                                      _lib.current_stream(dev)), 'pose_solve')
         return euler.cpu().numpy(), alpha.cpu().numpy()
 
+    # ------------------------------------------------------------------
+    # reprojection refinement of the lifted cuboid (the reference's pnp_refine, transformation.py:143-157, without cv2)
+    # ------------------------------------------------------------------
+    @staticmethod
+    def _intrinsics(K, n, device=None):
+        """K [3,3] | [n,3,3] -> [n,4] float64 rows (fx, fy, cx, cy); a device tensor when ``device`` is given."""
+        if device is None:
+            K = np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, dtype=np.float64)
+        else:
+            K = _dev_f64(K, device)
+        if tuple(K.shape) not in ((3, 3), (n, 3, 3)):
+            raise ValueError('K must be [3,3] or [n,3,3], got %s' % (tuple(K.shape),))
+        K = K.reshape(-1, 3, 3)
+        rows = [K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]]
+        intr = np.stack(rows, 1) if device is None else torch.stack(rows, 1)
+        if len(intr) != n:
+            intr = np.tile(intr, (n, 1)) if device is None else intr.expand(n, 4)
+        return np.ascontiguousarray(intr) if device is None else intr.contiguous()
+
+    @staticmethod
+    def _refine_device(shape, kpts_2d, intr, roots, weights, max_shift):
+        """One launch of egn_pnp_refine_f64 on the current stream of ``shape``'s device; no synchronisation."""
+        dev = shape.device
+        n = shape.shape[0]
+        J = shape.shape[1] + 1
+        shape = _dev_f64(shape, dev)
+        k = _dev_f64(kpts_2d, dev).reshape(n, J, 2)
+        r0 = None if roots is None else _dev_f64(roots, dev).reshape(n, 3)
+        w = None if weights is None else _dev_f64(weights, dev).reshape(n, J)
+        out = {'kpts_3d_refined': torch.empty(n, J, 3, dtype=torch.float64, device=dev),
+               'rt': torch.empty(n, 12, dtype=torch.float64, device=dev),
+               'cost': torch.empty(n, 2, dtype=torch.float64, device=dev),
+               'iters': torch.empty(n, dtype=torch.int32, device=dev),
+               'status': torch.empty(n, dtype=torch.int32, device=dev),
+               'dims': torch.empty(n, 3, dtype=torch.float64, device=dev)}
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().egn_pnp_refine_f64(
+                _lib.ptr(shape), _lib.ptr(k), _lib.ptr(intr), _lib.ptr(w), _lib.ptr(r0), n, J, float(max_shift),
+                _lib.ptr(out['kpts_3d_refined']), _lib.ptr(out['rt']), _lib.ptr(out['cost']), _lib.ptr(out['iters']),
+                _lib.ptr(out['status']), _lib.ptr(out['dims']), _lib.current_stream(dev)), 'pnp_refine')
+        return out
+
+    @staticmethod
+    def _refine_host(shape, kpts_2d, intr, roots, weights, max_shift):
+        """The host twin (egn_pnp_refine_host_f64, the same pnp_math.h) on numpy arrays."""
+        def arr(a, shp):
+            a = a.detach().cpu().numpy() if torch.is_tensor(a) else a
+            return np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shp))
+        n = len(shape)
+        shape = arr(shape, (n, -1, 3))
+        J = shape.shape[1] + 1
+        k = arr(kpts_2d, (n, J, 2))
+        r0 = None if roots is None else arr(roots, (n, 3))
+        w = None if weights is None else arr(weights, (n, J))
+        out = {'kpts_3d_refined': np.empty((n, J, 3)), 'rt': np.empty((n, 12)), 'cost': np.empty((n, 2)),
+               'iters': np.empty(n, dtype=np.int32), 'status': np.empty(n, dtype=np.int32), 'dims': np.empty((n, 3))}
+        _lib.check(_lib.lib().egn_pnp_refine_host_f64(
+            shape.ctypes.data, k.ctypes.data, intr.ctypes.data, None if w is None else w.ctypes.data,
+            None if r0 is None else r0.ctypes.data, n, J, float(max_shift), out['kpts_3d_refined'].ctypes.data,
+            out['rt'].ctypes.data, out['cost'].ctypes.data, out['iters'].ctypes.data, out['status'].ctypes.data,
+            out['dims'].ctypes.data), 'pnp_refine_host')
+        return out
+
+    def refine_pnp(self, kpts_3d, kpts_2d, K, roots=None, weights=None, max_shift=5.0):
+        """Fit each lifted cuboid rigidly to its own screen key points: minimise the (weighted) squared reprojection
+        error over a rotation and a translation, from R = I and T = ``roots`` (default: a weak-perspective start).
+          kpts_3d [n,J-1,3] shape relative to the root; kpts_2d [n,J,2] | [n,2J], key point 0 = the root's;
+          K [3,3] | [n,3,3]; roots [n,3]; weights [n,J] (0 drops a correspondence);
+          max_shift: a fit whose root moved further than this from ``roots`` is discarded (status 0).
+        Returns ``kpts_3d_refined`` [n,J,3] (camera coordinates, root first), ``rt`` [n,12] (R row-major, T),
+        ``cost`` [n,2] (squared pixel error before / after), ``iters`` [n], ``status`` [n] (1 refined, 0 discarded
+        by ``max_shift``, -1 not usable; for 0 / -1 the unrefined placement comes back) and ``dims`` [n,3] = (l, h, w).
+        CUDA tensors in give CUDA tensors out: one launch on the current stream, no synchronisation.  numpy inputs
+        (or CPU tensors) run the same arithmetic on the host and give numpy arrays.
+        This is the optimum of the objective from the prediction, not cv2.solvePnP's result: on an instance with
+        several minima the two can differ."""
+        if torch.is_tensor(kpts_3d) and kpts_3d.is_cuda:
+            n = kpts_3d.shape[0]
+            shape = kpts_3d.reshape(n, -1, 3)
+            return self._refine_device(shape, kpts_2d, self._intrinsics(K, n, kpts_3d.device), roots, weights,
+                                       max_shift)
+        n = len(kpts_3d)
+        return self._refine_host(kpts_3d, kpts_2d, self._intrinsics(K, n), roots, weights, max_shift)
+
+    def _refine_record(self, record, max_shift):
+        """``refine=True`` of gather_lifting_results: initial roots from the record's 3-D boxes where it has usable
+        ones (box centre = locations - (0, h/2, 0), car_instance.py:734-739, 761), else the weak-perspective start.
+        A CUDA model runs the kernel, a CPU model the host twin (like ``_pose``)."""
+        if 'K' not in record:
+            raise ValueError("refine needs record['K']")
+        shape = np.asarray(record['kpts_3d_pred'], dtype=np.float64)
+        n = len(shape)
+        shape = shape.reshape(n, -1, 3)
+        k2d = np.concatenate([np.asarray(k, dtype=np.float64).reshape(1, -1) for k in record['kpts_2d_pred']])
+        rows = record.get('raw_txt_format')
+        has_box = np.zeros(n, dtype=bool)
+        roots = np.zeros((n, 3))
+        if rows is not None and len(rows) == n:
+            for i, r in enumerate(rows):
+                if 'locations' in r and 'dimensions' in r and r['locations'][2] > 0:
+                    has_box[i] = True
+                    roots[i] = (r['locations'][0], r['locations'][1] - 0.5 * r['dimensions'][1], r['locations'][2])
+        dev = next(self.parameters()).device
+        intr = self._intrinsics(record['K'], n)
+
+        def run(sel, r0):
+            if dev.type != 'cuda':
+                return self._refine_host(shape[sel], k2d[sel], intr[sel], r0, None, max_shift)
+            out = self._refine_device(_dev_f64(shape[sel], dev), k2d[sel], _dev_f64(intr[sel], dev), r0, None,
+                                      max_shift)
+            return {k: v.cpu().numpy() for k, v in out.items()}
+        if has_box.all() or not has_box.any():      # the usual case: one call
+            return run(slice(None), roots if has_box.all() and n else None)
+        with_box, without = run(has_box, roots[has_box]), run(~has_box, None)
+        out = {}
+        for key, a in with_box.items():
+            out[key] = np.empty((n,) + a.shape[1:], dtype=a.dtype)
+            out[key][has_box], out[key][~has_box] = a, without[key]
+        return out
+
     @staticmethod
     def _wrap(alpha):
         while alpha > math.pi:
@@ -260,9 +415,20 @@ class EgoNet(nn.Module):
         return np.array([self._wrap(e[1] - math.atan2(-f, k[0, 0] - cx) - 0.5 * math.pi)
                          for e, k in zip(euler_angles, kpts)])
 
-    def gather_lifting_results(self, record, alpha_mode='trans', get_str=False):
-        """egonet.py:297-339 without plotting."""
-        record['euler_angles'], record['translation'] = self.get_6d_rep(record['kpts_3d_pred'])
+    def gather_lifting_results(self, record, alpha_mode='trans', get_str=False, refine=False, max_shift=5.0):
+        """egonet.py:297-339 without plotting.  ``refine``: the reference's switch (egonet.py:297-311 with the flow of
+        tools/inference_legacy.py:518-547) -- the lifted cuboid is fitted to ``record['kpts_2d_pred']`` under
+        ``record['K']`` first (``refine_pnp``); angles come from the refined points, ``translation`` is the refined
+        root, and the record gains ``kpts_3d_refined``, ``refine_status`` and ``refine_dims``."""
+        if refine:
+            ref = self._refine_record(record, max_shift)
+            refined = ref['kpts_3d_refined']
+            record['kpts_3d_refined'], record['refine_status'] = refined, ref['status']
+            record['refine_dims'], record['refine_rt'] = ref['dims'], ref['rt']
+            record['euler_angles'], _ = self.get_6d_rep(refined[:, 1:] - refined[:, :1])
+            record['translation'] = refined[:, 0, :].copy()
+        else:
+            record['euler_angles'], record['translation'] = self.get_6d_rep(record['kpts_3d_pred'])
         if alpha_mode == 'trans':
             record['alphas'] = self.get_observation_angle_trans(record['euler_angles'],
                                                                 record['translation'])
@@ -276,15 +442,17 @@ class EgoNet(nn.Module):
         return record
 
     def post_process(self, records, visualize=False, color_dict=None, save_dict=None,
-                     alpha_mode='trans'):
+                     alpha_mode='trans', refine=False, max_shift=5.0):
         """egonet.py:385-408 (+ plot_one_image :341-383 minus the plotting): pose angles
         per image and, with ``save_dict = {'flag': True, 'save_dir': ...}``, one KITTI
-        result file per image (needs ``raw_txt_format`` in the record)."""
+        result file per image (needs ``raw_txt_format`` in the record).  ``refine`` / ``max_shift``: see
+        ``gather_lifting_results``."""
         if visualize:
             raise NotImplementedError('visualisation is outside the hot path')
         save = bool(save_dict and save_dict.get('flag'))
         for path in records:
-            records[path] = self.gather_lifting_results(records[path], alpha_mode=alpha_mode, get_str=save)
+            records[path] = self.gather_lifting_results(records[path], alpha_mode=alpha_mode, get_str=save,
+                                                        refine=refine, max_shift=max_shift)
             if save:
                 save_txt_file(path, records[path], save_dict)
         return records

@@ -828,6 +828,47 @@ int egn_angle_metrics_reset(double* acc, void* stream);
 int egn_angle_metrics_update_f32(const float* pred, long N, int ld, const double* angles_gt, void* ws, long ws_bytes,
                                  double* acc, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Reprojection refinement of lifted cuboids against their own 2-D key points (csrc/pnp_refine.hip, math in
+ * csrc/pnp_math.h): the reference's pnp_refine (libs/common/transformation.py:143-157) with the flow of
+ * tools/inference_legacy.py:518-547, for a batch in one launch.  Per instance a rigid pose (R, T) minimises
+ *     sum_i w_i | pi(R X_i + T) - k_i |^2,   X_0 = 0 (the root), X_i = shape[i-1],
+ * pi the pinhole projection with (fx, fy, cx, cy); no distortion, no scale.  Levenberg-Marquardt from R = I and
+ * T = root0 (or, root0 == NULL, the weak-perspective start z0 = sqrt(sum w (Sx^2 + Sy^2) / sum w |(k_i - k_0)/fx|^2),
+ * T = z0 K^-1 (k_0, 1)); left-multiplicative rotation update, analytic Jacobian, 6x6 normal equations with
+ * Marquardt's diagonal scaling, Cholesky; a step is taken only if the cost does not increase (decided down to the resolution of the cost's own
+ * evaluation, EGN_PNP_COST_RES); ends on a step below
+ * EGN_PNP_STEP_TOL or after EGN_PNP_MAX_ITERS trial steps (pnp_math.h).  It is pinned on the optimum of this
+ * objective, not on cv2.solvePnP: it starts from the prediction rather than from a DLT, so on an instance with
+ * several minima the two can end in different ones.
+ *   shape   [n, J-1, 3] f64   lifted shape relative to the root
+ *   kpts2d  [n, J, 2]   f64   screen key points, key point 0 = the root's projection
+ *   intr    [n, 4]      f64   fx fy cx cy
+ *   weights [n, J]      f64 or NULL (ones); a weight that is not > 0 drops the correspondence
+ *   root0   [n, 3]      f64 or NULL
+ *   max_shift                 >= 0 or +inf; applies only with root0
+ *   refined [n, J, 3]   f64   absolute camera coordinates, root first
+ *   rt      [n, 12]     f64   R row-major, then T, of the returned placement
+ *   cost    [n, 2]      f64   weighted squared pixel error at the start / of the returned placement
+ *   iters   [n] i32           trial steps taken
+ *   status  [n] i32           1 refined;  0 converged but |T - root0| > max_shift;  -1 not usable (a used point with
+ *                             z <= 0 at the start, a non-finite start, a singular system, or the cap reached).
+ *                             For 0 and -1 the output is the unrefined placement [T_start; T_start + shape],
+ *                             rt = (I, T_start) and cost[1] = cost[0]; every output is finite for finite inputs.
+ *   dims    [n, 3]      f64   (l, h, w): mean edge lengths of the returned cuboid, corners = points 1..8, by the
+ *                             rule of the pose solve (zeros when J < 9)
+ * 2 <= J <= 64; n == 0 is a no-op (no launch); n < 0, a J outside the range, a negative or NaN max_shift, or with
+ * n > 0 a NULL required pointer: EGN_E_BADARG.  One launch, one wave per instance, added to the launch counter;
+ * fixed-order sums, so equal inputs give equal bits.  The _host_ entry runs the same header as a plain loop over
+ * HOST pointers (numpy inputs / a CPU model) and is never used for device tensors.
+ * ---------------------------------------------------------------------- */
+int egn_pnp_refine_f64(const double* shape, const double* kpts2d, const double* intr, const double* weights,
+                       const double* root0, int n, int J, double max_shift, double* refined, double* rt,
+                       double* cost, int* iters, int* status, double* dims, void* stream);
+int egn_pnp_refine_host_f64(const double* shape, const double* kpts2d, const double* intr, const double* weights,
+                            const double* root0, int n, int J, double max_shift, double* refined, double* rt,
+                            double* cost, int* iters, int* status, double* dims);
+
 #ifdef __cplusplus
 }
 #endif

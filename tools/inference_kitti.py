@@ -6,6 +6,13 @@ GPU crops -> HRNet key-points -> lifter -> pose solve -> KITTI result files ->
     python tools/inference_kitti.py --images <dir of png> --boxes <dir of KITTI label/detection txt>
         [--calib <dir>] --out <result dir> [--ckpt <dir with HC.pth L.pth LS.npy> | --synthetic]
         [--gt <label dir>] [--classes Car] [--conf-thres 0] [--alpha-mode proj|trans] [--frames-per-step 8]
+        [--refine pnp [--refine-max-shift 5.0] [--write-3d]]
+
+``--refine pnp`` fits every lifted cuboid rigidly to its own key points before the angles are read off
+(EgoNet.refine_pnp, the reference's ``pnp_refine`` flow without cv2); ``rot_y`` / ``alpha`` then come from the refined
+points.  ``--write-3d`` (opt-in, needs ``--refine``) also replaces ``locations`` and ``dimensions`` of the refined
+instances by the fit's own (bottom-face centre = refined root + R (0, h/2, 0); l, h, w = mean edge lengths), so boxes
+of a 2-D detector, which carry -1000 there, give result lines the BEV / 3-D evaluator can score.
 
 Multi-GPU (BASELINE config 5's 8-GPU form): launch one process per GPU with
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...``;
@@ -74,6 +81,22 @@ def build_model(a):
     return ego.eval().cuda()
 
 
+def write_3d(record):
+    """``--write-3d``: a copy of the record's ``raw_txt_format`` whose refined instances (status 1) carry the fit's own
+    ``locations`` (refined root + R (0, h/2, 0), the bottom-face centre) and ``dimensions`` (l, h, w)."""
+    rows = []
+    for i, row in enumerate(record['raw_txt_format']):
+        row = dict(row)
+        if record['refine_status'][i] == 1:
+            l, h, w = (float(v) for v in record['refine_dims'][i])
+            R = record['refine_rt'][i, :9].reshape(3, 3)
+            loc = record['translation'][i] + R @ np.array([0., 0.5 * h, 0.])
+            row['locations'] = [float(v) for v in loc]
+            row['dimensions'] = [l, h, w]
+        rows.append(row)
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', required=True)
@@ -88,9 +111,16 @@ def main(argv=None):
     ap.add_argument('--conf-thres', type=float, default=0.0)
     ap.add_argument('--alpha-mode', default='proj', choices=['proj', 'trans'])
     ap.add_argument('--frames-per-step', type=int, default=8)
+    ap.add_argument('--refine', default=None, choices=['pnp'], help='fit the lifted cuboid to its key points first')
+    ap.add_argument('--refine-max-shift', type=float, default=5.0,
+                    help='discard a fit whose root moved further than this (m) from the box it started at')
+    ap.add_argument('--write-3d', action='store_true',
+                    help="write the fit's own locations / dimensions for refined instances (needs --refine)")
     a = ap.parse_args(argv)
     if not a.ckpt and not a.synthetic:
         ap.error('give --ckpt <dir> or --synthetic')
+    if a.write_3d and not a.refine:
+        ap.error('--write-3d needs --refine')
     classes = {c.strip().lower() for c in a.classes.split(',')}
     data_dir = os.path.join(a.out, 'data')
     os.makedirs(data_dir, exist_ok=True)
@@ -109,7 +139,7 @@ def main(argv=None):
     if world > 1:
         lo_r, hi_r = shard_range(len(names), world, rank)
         names = names[lo_r:hi_r]
-    n_inst, t0 = 0, time.perf_counter()
+    n_inst, n_refined, t0 = 0, 0, time.perf_counter()
     for lo in range(0, len(names), a.frames_per_step):
         annot = {'path': [], 'boxes': [], 'raw_txt_format': [], 'K': []}
         images = {}
@@ -127,7 +157,18 @@ def main(argv=None):
         if not annot['path']:
             continue
         records = ego(annot, images=images)
-        ego.post_process(records, save_dict={'flag': True, 'save_dir': data_dir}, alpha_mode=a.alpha_mode)
+        save = {'flag': True, 'save_dir': data_dir}
+        if not a.write_3d:
+            ego.post_process(records, save_dict=save, alpha_mode=a.alpha_mode, refine=a.refine == 'pnp',
+                             max_shift=a.refine_max_shift)
+        else:       # get_pred_str stays as it is: it formats this tool's edited copy of raw_txt_format
+            for path, rec in records.items():
+                rec = ego.gather_lifting_results(rec, alpha_mode=a.alpha_mode, refine=True,
+                                                 max_shift=a.refine_max_shift)
+                n_refined += int((rec['refine_status'] == 1).sum())
+                rec['raw_txt_format'] = write_3d(rec)
+                rec['pred_str'] = kfmt.get_pred_str(rec)
+                kfmt.save_txt_file(path, rec, save)
         n_inst += sum(len(b) for b in annot['boxes'])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -148,6 +189,10 @@ def main(argv=None):
             open(os.path.join(data_dir, stem), 'w').close()
     out = {'frames': len(names), 'instances': n_inst, 'seconds': round(dt, 3), 'n_gpus': world,
            'instances_per_s': round(n_inst / dt, 1) if dt > 0 else None, 'result_dir': data_dir}
+    if a.refine:
+        out['refine'] = a.refine
+    if a.write_3d and world == 1:
+        out['refined_3d'] = n_refined
     if dist is not None:
         dist.destroy_process_group()
     if a.gt:
