@@ -125,6 +125,8 @@ SIGNATURES = {
     'egn_program_add_nhwc_to_nchw': (_i, [_p, Ref, Ref, _i, _i, _i, _i, _i]),
     'egn_program_add_pixel_shuffle': (_i, [_p, Ref, Ref, _i, _i, _i, _i, _i, _i]),
     'egn_program_add_pw_pair': (_i, [_p] + [Ref] * 8 + [_i, _i]),
+    'egn_program_add_conv2d_pair': (_i, [_p] + ([Ref] * 6 + [_i] * 6) * 2 + [_i]),
+    'egn_conv_pair_plan_query': (_i, [_i] * 13 + [C.POINTER(_i)]),
     'egn_pw_pair_f32': (_i, [_p] * 8 + [_i, _i, _p]),
     'egn_program_add_ramps': (_i, [_p, Ref, _i, _i, _i, _i, _i]),
     'egn_program_add_decode': (_i, [_p, Ref, _i, _i, _i, _i, _i, Ref, Ref, Ref]),

@@ -48,6 +48,7 @@
 // Reference: the 3x3 stride-1 convolutions of libs/model/heatmapModel/hrnet.py (BasicBlock :49-76 and the
 // branches built from it); tolerance as for the F(2x2,3x3) kernels, see tools/wino43_network_study.py.
 #include "conv_wino4.h"
+#include "conv_wino4w_body.h"
 
 // ABL != 0: timing ablations (WRONG RESULTS; probe builds only -- -DEGN_PROBES, tools/wino_probe.py): bit 0 no input
 // transform, bit 1 no MFMAs, bit 2 no exchange / output transform / stores, bit 3 no filter loads, bit 4 no halo DMA,
@@ -58,8 +59,10 @@
 // what the lane stores, per block and output channel, as conv_wino9_kernel writes them: egn_bn_stats_finalize_f32 adds
 // the rows of all blocks in a fixed order).  A block's items all have the same co-tile (the grid is a multiple of
 // 8 x co-tiles x KS, tests/test_wino4_design_cpu.py), so its row covers 48 channels and is zero elsewhere.
+// blk / nblk: the block's index in its launch share and the share's size -- blockIdx.x / gridDim.x in the single-conv
+// kernels, the second share of conv_wino4_pair_kernel; the item order assumes block blk runs on XCD blk & 7.
 template <int ABL, int GEO, int KS = 1, bool ST = false>
-__device__ __forceinline__ void w4_body(const ConvArgs& a) {
+__device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
   typedef W4G<GEO> Q;
   extern __shared__ float4 w4_smem[];
   const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)(lds_ptr_w4_t)w4_smem;
@@ -134,7 +137,7 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a) {
   const int nreg = regs_xy * ((a.N + Q::NIMG - 1) / Q::NIMG);
   const int imode = w4_item_mode(nct);     // what the XCD owns: regions / co-tiles (w4_item_mode)
   const int nwork = w4_item_count(imode, nreg, nct, KS);
-  const int gsz = __builtin_amdgcn_readfirstlane((int)gridDim.x);
+  const int gsz = __builtin_amdgcn_readfirstlane(nblk);
   const float act_lo = (a.act & EGN_ACT_MASK) == EGN_ACT_RELU ? 0.f : -__builtin_inff();
   // K split: with a ticket word per item pair (ConvArgs::tickets, programs) the second half to finish does the
   // epilogue; without one both halves add into a zeroed y (see the launcher)
@@ -163,7 +166,7 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a) {
     static_assert(ABL == 0, "the statistics build has no ablations");
     for (int e = tid; e < W4_NW * 2 * 16; e += W4_NTH) sS[e] = 0.0;
   }
-  for (int w = blockIdx.x; w < nwork; w += gsz) {
+  for (int w = blk; w < nwork; w += gsz) {
     // item -> (region, co-tile): blocks w, w + 8, ... stay on one XCD (conv_wino.hip: wino8_grid)
     const unsigned wi = (unsigned)__builtin_amdgcn_readfirstlane(w);
     const unsigned xq = wi & 7u, q_ = wi >> 3;
@@ -564,16 +567,28 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a) {
 }
 
 template <int ABL>
-__global__ __launch_bounds__(W4_NTH, 1) void conv_wino4_kernel(ConvArgs a) { w4_body<ABL, 0>(a); }
+__global__ __launch_bounds__(W4_NTH, 1) void conv_wino4_kernel(ConvArgs a) { w4_body<ABL, 0>(a, (int)blockIdx.x, (int)gridDim.x); }
 template <int ABL>
-__global__ __launch_bounds__(W4_NTH, 1) void conv_wino4b_kernel(ConvArgs a) { w4_body<ABL, 1>(a); }
+__global__ __launch_bounds__(W4_NTH, 1) void conv_wino4b_kernel(ConvArgs a) { w4_body<ABL, 1>(a, (int)blockIdx.x, (int)gridDim.x); }
 template <int ABL>      // conv_wino4b_kernel with the input channels of an item split over two blocks (as conv_wino4c_kernel<., 2>)
-__global__ __launch_bounds__(W4_NTH, 1) void conv_wino4bk_kernel(ConvArgs a) { w4_body<ABL, 1, 2>(a); }
+__global__ __launch_bounds__(W4_NTH, 1) void conv_wino4bk_kernel(ConvArgs a) { w4_body<ABL, 1, 2>(a, (int)blockIdx.x, (int)gridDim.x); }
 template <int ABL, int KS>
-__global__ __launch_bounds__(W4_NTH, 1) void conv_wino4c_kernel(ConvArgs a) { w4_body<ABL, 2, KS>(a); }
+__global__ __launch_bounds__(W4_NTH, 1) void conv_wino4c_kernel(ConvArgs a) { w4_body<ABL, 2, KS>(a, (int)blockIdx.x, (int)gridDim.x); }
 // the training tape's builds (BatchNorm statistics in the item end, `ConvArgs::stats`): every geometry / K split above
 template <int GEO, int KS>
-__global__ __launch_bounds__(W4_NTH, 1) void conv_wino4s_kernel(ConvArgs a) { w4_body<0, GEO, KS, true>(a); }
+__global__ __launch_bounds__(W4_NTH, 1) void conv_wino4s_kernel(ConvArgs a) { w4_body<0, GEO, KS, true>(a, (int)blockIdx.x, (int)gridDim.x); }
+
+// Two independent convolutions in ONE launch [pair]: blocks [0, blocks_a) run conv_wino4w_kernel's body on `a` (16 x 16
+// regions x 96 output channels per item), the others conv_wino4c_kernel<0, 1>'s on `b` (four 8 x 8 images per region,
+// whole-K items).  Both forms are the cheap ones in CU-time and lose stand-alone only because their grids fill half the
+// chip at 64 crops (128 items each); side by side they fill it.  blocks_a is a multiple of 8, so a block of either share
+// keeps the XCD (index & 7) its item order assumes.  The shares never meet: no barrier, no flag, no shared word.
+// Bit-identical to the two single launches (same bodies, same item order per share, same MFMA order per accumulator).
+__global__ __launch_bounds__(W4_NTH, 1) void conv_wino4_pair_kernel(ConvArgs a, ConvArgs b, int blocks_a) {
+  const int bid = (int)blockIdx.x;
+  if (bid < blocks_a) w4w_body<0>(a, bid, blocks_a);
+  else w4_body<0, 2, 1>(b, bid - blocks_a, (int)gridDim.x - blocks_a);
+}
 
 // second pass of the K-split form: y holds the sum of the items' raw outputs; y = act(y * scale + shift + res) in place
 __global__ __launch_bounds__(256) void conv_wino4_finish_kernel(float* __restrict__ y, const float* __restrict__ res,
@@ -805,4 +820,65 @@ int egn_conv_launch_wino4(ConvArgs a, size_t lds, Wino4Kernel k, int abl, hipStr
       }
   }
   return EGN_E_BADARG;
+}
+
+// ---- the paired launch: conv_wino4w_kernel's items on `a` beside conv_wino4c_kernel<0, 1>'s on `b` ----
+// Plan (host only, no GPU): does the pair apply, and how are `cus` blocks split?  a and b are planned for Wino4w / Wino4c
+// (egn_conv_plan with cfg 86 / 82).  Each share follows its single launcher's rule: all its items if they fit its part
+// of the chip, else whole XCD rounds of (8 x co-tile pairs) / (8 x co-tiles) blocks, so that the items of a block share
+// their co-tile (pair).  The chip is divided by item count (an item of either kind is 16 tiles x 96 channels x Cin
+// resp. 16 tiles x 48 channels x Cin of MFMA work behind one prologue: the same order of cost); a share never gets less
+// than one round.  Both counts are multiples of 8.
+int egn_conv_pair_plan(const ConvArgs* a, const ConvArgs* b, int cus, int* blocks_a, int* blocks_b) {
+  if (!a || !b || cus <= 0) return EGN_E_BADARG;
+  if (a->stats || b->stats || a->tickets || b->tickets) return EGN_E_BADARG;
+  if (!egn_conv_wino4w_applies(*a) || !egn_conv_wino4_applies(*b, Wino4c)) return EGN_E_BADARG;
+  if (a->tiles_x <= 0 || a->tiles_y <= 0 || b->tiles_x != 1 || b->tiles_y != 1) return EGN_E_BADARG;   // (not planned)
+  const int ncp = a->Cout / (2 * W4_CO), nct = b->Cout / W4_CO;
+  const int nreg_a = a->tiles_x * a->tiles_y * a->N, nreg_b = (b->N + 3) / 4;
+  const int nwork_a = w4_item_count(w4_item_mode(ncp), nreg_a, ncp, 1);
+  const int nwork_b = w4_item_count(w4_item_mode(nct), nreg_b, nct, 1);
+  // the item index divisions run as one multiply-high each (wino4_launch)
+  if ((unsigned long long)nwork_a * (unsigned)(8 * ncp) >= 0x100000000ull ||
+      (unsigned long long)(nreg_a + 8) * (unsigned)(a->tiles_x * a->tiles_y) >= 0x100000000ull ||
+      (unsigned long long)nwork_b * (unsigned)(8 * nct) >= 0x100000000ull)
+    return EGN_E_BADARG;
+  int ga = nwork_a, gb = nwork_b;
+  if ((long long)nwork_a + nwork_b > cus) {
+    const int ra = 8 * ncp, rb = 8 * nct;
+    long long share = (long long)cus * nwork_a / ((long long)nwork_a + nwork_b);
+    int cap_a = (int)(share / ra) * ra;
+    if (cap_a < ra) cap_a = ra;
+    ga = nwork_a < cap_a ? nwork_a : cap_a;
+    int cap_b = (cus - ga) / rb * rb;
+    if (cap_b < rb) cap_b = rb;
+    gb = nwork_b < cap_b ? nwork_b : cap_b;
+  }
+  if (blocks_a) *blocks_a = ga;
+  if (blocks_b) *blocks_b = gb;
+  return 0;
+}
+
+// cus <= 0: the device's CU count (a test may cap the grid to make the persistent loops iterate)
+int egn_conv_launch_wino4_pair(ConvArgs a, ConvArgs b, int cus, hipStream_t stream) {
+  int ga = 0, gb = 0;
+  const int rc = egn_conv_pair_plan(&a, &b, cus > 0 ? cus : w4_cus(), &ga, &gb);
+  if (rc) return rc;
+  static bool raised[EGN_MAX_DEVICES];
+  void (*kern)(ConvArgs, ConvArgs, int) = &conv_wino4_pair_kernel;
+  if (egn_first_use_on_device(raised)) {
+    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      160 * 1024 - 512));
+  }
+  const int ncp = a.Cout / (2 * W4_CO), nct = b.Cout / W4_CO;
+  const int ma = w4_item_mode(ncp), mb = w4_item_mode(nct);
+  a.mg_nct = ma == 1 ? 0u : w4_magic(ma == 2 ? ncp / 8 : ncp);
+  a.mg_txy = w4_magic(a.tiles_x * a.tiles_y);
+  a.mg_tx = w4_magic(a.tiles_x);
+  b.mg_nct = mb == 1 ? 0u : w4_magic(mb == 2 ? nct / 8 : nct);
+  b.mg_txy = w4_magic(b.tiles_x * b.tiles_y);
+  b.mg_tx = w4_magic(b.tiles_x);
+  const size_t lds = egn_conv_wino4_lds_bytes(Wino4c);      // the larger of the two bodies' (GEO 2), + the stamp area
+  hipLaunchKernelGGL(kern, dim3(ga + gb), dim3(W4_NTH), lds, stream, a, b, ga);
+  return (int)hipGetLastError();
 }

@@ -132,5 +132,12 @@ const ConvConfig* egn_conv_config(int cfg);
 int egn_conv_stats_rows(const ConvArgs& a, int cfg_id);
 int egn_conv_ticket_count(const ConvArgs& a, int cfg_id);   // a planned for cfg_id; 0 = the config uses none
 
+// The paired F(4x4,3x3) launch (conv_wino4.hip): a planned for cfg 86 (conv_wino4w_kernel), b for cfg 82
+// (conv_wino4c_kernel<0, 1>).  egn_conv_pair_plan is host-only: 0 and the two grid shares (multiples of 8) where the
+// pair applies (both kernels take their shape, no BatchNorm statistics, no ticket words), else EGN_E_BADARG.
+constexpr int EGN_PAIR_CFG_A = 86, EGN_PAIR_CFG_B = 82;
+int egn_conv_pair_plan(const ConvArgs* a, const ConvArgs* b, int cus, int* blocks_a, int* blocks_b);
+int egn_conv_launch_wino4_pair(ConvArgs a, ConvArgs b, int cus, hipStream_t stream);   // cus <= 0: the device's
+
 // adds n to egn_launch_count() (program.hip): entry points outside programs that want their launches provable
 void egn_count_launches(long n);

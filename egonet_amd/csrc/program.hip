@@ -161,7 +161,7 @@ extern "C" int egn_conv_plan_query(int N, int H, int W, int Cin, int cs_in, int 
 // programs
 // ---------------------------------------------------------------------------
 enum OpKind { OP_CONV = 1, OP_FUSE = 2, OP_NCHW2NHWC = 3, OP_NHWC2NCHW = 4, OP_RAMPS = 5, OP_DECODE = 6,
-              OP_FORK = 7, OP_JOIN = 8, OP_PIXSHUF = 9, OP_PWPAIR = 10 };
+              OP_FORK = 7, OP_JOIN = 8, OP_PIXSHUF = 9, OP_PWPAIR = 10, OP_CONVPAIR = 11 };
 constexpr int kMaxLanes = 4;  // concurrent launch lanes (HRNet has at most 4 branches)
 
 struct Op {
@@ -169,8 +169,9 @@ struct Op {
   int lane = 0;  // launch lane (0 = the caller's stream, 1.. = side streams) inside a fork/join region
   // conv
   ConvArgs conv;
+  ConvArgs conv2;  // OP_CONVPAIR: the second convolution (refs r[6..11])
   int cfg;
-  egn_ref r[8];  // pointer refs, meaning depends on kind
+  egn_ref r[12];  // pointer refs, meaning depends on kind
   // generic ints
   int i[12];
   std::string tag;
@@ -359,6 +360,60 @@ extern "C" int egn_program_add_conv2d(egn_program* p, egn_ref x, egn_ref wpack, 
   return 0;
 }
 
+// 3x3 / stride 1 / pad 1 convolution with unpadded channel strides, planned for `cfg`
+static int plan_pair_half(ConvArgs& a, int N, int H, int W, int Cin, int Cout, int act, int cfg) {
+  int rc = fill_conv_args(a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, Cin, Cin, Cout, Cout, 3, 3, 1,
+                          1, act, 0);
+  if (rc) return rc;
+  size_t lds;
+  return egn_conv_plan(a, cfg, lds);
+}
+
+extern "C" int egn_conv_pair_plan_query(int Na, int Ha, int Wa, int Cin_a, int Cout_a, int Nb, int Hb, int Wb,
+                                        int Cin_b, int Cout_b, int cus, int with_stats, int with_tickets, int* out) {
+  if (!out) return EGN_E_BADARG;
+  ConvArgs a, b;
+  if (plan_pair_half(a, Na, Ha, Wa, Cin_a, Cout_a, 0, EGN_PAIR_CFG_A) ||
+      plan_pair_half(b, Nb, Hb, Wb, Cin_b, Cout_b, 0, EGN_PAIR_CFG_B))
+    return EGN_E_BADARG;
+  static double some_stats;
+  static unsigned some_tickets;
+  if (with_stats) a.stats = &some_stats;          // (never dereferenced: the plan refuses)
+  if (with_tickets) b.tickets = &some_tickets;
+  return egn_conv_pair_plan(&a, &b, cus, &out[0], &out[1]);
+}
+
+// Two independent 3x3 / stride 1 / pad 1 convolutions as ONE launch (conv_wino4_pair_kernel, conv_wino4.hip): `a` the
+// way cfg 86 runs it, `b` the way cfg 82 does -- their filter packing (kind 3), their results bit for bit.
+extern "C" int egn_program_add_conv2d_pair(egn_program* p, egn_ref xa, egn_ref wa, egn_ref scale_a, egn_ref shift_a,
+                                           egn_ref res_a, egn_ref ya, int Na, int Ha, int Wa, int Cin_a, int Cout_a,
+                                           int act_a, egn_ref xb, egn_ref wb, egn_ref scale_b, egn_ref shift_b,
+                                           egn_ref res_b, egn_ref yb, int Nb, int Hb, int Wb, int Cin_b, int Cout_b,
+                                           int act_b, int grid_cap) {
+  if (!p) return EGN_E_BADARG;
+  Op op;
+  op.kind = OP_CONVPAIR;
+  int rc = plan_pair_half(op.conv, Na, Ha, Wa, Cin_a, Cout_a, act_a, EGN_PAIR_CFG_A);
+  if (!rc) rc = plan_pair_half(op.conv2, Nb, Hb, Wb, Cin_b, Cout_b, act_b, EGN_PAIR_CFG_B);
+  if (rc) return rc;
+  int ga, gb;
+  rc = egn_conv_pair_plan(&op.conv, &op.conv2, grid_cap > 0 ? grid_cap : 256, &ga, &gb);
+  if (rc) return rc;
+  op.cfg = 0;
+  op.i[0] = grid_cap;
+  const egn_ref refs[12] = {xa, wa, scale_a, shift_a, res_a, ya, xb, wb, scale_b, shift_b, res_b, yb};
+  for (int k = 0; k < 12; ++k) {
+    if (!ref_ok(p, refs[k]) || (refs[k].slot < 0 && k % 6 != 4)) return EGN_E_BADARG;    // (only the residuals may be NULL)
+    op.r[k] = refs[k];
+  }
+  op.flops = 2.0 * 9.0 * ((double)Na * Ha * Wa * Cout_a * Cin_a + (double)Nb * Hb * Wb * Cout_b * Cin_b);
+  op.bytes = 4.0 * ((double)Na * Ha * Wa * (Cin_a + Cout_a * (res_a.slot >= 0 ? 2.0 : 1.0)) + 9.0 * Cout_a * Cin_a +
+                    (double)Nb * Hb * Wb * (Cin_b + Cout_b * (res_b.slot >= 0 ? 2.0 : 1.0)) + 9.0 * Cout_b * Cin_b);
+  op.lane = p->cur_lane;
+  p->ops.push_back(op);
+  return 0;
+}
+
 extern "C" int egn_program_add_fuse(egn_program* p, egn_ref y, int N, int H, int W, int C, int cs, int nterms,
                                     const egn_ref* terms, const int* shifts, int relu) {
   if (!p || nterms < 1 || nterms > 4 || cs % 4 || C > cs) return EGN_E_BADARG;
@@ -508,6 +563,16 @@ static int launch_op(egn_program* p, Op& op, hipStream_t s) {
       a.res = (const float*)resolve(p, op.r[4]);
       a.y = (float*)resolve(p, op.r[5]);
       return egn_conv_launch(a, op.cfg, s);
+    }
+    case OP_CONVPAIR: {
+      ConvArgs a = op.conv, b = op.conv2;
+      a.x = (const float*)resolve(p, op.r[0]);   b.x = (const float*)resolve(p, op.r[6]);
+      a.w = (const float*)resolve(p, op.r[1]);   b.w = (const float*)resolve(p, op.r[7]);
+      a.scale = (const float*)resolve(p, op.r[2]);   b.scale = (const float*)resolve(p, op.r[8]);
+      a.shift = (const float*)resolve(p, op.r[3]);   b.shift = (const float*)resolve(p, op.r[9]);
+      a.res = (const float*)resolve(p, op.r[4]);   b.res = (const float*)resolve(p, op.r[10]);
+      a.y = (float*)resolve(p, op.r[5]);   b.y = (float*)resolve(p, op.r[11]);
+      return egn_conv_launch_wino4_pair(a, b, op.i[0], s);
     }
     case OP_FUSE: {
       const float* terms[4];

@@ -251,6 +251,23 @@ class _Recorder(object):
         self._push('conv', op)
         return dst
 
+    def conv_pair(self, xa, conv_a, bn_a, act_a, res_a, xb, conv_b, bn_b, act_b, res_b, tag=''):
+        """Two independent 3x3 / stride 1 / pad 1 convolutions (+ folded BatchNorm, residual, ReLU) as ONE launch
+        (csrc/conv_wino4.hip, conv_wino4_pair_kernel): ``a`` as tile configuration 86 runs it, ``b`` as 82 does.  The
+        caller asked ``tuner.pair_usable`` first.  Returns (ya, yb).  Only the inference recorder has this op: the
+        training tape records its layers one by one."""
+        halves = []
+        for x, conv, bn, act, res, which in ((xa, conv_a, bn_a, act_a, res_a, 'a'), (xb, conv_b, bn_b, act_b, res_b, 'b')):
+            cout, cin, kh, kw = conv.weight.shape
+            assert (cin, kh, kw) == (x.c, 3, 3) and x.cs == x.c and cout % 4 == 0, (conv.weight.shape, x.c, x.cs, tag)
+            y = self.new(x.n, x.h, x.w, cout, name='%s.%s' % (tag, which))
+            scale, shift = fold_scale_shift(cout, None, bn)
+            halves.append(dict(x=x, w=None, w_src=conv.weight, scale=self.weight(scale), shift=self.weight(shift), res=res,
+                               y=y, cin=cin, cout=cout, act=act))
+        self._touch(*[h[k] for h in halves for k in ('x', 'res', 'y')])
+        self._push('convpair', dict(a=halves[0], b=halves[1], tag=tag))
+        return halves[0]['y'], halves[1]['y']
+
     def fuse(self, terms, relu, tag=''):
         """terms: list of (Buf, shift); output resolution = that of a shift-0 term."""
         base = [t for t, s in terms if s == 0][0]
@@ -417,6 +434,11 @@ class Program(object):
         """Tile configuration per conv (measured table / autotune) and the filter in the layout
         that configuration's kernel stages through LDS."""
         for kind, op in rec.ops:
+            if kind == 'convpair':          # both halves read the F(4x4,3x3) register-feed layout (configs 86 / 82)
+                for half in (op['a'], op['b']):
+                    if half['w'] is None:
+                        half['w'] = rec.weight(pack_for_kind(half['w_src'], 3))
+                continue
             if kind != 'conv' or op.get('w') is not None:
                 continue
             if 'cfg' not in op:
@@ -445,6 +467,20 @@ class Program(object):
                             + op['cout'] * op['cin'] * op['kh'] * op['kw'])
             klass = 'conv%dx%ds%d %d->%d@%dx%d' % (op['kh'], op['kw'], op['stride'], op['cin'],
                                                     op['cout'], op['ho'], op['wo'])
+        elif kind == 'convpair':
+            args, klass = [], []
+            for half in (op['a'], op['b']):
+                x, y = half['x'], half['y']
+                res = half['res'].ref() if half['res'] is not None else NULL_REF
+                args += [x.ref(), half['w'], half['scale'], half['shift'], res, y.ref(), x.n, x.h, x.w, half['cin'],
+                         half['cout'], half['act']]
+                m = x.n * x.h * x.w
+                flops += 2.0 * m * half['cout'] * half['cin'] * 9
+                nbytes += 4.0 * (m * half['cin'] + m * half['cout'] * (2 if half['res'] is not None else 1)
+                                 + half['cout'] * half['cin'] * 9)
+                klass.append('%d->%d@%dx%d' % (half['cin'], half['cout'], x.h, x.w))
+            _lib.check(L.egn_program_add_conv2d_pair(h, *(args + [0])), op['tag'])
+            klass = 'convpair3x3s1 ' + ' + '.join(klass)
         elif kind == 'fuse':
             y = op['y']
             terms = op['terms']
@@ -664,13 +700,51 @@ class HRNetEngine(object):
                        tag='%s.%d' % (tag, s))
         return t
 
-    def _module(self, r, xs, mod, tag, region_open=False, keep_open=False):
+    @staticmethod
+    def _pair_branches(r, xs, mod):
+        """(ia, ib) if branches ia and ib of ``mod`` run level by level as paired launches (``_Recorder.conv_pair``), else
+        None: the recorder has the op (the training tape has not), both are chains of plain BasicBlocks of equal length,
+        and ``tuner.pair_usable`` -- the one place that says whether a pair is used -- takes their shapes with and
+        without the residual.  Stage 4 of W48 at 64 crops: the 192-channel 16 x 16 branch beside the 384-channel 8 x 8 one
+        (hrnet.py:286-287: the branches are independent at every depth)."""
+        if mod is None or not hasattr(r, 'conv_pair'):
+            return None
+
+        def plain(branch, x):
+            for blk in branch:
+                if getattr(blk, 'depth', 0) != 2 or blk.downsample is not None:
+                    return False
+                for conv in (blk.conv1, blk.conv2):
+                    if tuple(conv.weight.shape) != (x.c, x.c, 3, 3) or conv.stride[0] != 1 or conv.padding[0] != 1 \
+                            or conv.bias is not None:
+                        return False
+            return x.cs == x.c and len(branch) > 0
+
+        def key(x, has_res):
+            return (x.n, x.h, x.w, x.c, x.c, x.c, x.c, 3, 3, 1, 1, has_res, False)
+        nb = mod.num_branches
+        for ia in reversed(range(nb)):          # (the coarsest pair first: what the measured table holds)
+            for ib in reversed(range(nb)):
+                if ia == ib or len(mod.branches[ia]) != len(mod.branches[ib]):
+                    continue
+                if not (plain(mod.branches[ia], xs[ia]) and plain(mod.branches[ib], xs[ib])):
+                    continue
+                if all(tuner.pair_usable(key(xs[ia], res), key(xs[ib], res)) for res in (False, True)):
+                    return ia, ib
+        return None
+
+    def _module(self, r, xs, mod, tag, region_open=False, keep_open=False, nxt=None):
         """``region_open``: the previous module left its fuse region open -- output i was
         produced on lane i, which is exactly what branch i of this module reads, so the
         branches continue on their lanes without a join/fork pair in between (lane 0 does
         not wait for the coarse lanes' fuse work).  ``keep_open``: leave this module's fuse
-        region open for the next one (same stage, same branch count).  Returns (outs, open)."""
+        region open for the next one, ``nxt`` (same stage, same branch count).  Returns (outs, open).
+        A paired launch reads tensors of two branches: both chains are recorded on the lane of the lower branch, and
+        where the next module pairs too and the region stays open, so are the two fuse outputs that feed them -- every
+        tensor a pair reads was written on its own lane (stream order; ``_Recorder.happens_before`` sees it).  The
+        other branches keep their lanes: lane 0 runs on into the next module without waiting for the coarse ones."""
         xs = list(xs)
+        pair = self._pair_branches(r, xs, mod)
         # the resolution branches are independent (hrnet.py:286-287): one launch
         # lane each, so their kernels overlap each other's prologue / epilogue /
         # tail and the small coarse-branch grids do not leave the chip idle
@@ -678,8 +752,19 @@ class HRNetEngine(object):
         if lanes and not region_open:
             r.fork()
         for b, branch in enumerate(mod.branches):
+            if pair is not None and b == max(pair):
+                continue                # (recorded with its partner)
             if lanes:
                 r.lane(b)
+            if pair is not None and b == min(pair):
+                ia, ib = pair
+                for k, (ba, bb) in enumerate(zip(mod.branches[ia], mod.branches[ib])):
+                    q = '%s.branches.%d+%d.%d' % (tag, ia, ib, k)
+                    ha, hb = r.conv_pair(xs[ia], ba.conv1, ba.bn1, ACT_RELU, None,
+                                         xs[ib], bb.conv1, bb.bn1, ACT_RELU, None, tag=q + '.conv1')
+                    xs[ia], xs[ib] = r.conv_pair(ha, ba.conv2, ba.bn2, ACT_RELU, xs[ia],
+                                                 hb, bb.conv2, bb.bn2, ACT_RELU, xs[ib], tag=q + '.conv2')
+                continue
             for k, blk in enumerate(branch):
                 xs[b] = self._block(r, xs[b], blk, '%s.branches.%d.%d' % (tag, b, k))
         if lanes:
@@ -687,11 +772,13 @@ class HRNetEngine(object):
         if mod.fuse_layers is None:
             return xs, False
         outs = []
+        stay = lanes and keep_open and self.chain_regions and len(mod.fuse_layers) == mod.num_branches
+        pair_next = self._pair_branches(r, xs, nxt) if stay else None
         if lanes:                       # the fuse outputs are independent too (hrnet.py:291-298)
             r.fork()
         for i, row in enumerate(mod.fuse_layers):
             if lanes:
-                r.lane(i)
+                r.lane(min(pair_next) if pair_next is not None and i in pair_next else i)
             terms = []
             for j in range(mod.num_branches):
                 q = '%s.fuse_layers.%d.%d' % (tag, i, j)
@@ -704,7 +791,6 @@ class HRNetEngine(object):
                 else:
                     terms.append((self._unit_chain(r, xs[j], row[j], q), 0))
             outs.append(r.fuse(terms, True, tag='%s.fuse%d' % (tag, i)))
-        stay = lanes and keep_open and self.chain_regions and len(outs) == mod.num_branches
         if lanes and not stay:
             r.join()
         return outs, stay
@@ -736,7 +822,8 @@ class HRNetEngine(object):
             for k, mod in enumerate(stage):
                 nxt = stage[k + 1] if k + 1 < len(stage) else None
                 keep = nxt is not None and nxt.num_branches == mod.num_branches
-                xs, open_ = self._module(r, xs, mod, 'stage%d.%d' % (idx + 1, k), region_open=open_, keep_open=keep)
+                xs, open_ = self._module(r, xs, mod, 'stage%d.%d' % (idx + 1, k), region_open=open_, keep_open=keep,
+                                         nxt=nxt if keep else None)
             ys = xs
         trunk = ys[0]
         J = m.num_joints

@@ -209,6 +209,126 @@ def choose(device, key, kinds=DIRECT, ticket_cap=None, inplace_res=False):
     return _pick(entry, key, kinds, ticket_cap, inplace_res)
 
 
+# ---------------------------------------------------------------------------
+# paired launches: two independent 3x3 convolutions as one op (csrc/conv_wino4.hip, conv_wino4_pair_kernel)
+# ---------------------------------------------------------------------------
+PAIRS_PATH = os.path.join(_HERE, 'tuned', 'gfx950_pairs.json')
+PAIR_CFGS = (86, 82)          # the single-convolution forms of the pair's two shares
+PAIR_DEFAULT = '0'            # EGONET_AMD_PAIR when unset
+_pairs = None
+
+
+def _load_pairs():
+    global _pairs
+    if _pairs is None:
+        _pairs = {}
+        try:
+            with open(PAIRS_PATH) as f:
+                _pairs = {k: v for k, v in json.load(f).items() if not k.startswith('_')}
+        except (OSError, ValueError):
+            _pairs = {}
+    return _pairs
+
+
+def pair_key(key_a, key_b):
+    return shape_key(*key_a) + '+' + shape_key(*key_b)
+
+
+def pair_plans(key_a, key_b, cus=256):
+    """(blocks on a, blocks on b) of the paired launch on a chip of ``cus`` compute units, None where the library's
+    planner refuses the two shapes (egn_conv_pair_plan_query; no GPU needed)."""
+    if any(tuple(k[7:11]) != (3, 3, 1, 1) or k[3] != k[4] or k[5] != k[6] or k[12] for k in (key_a, key_b)):
+        return None
+    out = (C.c_int * 2)()
+    rc = _lib.lib().egn_conv_pair_plan_query(*key_a[:4], key_a[5], *key_b[:4], key_b[5], cus, 0, 0, out)
+    return (out[0], out[1]) if rc == 0 else None
+
+
+def pair_usable(key_a, key_b):
+    """THE rule for running convolutions ``key_a`` and ``key_b`` (``shape_key`` arguments) as one paired launch
+    (engine._Recorder.conv_pair).  Measured like every other choice: the pair is used where tuned/gfx950_pairs.json
+    (``tune_pair``: the pair op as a one-op program against the sum of the two tabled singles) says it won -- a shape
+    without an entry is not paired.  EGONET_AMD_PAIR=1 pairs by that table, =force wherever the planner takes the shapes
+    (tests), =0 never.  The default is 0 (PAIR_DEFAULT; DESIGN 3.2d says why and what was measured).  Anything that
+    keeps config 86 or 82 away from a caller keeps the pair away too: EGONET_AMD_SKIP_CFG naming one of them, any
+    EGONET_AMD_WINO forcing, EGONET_AMD_F43=0."""
+    key_a, key_b = tuple(key_a), tuple(key_b)
+    mode = os.environ.get('EGONET_AMD_PAIR', PAIR_DEFAULT)
+    if mode == '0' or os.environ.get('EGONET_AMD_WINO', '') or os.environ.get('EGONET_AMD_F43', '1') == '0':
+        return False
+    skip = {int(v) for v in os.environ.get('EGONET_AMD_SKIP_CFG', '').split(',') if v.strip()}
+    if skip & set(PAIR_CFGS):
+        return False
+    if mode != 'force':
+        entry = _load_pairs().get(pair_key(key_a, key_b))
+        if entry is None or not entry.get('pair'):
+            return False
+    return pair_plans(key_a, key_b) is not None
+
+
+def _time_program(L, build, stream):
+    """Min of 5 after 2 warm-ups, ms, of the program ``build(prog)`` records (None: it refused)."""
+    prog = C.c_void_p(L.egn_program_create(16))
+    if not prog:
+        return None
+    try:
+        if not build(prog) or L.egn_program_run(prog, stream) != 0:
+            return None
+        L.egn_program_run(prog, stream)
+        best = None
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            L.egn_program_run(prog, stream)
+            e1.record()
+            e1.synchronize()
+            t = e0.elapsed_time(e1)
+            best = t if best is None or t < best else best
+        return best
+    finally:
+        torch.cuda.synchronize()
+        L.egn_program_destroy(prog)
+
+
+def tune_pair(device, key_a, key_b):
+    """Time the pair op as a one-op program against the two TABLED singles (``choose``), each a one-op program; the
+    entry for tuned/gfx950_pairs.json: pair = it beat their sum."""
+    L = _lib.lib()
+    key_a, key_b = tuple(key_a), tuple(key_b)
+    with torch.cuda.device(device):
+        stream = _lib.current_stream(device)
+        halves, singles = [], {}
+        for which, key in (('a', key_a), ('b', key_b)):
+            n, h, w, cin, _, cout = key[:6]
+            t = dict(x=torch.randn(n * h * w * cin, device=device), w=torch.randn(cout * cin * 48, device=device) * 0.05,
+                     sc=torch.ones(cout, device=device), sh=torch.zeros(cout, device=device),
+                     res=torch.randn(n * h * w * cout, device=device) if key[11] else None,
+                     y=torch.empty(n * h * w * cout, device=device))
+            halves.append(t)
+            cfg = choose(device, key, ALL_KINDS)
+            singles[which] = (cfg, _time_cfg(L, key, cfg, stream, t['x'], t['w'], t['sc'], t['sh'], t['res'], t['y']))
+
+        def build(prog):
+            args, slot = [], 0
+            for t, key in zip(halves, (key_a, key_b)):
+                for name in ('x', 'w', 'sc', 'sh', 'res', 'y'):
+                    if t[name] is None:
+                        args.append(_lib.NULL_REF)
+                        continue
+                    if L.egn_program_bind(prog, slot, _lib.ptr(t[name])) != 0:
+                        return False
+                    args.append(_lib.Ref(slot, 0))
+                    slot += 1
+                args += [key[0], key[1], key[2], key[3], key[5], 1]
+            return L.egn_program_add_conv2d_pair(prog, *(args + [0])) == 0
+        t_pair = _time_program(L, build, stream)
+    ta, tb = singles['a'][1], singles['b'][1]
+    won = t_pair is not None and ta is not None and tb is not None and t_pair < ta + tb
+    return {'pair': bool(won), 'ms': {'pair': None if t_pair is None else round(t_pair, 5),
+                                      'a_cfg%d' % singles['a'][0]: None if ta is None else round(ta, 5),
+                                      'b_cfg%d' % singles['b'][0]: None if tb is None else round(tb, 5)}}
+
+
 def tuned_in_process():
     return dict(_tuned_here)
 

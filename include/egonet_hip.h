@@ -674,6 +674,23 @@ int egn_program_poke_ticket(egn_program* p, int op, int word, unsigned value);
 int egn_program_add_pw_pair(egn_program* p, egn_ref h, egn_ref res, egn_ref w3, egn_ref shift3,
                             egn_ref w1, egn_ref shift1, egn_ref out, egn_ref hn, int M,
                             int relu1);
+/* Two independent 3x3 / stride 1 / pad 1 convolutions (unpadded channel strides) as ONE launch and one op
+ * (conv_wino4_pair_kernel, csrc/conv_wino4.hip): `a` on 16-divisible maps with Cout_a % 96 == 0 the way config 86 runs
+ * it, `b` on 8 x 8 maps with Cout_b % 48 == 0 the way config 82 does -- both filters in the F(4x4,3x3) register-feed
+ * layout (kind 3), both outputs bit-identical to the two single-convolution ops.  The two grids share the chip: the
+ * coarse HRNet branches (hrnet.py:286-287: independent at every depth) have 128 + 128 such items at 64 crops.  res_a /
+ * res_b may be NULL.  grid_cap: 0, or a TEST HOOK -- plan for this many compute units (makes the persistent item loops
+ * iterate on small inputs).  egn_conv_pair_plan_query is host-only (no GPU needed): returns non-zero where
+ * egn_program_add_conv2d_pair would refuse the shapes, else out[0..1] = the blocks of the launch that work on `a` / on
+ * `b` when the chip has `cus` compute units; with_stats / with_tickets != 0: as if the caller also asked for BatchNorm
+ * statistics / brought K-split ticket words (refused: the pair has neither). */
+int egn_program_add_conv2d_pair(egn_program* p, egn_ref xa, egn_ref wa, egn_ref scale_a, egn_ref shift_a,
+                                egn_ref res_a, egn_ref ya, int Na, int Ha, int Wa, int Cin_a, int Cout_a,
+                                int act_a, egn_ref xb, egn_ref wb, egn_ref scale_b, egn_ref shift_b,
+                                egn_ref res_b, egn_ref yb, int Nb, int Hb, int Wb, int Cin_b, int Cout_b,
+                                int act_b, int grid_cap);
+int egn_conv_pair_plan_query(int Na, int Ha, int Wa, int Cin_a, int Cout_a, int Nb, int Hb, int Wb,
+                             int Cin_b, int Cout_b, int cus, int with_stats, int with_tickets, int* out);
 /* number of kernel launches issued through egn_program_run / _run_timed / _replay
  * since the library was loaded (process wide, all devices).  Test hook: a caller
  * can prove that a forward went through this library's kernels. */

@@ -55,7 +55,9 @@ KERNELS = ('conv_wino4_kernelILi0E', 'conv_wino4b_kernelILi0E', 'conv_wino4bk_ke
            'conv_wino4c_kernelILi0ELi2E',
            # the training tape's builds (BatchNorm statistics in the item end) [round 5]
            'conv_wino4s_kernelILi0ELi1E', 'conv_wino4s_kernelILi1ELi1E', 'conv_wino4s_kernelILi1ELi2E',
-           'conv_wino4s_kernelILi2ELi1E', 'conv_wino4s_kernelILi2ELi2E')
+           'conv_wino4s_kernelILi2ELi1E', 'conv_wino4s_kernelILi2ELi2E',
+           # the paired launch: conv_wino4w_kernel's body and conv_wino4c_kernel<0, 1>'s inlined into one kernel
+           'conv_wino4_pair_kernel')
 
 
 # conv_wino4w.hip [round 6]: 96 output channels per item

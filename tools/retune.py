@@ -43,6 +43,9 @@ def main():
         ms = dict(table[key].get('ms', {}))
         ms.update({str(k): round(v, 5) for k, v in times.items()})
         best = int(min(ms, key=ms.get))
+        if table[key].get('pinned'):      # chosen by a whole-network A/B, not by the stand-alone time: keep it
+            table[key]['ms'] = ms
+            continue
         if best != int(table[key]['cfg']):
             print('%s: cfg %s (%.4f ms) -> %d (%.4f ms)' % (key, table[key]['cfg'], ms[str(table[key]['cfg'])],
                                                            best, ms[str(best)]))
