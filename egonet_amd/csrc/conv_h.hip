@@ -1,0 +1,298 @@
+// conv_h.hip -- the opt-in f16-OPERAND family: a direct (implicit-GEMM) 3x3 / stride 1 / pad 1 convolution on
+// v_mfma_f32_16x16x32_f16 with fp32 accumulators (precision = 'f16', DESIGN "f16-operand mode").  It lives BESIDE the
+// config table and the tuner (no kConfigs row, no filter kind of theirs): egn_conv3x3_h_applies is the one predicate.
+//
+// Activations stay fp32 NHWC in HBM.  A block owns TM output pixels (TNB images x TH x TW, all powers of two, so a map
+// smaller than 8 x 8 packs several images into the tile) x TN output channels.  The input channels are walked in chunks
+// of 48: per chunk the block stages the halo tile [TNB][TH+2][TW+2][48] into LDS, converting fp32 -> f16 on the way
+// (clamp to +-65504, then the compiler's v_cvt_pk_f16_f32 under the default mode: round-to-nearest-even -- not the
+// truncating v_cvt_pkrtz_f16_f32 --, saturating, never inf), and
+// runs the chunk's K = 9 * 48 = 432 products.
+// K choice: K is FLATTENED per chunk (k = 48 * tap + c) and zero-padded 432 -> 448 = 14 steps of 32.  A lane's fragment
+// (8 consecutive k) lies inside one tap because 48 % 8 == 0, so it is ONE 16-byte LDS read of 8 channels of one halo
+// pixel; the two fragments past k = 432 are zeros on both sides (the A side reads 16 zero bytes kept in LDS).
+//   A (pixels):  lane l holds A[row l & 15][k = 8 (l >> 4) + j], j = 0..7     -- from LDS
+//   B (filter):  lane l holds B[k = 8 (l >> 4) + j][col l & 15]               -- straight from HBM / L2, 16 B per lane,
+//                pre-packed by engine.pack_conv_weight_f16: [Cout/16][Cin/48][14 steps][64 lanes][8] f16
+//   C/D:         col = l & 15 (output channel), row = 4 (l >> 4) + r (pixel)
+// Epilogue (the project's): acc * scale + shift, + residual, ReLU / none, through LDS to float4 along the channel axis,
+// 16-byte buffer stores; out-of-range pixels get the OOB offset (loads 0, drops the store), as conv_common.h does.
+// No BatchNorm statistics, no ticket words, no K split.
+#include <string.h>
+
+#include <atomic>
+
+#include "conv_common.h"
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+constexpr int H_CK = 48;      // input channels per chunk
+constexpr int H_KS = 14;      // MFMA K steps per chunk (432 -> 448)
+constexpr int H_PIXB = 112;   // LDS bytes per halo pixel: 96 + 16 (28-dword stride: 16 neighbouring pixels hit 16 bank quads)
+constexpr float H_F16_MAX = 65504.0f;
+
+// a 16-byte B fragment: lane offset in a VGPR, wave-uniform offset in an SGPR (non-template wrapper, as conv_common.h's)
+__device__ __forceinline__ f16x8 h_load_b(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
+  return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
+}
+
+template <int WM, int WN, int MT, int NT>
+struct ConvHTile {
+  static constexpr int TM = WM * MT * 16, TN = WN * NT * 16;
+  static constexpr int SC_LD = NT * 16 + 4;                         // floats per row of a wave's epilogue slab
+  static constexpr int EPI_BYTES = WM * WN * MT * 16 * SC_LD * 4;
+  // float4 a thread stages per batch: 5 * 256 covers the 100-pixel halo of an 8 x 8 tile, the 180 pixels of 8 x 16 are two
+  static constexpr int SB = 5;
+  // the next chunk's batch 0 in flight during the products: not for the 48-output-channel tile, whose layers in HRNet have
+  // one chunk (48 -> 48) and whose staging registers, live across the products, would cost it a wave per SIMD
+  static constexpr bool PREFETCH = TM != 128;
+};
+
+template <int WM, int WN, int MT, int NT>
+__global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
+  using T = ConvHTile<WM, WN, MT, NT>;
+  static_assert(WM * WN == 4, "four waves");
+  extern __shared__ float4 smem_f4[];
+  char* smem = reinterpret_cast<char*>(smem_f4);
+  unsigned* sOff = reinterpret_cast<unsigned*>(smem);        // [npix] byte offset of halo pixel (channel 0) in x, or EGN_OOB
+  int* sKoff = reinterpret_cast<int*>(smem + a.tab_bytes - H_KS * 4 * 4);   // the last 224 bytes of the table region
+  char* slab = smem + a.tab_bytes;                            // [npix][H_PIXB] f16 halo tile; later the epilogue slabs
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / WN, wn = wave % WN;
+  const int li = lane & 15, g = lane >> 4;
+
+  const int nct = a.Cout / T::TN;
+  const int ct = blockIdx.x % nct;
+  int tile = blockIdx.x / nct;
+  const int tx = tile % a.tiles_x;
+  tile /= a.tiles_x;
+  const int ty = tile % a.tiles_y;
+  const int n_base = (tile / a.tiles_y) * a.TNB;
+  const int oy0 = ty * a.TH, ox0 = tx * a.TW;
+  const int px_mask = (1 << (a.lth + a.ltw)) - 1;
+
+  for (int p = tid; p < a.npix; p += 256) {
+    const int b = p / (a.HH * a.HW);
+    const int rem = p - b * (a.HH * a.HW);
+    const int hy = rem / a.HW;
+    const int hx = rem - hy * a.HW;
+    const int n = n_base + b, iy = oy0 + hy - 1, ix = ox0 + hx - 1;
+    const bool ok = n < a.N && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+    sOff[p] = ok ? (unsigned)((n * a.H + iy) * a.W + ix) * (unsigned)(a.Cin * 4) : EGN_OOB;
+  }
+
+  // per lane: LDS byte offset of the top-left tap of its MT tile rows, and per K step the offset of its 8 channels
+  int abase[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const int m = (wm * MT + mt) * 16 + li;
+    const int b = m >> (a.lth + a.ltw);
+    const int rem = m & px_mask;
+    const int y = rem >> a.ltw, x = rem & (a.TW - 1);
+    abase[mt] = a.tab_bytes + ((b * a.HH + y) * a.HW + x) * H_PIXB;      // from smem
+  }
+  // sKoff[4 ks + g]: LDS byte offset of the 8 channels a lane of group g reads at K step ks (tap and channel group of
+  // k = 8 (4 ks + g)); -1 past k = 432.  A table in LDS, not 14 registers per lane: the kernel keeps 4 waves per SIMD.
+  const int zoff = a.tab_bytes - H_KS * 4 * 4 - 16;   // 16 zero bytes: the A fragment of the padding steps, read without a branch
+  if (tid < 4) reinterpret_cast<int*>(smem + zoff)[tid] = 0;
+  if (tid < H_KS * 4) {
+    const int tap = tid / 6, c8 = tid - tap * 6;
+    const int ky = tap / 3, kx = tap - ky * 3;
+    sKoff[tid] = tid < 54 ? (ky * a.HW + kx) * H_PIXB + c8 * 16 : -1;
+  }
+
+  f32x4 acc[MT][NT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(a.x), 0, (unsigned)((size_t)a.N * a.H * a.W * a.Cin * 4), 0x00020000);
+  const int nchunk = a.Cin / H_CK;
+  const int nstage = a.npix * (H_CK / 4);   // float4 items of a chunk's halo tile
+  // B fragments: [cout tile][chunk][step][lane] x 16 bytes -- one lane offset in a register, the rest is wave-uniform
+  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<void*>(a.w), 0, (unsigned)((a.Cout / 16) * nchunk * (H_KS * 1024)), 0x00020000);
+  const unsigned wlane = lane * 16;
+  int wb[NT];      // byte offset of (cout tile, chunk 0, step 0)
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) wb[nt] = (ct * (T::TN / 16) + wn * NT + nt) * nchunk * (H_KS * 1024);
+
+  // Staging of a chunk's halo tile, T::SB float4 per thread and batch: all loads of a batch are issued before the first
+  // is converted, and (T::PREFETCH) batch 0 of the NEXT chunk is issued before the current chunk's products, so its HBM latency
+  // hides behind them (an 8 x 8 tile is one batch, 8 x 16 two; tiles of many tiny images have more).
+  f32x4 sv[T::SB];
+  auto stage_load = [&](int chunk, int batch) {
+#pragma unroll
+    for (int j = 0; j < T::SB; ++j) {
+      const int idx = (batch * T::SB + j) * 256 + tid;
+      const int p = idx / (H_CK / 4);
+      const int c4 = idx - p * (H_CK / 4);
+      const unsigned off = idx < nstage ? sOff[p] : EGN_OOB;
+      sv[j] = egn_buf_load16(rx, off == EGN_OOB ? EGN_OOB : off + (unsigned)(chunk * H_CK + c4 * 4) * 4u);
+    }
+  };
+  auto stage_store = [&](int batch) {
+#pragma unroll
+    for (int j = 0; j < T::SB; ++j) {
+      const int idx = (batch * T::SB + j) * 256 + tid;
+      const int p = idx / (H_CK / 4);
+      const int c4 = idx - p * (H_CK / 4);
+      const f32x4 v = sv[j];
+      f16x4 h;
+      h.x = (_Float16)__builtin_fminf(__builtin_fmaxf(v.x, -H_F16_MAX), H_F16_MAX);
+      h.y = (_Float16)__builtin_fminf(__builtin_fmaxf(v.y, -H_F16_MAX), H_F16_MAX);
+      h.z = (_Float16)__builtin_fminf(__builtin_fmaxf(v.z, -H_F16_MAX), H_F16_MAX);
+      h.w = (_Float16)__builtin_fminf(__builtin_fmaxf(v.w, -H_F16_MAX), H_F16_MAX);
+      if (idx < nstage) *reinterpret_cast<f16x4*>(slab + p * H_PIXB + c4 * 8) = h;
+    }
+  };
+  const int nbatch = (nstage + T::SB * 256 - 1) / (T::SB * 256);
+  __syncthreads();   // sOff is written
+  if (T::PREFETCH) stage_load(0, 0);
+  for (int chunk = 0; chunk < nchunk; ++chunk) {
+    if (chunk) __syncthreads();   // the previous chunk's fragment reads are done
+    if (!T::PREFETCH) stage_load(chunk, 0);
+    stage_store(0);
+    for (int b = 1; b < nbatch; ++b) {
+      stage_load(chunk, b);
+      stage_store(b);
+    }
+    __syncthreads();
+    if (T::PREFETCH && chunk + 1 < nchunk) stage_load(chunk + 1, 0);
+
+    f16x8 bf[2][NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) bf[0][nt] = h_load_b(rw, wlane, wb[nt] + chunk * (H_KS * 1024));
+#pragma unroll
+    for (int ks = 0; ks < H_KS; ++ks) {
+      if (ks + 1 < H_KS) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+          bf[(ks + 1) & 1][nt] = h_load_b(rw, wlane, wb[nt] + chunk * (H_KS * 1024) + (ks + 1) * 1024);
+      }
+      f16x8 af[MT];
+      const int koff = sKoff[ks * 4 + g];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) af[mt] = *reinterpret_cast<const f16x8*>(smem + (koff >= 0 ? abase[mt] + koff : zoff));
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt], bf[ks & 1][nt], acc[mt][nt], 0, 0, 0);
+    }
+  }
+
+  // ---- epilogue: accumulators -> the wave's LDS slab -> float4 along the channel axis ----
+  __syncthreads();   // every wave is done with the halo tile
+  float* sC = reinterpret_cast<float*>(slab) + wave * (MT * 16) * T::SC_LD;
+  const int cbase = ct * T::TN + wn * NT * 16;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const float sc = a.scale[cbase + nt * 16 + li];
+    const float sh = a.shift[cbase + nt * 16 + li];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sC[(mt * 16 + g * 4 + r) * T::SC_LD + nt * 16 + li] = acc[mt][nt][r] * sc + sh;
+  }
+  __syncthreads();
+  const unsigned ybytes = (unsigned)((size_t)a.N * a.H * a.W * a.Cout * 4);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, ybytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rr =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, ybytes, 0x00020000);
+  constexpr int C4 = NT * 4;   // float4 per slab row
+#pragma unroll
+  for (int it = 0; it < MT * NT; ++it) {
+    const int idx = it * 64 + lane;
+    const int row = idx / C4;
+    const int c4 = idx - row * C4;
+    const int m = wm * MT * 16 + row;
+    const int b = m >> (a.lth + a.ltw);
+    const int rem = m & px_mask;
+    const int n = n_base + b, oy = oy0 + (rem >> a.ltw), ox = ox0 + (rem & (a.TW - 1));
+    const bool ok = n < a.N && oy < a.H && ox < a.W;
+    const unsigned voff = ok ? (unsigned)(((n * a.H + oy) * a.W + ox) * a.Cout + cbase + c4 * 4) * 4u : EGN_OOB;
+    f32x4 v = *reinterpret_cast<const f32x4*>(&sC[row * T::SC_LD + c4 * 4]);
+    if (a.res) v += egn_buf_load16(rr, voff);
+    if (a.act == EGN_ACT_RELU) {
+      v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+    }
+    egn_buf_store16(ry, voff, v);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+static bool h_width(int c) { return c == 48 || c == 96 || c == 192 || c == 384; }
+static int h_pow2_ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
+static int h_log2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+
+// Host-only: 1 where the family runs the layer.  The W48 widths with unpadded channel strides, a plain epilogue (scale /
+// shift, optional residual added before the activation, ReLU or none), tensors below 2 GiB (32-bit buffer offsets).  The
+// Pedestrian widths (32 / 64 / 128 / 256) and 256 -> 48 are REFUSED: 48-channel chunks do not divide them.
+extern "C" int egn_conv3x3_h_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act) {
+  if (N < 1 || H < 2 || W < 2 || !h_width(Cin) || !h_width(Cout) || cs_in != Cin || cs_out != Cout) return 0;
+  if (act != EGN_ACT_NONE && act != EGN_ACT_RELU) return 0;     // (sigmoid, leaky and RES_AFTER stay on the fp32 kernels)
+  if (has_res != 0 && has_res != 1) return 0;
+  const long long px = (long long)N * H * W;
+  if (px * Cin * 4 >= (1ll << 31) || px * Cout * 4 >= (1ll << 31)) return 0;
+  return 1;
+}
+
+extern "C" long egn_conv3x3_h_wpack_bytes(int Cin, int Cout) {
+  if (!h_width(Cin) || !h_width(Cout)) return 0;
+  return (long)(Cout / 16) * (Cin / H_CK) * H_KS * 64 * 16;
+}
+
+int egn_conv_h_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act) {
+  if (!egn_conv3x3_h_applies(N, H, W, Cin, Cin, Cout, Cout, has_res, act)) return EGN_E_BADARG;
+  memset(&a, 0, sizeof(a));
+  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.act = act;
+  a.wide = Cout % 96 == 0;                           // 64 pixels x 96 channels, else 128 pixels x 48 channels
+  const int TM = a.wide ? 64 : 128;
+  a.TH = h_pow2_ceil(H) < 8 ? h_pow2_ceil(H) : 8;
+  a.TW = h_pow2_ceil(W) < TM / 8 ? h_pow2_ceil(W) : TM / 8;
+  a.TNB = TM / (a.TH * a.TW);
+  a.lth = h_log2(a.TH); a.ltw = h_log2(a.TW);
+  a.HH = a.TH + 2; a.HW = a.TW + 2;
+  a.npix = a.TNB * a.HH * a.HW;
+  a.tiles_x = (W + a.TW - 1) / a.TW;
+  a.tiles_y = (H + a.TH - 1) / a.TH;
+  a.tab_bytes = (a.npix * 4 + 15) / 16 * 16 + 16 + H_KS * 4 * 4;   // halo offsets, 16 zero bytes, the K-step offsets (224 bytes)
+  const int epi = a.wide ? ConvHTile<2, 2, 2, 3>::EPI_BYTES : ConvHTile<4, 1, 2, 3>::EPI_BYTES;
+  const int halo = a.npix * H_PIXB;
+  a.lds_bytes = a.tab_bytes + (halo > epi ? halo : epi);
+  const long long blocks = (long long)a.tiles_x * a.tiles_y * ((N + a.TNB - 1) / a.TNB) * (Cout / (a.wide ? 96 : 48));
+  if (a.lds_bytes > 64 * 1024 || blocks > 0x7fffffffll) return EGN_E_BADARG;
+  a.blocks = (int)blocks;
+  return 0;
+}
+
+int egn_conv_h_launch(const ConvHArgs& a, hipStream_t stream) {
+  if (!a.x || !a.w || !a.scale || !a.shift || !a.y) return EGN_E_BADARG;
+  if (a.wide)
+    hipLaunchKernelGGL((conv_h_kernel<2, 2, 2, 3>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);
+  else
+    hipLaunchKernelGGL((conv_h_kernel<4, 1, 2, 3>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);
+  EGN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+extern std::atomic<long> g_egn_direct_convs;
+
+extern "C" int egn_conv3x3_h_f32(const float* x, const void* wpack_f16, const float* scale, const float* shift,
+                                 const float* res, float* y, int N, int H, int W, int Cin, int Cout, int act,
+                                 void* stream) {
+  g_egn_direct_convs.fetch_add(1, std::memory_order_relaxed);
+  ConvHArgs a;
+  int rc = egn_conv_h_plan(a, N, H, W, Cin, Cout, res != nullptr, act);
+  if (rc) return rc;
+  a.x = x; a.w = wpack_f16; a.scale = scale; a.shift = shift; a.res = res; a.y = y;
+  return egn_conv_h_launch(a, (hipStream_t)stream);
+}

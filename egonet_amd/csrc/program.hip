@@ -161,7 +161,7 @@ extern "C" int egn_conv_plan_query(int N, int H, int W, int Cin, int cs_in, int 
 // programs
 // ---------------------------------------------------------------------------
 enum OpKind { OP_CONV = 1, OP_FUSE = 2, OP_NCHW2NHWC = 3, OP_NHWC2NCHW = 4, OP_RAMPS = 5, OP_DECODE = 6,
-              OP_FORK = 7, OP_JOIN = 8, OP_PIXSHUF = 9, OP_PWPAIR = 10, OP_CONVPAIR = 11 };
+              OP_FORK = 7, OP_JOIN = 8, OP_PIXSHUF = 9, OP_PWPAIR = 10, OP_CONVPAIR = 11, OP_CONVH = 12 };
 constexpr int kMaxLanes = 4;  // concurrent launch lanes (HRNet has at most 4 branches)
 
 struct Op {
@@ -170,6 +170,7 @@ struct Op {
   // conv
   ConvArgs conv;
   ConvArgs conv2;  // OP_CONVPAIR: the second convolution (refs r[6..11])
+  ConvHArgs convh; // OP_CONVH (conv_h.hip)
   int cfg;
   egn_ref r[12];  // pointer refs, meaning depends on kind
   // generic ints
@@ -414,6 +415,27 @@ extern "C" int egn_program_add_conv2d_pair(egn_program* p, egn_ref xa, egn_ref w
   return 0;
 }
 
+// the f16-operand 3x3 / stride 1 / pad 1 convolution (conv_h.hip, egn_conv3x3_h_f32) as one op
+extern "C" int egn_program_add_conv3x3_h(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
+                                         egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act) {
+  if (!p) return EGN_E_BADARG;
+  Op op;
+  op.kind = OP_CONVH;
+  int rc = egn_conv_h_plan(op.convh, N, H, W, Cin, Cout, res.slot >= 0, act);
+  if (rc) return rc;
+  op.cfg = 0;
+  const egn_ref refs[6] = {x, wpack, scale, shift, res, y};
+  for (int k = 0; k < 6; ++k) {
+    if (!ref_ok(p, refs[k]) || (refs[k].slot < 0 && k != 4)) return EGN_E_BADARG;    // (only the residual may be NULL)
+    op.r[k] = refs[k];
+  }
+  op.flops = 2.0 * 9.0 * N * H * W * (double)Cout * Cin;
+  op.bytes = 4.0 * N * H * W * (Cin + Cout * (res.slot >= 0 ? 2.0 : 1.0)) + 2.0 * 9.0 * Cout * Cin;
+  op.lane = p->cur_lane;
+  p->ops.push_back(op);
+  return 0;
+}
+
 extern "C" int egn_program_add_fuse(egn_program* p, egn_ref y, int N, int H, int W, int C, int cs, int nterms,
                                     const egn_ref* terms, const int* shifts, int relu) {
   if (!p || nterms < 1 || nterms > 4 || cs % 4 || C > cs) return EGN_E_BADARG;
@@ -573,6 +595,16 @@ static int launch_op(egn_program* p, Op& op, hipStream_t s) {
       a.res = (const float*)resolve(p, op.r[4]);   b.res = (const float*)resolve(p, op.r[10]);
       a.y = (float*)resolve(p, op.r[5]);   b.y = (float*)resolve(p, op.r[11]);
       return egn_conv_launch_wino4_pair(a, b, op.i[0], s);
+    }
+    case OP_CONVH: {
+      ConvHArgs a = op.convh;
+      a.x = (const float*)resolve(p, op.r[0]);
+      a.w = resolve(p, op.r[1]);
+      a.scale = (const float*)resolve(p, op.r[2]);
+      a.shift = (const float*)resolve(p, op.r[3]);
+      a.res = (const float*)resolve(p, op.r[4]);
+      a.y = (float*)resolve(p, op.r[5]);
+      return egn_conv_h_launch(a, s);
     }
     case OP_FUSE: {
       const float* terms[4];

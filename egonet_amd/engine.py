@@ -111,6 +111,91 @@ def pack_wino4_weight(w):
     return pad.reshape(ct, st, 2, 12, 3, 4, 64).permute(0, 1, 2, 3, 4, 6, 5).contiguous().reshape(-1)   # q lane r
 
 
+H_CK, H_KS = 48, 14     # csrc/conv_h.hip: input channels per chunk, MFMA K steps of 32 per chunk (9 * 48 = 432 -> 448)
+PRECISIONS = ('f32', 'f16')
+
+
+def pack_conv_weight_f16(w):
+    """[Cout,Cin,3,3] -> the filter rounded ONCE to f16 (``w.half()``: round-to-nearest-even) in the layout the waves of
+    csrc/conv_h.hip load straight into MFMA B registers, 16 bytes per lane:
+    flat f16 [co-tile = Cout/16][chunk = Cin/48][step 0..13][lane = 16 g + li][j 0..7] holding W[16 ct + li][48 chunk + c][tap]
+    at k = 32 step + 8 g + j = 48 tap + c; k >= 432 is zero padding.  Returned as a flat fp32 VIEW of those bytes (the
+    weights blob is one fp32 tensor); ``unpack_conv_weight_f16`` is the inverse."""
+    w = w.detach().to(torch.float32).cpu()
+    cout, cin, kh, kw = w.shape
+    assert (kh, kw) == (3, 3) and cout % 16 == 0 and cin % H_CK == 0, w.shape
+    ct, nch = cout // 16, cin // H_CK
+    u = w.half().reshape(ct, 16, nch, H_CK, 9).permute(0, 2, 4, 3, 1).reshape(ct, nch, 9 * H_CK, 16)   # ct chunk k li
+    pad = torch.zeros(ct, nch, H_KS * 32, 16, dtype=torch.float16)
+    pad[:, :, :9 * H_CK] = u
+    pad = pad.reshape(ct, nch, H_KS, 4, 8, 16).permute(0, 1, 2, 3, 5, 4).contiguous()                   # ... g li j
+    return pad.reshape(-1).view(torch.float32)
+
+
+def unpack_conv_weight_f16(packed, cout, cin):
+    """The f16 filter [Cout,Cin,3,3] a ``pack_conv_weight_f16`` result holds."""
+    ct, nch = cout // 16, cin // H_CK
+    u = packed.view(torch.float16).reshape(ct, nch, H_KS, 4, 16, 8).permute(0, 1, 2, 3, 5, 4)            # ... g j li
+    u = u.reshape(ct, nch, H_KS * 32, 16)[:, :, :9 * H_CK].reshape(ct, nch, 9, H_CK, 16)
+    return u.permute(0, 4, 1, 3, 2).reshape(cout, cin, 3, 3).contiguous()
+
+
+def _h_applies(n, h, w, cin, cs_in, cout, cs_out, has_res, act):
+    return bool(_lib.lib().egn_conv3x3_h_applies(n, h, w, cin, cs_in, cout, cs_out, int(has_res), act))
+
+
+def f16_eligible(conv, n, h, w):
+    """THE rule for which layers precision = 'f16' moves to the f16-operand kernels (csrc/conv_h.hip): ``conv`` is a
+    3x3 / stride 1 / pad 1 nn.Conv2d without bias, groups or dilation, and the library's host-only predicate
+    egn_conv3x3_h_applies takes its [n, Cin, h, w] input (unpadded channel strides).  The epilogue is not the module's:
+    the recorder asks the same predicate with the layer's own (every such layer of HRNet has a plain one: folded
+    BatchNorm, optional residual, ReLU or none)."""
+    if not isinstance(conv, nn.Conv2d):
+        return False
+    if (tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation), conv.groups) != \
+            ((3, 3), (1, 1), (1, 1), (1, 1), 1) or conv.bias is not None or conv.padding_mode != 'zeros':
+        return False
+    cin, cout = conv.in_channels, conv.out_channels
+    return _h_applies(n, h, w, cin, cin, cout, cout, False, ACT_RELU)
+
+
+class f16_emulation(object):
+    """Context manager: the torch graph of ``model`` computing what precision = 'f16' computes, up to the fp32 summation
+    order -- every ``f16_eligible`` convolution sees its input as f16(clamp(x, +-65504)) and its filter as f16(w), both
+    round-to-nearest-even and widened back to fp32.  The measuring stick of the mode's network-level error (CPU or any
+    device; tests/golden/make_f16_bounds.py, tools/precision_bench.py), never a way to run the network."""
+
+    def __init__(self, model):
+        self.model, self.handles, self.saved, self.hit = model, [], {}, []
+
+    def _pre(self, mod, args):
+        x = args[0]
+        if x.dim() != 4 or not f16_eligible(mod, x.shape[0], x.shape[2], x.shape[3]):
+            return None
+        self.saved[mod] = mod.weight.data
+        mod.weight.data = mod.weight.data.half().float()
+        self.hit.append(mod)
+        return (x.clamp(-65504.0, 65504.0).half().float(),) + tuple(args[1:])
+
+    def _post(self, mod, args, out):
+        if mod in self.saved:
+            mod.weight.data = self.saved.pop(mod)
+
+    def __enter__(self):
+        for m in self.model.modules():
+            if isinstance(m, nn.Conv2d):
+                self.handles += [m.register_forward_pre_hook(self._pre), m.register_forward_hook(self._post)]
+        return self
+
+    def __exit__(self, *exc):
+        for h in self.handles:
+            h.remove()
+        for mod, w in self.saved.items():
+            mod.weight.data = w
+        self.handles, self.saved = [], {}
+        return False
+
+
 def pack_for_kind(w, kind):
     """The filter in the layout the kernels of a tile-configuration KIND read (tuner.kind_of):
     0 direct, 1 Winograd F(2x2,3x3), 2 / 3 Winograd F(4x4,3x3) (conv_wino43_kernel / conv_wino4_kernel)."""
@@ -181,6 +266,7 @@ class _Recorder(object):
         self.bufs = []
         self.region = 0        # fork/join regions are totally ordered
         self.cur_lane = 0      # launch lane inside the current region
+        self.f16 = False       # precision = 'f16': eligible 3x3 convs are recorded as 'convh' ops (csrc/conv_h.hip)
 
     def _push(self, kind, op):
         op['region'], op['lane'] = self.region, self.cur_lane
@@ -236,11 +322,19 @@ class _Recorder(object):
         assert cin == x.c, (cin, x.c, tag)
         ho = (x.h + 2 * pad - kh) // stride + 1
         wo = (x.w + 2 * pad - kw) // stride + 1
+        dst_given = dst is not None
         if dst is None:
             dst = self.new(x.n, ho, wo, cout, name=tag)
             if cout_cs is not None:
                 dst.cs = cout_cs
                 dst.nbytes = x.n * ho * wo * cout_cs * 4
+        if self.f16 and self.takes_f16(x, weight, bias, act, res, stride, pad, out_nchw, cout_cs, dst_given):
+            scale, shift = fold_scale_shift(cout, None, bn)
+            op = dict(x=x, w=self.weight(pack_conv_weight_f16(weight)), scale=self.weight(scale), shift=self.weight(shift),
+                      res=res, y=dst, cin=cin, cout=cout, act=act, tag=tag)
+            self._touch(x, res, dst)
+            self._push('convh', op)
+            return dst
         scale, shift = fold_scale_shift(cout, bias, bn)
         # the filter is packed when the program is built: the layout depends on the tile
         # configuration the tuner picks for the shape (direct vs Winograd kernels)
@@ -250,6 +344,14 @@ class _Recorder(object):
         self._touch(x, res, dst)
         self._push('conv', op)
         return dst
+
+    @staticmethod
+    def takes_f16(x, weight, bias, act, res, stride, pad, out_nchw=False, cout_cs=None, dst_given=False):
+        """``f16_eligible`` on a recorded layer: the same C predicate, asked with the layer's own epilogue."""
+        cout, cin, kh, kw = weight.shape
+        if (kh, kw, stride, pad) != (3, 3, 1, 1) or bias is not None or out_nchw or cout_cs is not None or dst_given:
+            return False
+        return _h_applies(x.n, x.h, x.w, cin, x.cs, cout, _round_up(cout, 4), res is not None, act)
 
     def conv_pair(self, xa, conv_a, bn_a, act_a, res_a, xb, conv_b, bn_b, act_b, res_b, tag=''):
         """Two independent 3x3 / stride 1 / pad 1 convolutions (+ folded BatchNorm, residual, ReLU) as ONE launch
@@ -467,6 +569,15 @@ class Program(object):
                             + op['cout'] * op['cin'] * op['kh'] * op['kw'])
             klass = 'conv%dx%ds%d %d->%d@%dx%d' % (op['kh'], op['kw'], op['stride'], op['cin'],
                                                     op['cout'], op['ho'], op['wo'])
+        elif kind == 'convh':
+            x, y = op['x'], op['y']
+            res = op['res'].ref() if op['res'] is not None else NULL_REF
+            _lib.check(L.egn_program_add_conv3x3_h(h, x.ref(), op['w'], op['scale'], op['shift'], res, y.ref(),
+                                                   x.n, x.h, x.w, op['cin'], op['cout'], op['act']), op['tag'])
+            m = x.n * x.h * x.w
+            flops = 2.0 * m * op['cout'] * op['cin'] * 9
+            nbytes = 4.0 * m * (op['cin'] + op['cout'] * (2 if op['res'] is not None else 1)) + 2.0 * op['cout'] * op['cin'] * 9
+            klass = 'conv3x3h %d->%d@%dx%d' % (op['cin'], op['cout'], x.h, x.w)
         elif kind == 'convpair':
             args, klass = [], []
             for half in (op['a'], op['b']):
@@ -628,6 +739,17 @@ class HRNetEngine(object):
         self.fuse_layer1 = os.environ.get('EGONET_AMD_PW_FUSE', '1') != '0'      # layer1's 1x1 pairs on csrc/conv_pw.hip
         # fuse output i -> branch i of the next module on the same lane, no join in between
         self.chain_regions = os.environ.get('EGONET_AMD_CHAIN', '1') != '0'
+        self.last_f16_ops = []    # tags of the layers the last recording lowered to the f16-operand op (precision = 'f16')
+
+    @property
+    def precision(self):
+        """The model's ``precision`` attribute ('f32', the default, or 'f16'): read at every forward, part of the
+        program key.  'f16' moves the layers ``f16_eligible`` names to csrc/conv_h.hip; everything else, and the
+        training tape, is recorded exactly as in 'f32'."""
+        prec = getattr(self.model, 'precision', 'f32')
+        if prec not in PRECISIONS:
+            raise ValueError("precision must be 'f32' or 'f16', got %r" % (prec,))
+        return prec
 
     # -- recording ---------------------------------------------------------
     def _block(self, r, x, blk, tag):
@@ -709,6 +831,11 @@ class HRNetEngine(object):
         (hrnet.py:286-287: the branches are independent at every depth)."""
         if mod is None or not hasattr(r, 'conv_pair'):
             return None
+        lowered = [False] * mod.num_branches        # precision = 'f16': a layer the f16-operand op takes is never half of a pair
+        if getattr(r, 'f16', False):
+            lowered = [any(r.takes_f16(x, conv.weight, conv.bias, ACT_RELU, None, conv.stride[0], conv.padding[0])
+                           for blk in b for conv in (blk.conv1, blk.conv2) if getattr(blk, 'depth', 0) == 2)
+                       for b, x in zip(mod.branches, xs)]
 
         def plain(branch, x):
             for blk in branch:
@@ -725,7 +852,7 @@ class HRNetEngine(object):
         nb = mod.num_branches
         for ia in reversed(range(nb)):          # (the coarsest pair first: what the measured table holds)
             for ib in reversed(range(nb)):
-                if ia == ib or len(mod.branches[ia]) != len(mod.branches[ib]):
+                if ia == ib or len(mod.branches[ia]) != len(mod.branches[ib]) or lowered[ia] or lowered[ib]:
                     continue
                 if not (plain(mod.branches[ia], xs[ia]) and plain(mod.branches[ib], xs[ib])):
                     continue
@@ -800,7 +927,10 @@ class HRNetEngine(object):
         The default recorder builds an inference program; egonet_amd.train_hrnet
         passes a tape that executes train-mode layers and records their backward."""
         m = self.model
-        r = _Recorder() if r is None else r
+        own = r is None
+        if own:
+            r = _Recorder()
+            r.f16 = self.precision == 'f16'     # (the training tape brings its own recorder: the switch is not its)
         x = r.nchw_to_nhwc(Ref(SLOT_USER0, 0), n, cin, h, w, tag='input')
         t = r.conv(x, m.conv1.weight, None, m.bn1, ACT_RELU, None, 2, 1, tag='conv1')
         t = r.conv(t, m.conv2.weight, None, m.bn2, ACT_RELU, None, 2, 1, tag='conv2')
@@ -900,6 +1030,8 @@ class HRNetEngine(object):
                      Ref(SLOT_USER0 + nslots + 1, 0), Ref(SLOT_USER0 + nslots + 2, 0), tag='decode')
             out_shapes['decode_slot'] = SLOT_USER0 + nslots
             nslots += 3
+        if own:
+            self.last_f16_ops = [op['tag'] for kind, op in r.ops if kind == 'convh']
         return r, nslots, out_shapes
 
     def program(self, x, decode_mode=None, slot=0):
@@ -910,6 +1042,8 @@ class HRNetEngine(object):
             self.programs.clear()
         n, c, h, w = x.shape
         key = (x.device, n, c, h, w, decode_mode) if not slot else (x.device, n, c, h, w, decode_mode, slot)
+        if self.precision != 'f32':
+            key = key + (self.precision,)
         prog = self.programs.get(key)
         if prog is None:
             if h % 32 or w % 32:

@@ -41,12 +41,19 @@ def _dev_f64(a, device):
 
 
 class EgoNet(nn.Module):
-    def __init__(self, cfgs, pre_trained=False):
+    def __init__(self, cfgs, pre_trained=False, precision=None):
+        """``precision``: None (what ``cfgs['heatmapModel']['precision']`` says, default 'f32'), 'f32' or 'f16' -- the
+        opt-in fast inference mode of HC's HIP program (PoseHighResolutionNet.precision).  The lifter, training and
+        every CPU path compute in fp32 whatever it says."""
         super().__init__()
         hm = cfgs['heatmapModel']
         self.cfgs = cfgs
         # plugin lookup by name, as in the reference (egonet.py:43-44)
         self.HC = eval('models.heatmapModel.' + hm['name'] + '.get_pose_net')(cfgs, is_train=False)
+        if precision is not None:
+            if precision not in ('f32', 'f16'):
+                raise ValueError("precision must be 'f32' or 'f16', got %r" % (precision,))
+            self.HC.precision = precision
         self.resolution = hm['input_size']
         self.xy_dict = {'flag': hm['add_xy']} if 'add_xy' in hm else None
         fc = cfgs['FCModel']

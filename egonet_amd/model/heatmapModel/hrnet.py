@@ -298,6 +298,11 @@ class PoseHighResolutionNet(nn.Module):
         return self._torch_forward(x)
 
     hip_eval = True          # eval-mode CUDA forwards run the HIP program (see forward)
+    # 'f32' (default) or 'f16': the opt-in fast inference mode.  'f16' runs the 3x3 / stride 1 convolutions that
+    # engine.f16_eligible names with f16 OPERANDS (round-to-nearest-even, fp32 accumulation, csrc/conv_h.hip); activations
+    # stay fp32 in memory.  Only the eval-mode HIP program reads it: training, the autograd bridge and the torch graph
+    # (so every CPU input, whatever the value) compute in fp32.  Any other value raises ValueError at the next forward.
+    precision = 'f32'
 
     def _native_autograd_ok(self):
         """The train-mode bridge runs ONE autograd node on the native tape: the nn.Module graph below this module is
@@ -431,4 +436,8 @@ def get_pose_net(cfgs, is_train, **kwargs):
             print('{:s} freezed during training.'.format(name))
     if hm.get('add_xy'):
         model.modify_input_channel(5)
+    if hm.get('precision') is not None:
+        if hm['precision'] not in ('f32', 'f16'):
+            raise ValueError("heatmapModel.precision must be 'f32' or 'f16', got %r" % (hm['precision'],))
+        model.precision = hm['precision']
     return model

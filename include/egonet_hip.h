@@ -691,6 +691,25 @@ int egn_program_add_conv2d_pair(egn_program* p, egn_ref xa, egn_ref wa, egn_ref 
                                 int act_b, int grid_cap);
 int egn_conv_pair_plan_query(int Na, int Ha, int Wa, int Cin_a, int Cout_a, int Nb, int Hb, int Wb,
                              int Cin_b, int Cout_b, int cus, int with_stats, int with_tickets, int* out);
+/* The f16-OPERAND 3x3 / stride 1 / pad 1 convolution (csrc/conv_h.hip): the opt-in fast inference mode
+ * (PoseHighResolutionNet.precision = 'f16').  Activations stay fp32 NHWC (x [N][H][W][Cin], y / res [N][H][W][Cout],
+ * unpadded channel strides); every activation element is rounded to f16 (nearest-even, saturating at +-65504) while it
+ * is staged, the filter is rounded once on the host (engine.pack_conv_weight_f16, egn_conv3x3_h_wpack_bytes bytes in the
+ * MFMA B-operand layout), products run on v_mfma_f32_16x16x32_f16 with fp32 accumulators:
+ *     y = act(conv(f16(x), f16(w)) * scale + shift (+ res)),    act = EGN_ACT_NONE or EGN_ACT_RELU.
+ * The family lives beside the tile-config table (no config id, never a tuner answer).  egn_conv3x3_h_applies is its one
+ * predicate, host-only (no GPU needed): 1 where the family takes the layer -- Cin, Cout in {48, 96, 192, 384} with
+ * cs == C, N >= 1, H, W >= 2, tensors below 2 GiB, a plain epilogue -- else 0 (the Pedestrian widths 32 / 64 / 128 / 256
+ * and 256 -> 48 are refused); the other entry points return EGN_E_BADARG where it says 0.  The reference has no
+ * counterpart (libs/model/heatmapModel/hrnet.py:63-92 runs these layers as fp32 torch calls). */
+int egn_conv3x3_h_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act);
+long egn_conv3x3_h_wpack_bytes(int Cin, int Cout);
+int egn_conv3x3_h_f32(const float* x, const void* wpack_f16, const float* scale, const float* shift,
+                      const float* res, float* y, int N, int H, int W, int Cin, int Cout, int act,
+                      void* stream);
+/* the same as a program op (fork / join lanes, egn_program_run_timed, egn_program_op_info, capture / replay); res may be NULL */
+int egn_program_add_conv3x3_h(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
+                              egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act);
 /* number of kernel launches issued through egn_program_run / _run_timed / _replay
  * since the library was loaded (process wide, all devices).  Test hook: a caller
  * can prove that a forward went through this library's kernels. */

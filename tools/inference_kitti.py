@@ -6,7 +6,11 @@ GPU crops -> HRNet key-points -> lifter -> pose solve -> KITTI result files ->
     python tools/inference_kitti.py --images <dir of png> --boxes <dir of KITTI label/detection txt>
         [--calib <dir>] --out <result dir> [--ckpt <dir with HC.pth L.pth LS.npy> | --synthetic]
         [--gt <label dir>] [--classes Car] [--conf-thres 0] [--alpha-mode proj|trans] [--frames-per-step 8]
-        [--refine pnp [--refine-max-shift 5.0] [--write-3d]]
+        [--refine pnp [--refine-max-shift 5.0] [--write-3d]] [--precision f32|f16]
+
+``--precision f16`` (default f32) is the opt-in fast mode of the key-point network: the 3x3 / stride 1 convolutions of
+HRNet's stages 2-4 run with f16 operands and fp32 accumulation (csrc/conv_h.hip); results differ from the default's at
+the 1e-3 px level ("f16-operand mode").
 
 ``--refine pnp`` fits every lifted cuboid rigidly to its own key points before the angles are read off
 (EgoNet.refine_pnp, the reference's ``pnp_refine`` flow without cv2); ``rot_y`` / ``alpha`` then come from the refined
@@ -73,8 +77,8 @@ def build_model(a):
         8, (64, 64), 33, 'coordinates', modules=(1, 1, 1), num_blocks=1, lifter_neurons=128)
     if a.ckpt:
         cfg['dirs'] = {'ckpt': a.ckpt}
-        return EgoNet(cfg, pre_trained=True).eval().cuda()
-    ego = EgoNet(cfg, pre_trained=False)               # --synthetic: seeded random weights (no checkpoint offline)
+        return EgoNet(cfg, pre_trained=True, precision=a.precision).eval().cuda()
+    ego = EgoNet(cfg, pre_trained=False, precision=a.precision)               # --synthetic: seeded random weights (no checkpoint offline)
     ego.HC.load_state_dict(synth.synth_state_dict(ego.HC.state_dict(), seed=6))
     ego.L.load_state_dict(synth.synth_state_dict(ego.L.state_dict(), seed=7))
     ego.LS = synth.synth_lifter_stats(66, 96, seed=1)
@@ -116,6 +120,8 @@ def main(argv=None):
                     help='discard a fit whose root moved further than this (m) from the box it started at')
     ap.add_argument('--write-3d', action='store_true',
                     help="write the fit's own locations / dimensions for refined instances (needs --refine)")
+    ap.add_argument('--precision', default='f32', choices=['f32', 'f16'],
+                    help="f16: the key-point network's 3x3 stride-1 convolutions with f16 operands (opt-in fast mode)")
     a = ap.parse_args(argv)
     if not a.ckpt and not a.synthetic:
         ap.error('give --ckpt <dir> or --synthetic')
