@@ -171,7 +171,10 @@ SIGNATURES = {
     'egn_angle_metrics_update_f32': (_i, [_p, C.c_long, _i, _p, _p, C.c_long, _p, _p]),
     'egn_pnp_refine_f64': (_i, [_p] * 5 + [_i, _i, _d] + [_p] * 6 + [_p]),
     'egn_pnp_refine_host_f64': (_i, [_p] * 5 + [_i, _i, _d] + [_p] * 6),
-    'egn_program_op_info': (_i,[_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), C.c_char_p, _i]),
+    'egn_overlay_tile_capacity': (_i, []),
+    'egn_overlay_draw_u8': (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _i, _i, _p]),
+    'egn_overlay_draw_host_u8': (_i, [_p, _p, _i, _p, _p, _i, _i]),
+    'egn_program_op_info':(_i,[_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), C.c_char_p, _i]),
 }
 
 _LIB = None

@@ -14,9 +14,10 @@ the reference loops over instances in Python (egonet.py:443-453, 469-486,
 279-295).  ``get_keypoints`` / ``lift_2d_to_3d`` are thin record-keeping
 wrappers over that batched path and return the reference's dictionaries.
 
-Crop extraction (``crop_instances``, cv2.warpAffine) and plotting are outside
-the hot path: ``forward(annot_dict)`` needs ``cv2`` and
-imports it lazily.
+Crop extraction (``crop_instances``) runs on the GPU (common/crop_gpu.py); the
+reference's cv2.warpAffine route needs ``cv2`` and imports it lazily.
+``post_process(visualize=True)`` draws the predictions on the frames with the
+rasteriser of csrc/overlay.hip (egonet_amd/visualization).
 """
 import math
 from os.path import join as pjoin
@@ -449,20 +450,74 @@ class EgoNet(nn.Module):
         return record
 
     def post_process(self, records, visualize=False, color_dict=None, save_dict=None,
-                     alpha_mode='trans', refine=False, max_shift=5.0):
-        """egonet.py:385-408 (+ plot_one_image :341-383 minus the plotting): pose angles
+                     alpha_mode='trans', refine=False, max_shift=5.0, images=None, gt_rows=None):
+        """egonet.py:385-408 (+ plot_one_image :341-383): pose angles
         per image and, with ``save_dict = {'flag': True, 'save_dir': ...}``, one KITTI
         result file per image (needs ``raw_txt_format`` in the record).  ``refine`` / ``max_shift``: see
-        ``gather_lifting_results``."""
-        if visualize:
-            raise NotImplementedError('visualisation is outside the hot path')
+        ``gather_lifting_results``.
+        ``visualize``: draw every record on its frame (``draw_records``); ``images`` optionally maps a path to its
+        [H,W,3] uint8 RGB frame (array or CUDA tensor), ``gt_rows`` a path to label rows for the top view."""
         save = bool(save_dict and save_dict.get('flag'))
         for path in records:
             records[path] = self.gather_lifting_results(records[path], alpha_mode=alpha_mode, get_str=save,
                                                         refine=refine, max_shift=max_shift)
             if save:
                 save_txt_file(path, records[path], save_dict)
+        if visualize and records:
+            self.draw_records(records, color_dict, save_dict, images, gt_rows)
         return records
+
+    def draw_records(self, records, color_dict=None, save_dict=None, images=None, gt_rows=None):
+        """``post_process(visualize=True)``, for records that have their angles: 2-D boxes, projected cuboids and key points on every frame
+        (visualization.build_primitives) and a top view for records with placed boxes (build_bev_primitives), all
+        frames and canvases of the call in ONE launch of the rasteriser (csrc/overlay.hip).  A CUDA model draws on the
+        device -- frames that are not there yet are uploaded, the drawn ones read back -- a CPU model runs the host
+        twin (like ``_pose``).  Sets ``records[path]['plots'] = {'image': uint8 [H,W,3], 'bev': uint8 [h,w,3] or
+        None}`` (numpy; the key the reference keeps its figures under) and, with ``save_dict['vis_dir']``, writes
+        ``<vis_dir>/<stem>.png`` and ``<stem>_bev.png``.  The frames in ``images`` are not modified."""
+        import os
+        from ..common import crop_gpu
+        from ..visualization import OverlayRenderer, build_bev_primitives, build_primitives
+        dev = next(self.parameters()).device
+        frames, prims, colors, ranges, slots, n_prims = [], [], [], [], [], 0
+
+        def add(frame, p, c):
+            nonlocal n_prims
+            frames.append(frame)
+            prims.append(p)
+            colors.append(c)
+            ranges.append((n_prims, n_prims + len(p)))
+            n_prims += len(p)
+        for path, rec in records.items():
+            img = images[path] if images is not None and path in images else crop_gpu.load_rgb(path)
+            if dev.type == 'cuda':
+                img = torch.as_tensor(img).to(dev, copy=True).contiguous()
+            else:
+                img = np.ascontiguousarray(img.cpu().numpy() if torch.is_tensor(img) else img)
+            add(img, *build_primitives(rec, color_dict))
+            slots.append((path, 'image'))
+            p, c, (h, w), n = build_bev_primitives(rec, gt_rows=None if gt_rows is None else gt_rows.get(path),
+                                                   color_dict=color_dict)
+            if n:
+                canvas = torch.full((h, w, 3), 255, dtype=torch.uint8, device=dev)
+                add(canvas if dev.type == 'cuda' else canvas.numpy(), p, c)
+                slots.append((path, 'bev'))
+        if not hasattr(self, '_overlay') or self._overlay.device != dev:
+            self._overlay = OverlayRenderer(dev)
+        drawn = self._overlay.draw(frames, np.concatenate(prims), np.concatenate(colors), ranges)
+        for rec in records.values():
+            rec['plots'] = {'image': None, 'bev': None}
+        for (path, key), frame in zip(slots, drawn):
+            records[path]['plots'][key] = frame.cpu().numpy() if torch.is_tensor(frame) else frame
+        vis_dir = save_dict.get('vis_dir') if save_dict else None
+        if vis_dir:
+            from PIL import Image
+            os.makedirs(vis_dir, exist_ok=True)
+            for path, rec in records.items():
+                stem = os.path.splitext(os.path.basename(path))[0]
+                Image.fromarray(rec['plots']['image']).save(os.path.join(vis_dir, stem + '.png'))
+                if rec['plots']['bev'] is not None:
+                    Image.fromarray(rec['plots']['bev']).save(os.path.join(vis_dir, stem + '_bev.png'))
 
     # ------------------------------------------------------------------
     # crop extraction (adjacent to the hot path; needs cv2 like the reference)

@@ -1,0 +1,3 @@
+"""Drawing predictions: primitive lists on the host (a few hundred rows), rasterised by csrc/overlay.hip."""
+from .overlay import (CUBOID_EDGES, OverlayRenderer, build_bev_primitives, build_primitives,  # noqa: F401
+                      parse_color)

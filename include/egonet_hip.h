@@ -905,6 +905,43 @@ int egn_pnp_refine_host_f64(const double* shape, const double* kpts2d, const dou
                             const double* root0, int n, int J, double max_shift, double* refined, double* rt,
                             double* cost, int* iters, int* status, double* dims);
 
+/* ------------------------------------------------------------------------
+ * Overlay rasteriser (csrc/overlay.hip, definition in csrc/overlay_math.h): draws predictions into uint8 frames.
+ * One primitive, the capsule: a segment (x0,y0)-(x1,y1) of radius r in an RGB8 colour at opacity a (clamped to
+ * [0, 1]); a zero-length segment is a disc.  Primitives are drawn in list order; one with a non-finite field or
+ * r < 0 is dropped.  Pixel (x, y) has its centre at the integer coordinates.  Per pixel and primitive, in float64
+ * without contraction:
+ *     t = clamp(((p - p0) . (p1 - p0)) / |p1 - p0|^2, 0, 1), 0 for a zero length;   d = |p - p0 - t (p1 - p0)|
+ *     c = antialias ? clamp(r + 0.5 - d, 0, 1) : (d <= r);   w = c a
+ *     if w > 0, per channel:  v = floor(v + (col - v) w + 0.5), stored as uint8 before the next primitive
+ * so the device and the host entry give the same bytes, and a pixel no primitive reaches keeps its byte.
+ *   base              frames are addressed relative to it
+ *   frames [n_frames][6] i64  byte offset from base (>= 0), H, W, row stride in bytes (>= 3 W, any alignment),
+ *                             first primitive, one past the last; frames are uint8 HWC, RGB interleaved, and may
+ *                             differ in size
+ *   max_h, max_w              the largest H and W of the table: the grid is (tiles x, tiles y, frame) of 32 x 32
+ *                             pixel tiles, and blocks outside a smaller frame exit
+ *   prims  [n_prims][6] f32   x0 y0 x1 y1 r a
+ *   colors [n_prims]    u32   R | G << 8 | B << 16
+ *   cull                      1: every tile walks the primitives in chunks of egn_overlay_tile_capacity(), keeps those
+ *                             whose grown bounding box meets the tile, in index order, in an LDS list, and draws from
+ *                             it; 0: every primitive goes to every tile (kept for the measurement of what the
+ *                             binning buys).  Both give the same bytes.
+ * n_frames == 0 or n_prims == 0 is a successful no-op.  EGN_E_BADARG: a negative count or size, more than 65535
+ * frames, a NULL required pointer; the host entry also refuses a table row with a negative size or offset, a stride
+ * below 3 W or a primitive range outside [0, n_prims].  The device entry cannot read its table without a
+ * synchronisation: there a block that finds such a row draws nothing into that frame (callers check the table while
+ * it is still on the host, as egonet_amd.visualization.OverlayRenderer does).  One launch on `stream`, added to the
+ * launch counter; no synchronisation, no allocation.  The _host_ entry takes HOST pointers and is never used for
+ * device frames.
+ * ---------------------------------------------------------------------- */
+int egn_overlay_tile_capacity(void);
+int egn_overlay_draw_u8(void* base, const int64_t* frames_dev, int n_frames, int max_h, int max_w,
+                        const float* prims_dev, const uint32_t* colors_dev, int n_prims, int antialias, int cull,
+                        void* stream);
+int egn_overlay_draw_host_u8(void* base, const int64_t* frames, int n_frames, const float* prims,
+                             const uint32_t* colors, int n_prims, int antialias);
+
 #ifdef __cplusplus
 }
 #endif

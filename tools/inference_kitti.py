@@ -6,7 +6,11 @@ GPU crops -> HRNet key-points -> lifter -> pose solve -> KITTI result files ->
     python tools/inference_kitti.py --images <dir of png> --boxes <dir of KITTI label/detection txt>
         [--calib <dir>] --out <result dir> [--ckpt <dir with HC.pth L.pth LS.npy> | --synthetic]
         [--gt <label dir>] [--classes Car] [--conf-thres 0] [--alpha-mode proj|trans] [--frames-per-step 8]
-        [--refine pnp [--refine-max-shift 5.0] [--write-3d]] [--precision f32|f16]
+        [--refine pnp [--refine-max-shift 5.0] [--write-3d]] [--precision f32|f16] [--draw <dir> [--draw-gt]]
+
+``--draw DIR`` also draws every frame's predictions (2-D boxes, projected cuboids, key points) with the GPU rasteriser
+(EgoNet.post_process(visualize=True), csrc/overlay.hip) and writes ``DIR/<stem>.png`` plus, where the boxes carry 3-D
+placements, the top view ``DIR/<stem>_bev.png``; ``--draw-gt`` (needs ``--gt``) adds the label boxes to the top view.
 
 ``--precision f16`` (default f32) is the opt-in fast mode of the key-point network: the 3x3 / stride 1 convolutions of
 HRNet's stages 2-4 run with f16 operands and fp32 accumulation (csrc/conv_h.hip); results differ from the default's at
@@ -122,7 +126,11 @@ def main(argv=None):
                     help="write the fit's own locations / dimensions for refined instances (needs --refine)")
     ap.add_argument('--precision', default='f32', choices=['f32', 'f16'],
                     help="f16: the key-point network's 3x3 stride-1 convolutions with f16 operands (opt-in fast mode)")
+    ap.add_argument('--draw', default=None, metavar='DIR', help='draw the predictions on the frames, PNGs into DIR')
+    ap.add_argument('--draw-gt', action='store_true', help='add the label boxes of --gt to the top view')
     a = ap.parse_args(argv)
+    if a.draw_gt and not (a.draw and a.gt):
+        ap.error('--draw-gt needs --draw and --gt')
     if not a.ckpt and not a.synthetic:
         ap.error('give --ckpt <dir> or --synthetic')
     if a.write_3d and not a.refine:
@@ -145,7 +153,8 @@ def main(argv=None):
     if world > 1:
         lo_r, hi_r = shard_range(len(names), world, rank)
         names = names[lo_r:hi_r]
-    n_inst, n_refined, t0 = 0, 0, time.perf_counter()
+    n_inst, n_refined, n_drawn, t0 = 0, 0, 0, time.perf_counter()
+    colors = {'bbox_2d': 'r', 'bbox_3d': 'r', 'kpts': ['rx', 'r']}      # tools/inference.py:185-188
     for lo in range(0, len(names), a.frames_per_step):
         annot = {'path': [], 'boxes': [], 'raw_txt_format': [], 'K': []}
         images = {}
@@ -164,9 +173,16 @@ def main(argv=None):
             continue
         records = ego(annot, images=images)
         save = {'flag': True, 'save_dir': data_dir}
+        gt_rows = None
+        if a.draw:
+            save['vis_dir'] = a.draw
+            if a.draw_gt:
+                gt_rows = {p: read_boxes(os.path.join(a.gt, os.path.splitext(os.path.basename(p))[0] + '.txt'),
+                                         classes, 0.0) for p in annot['path']}
         if not a.write_3d:
-            ego.post_process(records, save_dict=save, alpha_mode=a.alpha_mode, refine=a.refine == 'pnp',
-                             max_shift=a.refine_max_shift)
+            ego.post_process(records, visualize=bool(a.draw), color_dict=colors, save_dict=save,
+                             alpha_mode=a.alpha_mode, refine=a.refine == 'pnp', max_shift=a.refine_max_shift,
+                             images=images, gt_rows=gt_rows)
         else:       # get_pred_str stays as it is: it formats this tool's edited copy of raw_txt_format
             for path, rec in records.items():
                 rec = ego.gather_lifting_results(rec, alpha_mode=a.alpha_mode, refine=True,
@@ -175,6 +191,10 @@ def main(argv=None):
                 rec['raw_txt_format'] = write_3d(rec)
                 rec['pred_str'] = kfmt.get_pred_str(rec)
                 kfmt.save_txt_file(path, rec, save)
+            if a.draw:
+                ego.draw_records(records, colors, save, images, gt_rows)
+        if a.draw:
+            n_drawn += sum(v is not None for rec in records.values() for v in rec['plots'].values())
         n_inst += sum(len(b) for b in annot['boxes'])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -199,6 +219,8 @@ def main(argv=None):
         out['refine'] = a.refine
     if a.write_3d and world == 1:
         out['refined_3d'] = n_refined
+    if a.draw and world == 1:
+        out['drawn'] = n_drawn
     if dist is not None:
         dist.destroy_process_group()
     if a.gt:
