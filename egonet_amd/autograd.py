@@ -28,8 +28,9 @@ import torch
 
 from . import _lib
 from .engine import invalidate
-from .train_hrnet import TapeOwner, _Tape, _gc_paused
-from .train_lifter import LifterTrainStep
+from .train_common import _gc_paused, grad_views
+from .train_hrnet import TapeOwner, _Tape
+from .train_lifter import LifterCore
 
 
 class _HRNetFn(torch.autograd.Function):
@@ -83,68 +84,17 @@ class HRNetAutograd(TapeOwner):
             self.walker._record(n, cin, h, w, None, r=tape)
             torch._foreach_add_([bn.num_batches_tracked for bn in tape.bns], 1)
             invalidate(m)                    # BatchNorm running statistics were written through raw pointers
-            J = m.num_joints
-            if m.head_type == 'coordinates':
-                outs = (tape.maps_user, tape.user['head2.4'].view(n, J, 2))
-            elif m.head_type == 'angleregression':
-                outs = (tape.user['final_fc.3'].view(n, -1),)
-            elif m.pixel_shuffle:
-                outs = (tape.user['upsample_layer.3'],)
-            else:
-                outs = (tape.user['final_layer'],)
+            outs = tuple(o.user for o in self.head_outputs(tape))
         return tape, outs
 
     @torch.no_grad()
     def _backward(self, tape, gouts):
-        m, L = self.model, self.L
-        params = self.params()
         with _gc_paused(), torch.cuda.device(self.dev):
-            st = _lib.current_stream(self.dev)
-            # one fresh flat buffer per backward; the views go back to autograd, which accumulates them into
-            # (or, when .grad is None, adopts them as) the parameters' .grad
-            sizes = [(p.numel() + 3) // 4 * 4 for p in params]
-            flat = torch.zeros(sum(sizes), dtype=torch.float32, device=self.dev)
-            self._grads, views, off = {}, [], 0
-            for p, sz in zip(params, sizes):
-                v = flat[off:off + p.numel()].view_as(p)
-                self._grads[id(p)] = v
-                views.append(v)
-                off += sz
-            J = m.num_joints
-            n = tape.images.shape[0]
-            if m.head_type == 'coordinates':
-                aug, coords = tape.named['head1'], tape.named['head2.4']
-                g_maps, g_coords = gouts
-                if g_coords is not None:
-                    dc = g_coords.contiguous().float().view(n, 2 * J)
-                    dpad = tape._empty(n * coords.cs)             # back to the padded NHWC row layout
-                    _lib.check(L.egn_nchw_to_nhwc_f32(_lib.ptr(dc), _lib.ptr(dpad), n, 2 * J, 1, 1, coords.cs, st))
-                    tape.grad[id(coords)] = [dpad, True]
-            elif m.head_type == 'angleregression':
-                aug, g_maps = None, None
-                out = tape.named['final_fc.3']
-                if gouts[0] is not None:
-                    g = gouts[0].contiguous().float().view(n, out.c)
-                    dpad = tape._empty(n * out.cs)                # [N, 2] -> the padded row layout of final_fc.3
-                    _lib.check(L.egn_nchw_to_nhwc_f32(_lib.ptr(g), _lib.ptr(dpad), n, out.c, 1, 1, out.cs, st))
-                    tape.grad[id(out)] = [dpad, True]
-            elif m.pixel_shuffle:
-                aug, g_maps = None, None
-                u = tape.named['upsample_layer.3']               # the pre-shuffle activations
-                if gouts[0] is not None:
-                    gm = gouts[0].contiguous().float()
-                    du = tape._empty(n * u.h * u.w * u.cs)
-                    _lib.check(L.egn_pixel_unshuffle_nchw_to_nhwc_f32(_lib.ptr(gm), _lib.ptr(du), n, J, u.h, u.w, u.cs,
-                                                                     int(m.upsamp_fact), st), 'pixel_unshuffle')
-                    tape._accum(u, du)
-            else:
-                aug = tape.named['final_layer']
-                g_maps = gouts[0]
-            if g_maps is not None:
-                gm = g_maps.contiguous().float()
-                da = tape._empty(n * aug.h * aug.w * aug.cs)
-                _lib.check(L.egn_nchw_to_nhwc_f32(_lib.ptr(gm), _lib.ptr(da), n, J, aug.h, aug.w, aug.cs, st))
-                tape._accum(aug, da)
+            views, self._grads = grad_views(self.params(), self.dev)
+            # (last output first: the coordinates' gradient before the maps', the native step's order)
+            for out, g in reversed(list(zip(self.head_outputs(tape), gouts))):
+                if g is not None:
+                    self.seed_grad(tape, out, g.contiguous().float())
             for fn in reversed(tape.back):
                 fn()
             tape.join_side()
@@ -199,50 +149,20 @@ class _LifterFn(torch.autograd.Function):
             ctx.token.release()
 
 
-class LifterAutograd(LifterTrainStep):
+class LifterAutograd(LifterCore):
     """``bridge(x)`` = ``FCModel(x)`` in train mode under autograd, on the native kernels (the GEMMs,
-    BatchNorm1d / ReLU / dropout forward and backward of ``LifterTrainStep``; torch owns loss and optimiser)."""
+    BatchNorm1d / ReLU / dropout forward and backward of ``LifterCore``; parameters stay ordinary tensors: torch
+    owns loss and optimiser)."""
 
     def __init__(self, model):
-        # the parent's machinery without its flat parameter buffer / optimiser state: parameters stay
-        # ordinary tensors that torch's optimiser updates
-        import os
-        from .train_hrnet import PackedFilters
-        from .train_lifter import _Unit
-        from .engine import _round_up
-        p0 = next(model.parameters())
-        if not p0.is_cuda:
-            raise ValueError('LifterAutograd needs the model on a GPU')
-        self.model = model
-        self.dev = p0.device
-        self.act = 2 if model.leaky else 1
-        self.grad_sync = None
-        self.units = [_Unit(model.w1, model.batch_norm1)]
-        for blk in model.res_blocks:
-            self.units += [_Unit(blk.w1, blk.batch_norm1), _Unit(blk.w2, blk.batch_norm2)]
-        self.final = model.w2
-        self.packs = PackedFilters(p0.device)
-        self.w4 = {}
-        for fc in [u.fc for u in self.units] + [self.final]:
-            self.w4[id(fc.weight)] = fc.weight.detach().view(fc.out_features, fc.in_features, 1, 1)
-        self._ws = {}
-        self._wgrad_floats = 0
-        widest = _round_up(max([u.outf for u in self.units] + [u.inf for u in self.units]
-                               + [self.final.out_features]), 16) + 16
-        self.ones = torch.ones(widest, dtype=torch.float32, device=self.dev)
-        self.zeros = torch.zeros(widest, dtype=torch.float32, device=self.dev)
-        self.L = _lib.lib()
-        self.wgrad_stream = torch.cuda.Stream(device=self.dev) \
-            if os.environ.get('EGONET_AMD_WGRAD_STREAM', '1') != '0' else None
-        self._side_used = False
-        self._side_keep = []
-        self.timing = None
-        self._grads = None
         # in-kernel dropout: forward and backward of one call share (seed, unit, counter value); the counter is a
         # device tensor bumped once per forward -- a backward runs before the next forward of the reference's
         # loop; with several forwards in flight (test: two forwards, two backwards) the masks are torch tensors
-        self.drop_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self.drop_step = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        dev = next(model.parameters()).device
+        self._init_lifter_core(model, int(torch.randint(0, 2 ** 62, (1,)).item()),
+                               torch.zeros(1, dtype=torch.int32, device=dev))
+        self.rng_dropout = LifterCore.rng_dropout      # per forward: the switch, and no other forward pending
+        self._grads = None
         self._pending = 0
         self._last_token = None
 
@@ -265,6 +185,7 @@ class LifterAutograd(LifterTrainStep):
 
     @torch.no_grad()
     def _fwd(self, x):
+        self._check_input(x)
         # filter views follow the parameters (an optimiser may have re-bound .data)
         for fc in [u.fc for u in self.units] + [self.final]:
             w4 = self.w4.get(id(fc.weight))
@@ -272,26 +193,18 @@ class LifterAutograd(LifterTrainStep):
                 self.w4[id(fc.weight)] = fc.weight.detach().view(fc.out_features, fc.in_features, 1, 1)
         with _gc_paused(), torch.cuda.device(self.dev):
             # the counter value must still be this forward's when its backward runs: only one forward may be pending
-            self.rng_dropout = LifterTrainStep.rng_dropout and self._pending == 0
+            self.rng_dropout = LifterCore.rng_dropout and self._pending == 0
             if self.rng_dropout:
                 self.drop_step.add_(1)
             self._last_token = _Pending(self)          # handed to the autograd node's context by _LifterFn.forward
-            pred, saved = self._forward(x, fresh=True)
+            pred, saved = self._forward(x, tick=True, fresh=True)
             invalidate(self.model)
         return pred, saved
 
     @torch.no_grad()
     def _bwd(self, saved, gout):
-        params = self.params()
         with _gc_paused(), torch.cuda.device(self.dev):
-            sizes = [(p.numel() + 3) // 4 * 4 for p in params]
-            flat = torch.zeros(sum(sizes), dtype=torch.float32, device=self.dev)
-            self._grads, views, off = {}, [], 0
-            for p, sz in zip(params, sizes):
-                v = flat[off:off + p.numel()].view_as(p)
-                self._grads[id(p)] = v
-                views.append(v)
-                off += sz
+            views, self._grads = grad_views(self.params(), self.dev)
             self._backward(saved, gout.contiguous().float())
             self.packs.finalize()
             self._grads = None

@@ -45,8 +45,6 @@ class GraphedStep(object):
         self._saved_stream = getattr(trainer, 'wgrad_stream', None)
         if self._saved_stream is not None:
             trainer.wgrad_stream = None
-            if hasattr(trainer, '_wgrad_ws'):
-                trainer._wgrad_ws = None
         self.static = [None if t is None else t.clone() for t in inputs]
         self.kwargs = kwargs
         dev = next(t for t in self.static if t is not None).device
@@ -76,10 +74,7 @@ class GraphedStep(object):
         invalidate(self.trainer.model)      # replays write the weights through raw pointers
 
     def __call__(self, *inputs):
-        flat = self.trainer.flat
-        if self.trainer.lr != flat._lr_host:          # scheduler step since the last iteration
-            flat.lr_dev.fill_(self.trainer.lr)
-            flat._lr_host = self.trainer.lr
+        self.trainer.flat.set_lr(self.trainer.lr)     # scheduler step since the last iteration
         for dst, src in zip(self.static, inputs):
             if dst is not None:
                 dst.copy_(src, non_blocking=True)

@@ -213,7 +213,7 @@ class _SyncSession(object):
 class FlatGradSync(object):
     """Gradient all-reduce (mean) over ONE flat gradient buffer, in place, in
     slices of ``bucket_mb`` -- the ``grad_sync`` hook of the native training steps
-    (egonet_amd.train_hrnet.FlatParams keeps every gradient in one allocation,
+    (egonet_amd.train_common.FlatParams keeps every gradient in one allocation,
     so nothing is packed or copied).
 
     Two ways to use it:

@@ -32,8 +32,7 @@ torch autograd / MIOpen are not involved:
   The flat gradient is also what a data-parallel job all-reduces (one RCCL
   call per bucket, ``egonet_amd.parallel``).
 """
-import contextlib
-import gc
+import collections
 import ctypes as C
 import os
 
@@ -43,186 +42,8 @@ from . import _lib, tuner
 from .engine import invalidate
 from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID
 from .engine import Buf, HRNetEngine, _round_up
-
-
-class StepCounters(object):
-    """The BatchNorm layers' ``num_batches_tracked`` += 1 and the loss accumulator = 0 as ONE launch at the start of a
-    native step (``egn_step_counters_i64``) instead of a ``torch._foreach_add_`` and a ``tensor.zero_()`` [round 6]: the
-    device array of the counters' addresses is built once and rebuilt if a buffer moved (``.to()``, ``load_state_dict``
-    onto new storage)."""
-
-    def __init__(self):
-        self.ptrs = None
-        self.table = None
-
-    def tick(self, bns, loss_dev, stream):
-        L = _lib.lib()
-        ptrs = [bn.num_batches_tracked.data_ptr() for bn in bns if bn.num_batches_tracked is not None]
-        if ptrs != self.ptrs:
-            dev = loss_dev.device if loss_dev is not None else bns[0].num_batches_tracked.device
-            self.table = torch.tensor(ptrs, dtype=torch.int64, device=dev) if ptrs else None
-            self.ptrs = ptrs
-        _lib.check(L.egn_step_counters_i64(_lib.ptr(self.table), len(ptrs), _lib.ptr(loss_dev), stream), 'step counters')
-
-
-class FlatParams(object):
-    """Trainable parameters as views of one flat fp32 buffer (+ flat grad, m, v)."""
-
-    def __init__(self, params):
-        self.params = [p for p in params if p.requires_grad]
-        if not self.params:
-            raise ValueError('no trainable parameters')
-        dev = self.params[0].device
-        self.offsets = []
-        total = 0
-        for p in self.params:
-            self.offsets.append(total)
-            total += _round_up(p.numel(), 4)          # every view stays 16-byte aligned
-        self.numel = total
-        self.flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.m = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(total, dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            for p, off in zip(self.params, self.offsets):
-                view = self.flat[off:off + p.numel()].view_as(p)
-                view.copy_(p.data)
-                p.data = view
-                p.grad = self.grad[off:off + p.numel()].view_as(p)
-        # step counter and learning rate live in device memory (hipGraph-safe)
-        self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._lr_host = None
-
-    @property
-    def t(self):
-        return int(self.step_dev.item())
-
-    def adam_step(self, lr, betas, eps, stream, weight_decay=0.0):
-        """torch.optim.Adam (optimizer.py:19-21); weight_decay is the coupled L2 form torch implements."""
-        if lr != self._lr_host:                 # only when the scheduler changed it (never inside a graph)
-            self.lr_dev.fill_(lr)
-            self._lr_host = lr
-        L = _lib.lib()
-        if weight_decay:
-            _lib.check(L.egn_adam_l2_step_dev_f32(_lib.ptr(self.flat), _lib.ptr(self.grad), _lib.ptr(self.m),
-                                                  _lib.ptr(self.v), self.numel, _lib.ptr(self.lr_dev), betas[0],
-                                                  betas[1], eps, weight_decay, _lib.ptr(self.step_dev), stream), 'adam')
-        else:
-            _lib.check(L.egn_adam_step_dev_f32(_lib.ptr(self.flat), _lib.ptr(self.grad), _lib.ptr(self.m),
-                                               _lib.ptr(self.v), self.numel, _lib.ptr(self.lr_dev), betas[0],
-                                               betas[1], eps, _lib.ptr(self.step_dev), stream), 'adam')
-
-    def sgd_step(self, lr, momentum, weight_decay, stream):
-        """torch.optim.SGD(momentum, weight_decay), dampening 0, no Nesterov (optimizer.py:23-26); the
-        momentum buffer lives in ``m``."""
-        if lr != self._lr_host:
-            self.lr_dev.fill_(lr)
-            self._lr_host = lr
-        _lib.check(_lib.lib().egn_sgd_step_dev_f32(_lib.ptr(self.flat), _lib.ptr(self.grad), _lib.ptr(self.m),
-                                                   self.numel, _lib.ptr(self.lr_dev), momentum, weight_decay,
-                                                   _lib.ptr(self.step_dev), stream), 'sgd')
-
-    def update(self, o, stream):
-        """One optimizer step as configured on the step object ``o`` (lr, optim_type, betas, eps, momentum,
-        weight_decay)."""
-        if o.optim_type == 'sgd':
-            self.sgd_step(o.lr, o.momentum, o.weight_decay, stream)
-        else:
-            self.adam_step(o.lr, o.betas, o.eps, stream, o.weight_decay)
-
-
-@contextlib.contextmanager
-def _gc_paused():
-    was = gc.isenabled()
-    gc.disable()
-    try:
-        yield
-    finally:
-        if was:
-            gc.enable()
-
-
-class PackedFilters(object):
-    """The packed forward / data-gradient filters of every conv weight of a model.
-
-    The weights change once per iteration (in the optimizer step), so from the second
-    step on ALL filters are packed by one launch at the start of the step
-    (``egn_pack_conv_weights_batch_f32``) instead of ~600 small ones; the first step
-    packs them one by one while it discovers which (weight, direction) pairs exist."""
-
-    _DESC = [('w', '<u8'), ('dst', '<u8'), ('Cout', '<i4'), ('Cin', '<i4'), ('taps', '<i4'), ('dgrad', '<i4'),
-             ('begin', '<i8')]
-
-    def __init__(self, device):
-        self.dev = device
-        self.L = _lib.lib()
-        self.entries = {}          # (id(weight), dgrad) -> (weight, packed tensor)
-        self.table = None          # device descriptor table once the set is known
-        self.total = 0
-        self.ptrs = None
-
-    def get(self, weight, dgrad, stream, wino=False):
-        """``wino``: the Winograd-transformed filter instead of the direct pack -- True / 1: F(2x2,3x3) (conv_wino.hip,
-        tuner.kind_of 1), 3: F(4x4,3x3) in conv_wino4.hip's register-feed layout (kind 3)."""
-        wino = int(wino)
-        code = int(dgrad) | (4 if wino == 3 else (2 if wino else 0))
-        ent = self.entries.get((id(weight), code))
-        if ent is not None and self.table is not None:
-            return ent[1]
-        cout, cin, kh, kw = weight.shape
-        if ent is None:
-            nfl = self.L.egn_wino4_pack_weight_floats(cout, cin, dgrad) if wino == 3 else \
-                (self.L.egn_wino_weight_floats(cout, cin, dgrad) if wino else
-                 self.L.egn_packed_weight_floats(cout, cin, kh, kw, dgrad))
-            if nfl <= 0:
-                raise ValueError('no packed layout %d for a %s filter' % (wino, tuple(weight.shape)))
-            wp = torch.empty(nfl, dtype=torch.float32, device=self.dev)
-            self.entries[(id(weight), code)] = (weight, wp)
-            self.table = None
-        else:
-            wp = ent[1]
-        if wino == 3:
-            _lib.check(self.L.egn_wino4_pack_weight_f32(_lib.ptr(weight), cout, cin, dgrad, _lib.ptr(wp), stream),
-                       'wino4 pack')
-        elif wino:
-            _lib.check(self.L.egn_wino_pack_weight_f32(_lib.ptr(weight), cout, cin, dgrad, _lib.ptr(wp), stream),
-                       'wino pack')
-        else:
-            _lib.check(self.L.egn_pack_conv_weight_f32(_lib.ptr(weight), cout, cin, kh, kw, dgrad, _lib.ptr(wp),
-                                                       stream), 'pack')
-        return wp
-
-    def _pointers(self):
-        return [w.data_ptr() for (w, _) in self.entries.values()]
-
-    def finalize(self):
-        """Build the device descriptor table for the (weight, direction) pairs seen so far."""
-        import numpy as np
-        if self.table is not None or not self.entries:
-            return
-        desc = np.zeros(len(self.entries), dtype=np.dtype(self._DESC, align=True))
-        assert desc.dtype.itemsize == self.L.egn_pack_desc_bytes(), (desc.dtype.itemsize, self.L.egn_pack_desc_bytes())
-        begin = 0
-        for i, ((_, code), (w, wp)) in enumerate(self.entries.items()):
-            cout, cin, kh, kw = w.shape
-            desc[i] = (w.data_ptr(), wp.data_ptr(), cout, cin, kh * kw, code, begin)
-            begin += wp.numel() // (48 if code & 4 else (64 if code & 2 else 4))     # work units (egonet_hip.h)
-        self.total = begin
-        self.table = torch.from_numpy(desc.view(np.uint8)).to(self.dev)
-        self.ptrs = self._pointers()
-
-    def pack_all(self, stream):
-        """One launch for every filter; False if the table is not built yet (first step) or a
-        parameter was re-allocated since (``.to()`` / ``load_state_dict`` on a new storage)."""
-        if self.table is None:
-            return False
-        if self._pointers() != self.ptrs:
-            self.table = None
-            return False
-        _lib.check(self.L.egn_pack_conv_weights_batch_f32(_lib.ptr(self.table), len(self.entries), self.total,
-                                                          stream), 'pack all')
-        return True
+from .train_common import (FlatParams, PackedFilters, StepCounters, _gc_paused, begin_grad_sync, finish_step,
+                           fork_wgrad, join_wgrad, timing_begin, timing_end, wgrad_side_stream)
 
 
 class _Tape(object):
@@ -320,10 +141,7 @@ class _Tape(object):
             nrows = self.L.egn_conv2d_bnstats_rows(n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, cfg)
             if nrows > 0:
                 stats = (torch.empty(nrows * 2 * cout, dtype=torch.float64, device=self.dev), nrows)
-        tm = self.o.timing
-        if tm is not None:         # bench.py: hipEvents around every forward / data-gradient conv launch
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(self.dev))
+        e0 = timing_begin(self.o.timing, self.dev)     # bench.py: hipEvents around every forward / data-gradient conv
         if kind == 3:
             _lib.check(self.L.egn_conv2d_ex_f32(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(self.o.ones), _lib.ptr(shift),
                                                 _lib.ptr(res), _lib.ptr(y), n, h, w, cin, cs_in, cout, cs_out, kh, kw,
@@ -339,10 +157,10 @@ class _Tape(object):
             _lib.check(self.L.egn_conv2d_f32(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(self.o.ones), _lib.ptr(shift),
                                              _lib.ptr(res), _lib.ptr(y), n, h, w, cin, cs_in, cout, cs_out, kh, kw,
                                              stride, pad, act, 0, cfg, self.st), 'conv')
-        if tm is not None:
-            e1.record(torch.cuda.current_stream(self.dev))
+        if e0 is not None:
             ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
-            tm.append((cfg, 2.0 * n * ho * wo * cout * cin * kh * kw, e0, e1, stats is not None and kind == 3))
+            timing_end(self.o.timing, self.dev, e0, cfg, 2.0 * n * ho * wo * cout * cin * kh * kw,
+                       stats is not None and kind == 3)
         return stats
 
     def _wgrad(self, x, xd, dy, cs_out, weight, stride, pad):
@@ -354,13 +172,7 @@ class _Tape(object):
         ws = self.o.wgrad_ws(need)
         st = self.st
         if self.side is not None:
-            # nothing on the backward chain waits for a weight gradient (only the optimizer does):
-            # issue it on the side stream once dy exists, so the latency-bound BatchNorm / reduction
-            # kernels of the chain overlap its MFMA work.  One side stream: the launches share ws.
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.dev))
-            self.side.wait_event(ev)
-            self.side_keep.append((xd, dy))
+            fork_wgrad(self.side, self.dev, self.side_keep, (xd, dy))
             st = self.side_st
         _lib.check(L.egn_conv2d_wgrad_f32(_lib.ptr(xd), _lib.ptr(dy), _lib.ptr(self.o.grad_of(self.o.param_of(weight))),
                                           x.n, x.h, x.w, cin, x.cs,
@@ -380,13 +192,7 @@ class _Tape(object):
         self.side_keep = []
 
     def join_side(self):
-        """The side stream's weight gradients are complete for everything issued after this on the
-        main stream (gradient all-reduce, Adam); the tensors they read may be released."""
-        if self.side is not None and self.side_keep:
-            ev = torch.cuda.Event()
-            ev.record(self.side)
-            torch.cuda.current_stream(self.dev).wait_event(ev)
-            self.side_keep = []
+        join_wgrad(self.side, self.dev, self.side_keep)
 
     def _accum_dgrad(self, x, dy, ho, wo, cs_out, weight, stride, pad):
         """grad(x) += data gradient of the conv.  Where x already has a gradient tensor of its own (the
@@ -634,6 +440,12 @@ class _Tape(object):
         return y
 
 
+# One output of the module on a finished tape: ``user`` = the tensor the caller sees, ``buf`` = the Buf where its
+# gradient enters the tape, ``c`` = the caller tensor's channels (``buf`` may be wider: head1 carries two coordinate
+# ramps), ``shuffle`` = the pixel-shuffle factor when ``buf`` holds the pre-shuffle activations (else 0)
+HeadOutput = collections.namedtuple('HeadOutput', 'user buf c shuffle')
+
+
 class TapeOwner(object):
     """What a ``_Tape`` needs from the object that drives it: the library, scratch vectors, the packed-filter
     cache, the weight-gradient side stream and workspace, the kernel-family switches, and ``grad_of(param)`` =
@@ -656,13 +468,11 @@ class TapeOwner(object):
         self.ones = torch.ones(_round_up(widest, 16), dtype=torch.float32, device=self.dev)
         self.zeros = torch.zeros(_round_up(widest, 16), dtype=torch.float32, device=self.dev)
         self.col_ws = torch.zeros(self.L.egn_colreduce_ws_bytes(widest) // 4, dtype=torch.float32, device=self.dev)
-        self._wgrad_ws = None
-        # weight gradients on a second stream (EGONET_AMD_WGRAD_STREAM=0: everything on one stream)
-        # EGONET_AMD_WGRAD_PRIORITY: HIP stream priority of that stream (0 normal, positive = lower where the runtime
-        # has a low level): the chain's latency-bound BatchNorm / reduction kernels should not queue behind the
-        # weight gradients' grids
-        self.wgrad_stream = torch.cuda.Stream(device=self.dev, priority=int(os.environ.get('EGONET_AMD_WGRAD_PRIORITY', '0'))) \
-            if os.environ.get('EGONET_AMD_WGRAD_STREAM', '1') != '0' else None
+        self._wgrad_ws = None         # (the stream whose pool holds it, the workspace)
+        # EGONET_AMD_WGRAD_PRIORITY: HIP stream priority of the weight gradients' side stream (0 normal, positive =
+        # lower where the runtime has a low level): the chain's latency-bound BatchNorm / reduction kernels should not
+        # queue behind the weight gradients' grids.  Assignable: None = one stream (bench.py, GraphedStep).
+        self.wgrad_stream = wgrad_side_stream(self.dev, int(os.environ.get('EGONET_AMD_WGRAD_PRIORITY', '0')))
         self.walker = HRNetEngine(model)
         self.packs = PackedFilters(self.dev)
         self.debug_hook = None        # tests/train_debug.py: per-layer checks of the BatchNorm backward
@@ -702,13 +512,38 @@ class TapeOwner(object):
         return ent[1] if ent is not None and ent[0] is weight else weight
 
     def wgrad_ws(self, nbytes):
-        if self._wgrad_ws is None or self._wgrad_ws.numel() * 4 < nbytes:
-            # allocated in the pool of the stream that uses it: when it has to grow, the old block is
-            # only handed to later work of that same stream
-            with torch.cuda.stream(self.wgrad_stream if self.wgrad_stream is not None
-                                   else torch.cuda.current_stream(self.dev)):
-                self._wgrad_ws = torch.empty(nbytes // 4 + 1024, dtype=torch.float32, device=self.dev)
-        return self._wgrad_ws
+        side = self.wgrad_stream
+        if self._wgrad_ws is None or self._wgrad_ws[0] is not side or self._wgrad_ws[1].numel() * 4 < nbytes:
+            # allocated in the pool of the stream that uses it: when it has to grow, or ``wgrad_stream`` was
+            # reassigned, the old block is only handed to later work of the stream that used it
+            with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(self.dev)):
+                self._wgrad_ws = (side, torch.empty(nbytes // 4 + 1024, dtype=torch.float32, device=self.dev))
+        return self._wgrad_ws[1]
+
+    def head_outputs(self, tape):
+        """The module's outputs on ``tape`` as ``HeadOutput``s, in the order ``model(x)`` returns them."""
+        m, n, J = self.model, tape.images.shape[0], self.model.num_joints
+        if m.head_type == 'coordinates':
+            return [HeadOutput(tape.maps_user, tape.named['head1'], J, 0),
+                    HeadOutput(tape.user['head2.4'].view(n, J, 2), tape.named['head2.4'], 2 * J, 0)]
+        if m.head_type == 'angleregression':
+            out = tape.named['final_fc.3']
+            return [HeadOutput(tape.user['final_fc.3'].view(n, out.c), out, out.c, 0)]
+        if m.pixel_shuffle:            # the maps' gradient goes to the pre-shuffle activations
+            return [HeadOutput(tape.user['upsample_layer.3'], tape.named['upsample_layer.3'], J, int(m.upsamp_fact))]
+        return [HeadOutput(tape.user['final_layer'], tape.named['final_layer'], J, 0)]
+
+    def seed_grad(self, tape, out, g):
+        """The gradient ``g`` of ``out.user`` (contiguous fp32, the caller's layout) enters the tape: converted into
+        the padded NHWC layout of ``out.buf``."""
+        b = out.buf
+        d = tape._empty(b.n * b.h * b.w * b.cs)
+        if out.shuffle:
+            _lib.check(self.L.egn_pixel_unshuffle_nchw_to_nhwc_f32(_lib.ptr(g), _lib.ptr(d), b.n, out.c, b.h, b.w, b.cs,
+                                                                  out.shuffle, tape.st), 'pixel_unshuffle')
+        else:
+            _lib.check(self.L.egn_nchw_to_nhwc_f32(_lib.ptr(g), _lib.ptr(d), b.n, out.c, b.h, b.w, b.cs, tape.st))
+        tape._accum(b, d)
 
 class HRNetTrainStep(TapeOwner):
     """``step(images, target, joints_xy)`` = one iteration of trainer.py:183-209.  ``angle_type`` ('mse' | 'sl1'): the
@@ -786,12 +621,33 @@ class HRNetTrainStep(TapeOwner):
         self.counters = StepCounters()
         self.last_maps = self.last_coords = self.last_angles = None
 
-    def _angle_loss(self, tape, target, n, st):
+    def _drawn_target(self, joints_xy, joints_vis, n, h, w, mh, mw):
+        """Gaussian heat-map targets drawn on the device from the joints at heatmap_size (img_proc.py:347-409): the
+        [N,K,h,w] target never crosses PCIe.  Their weights stay in ``last_target_weight``."""
+        if joints_xy is None:
+            raise ValueError('step() needs target heat-maps or joints_xy to draw them from')
+        if mh != mw or h != w:
+            raise NotImplementedError('device-side targets: square maps only (the reference mixes the '
+                                      'width/height indices of input_size / heatmap_size, img_proc.py:376-383)')
+        from .common import img_proc
+        target, self.last_target_weight = img_proc.generate_target_batch(
+            joints_xy, torch.ones(n, self.model.num_joints) if joints_vis is None else joints_vis,
+            dict(target_type='gaussian', input_size=(w, h), heatmap_size=(mh, mw), sigma=self.sigma),
+            device=self.dev)
+        return target
+
+    def _target_weight(self, target_weight, n):
+        """JointsMSELoss's target_weight as [N, K] on the device (default: that of the device-drawn targets)."""
+        tw = target_weight if target_weight is not None else self.last_target_weight
+        if tw is None:
+            raise ValueError('use_target_weight needs target_weight [N,K(,1)] (or device-drawn targets)')
+        return torch.as_tensor(tw, dtype=torch.float32).reshape(n, self.model.num_joints).to(self.dev)
+
+    def _angle_loss(self, tape, out, target, n, st):
         """MSELoss1D / SmoothL1Loss1D (function.py:204-228: nn.MSELoss / nn.SmoothL1Loss, 'mean' over the 2N elements)
         and the gradient seed at final_fc.3 in one launch of egn_elem_loss_f32: rows of the padded activations against
         the compact [N, 2] target; the padding columns of the gradient stay zero."""
-        out = tape.named['final_fc.3']
-        self.last_angles = tape.user['final_fc.3'].view(n, out.c)
+        self.last_angles, out = out.user, out.buf
         if target is None or tuple(target.shape) != (n, out.c):
             raise ValueError('target must be [%d, %d] rows of [cos, sin], got %s'
                              % (n, out.c, None if target is None else tuple(target.shape)))
@@ -801,35 +657,19 @@ class HRNetTrainStep(TapeOwner):
                    'angle loss')
         tape.grad[id(out)] = [dpad, True]
 
-    def _pixshuf_loss(self, tape, target, joints_xy, joints_vis, target_weight, n, h, w, st):
+    def _pixshuf_loss(self, tape, out, target, joints_xy, joints_vis, target_weight, n, h, w, st):
         """The pixel-shuffle head's JointsMSELoss-style term (hrnet.py:373-383, 598-600; function.py:22-46) as ONE
         launch, egn_pixshuf_loss_f32: it reads the pre-shuffle activations and the NCHW target and writes the gradient
         in the pre-shuffle layout (the shuffled maps in ``last_maps`` are for the caller only)."""
-        m, L, J = self.model, self.L, self.model.num_joints
-        u = tape.named['upsample_layer.3']                # pre-shuffle Buf [N, h, w, J*f*f (padded)]
-        f = int(m.upsamp_fact)
+        L, J = self.L, self.model.num_joints
+        u, f = out.buf, out.shuffle                       # pre-shuffle Buf [N, h, w, J*f*f (padded)]
         mh, mw = u.h * f, u.w * f
         if target is None:
-            # Gaussian targets drawn on the device at heatmap_size (img_proc.py:347-409)
-            if joints_xy is None:
-                raise ValueError('step() needs target heat-maps or joints_xy to draw them from')
-            if mh != mw or h != w:
-                raise NotImplementedError('device-side targets: square maps only (the reference mixes the '
-                                          'width/height indices of input_size / heatmap_size, img_proc.py:376-383)')
-            from .common import img_proc
-            target, self.last_target_weight = img_proc.generate_target_batch(
-                joints_xy, torch.ones(n, J) if joints_vis is None else joints_vis,
-                dict(target_type='gaussian', input_size=(w, h), heatmap_size=(mh, mw), sigma=self.sigma),
-                device=self.dev)
+            target = self._drawn_target(joints_xy, joints_vis, n, h, w, mh, mw)
         if tuple(target.shape) != (n, J, mh, mw):
             raise ValueError('target must be %s, got %s' % ((n, J, mh, mw), tuple(target.shape)))
         target = target.contiguous().float()
-        twd = None
-        if self.use_target_weight:
-            tw = target_weight if target_weight is not None else self.last_target_weight
-            if tw is None:
-                raise ValueError('use_target_weight needs target_weight [N,K(,1)] (or device-drawn targets)')
-            twd = torch.as_tensor(tw, dtype=torch.float32).reshape(n, J).to(self.dev).contiguous()
+        twd = self._target_weight(target_weight, n).contiguous() if self.use_target_weight else None
         du = tape._empty(n * u.h * u.w * u.cs)
         _lib.check(L.egn_pixshuf_loss_f32(_lib.ptr(tape.data[id(u)]), _lib.ptr(target), _lib.ptr(twd), n, u.h, u.w, J,
                                           f, u.cs, self.hm_crit, 0.5 * self.w_hm, _lib.ptr(du), _lib.ptr(self.loss_dev),
@@ -904,14 +744,13 @@ class HRNetTrainStep(TapeOwner):
             self.walker._record(n, cin, h, w, None, r=tape)
             J = m.num_joints
             self.counters.tick(tape.bns, self.loss_dev, st)       # num_batches_tracked += 1, loss = 0: one launch
-            if m.head_type == 'angleregression':
-                aug = None
-                self._angle_loss(tape, target, n, st)             # loss and gradient seed in one launch
-            elif m.head_type == 'coordinates':
-                aug, coords = tape.named['head1'], tape.named['head2.4']
-                cd = tape.user['head2.4'].view(n, 2 * J)          # compact [N, 2K] = coords [N,K,2]
-                self.last_coords = cd.view(n, J, 2)
-                self.last_maps = tape.maps_user
+            outs = self.head_outputs(tape)
+            maps = outs[0]
+            if m.head_type != 'angleregression':                  # (the angle head has no map term)
+                self.last_maps = maps.user
+            if m.head_type == 'coordinates':
+                self.last_coords = outs[1].user
+                cd = self.last_coords.view(n, 2 * J)              # compact [N, 2K] = coords [N,K,2]
                 use_cr = self.w_cr is not None and self.apply_cr_loss
                 if self.w_coor or use_cr:
                     dc = tape._empty(cd.numel())
@@ -937,33 +776,15 @@ class HRNetTrainStep(TapeOwner):
                                                          self.target_cr, self.cr_loss_thres, self.cr_crit, self.w_cr,
                                                          _lib.ptr(dc), _lib.ptr(self.loss_dev), _lib.ptr(ws), st),
                                    'cross_ratio')
-                    dpad = tape._empty(n * coords.cs)             # back to the padded NHWC row layout
-                    _lib.check(L.egn_nchw_to_nhwc_f32(_lib.ptr(dc), _lib.ptr(dpad), n, 2 * J, 1, 1, coords.cs, st))
-                    tape.grad[id(coords)] = [dpad, True]
-            elif m.pixel_shuffle:
-                aug = None                                        # its loss reads the pre-shuffle activations
-                self.last_maps = tape.user['upsample_layer.3']
+                    self.seed_grad(tape, outs[1], dc)             # back to the padded NHWC row layout
+            if m.head_type == 'angleregression':
+                self._angle_loss(tape, outs[0], target, n, st)    # loss and gradient seed in one launch
+            elif maps.shuffle:                                    # its loss reads the pre-shuffle activations
+                self._pixshuf_loss(tape, maps, target, joints_xy, joints_vis, target_weight, n, h, w, st)
             else:
-                aug = tape.named['final_layer']
-                self.last_maps = tape.user['final_layer']
-            if self.angle_crit is not None:
-                pass                                              # no map term for the angle head
-            elif aug is None:
-                self._pixshuf_loss(tape, target, joints_xy, joints_vis, target_weight, n, h, w, st)
-            else:
+                aug = maps.buf
                 if target is None:
-                    # heat-map targets drawn on the device from the joints (img_proc.py:347-409):
-                    # the [N,K,h,w] target never crosses PCIe
-                    if joints_xy is None:
-                        raise ValueError('step() needs target heat-maps or joints_xy to draw them from')
-                    if aug.h != aug.w or h != w:
-                        raise NotImplementedError('device-side targets: square maps only (the reference mixes the '
-                                                  'width/height indices of input_size / heatmap_size, img_proc.py:376-383)')
-                    from .common import img_proc
-                    target, self.last_target_weight = img_proc.generate_target_batch(
-                        joints_xy, torch.ones(n, J) if joints_vis is None else joints_vis,
-                        dict(target_type='gaussian', input_size=(w, h), heatmap_size=(aug.h, aug.w), sigma=self.sigma),
-                        device=self.dev)
+                    target = self._drawn_target(joints_xy, joints_vis, n, h, w, aug.h, aug.w)
                 if tuple(target.shape) != (n_fs, J, aug.h, aug.w):
                     raise ValueError('target must be %s, got %s' % ((n_fs, J, aug.h, aug.w), tuple(target.shape)))
                 # the labelled crops are a contiguous prefix of the NHWC maps (function.py:183-186): the rows beyond
@@ -976,11 +797,8 @@ class HRNetTrainStep(TapeOwner):
                 if self.use_target_weight:
                     # 0.5 * mean((pred * w - gt * w)^2): the same kernel on the weighted maps, gradient * w afterwards
                     # (three broadcast multiplies over [N,h,w,K]; an option no shipped configuration switches on)
-                    tw = target_weight if target_weight is not None else self.last_target_weight
-                    if tw is None:
-                        raise ValueError('use_target_weight needs target_weight [N,K(,1)] (or device-drawn targets)')
                     wv = torch.zeros(n, 1, 1, aug.cs, dtype=torch.float32, device=self.dev)
-                    wv[:, 0, 0, :J] = torch.as_tensor(tw, dtype=torch.float32).reshape(n, J).to(self.dev)
+                    wv[:, 0, 0, :J] = self._target_weight(target_weight, n)
                     pred_flat = (pred_flat.view(n, aug.h, aug.w, aug.cs) * wv).reshape(-1)
                     tg = (tg.view(n, aug.h, aug.w, aug.cs) * wv).reshape(-1)
                 # (1/K) sum_k 0.5*crit_k = 0.5 * crit over all joints (equal element counts), function.py:95-111
@@ -990,28 +808,13 @@ class HRNetTrainStep(TapeOwner):
                 if wv is not None:
                     da = (da.view(n, aug.h, aug.w, aug.cs) * wv).reshape(-1)
                 tape._accum(aug, da)
-            # the gradient all-reduce of a slice of the flat buffer starts (on a communication
-            # stream) as soon as every parameter in it has its gradient kernels issued
-            sess = None
-            if hasattr(self.grad_sync, 'begin'):
-                # a parameter written by several closures (shared weights) is final after its LAST report
-                counts = {}
-                for fn in tape.back:
-                    for q in getattr(fn, 'params', ()):
-                        counts[id(q)] = counts.get(id(q), 0) + 1
-                sess = self.grad_sync.begin(self.flat, torch.cuda.current_stream(self.dev), self.wgrad_stream,
-                                            report_counts=counts)
+            sess = begin_grad_sync(self, tape.back)
             for fn in reversed(tape.back):
                 fn()
                 if sess is not None:
                     sess.done(getattr(fn, 'params', ()))
             tape.join_side()
-            if sess is not None:
-                sess.finish()
-            elif self.grad_sync is not None:
-                self.grad_sync(self.flat.grad)
-            if update:
-                self.flat.update(self, st)
+            finish_step(self, sess, update, st)
             self.packs.finalize()     # first step: the set of filters is known now
             invalidate(m)             # the inference engine caches folded weights (raw-pointer writes)
             if self.debug_hook is not None:

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from conftest import golden
-from egonet_amd import configs, synth
+from egonet_amd import _lib, configs, synth
 from egonet_amd.model import FCmodel
 from egonet_amd.train_lifter import LifterTrainStep
 from oracle.lifter_train_oracle import LifterTrainOracle
@@ -270,3 +270,25 @@ def test_lifter_inference_after_native_training_uses_the_updated_weights():
     fresh.load_state_dict({k: v.cpu() for k, v in net.state_dict().items()})
     want = fresh.eval()(x.cpu())                     # torch on the CPU with the trained weights
     np.testing.assert_allclose(y1.cpu().numpy(), want.detach().numpy(), atol=2e-5)
+
+
+@pytest.mark.parametrize('xshape,yshape', [((1, 10), (1, 12)),       # BatchNorm1d cannot train on one sample
+                                           ((4, 10), (4, 11))])      # a target row shorter than the prediction's
+def test_lifter_step_refuses_a_bad_batch_before_it_launches_or_counts(xshape, yshape):
+    """A batch the step cannot take raises ValueError with nothing launched and nothing counted -- not the BatchNorm
+    layers' num_batches_tracked, not the optimizer's step counter -- and the next valid step runs as the first."""
+    L = _lib.lib()
+    net = FCmodel.get_fc_model(1, configs.tiny_config(), 10, 12).cuda().train()
+    tr = LifterTrainStep(net, lr=1e-3)
+    g = torch.Generator().manual_seed(0)
+    torch.cuda.synchronize()
+    c0 = L.egn_direct_conv_count()
+    with pytest.raises(ValueError):
+        tr.step(torch.randn(*xshape, generator=g).cuda(), torch.randn(*yshape, generator=g).cuda())
+    assert L.egn_direct_conv_count() == c0
+    tracked = [b for k, b in net.named_buffers() if k.endswith('num_batches_tracked')]
+    assert tracked and all(int(b) == 0 for b in tracked)
+    assert tr.flat.t == 0
+    loss = tr.step(torch.randn(4, 10, generator=g).cuda(), torch.randn(4, 12, generator=g).cuda())
+    assert np.isfinite(float(loss.item()))
+    assert all(int(b) == 1 for b in tracked) and tr.flat.t == 1

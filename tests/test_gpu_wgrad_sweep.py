@@ -145,7 +145,7 @@ def test_launches_sharing_one_workspace_equal_private_workspaces():
 # the corpus is real: what training steps pass to egn_conv2d_wgrad_f32 is what the host derivation says
 # ---------------------------------------------------------------------------------------------------------------
 class _WgradRecorder(object):
-    """Context manager: wraps ``_Tape._wgrad`` and ``LifterTrainStep._wgrad`` the way conv_sweep.TapeRecorder wraps
+    """Context manager: wraps ``_Tape._wgrad`` and ``LifterCore._wgrad`` the way conv_sweep.TapeRecorder wraps
     the conv launch; records the (n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad) of every call."""
 
     def __init__(self):
@@ -154,7 +154,7 @@ class _WgradRecorder(object):
     def __enter__(self):
         from egonet_amd import train_hrnet as T, train_lifter as TL
         self._T, self._TL = T, TL
-        self._orig = (T._Tape._wgrad, TL.LifterTrainStep._wgrad)
+        self._orig = (T._Tape._wgrad, TL.LifterCore._wgrad)
         orig_t, orig_l = self._orig
         me = self
 
@@ -175,11 +175,11 @@ class _WgradRecorder(object):
             me.keys.append((c['rows'], 1, 1, c['inf'], c['ld_a'], c['outf'], c['ld_dz'], 1, 1, 1, 0))
             return orig_l(*args, **kw)
 
-        T._Tape._wgrad, TL.LifterTrainStep._wgrad = tape_wgrad, lifter_wgrad
+        T._Tape._wgrad, TL.LifterCore._wgrad = tape_wgrad, lifter_wgrad
         return self
 
     def __exit__(self, *exc):
-        self._T._Tape._wgrad, self._TL.LifterTrainStep._wgrad = self._orig
+        self._T._Tape._wgrad, self._TL.LifterCore._wgrad = self._orig
         return False
 
 
