@@ -222,9 +222,7 @@ static bool in_this_build(const ConvConfig& c) {
 #endif
   return true;
 }
-// 0 = direct kernels (wpack from egn_pack_conv_weight_f32), 1 = Winograd kernels (wpack from
-// egn_wino_pack_weight_f32), 2 = F(4x4,3x3) filter (engine.pack_wino43_weight), 3 = F(4x4,3x3) filter in the
-// register-feed layout (engine.pack_wino4_weight), -1 = not selectable (timing ablations, retired / invalid ids)
+// the filter layout (kind) cfg's kernel reads, -1 = not selectable: include/egonet_hip.h lists the kinds
 extern "C" int egn_conv_config_kind(int cfg) {
   if (cfg < 1 || cfg > kNumConfigs || !in_this_build(kConfigs[cfg - 1])) return -1;
   return kConfigs[cfg - 1].kind;

@@ -1979,57 +1979,3 @@ int egn_conv_launch_wino(const ConvArgs& a, size_t lds, WinoKernel k, int abl, h
   }
   return EGN_E_BADARG;
 }
-
-// ---------------------------------------------------------------------------------------------
-// Filter transform on the device: torch weight [Cout][Cin][3][3] -> U = G g G^T in the packed layout
-// above ([co-tile][chunk][f][quad][48][4]).  float64 arithmetic, one rounding to fp32.  dgrad = 1 packs
-// the data-gradient filter (in/out channels swapped, taps rotated by 180 degrees) like
-// egn_pack_conv_weight_f32.  One thread per (co, ci): 9 loads, 16 stores.
-__global__ __launch_bounds__(256) void wino_pack_weight_kernel(const float* __restrict__ w, int Cout, int Cin,
-                                                               int dgrad, float* __restrict__ dst) {
-  const int n_out = dgrad ? Cin : Cout, n_in = dgrad ? Cout : Cin;
-  const int nchunk = n_in / EGN_CK;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n_out * n_in; e += gridDim.x * blockDim.x) {
-    const int o = e / n_in, i = e - o * n_in;
-    double g[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b)
-        g[a][b] = dgrad ? (double)w[((size_t)i * Cin + o) * 9 + (2 - a) * 3 + (2 - b)]
-                        : (double)w[((size_t)o * Cin + i) * 9 + a * 3 + b];
-    double t[4][3];  // G g
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      t[0][b] = g[0][b];
-      t[1][b] = 0.5 * (g[0][b] + g[1][b] + g[2][b]);
-      t[2][b] = 0.5 * (g[0][b] - g[1][b] + g[2][b]);
-      t[3][b] = g[2][b];
-    }
-    const int cot = egn_wino_cot(n_out);
-    const int ct = o / cot, col = o - ct * cot;
-    const int chunk = i / EGN_CK, q = (i % EGN_CK) >> 2, r = i & 3;
-    float* base = dst + ((size_t)(ct * nchunk + chunk) * (16 * EGN_CKQ * cot)) * 4 + ((size_t)q * cot + col) * 4 + r;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const double u0 = t[a][0], u1 = 0.5 * (t[a][0] + t[a][1] + t[a][2]), u2 = 0.5 * (t[a][0] - t[a][1] + t[a][2]),
-                   u3 = t[a][2];
-      const double u[4] = {u0, u1, u2, u3};
-#pragma unroll
-      for (int b = 0; b < 4; ++b) base[(size_t)(a * 4 + b) * EGN_CKQ * cot * 4] = (float)u[b];
-    }
-  }
-}
-
-extern "C" long egn_wino_weight_floats(int Cout, int Cin, int dgrad) {
-  const int n_out = dgrad ? Cin : Cout, n_in = dgrad ? Cout : Cin;
-  if (n_out <= 0 || n_in <= 0 || egn_wino_cot(n_out) == 0 || n_in % EGN_CK) return 0;
-  return (long)n_out * n_in * 16;
-}
-extern "C" int egn_wino_pack_weight_f32(const float* w, int Cout, int Cin, int dgrad, float* dst, void* stream) {
-  if (!w || !dst || egn_wino_weight_floats(Cout, Cin, dgrad) == 0) return EGN_E_BADARG;
-  const long total = (long)Cout * Cin;
-  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(wino_pack_weight_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, dgrad, dst);
-  return (int)hipGetLastError();
-}

@@ -671,30 +671,6 @@ extern "C" long long egn_wino4_weight_floats(int cout, int cin) {
   return (long long)(cout / W4_CO) * (cin / 8) * 2 * W4_UKG;
 }
 
-// Filter transform on the device: torch weight [Cout][Cin][3][3] -> U = G g G^T (float64 arithmetic, one rounding to fp32)
-// in the register-feed layout above -- what engine.pack_wino4_weight computes on the host.  dgrad = 1: the data-gradient
-// filter (in / out channels swapped, taps rotated by 180 degrees), as egn_wino_pack_weight_f32 does for F(2x2,3x3).  One
-// thread per (co, ci): 9 loads, 36 stores; the thread of a co-tile's first 16 channels also zeroes the three padding
-// values per (wave, lane).  (Training weights change every step: the host transform cannot feed the tape.)
-__global__ __launch_bounds__(256) void wino4_pack_weight_kernel(const float* __restrict__ w, int Cout, int Cin, int dgrad,
-                                                                float* __restrict__ dst) {
-  const int n_out = dgrad ? Cin : Cout, n_in = dgrad ? Cout : Cin;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n_out * n_in; e += gridDim.x * blockDim.x) {
-    const int o = e / n_in, i = e - o * n_in;
-    w4p_pack_pair(w, Cin, dgrad, o, i, n_in, dst);
-  }
-}
-extern "C" long long egn_wino4_pack_weight_floats(int Cout, int Cin, int dgrad) {
-  return dgrad ? egn_wino4_weight_floats(Cin, Cout) : egn_wino4_weight_floats(Cout, Cin);
-}
-extern "C" int egn_wino4_pack_weight_f32(const float* w, int Cout, int Cin, int dgrad, float* dst, void* stream) {
-  if (!w || !dst || egn_wino4_pack_weight_floats(Cout, Cin, dgrad) == 0) return EGN_E_BADARG;
-  const long total = (long)Cout * Cin;
-  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(wino4_pack_weight_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, dgrad, dst);
-  return (int)hipGetLastError();
-}
-
 static unsigned w4_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 
 static int w4_cus() {

@@ -7,54 +7,17 @@
 // (a Linear is a 1x1 conv):  z = x W^T     -> weights packed from W
 //                            dx = dz W     -> weights packed from W^T
 //                            dW = dz^T x   -> "pixels" = rows of dz^T, weights packed from x^T
-// so what lives here is: on-device weight packing (every step, the weights
-// change), LDS-tiled transposes, per-column batch statistics, the fused
+// (packed on the device every step, the weights change: filter_pack.hip), so
+// what lives here is: LDS-tiled transposes, per-column batch statistics, the fused
 // BatchNorm(+ReLU+dropout) forward / backward, column sums, MSE and Adam.
 // Activations are row-major [rows, ld] fp32 = NHWC [rows,1,1,ld]; ld % 4 == 0.
 #include "egn_internal.h"
-#include "wino4_pack.h"
 
 static inline int grid_for(size_t work_items, int block) {
   size_t g = (work_items + block - 1) / block;
   if (g > 4096) g = 4096;
   if (g < 1) g = 1;
   return (int)g;
-}
-
-// ---------------------------------------------------------------------------
-// pack a row-major matrix as conv weights [nchunk][1][4][CoutP][4]
-//   transpose == 0: W[co][ci] = src[co*ld + ci]   (rows = Cout)
-//   transpose == 1: W[co][ci] = src[ci*ld + co]   (rows = Cin)
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pack_matrix_kernel(const float* __restrict__ src, int ld, int cout, int cin,
-                                                          int transpose, float4* __restrict__ dst, int coutp,
-                                                          int nchunk) {
-  const size_t total = (size_t)nchunk * 4 * coutp;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int co = (int)(e % coutp);
-    const int cq = (int)(e / coutp);  // chunk*4 + quad
-    const int ci0 = cq * 4;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (co < cout) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int ci = ci0 + r;
-        if (ci < cin) v[r] = transpose ? src[(size_t)ci * ld + co] : src[(size_t)co * ld + ci];
-      }
-    }
-    dst[e] = make_float4(v[0], v[1], v[2], v[3]);
-  }
-}
-
-extern "C" int egn_pack_matrix_f32(const float* src, int ld, int cout, int cin, int transpose, float* dst,
-                                   void* stream) {
-  if (cout <= 0 || cin <= 0 || ld < (transpose ? cout : cin)) return EGN_E_BADARG;
-  const int coutp = (cout + 15) & ~15;
-  const int nchunk = (cin + EGN_CK - 1) / EGN_CK;
-  const size_t total = (size_t)nchunk * 4 * coutp;
-  hipLaunchKernelGGL(pack_matrix_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, src, ld,
-                     cout, cin, transpose, reinterpret_cast<float4*>(dst), coutp, nchunk);
-  return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
@@ -854,176 +817,6 @@ extern "C" int egn_sgd_step_dev_f32(float* p, const float* g, float* buf, long n
 // ---------------------------------------------------------------------------
 // Convolution training support
 // ---------------------------------------------------------------------------
-// torch conv weight [Cout][Cin][KH][KW] -> the conv kernel's packed layout
-// [chunk][tap][quad][CoP][4] (input channel = chunk*16 + quad*4 + r), on the
-// device, every step (the weights change).
-//   dgrad == 0: the forward filter:   out channel = co, in channel = ci, tap
-//   dgrad == 1: the data-gradient filter (autograd's conv_transpose view):
-//               out channel = ci, in channel = co, tap rotated by 180 degrees,
-//               so  dx = conv(dy [zero-inserted for stride 2], packed, stride 1, pad K-1-p)
-__global__ __launch_bounds__(256) void pack_conv_weight_kernel(const float* __restrict__ w, int Cout, int Cin,
-                                                               int taps, int dgrad, float4* __restrict__ dst,
-                                                               int CoP, int nchunk) {
-  const size_t total = (size_t)nchunk * taps * 4 * CoP;
-  const int n_out = dgrad ? Cin : Cout;
-  const int n_in = dgrad ? Cout : Cin;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int o = (int)(e % CoP);
-    size_t r_ = e / CoP;
-    const int quad = (int)(r_ % 4);
-    r_ /= 4;
-    const int tap = (int)(r_ % taps);
-    const int chunk = (int)(r_ / taps);
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (o < n_out) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = chunk * EGN_CK + quad * 4 + r;
-        if (i < n_in)
-          v[r] = dgrad ? w[((size_t)i * Cin + o) * taps + (taps - 1 - tap)] : w[((size_t)o * Cin + i) * taps + tap];
-      }
-    }
-    dst[e] = make_float4(v[0], v[1], v[2], v[3]);
-  }
-}
-
-extern "C" long egn_packed_weight_floats(int Cout, int Cin, int KH, int KW, int dgrad) {
-  const int n_out = dgrad ? Cin : Cout, n_in = dgrad ? Cout : Cin;
-  if (n_out <= 0 || n_in <= 0 || KH <= 0 || KW <= 0) return -1;
-  return (long)((n_in + EGN_CK - 1) / EGN_CK) * KH * KW * 4 * ((n_out + 15) & ~15) * 4;
-}
-
-extern "C" int egn_pack_conv_weight_f32(const float* w, int Cout, int Cin, int KH, int KW, int dgrad, float* dst,
-                                        void* stream) {
-  if (!w || !dst || Cout <= 0 || Cin <= 0 || KH <= 0 || KW <= 0) return EGN_E_BADARG;
-  const int n_out = dgrad ? Cin : Cout, n_in = dgrad ? Cout : Cin;
-  const int CoP = (n_out + 15) & ~15;
-  const int nchunk = (n_in + EGN_CK - 1) / EGN_CK;
-  const size_t total = (size_t)nchunk * KH * KW * 4 * CoP;
-  hipLaunchKernelGGL(pack_conv_weight_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, w, Cout,
-                     Cin, KH * KW, dgrad, reinterpret_cast<float4*>(dst), CoP, nchunk);
-  return (int)hipGetLastError();
-}
-
-// All filters of a model in ONE launch: the training step packs every conv weight twice
-// per iteration (forward + data-gradient filter, ~600 small launches for HRNet-W48);
-// the weights only change in the optimizer step, so the step packs them all up front.
-// descs (device memory): one egn_pack_desc per (weight, direction), `begin` = index of
-// its first float4 in the global enumeration, ascending; the kernel finds its
-// descriptor by binary search.
-struct egn_pack_desc {
-  const float* w;
-  float* dst;
-  int Cout, Cin, taps, dgrad;
-  long long begin;  // first float4 of this descriptor
-};
-
-__global__ __launch_bounds__(256) void pack_conv_weights_batch_kernel(const egn_pack_desc* __restrict__ descs, int n,
-                                                                      long long total) {
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {  // last descriptor with begin <= e
-      const int mid = (lo + hi + 1) >> 1;
-      if (descs[mid].begin <= e) lo = mid; else hi = mid - 1;
-    }
-    const egn_pack_desc d = descs[lo];
-    const long long le = e - d.begin;
-    if (d.dgrad & 4) {
-      // [round 5] F(4x4,3x3) filter in conv_wino4.hip's register-feed layout (wino4_pack.h); one unit = one (co, ci)
-      // pair = 36 stores.  A wavefront covers the 16 channels li x 4 input channels kq of one (co sub-tile, k-group):
-      // each of its store instructions fills one 1 KB block of the (co-tile, k-group, wave) slab.
-      const int dg = d.dgrad & 1;
-      const int n_out = dg ? d.Cin : d.Cout, n_in = dg ? d.Cout : d.Cin;
-      const int li = (int)(le & 15), kq = (int)((le >> 4) & 3);
-      long long r_ = le >> 6;
-      const int nt = (int)(r_ % 3);
-      r_ /= 3;
-      const int h = (int)(r_ % (n_in >> 2));
-      const int ct = (int)(r_ / (n_in >> 2));
-      if (ct * W4P_CO < n_out) w4p_pack_pair(d.w, d.Cin, dg, ct * W4P_CO + nt * 16 + li, 4 * h + kq, n_in, d.dst);
-      continue;
-    }
-    if (d.dgrad & 2) {
-      // Winograd filter U = G g G^T (conv_wino.hip layout [co-tile][chunk][f][quad][48][4]); one unit =
-      // one (co-tile, chunk, quad, co) = 4 input channels x 16 frequencies = 16 coalesced float4 stores
-      const int dg = d.dgrad & 1;
-      const int n_out = dg ? d.Cin : d.Cout, n_in = dg ? d.Cout : d.Cin;
-      const int nchunk = n_in / EGN_CK;
-      const int cot = egn_wino_cot(n_out);   // 48 or 32 output channels per co-tile (conv_wino.hip)
-      const int col = (int)(le % cot);
-      long long r_ = le / cot;
-      const int quad = (int)(r_ % 4);
-      r_ /= 4;
-      const int chunk = (int)(r_ % nchunk);
-      const int ct = (int)(r_ / nchunk);
-      const int o = ct * cot + col;
-      float u[16][4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = chunk * EGN_CK + quad * 4 + r;
-        double g[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-          for (int b = 0; b < 3; ++b)
-            g[a][b] = dg ? (double)d.w[((size_t)i * d.Cin + o) * 9 + (2 - a) * 3 + (2 - b)]
-                         : (double)d.w[((size_t)o * d.Cin + i) * 9 + a * 3 + b];
-        double t[4][3];
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-          t[0][b] = g[0][b];
-          t[1][b] = 0.5 * (g[0][b] + g[1][b] + g[2][b]);
-          t[2][b] = 0.5 * (g[0][b] - g[1][b] + g[2][b]);
-          t[3][b] = g[2][b];
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          u[a * 4 + 0][r] = (float)t[a][0];
-          u[a * 4 + 1][r] = (float)(0.5 * (t[a][0] + t[a][1] + t[a][2]));
-          u[a * 4 + 2][r] = (float)(0.5 * (t[a][0] - t[a][1] + t[a][2]));
-          u[a * 4 + 3][r] = (float)t[a][2];
-        }
-      }
-      float4* slab = reinterpret_cast<float4*>(d.dst) + (size_t)(ct * nchunk + chunk) * (16 * 4 * cot);
-#pragma unroll
-      for (int f = 0; f < 16; ++f) slab[(f * 4 + quad) * cot + col] = make_float4(u[f][0], u[f][1], u[f][2], u[f][3]);
-      continue;
-    }
-    const int n_out = d.dgrad ? d.Cin : d.Cout;
-    const int n_in = d.dgrad ? d.Cout : d.Cin;
-    const int CoP = (n_out + 15) & ~15;
-    const int o = (int)(le % CoP);
-    long long r_ = le / CoP;
-    const int quad = (int)(r_ % 4);
-    r_ /= 4;
-    const int tap = (int)(r_ % d.taps);
-    const int chunk = (int)(r_ / d.taps);
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (o < n_out) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = chunk * EGN_CK + quad * 4 + r;
-        if (i < n_in)
-          v[r] = d.dgrad ? d.w[((size_t)i * d.Cin + o) * d.taps + (d.taps - 1 - tap)]
-                         : d.w[((size_t)o * d.Cin + i) * d.taps + tap];
-      }
-    }
-    reinterpret_cast<float4*>(d.dst)[le] = make_float4(v[0], v[1], v[2], v[3]);
-  }
-}
-
-extern "C" int egn_pack_desc_bytes(void) { return (int)sizeof(egn_pack_desc); }
-
-extern "C" int egn_pack_conv_weights_batch_f32(const void* descs_dev, int n, long total_float4, void* stream) {
-  if (!descs_dev || n <= 0 || total_float4 <= 0) return EGN_E_BADARG;
-  size_t g = ((size_t)total_float4 + 255) / 256;
-  if (g > 16384) g = 16384;
-  hipLaunchKernelGGL(pack_conv_weights_batch_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream,
-                     reinterpret_cast<const egn_pack_desc*>(descs_dev), n, (long long)total_float4);
-  return (int)hipGetLastError();
-}
-
 // up[n][2y][2x][:] = dy[n][y][x][:], everything else zero (data gradient of a
 // stride-2 convolution = stride-1 convolution over the zero-inserted dy)
 __global__ __launch_bounds__(256) void zero_insert2_kernel(const float4* __restrict__ dy, float4* __restrict__ up,

@@ -1,6 +1,6 @@
 // wino4_pack.h -- the F(4x4,3x3) filter transform of ONE (output channel, input channel) pair into conv_wino4.hip's
-// register-feed layout, shared by the stand-alone packer (conv_wino4.hip: egn_wino4_pack_weight_f32) and the training
-// step's one-launch packer of all filters (train_ops.hip: egn_pack_conv_weights_batch_f32, descriptor code bit 2).
+// register-feed layout: the F(4x4,3x3) unit of filter_pack.h (egn_wino4_pack_weight_f32 and the training step's
+// one-launch packer of all filters, egn_pack_conv_weights_batch_f32, descriptor code bit FP_WINO4).
 // Reference: the filters of the 3x3 stride-1 convolutions of libs/model/heatmapModel/hrnet.py:63-92.
 #pragma once
 

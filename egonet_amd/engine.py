@@ -11,8 +11,8 @@ A program is recorded once per (device, batch shape):
     arena by a best-fit free-list allocator (an HRNet-W48 forward at B=64 needs
     a few hundred MB instead of ~18 GB of distinct outputs, so the working set
     of neighbouring layers stays inside the 256 MB Infinity Cache);
-  * weights are folded (BatchNorm -> per-channel scale/shift) and prepacked into
-    ONE device blob in the layout the conv kernel stages through LDS;
+  * weights are folded (BatchNorm -> per-channel scale/shift) and prepacked (on
+    the host: filters.py) into ONE device blob in the layouts the conv kernels read;
   * the ops are emitted into a native ``egn_program`` whose pointers are
     (slot, offset) pairs: slot 0 arena, 1 weights, 2.. user tensors.
 A forward is then a single C call that issues ~320 kernel launches.
@@ -25,119 +25,13 @@ import torch.nn as nn
 
 from . import _lib, tuner
 from ._lib import Ref, NULL_REF, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_LEAKY
+from .filters import (CK, H_CK, H_KS, _round_up, pack_conv_weight, wino_cot, pack_wino_weight,   # noqa: F401
+                      pack_wino43_weight, pack_wino4_weight, pack_conv_weight_f16, unpack_conv_weight_f16, pack_for_kind)
 
-CK = 16                 # input channels per K chunk (EGN_CK in csrc/egn_internal.h)
 ACT_RES_AFTER = 0x10
 BN_EPS_DEFAULT = 1e-5
 SLOT_ARENA, SLOT_WEIGHTS, SLOT_USER0 = 0, 1, 2
-
-
-def _round_up(v, m):
-    return (v + m - 1) // m * m
-
-
-# ---------------------------------------------------------------------------
-# weight packing
-# ---------------------------------------------------------------------------
-def pack_conv_weight(w):
-    """[Cout,Cin,KH,KW] -> flat fp32 [nchunk][KH*KW][CK/4][CoutP][4]
-    (ci = chunk*16 + quad*4 + r; zero padded)."""
-    w = w.detach().to(torch.float32).cpu()
-    cout, cin, kh, kw = w.shape
-    coutp = _round_up(cout, 16)
-    nchunk = (cin + CK - 1) // CK
-    wp = torch.zeros(coutp, nchunk * CK, kh * kw, dtype=torch.float32)
-    wp[:cout, :cin] = w.reshape(cout, cin, kh * kw)
-    wp = wp.view(coutp, nchunk, CK // 4, 4, kh * kw).permute(1, 4, 2, 0, 3).contiguous()
-    return wp.reshape(-1)
-
-
-def wino_cot(cout):
-    """Output channels per block (co-tile) of the Winograd kernels: 48 where Cout allows (the W48
-    widths), else 32 (the W32 / Pedestrian widths and 64-channel layers); 0 = not supported
-    (egn_wino_cot in csrc/egn_internal.h)."""
-    return 48 if cout % 48 == 0 else (32 if cout % 32 == 0 else 0)
-
-
-def pack_wino_weight(w):
-    """[Cout,Cin,3,3] -> the Winograd F(2x2,3x3) filter U = G g G^T (float64, rounded once to
-    fp32) in the layout conv_wino.hip stages through LDS:
-    flat fp32 [co-tile = Cout/T][chunk = Cin/16][f = 4i+j][quad][T][4], T = wino_cot(Cout)
-    (ci = chunk*16 + quad*4 + r), one contiguous slab (48 KB for T = 48) per (co-tile, chunk)."""
-    w = w.detach().to(torch.float64).cpu()
-    cout, cin, kh, kw = w.shape
-    cot = wino_cot(cout)
-    assert (kh, kw) == (3, 3) and cot and cin % CK == 0, w.shape
-    G = torch.tensor([[1., 0., 0.], [.5, .5, .5], [.5, -.5, .5], [0., 0., 1.]], dtype=torch.float64)
-    u = torch.einsum('ia,ocab,jb->ocij', G, w, G).to(torch.float32)        # [Cout,Cin,4,4]
-    u = u.reshape(cout // cot, cot, cin // CK, CK // 4, 4, 16)             # ct, co, chunk, quad, r, f
-    return u.permute(0, 2, 5, 3, 1, 4).contiguous().reshape(-1)
-
-
-def pack_wino43_weight(w):
-    """[Cout,Cin,3,3] -> the Winograd F(4x4,3x3) filter U = G g G^T (points 0, +-1, +-2; float64, rounded once to
-    fp32) in the layout conv_wino43_kernel stages through LDS:
-    flat fp32 [co-tile = Cout/48][K step = Cin/4][f = 6i+j][kq = ci % 4][48], one contiguous 27 KB slab per
-    (co-tile, K step)."""
-    w = w.detach().to(torch.float64).cpu()
-    cout, cin, kh, kw = w.shape
-    assert (kh, kw) == (3, 3) and cout % 48 == 0 and cin % 4 == 0, w.shape
-    G = torch.tensor([[1 / 4., 0., 0.], [-1 / 6., -1 / 6., -1 / 6.], [-1 / 6., 1 / 6., -1 / 6.],
-                      [1 / 24., 1 / 12., 1 / 6.], [1 / 24., -1 / 12., 1 / 6.], [0., 0., 1.]], dtype=torch.float64)
-    u = torch.einsum('ia,ocab,jb->ocij', G, w, G).to(torch.float32)        # [Cout,Cin,6,6]
-    u = u.reshape(cout // 48, 48, cin // 4, 4, 36)                          # ct, col, step, kq, f
-    return u.permute(0, 2, 4, 3, 1).contiguous().reshape(-1)
-
-
-def pack_wino4_weight(w):
-    """[Cout,Cin,3,3] -> the Winograd F(4x4,3x3) filter U = G g G^T (float64, rounded once to fp32) in the layout
-    conv_wino4_kernel's waves load straight into MFMA B registers (csrc/conv_wino4.hip), three dwordx4 per wave
-    and k-group: flat fp32 [co-tile = Cout/48][stage = Cin/8][k-group g][wave 0..11][q 0..2][lane = 16 kq + li][4]
-    where value p = 4 q + r (p = 3 pl + nt < 9, the rest is padding) is point 3 wave + pl, co = 48 ct + 16 nt + li,
-    ci = 8 stage + 4 g + kq."""
-    w = w.detach().to(torch.float64).cpu()
-    cout, cin, kh, kw = w.shape
-    assert (kh, kw) == (3, 3) and cout % 48 == 0 and cin % 8 == 0, w.shape
-    G = torch.tensor([[1 / 4., 0., 0.], [-1 / 6., -1 / 6., -1 / 6.], [-1 / 6., 1 / 6., -1 / 6.],
-                      [1 / 24., 1 / 12., 1 / 6.], [1 / 24., -1 / 12., 1 / 6.], [0., 0., 1.]], dtype=torch.float64)
-    u = torch.einsum('ia,ocab,jb->ocij', G, w, G).to(torch.float32).reshape(cout, cin, 36)
-    #   co = (ct, nt, li)          ci = (stage, g, kq)        pt = (wave, pl)
-    u = u.reshape(cout // 48, 3, 16, cin // 8, 2, 4, 12, 3)   # ct nt li stage g kq wave pl
-    u = u.permute(0, 3, 4, 6, 7, 1, 5, 2).contiguous()        # ct stage g wave pl nt kq li
-    ct, st = cout // 48, cin // 8
-    u = u.reshape(ct, st, 2, 12, 9, 64)                        # ... p = 3 pl + nt, lane = 16 kq + li
-    pad = torch.zeros(ct, st, 2, 12, 12, 64, dtype=torch.float32)
-    pad[:, :, :, :, :9] = u
-    return pad.reshape(ct, st, 2, 12, 3, 4, 64).permute(0, 1, 2, 3, 4, 6, 5).contiguous().reshape(-1)   # q lane r
-
-
-H_CK, H_KS = 48, 14     # csrc/conv_h.hip: input channels per chunk, MFMA K steps of 32 per chunk (9 * 48 = 432 -> 448)
 PRECISIONS = ('f32', 'f16')
-
-
-def pack_conv_weight_f16(w):
-    """[Cout,Cin,3,3] -> the filter rounded ONCE to f16 (``w.half()``: round-to-nearest-even) in the layout the waves of
-    csrc/conv_h.hip load straight into MFMA B registers, 16 bytes per lane:
-    flat f16 [co-tile = Cout/16][chunk = Cin/48][step 0..13][lane = 16 g + li][j 0..7] holding W[16 ct + li][48 chunk + c][tap]
-    at k = 32 step + 8 g + j = 48 tap + c; k >= 432 is zero padding.  Returned as a flat fp32 VIEW of those bytes (the
-    weights blob is one fp32 tensor); ``unpack_conv_weight_f16`` is the inverse."""
-    w = w.detach().to(torch.float32).cpu()
-    cout, cin, kh, kw = w.shape
-    assert (kh, kw) == (3, 3) and cout % 16 == 0 and cin % H_CK == 0, w.shape
-    ct, nch = cout // 16, cin // H_CK
-    u = w.half().reshape(ct, 16, nch, H_CK, 9).permute(0, 2, 4, 3, 1).reshape(ct, nch, 9 * H_CK, 16)   # ct chunk k li
-    pad = torch.zeros(ct, nch, H_KS * 32, 16, dtype=torch.float16)
-    pad[:, :, :9 * H_CK] = u
-    pad = pad.reshape(ct, nch, H_KS, 4, 8, 16).permute(0, 1, 2, 3, 5, 4).contiguous()                   # ... g li j
-    return pad.reshape(-1).view(torch.float32)
-
-
-def unpack_conv_weight_f16(packed, cout, cin):
-    """The f16 filter [Cout,Cin,3,3] a ``pack_conv_weight_f16`` result holds."""
-    ct, nch = cout // 16, cin // H_CK
-    u = packed.view(torch.float16).reshape(ct, nch, H_KS, 4, 16, 8).permute(0, 1, 2, 3, 5, 4)            # ... g j li
-    u = u.reshape(ct, nch, H_KS * 32, 16)[:, :, :9 * H_CK].reshape(ct, nch, 9, H_CK, 16)
-    return u.permute(0, 4, 1, 3, 2).reshape(cout, cin, 3, 3).contiguous()
 
 
 def _h_applies(n, h, w, cin, cs_in, cout, cs_out, has_res, act):
@@ -194,14 +88,6 @@ class f16_emulation(object):
             mod.weight.data = w
         self.handles, self.saved = [], {}
         return False
-
-
-def pack_for_kind(w, kind):
-    """The filter in the layout the kernels of a tile-configuration KIND read (tuner.kind_of):
-    0 direct, 1 Winograd F(2x2,3x3), 2 / 3 Winograd F(4x4,3x3) (conv_wino43_kernel / conv_wino4_kernel)."""
-    if kind == 3:
-        return pack_wino4_weight(w)
-    return pack_wino43_weight(w) if kind == 2 else (pack_wino_weight(w) if kind == 1 else pack_conv_weight(w))
 
 
 def fold_scale_shift(cout, bias=None, bn=None):

@@ -9,7 +9,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .engine import pack_conv_weight, fold_scale_shift, _round_up
+from . import filters
+from .engine import fold_scale_shift, _round_up
 
 
 def _need_cuda(*ts):
@@ -55,25 +56,19 @@ class PackedConv(object):
     """Device-resident packed weights + folded scale/shift of one conv layer."""
 
     def __init__(self, weight, bias=None, bn=None, device='cuda', wino=False, kind=None):
-        """``wino``: pack for the fused Winograd kernels (config kind 1) ON THE DEVICE
-        (egn_wino_pack_weight_f32) instead of the direct layout; ``kind`` 2: the F(4x4,3x3) filter
-        (engine.pack_wino43_weight, host float64)."""
+        """``kind``: the filter kind to pack for (filters.DIRECT ...; None: direct, or F(2x2,3x3) with ``wino``).  The
+        F(2x2,3x3) filter is transformed ON THE DEVICE, the others on the host in float64."""
         self.cout, self.cin, self.kh, self.kw = weight.shape
-        if kind in (2, 3):
-            from .engine import pack_for_kind
-            self.w = pack_for_kind(weight, kind).to(device)
-        elif wino or kind == 1:
-            L = _lib.lib()
-            nfl = L.egn_wino_weight_floats(self.cout, self.cin, 0)
-            if nfl == 0 or (self.kh, self.kw) != (3, 3):
-                raise ValueError('no Winograd packing for a %s filter' % (tuple(weight.shape),))
+        if kind in (None, filters.DIRECT):
+            kind = filters.WINO2 if wino else filters.DIRECT
+        if kind == filters.WINO2:
+            nfl = filters.device_floats(kind, weight.shape, 0)
             wd = weight.detach().to(device=device, dtype=torch.float32).contiguous()
             self.w = torch.empty(nfl, dtype=torch.float32, device=device)
             with torch.cuda.device(self.w.device):
-                _lib.check(L.egn_wino_pack_weight_f32(_lib.ptr(wd), self.cout, self.cin, 0, _lib.ptr(self.w),
-                                                      _lib.current_stream(self.w.device)), 'wino_pack')
+                filters.pack_on_device(wd, kind, 0, self.w, _lib.current_stream(self.w.device))
         else:
-            self.w = pack_conv_weight(weight).to(device)
+            self.w = filters.pack_for_kind(weight, kind).to(device)
         s, b = fold_scale_shift(self.cout, bias, bn)
         self.scale, self.shift = s.to(device), b.to(device)
 

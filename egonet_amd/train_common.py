@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, filters
 from .engine import _round_up
 
 
@@ -122,47 +122,30 @@ class PackedFilters(object):
     (``egn_pack_conv_weights_batch_f32``) instead of ~600 small ones; the first step
     packs them one by one while it discovers which (weight, direction) pairs exist."""
 
-    _DESC = [('w', '<u8'), ('dst', '<u8'), ('Cout', '<i4'), ('Cin', '<i4'), ('taps', '<i4'), ('dgrad', '<i4'),
+    _DESC = [('w', '<u8'), ('dst', '<u8'), ('Cout', '<i4'), ('Cin', '<i4'), ('taps', '<i4'), ('code', '<i4'),
              ('begin', '<i8')]
 
     def __init__(self, device):
         self.dev = device
         self.L = _lib.lib()
-        self.entries = {}          # (id(weight), dgrad) -> (weight, packed tensor)
+        self.entries = {}          # (id(weight), kind, dgrad) -> (weight, packed tensor)
         self.table = None          # device descriptor table once the set is known
         self.total = 0
         self.ptrs = None
 
-    def get(self, weight, dgrad, stream, wino=False):
-        """``wino``: the Winograd-transformed filter instead of the direct pack -- True / 1: F(2x2,3x3) (conv_wino.hip,
-        tuner.kind_of 1), 3: F(4x4,3x3) in conv_wino4.hip's register-feed layout (kind 3)."""
-        wino = int(wino)
-        code = int(dgrad) | (4 if wino == 3 else (2 if wino else 0))
-        ent = self.entries.get((id(weight), code))
+    def get(self, weight, dgrad, stream, kind=filters.DIRECT):
+        """The filter of ``weight`` in the layout ``kind`` (filters.DIRECT / WINO2 / WINO4, what tuner.kind_of says
+        the chosen kernel reads); ``dgrad``: the data-gradient filter."""
+        key = (id(weight), kind, int(dgrad))
+        ent = self.entries.get(key)
         if ent is not None and self.table is not None:
             return ent[1]
-        cout, cin, kh, kw = weight.shape
         if ent is None:
-            nfl = self.L.egn_wino4_pack_weight_floats(cout, cin, dgrad) if wino == 3 else \
-                (self.L.egn_wino_weight_floats(cout, cin, dgrad) if wino else
-                 self.L.egn_packed_weight_floats(cout, cin, kh, kw, dgrad))
-            if nfl <= 0:
-                raise ValueError('no packed layout %d for a %s filter' % (wino, tuple(weight.shape)))
-            wp = torch.empty(nfl, dtype=torch.float32, device=self.dev)
-            self.entries[(id(weight), code)] = (weight, wp)
+            nfl = filters.device_floats(kind, weight.shape, dgrad)
+            ent = self.entries[key] = (weight, torch.empty(nfl, dtype=torch.float32, device=self.dev))
             self.table = None
-        else:
-            wp = ent[1]
-        if wino == 3:
-            _lib.check(self.L.egn_wino4_pack_weight_f32(_lib.ptr(weight), cout, cin, dgrad, _lib.ptr(wp), stream),
-                       'wino4 pack')
-        elif wino:
-            _lib.check(self.L.egn_wino_pack_weight_f32(_lib.ptr(weight), cout, cin, dgrad, _lib.ptr(wp), stream),
-                       'wino pack')
-        else:
-            _lib.check(self.L.egn_pack_conv_weight_f32(_lib.ptr(weight), cout, cin, kh, kw, dgrad, _lib.ptr(wp),
-                                                       stream), 'pack')
-        return wp
+        filters.pack_on_device(weight, kind, dgrad, ent[1], stream)
+        return ent[1]
 
     def _pointers(self):
         return [w.data_ptr() for (w, _) in self.entries.values()]
@@ -175,10 +158,11 @@ class PackedFilters(object):
         desc = np.zeros(len(self.entries), dtype=np.dtype(self._DESC, align=True))
         assert desc.dtype.itemsize == self.L.egn_pack_desc_bytes(), (desc.dtype.itemsize, self.L.egn_pack_desc_bytes())
         begin = 0
-        for i, ((_, code), (w, wp)) in enumerate(self.entries.items()):
+        for i, ((_, kind, dgrad), (w, wp)) in enumerate(self.entries.items()):
             cout, cin, kh, kw = w.shape
-            desc[i] = (w.data_ptr(), wp.data_ptr(), cout, cin, kh * kw, code, begin)
-            begin += wp.numel() // (48 if code & 4 else (64 if code & 2 else 4))     # work units (egonet_hip.h)
+            code, unit_floats = filters.DEVICE_PACK[kind]
+            desc[i] = (w.data_ptr(), wp.data_ptr(), cout, cin, kh * kw, code | dgrad, begin)
+            begin += wp.numel() // unit_floats
         self.total = begin
         self.table = torch.from_numpy(desc.view(np.uint8)).to(self.dev)
         self.ptrs = self._pointers()

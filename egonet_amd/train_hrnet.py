@@ -38,7 +38,7 @@ import os
 
 import torch
 
-from . import _lib, tuner
+from . import _lib, filters, tuner
 from .engine import invalidate
 from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID
 from .engine import Buf, HRNetEngine, _round_up
@@ -109,9 +109,6 @@ class _Tape(object):
         return None if cur is None else cur[0]
 
     # -- launches -----------------------------------------------------------
-    def _pack(self, weight, dgrad):
-        return self.o.packs.get(weight, dgrad, self.st)
-
     def _conv_launch(self, x, wp, shift, y, n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, act,
                      weight=None, dgrad=0, want_stats=False, res=None, f43_ok=True):
         """``wp``: the direct-packed filter (None: packed here from ``weight``).  With ``weight`` (+ ``dgrad``) given, the tuner may pick a
@@ -128,12 +125,8 @@ class _Tape(object):
         cfg = tuner.choose(self.dev, key, kinds, ticket_cap=self.o.tickets.numel(),
                            inplace_res=res is not None and res.data_ptr() == y.data_ptr())
         kind = tuner.kind_of(cfg)
-        if kind == 3:
-            wp = self.o.packs.get(weight, dgrad, self.st, wino=3)
-        elif kind == 1:
-            wp = self.o.packs.get(weight, dgrad, self.st, wino=True)
-        elif wp is None:
-            wp = self._pack(weight, dgrad)
+        if wp is None or kind != filters.DIRECT:
+            wp = self.o.packs.get(weight, dgrad, self.st, kind)
         stats = None
         if want_stats and self.o.fuse_bn_stats and cfg > 0:
             # BatchNorm batch statistics in the conv epilogue (per-tile partial sums, csrc/conv_wino.hip):
@@ -142,7 +135,7 @@ class _Tape(object):
             if nrows > 0:
                 stats = (torch.empty(nrows * 2 * cout, dtype=torch.float64, device=self.dev), nrows)
         e0 = timing_begin(self.o.timing, self.dev)     # bench.py: hipEvents around every forward / data-gradient conv
-        if kind == 3:
+        if kind == filters.WINO4:
             _lib.check(self.L.egn_conv2d_ex_f32(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(self.o.ones), _lib.ptr(shift),
                                                 _lib.ptr(res), _lib.ptr(y), n, h, w, cin, cs_in, cout, cs_out, kh, kw,
                                                 stride, pad, act, cfg, None if stats is None else _lib.ptr(stats[0]),
@@ -160,7 +153,7 @@ class _Tape(object):
         if e0 is not None:
             ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
             timing_end(self.o.timing, self.dev, e0, cfg, 2.0 * n * ho * wo * cout * cin * kh * kw,
-                       stats is not None and kind == 3)
+                       stats is not None and kind == filters.WINO4)
         return stats
 
     def _wgrad(self, x, xd, dy, cs_out, weight, stride, pad):

@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, filters
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 TABLE_PATH = os.path.join(_HERE, 'tuned', 'gfx950.json')
@@ -29,10 +29,12 @@ _table = None
 _tuned_here = {}
 
 # What a caller can feed: the filter kinds (kind_of) it packs.
-DIRECT = frozenset((0,))                 # a direct-packed filter only: the GEMM callers, a non-plain epilogue
-ALL_KINDS = frozenset((0, 1, 2, 3))      # the inference program (engine.pack_for_kind transforms on the host)
-TAPE_WINO, TAPE_F43 = frozenset((0, 1)), frozenset((0, 1, 3))      # the training tape: never kind 2
-F43_KINDS = frozenset((2, 3))
+DIRECT = frozenset((filters.DIRECT,))    # a direct-packed filter only: the GEMM callers, a non-plain epilogue
+# the inference program (filters.pack_for_kind transforms on the host)
+ALL_KINDS = frozenset((filters.DIRECT, filters.WINO2, filters.WINO43, filters.WINO4))
+# the training tape: never WINO43
+TAPE_WINO, TAPE_F43 = frozenset((filters.DIRECT, filters.WINO2)), frozenset((filters.DIRECT, filters.WINO2, filters.WINO4))
+F43_KINDS = frozenset((filters.WINO43, filters.WINO4))
 
 
 def _load():
@@ -96,7 +98,7 @@ def _time_cfg(L, args, cfg, stream, x, w, sc, sh, res, y):
 
 def kind_of(cfg):
     """Filter layout cfg's kernel reads (egn_conv_config_kind; -1: not selectable); the cost model, cfg <= 0: direct."""
-    return _lib.lib().egn_conv_config_kind(cfg) if cfg > 0 else 0
+    return _lib.lib().egn_conv_config_kind(cfg) if cfg > 0 else filters.DIRECT
 
 
 @functools.lru_cache(maxsize=None)
@@ -191,7 +193,7 @@ def choose(device, key, kinds=DIRECT, ticket_cap=None, inplace_res=False):
         first = {'43': (70, 80), '43b': (80, 70), '43w': (86, 80, 70)}.get(mode, ())
         ids = list(range(_lib.lib().egn_conv_num_configs(), 0, -1))
         for kind in sorted(kinds - DIRECT, reverse=True):
-            for cfg in (list(first) if kind == 3 else []) + ids:
+            for cfg in (list(first) if kind == filters.WINO4 else []) + ids:
                 if kind_of(cfg) == kind and usable(key, cfg, kinds, ticket_cap, inplace_res):
                     return cfg
     name = shape_key(*key)

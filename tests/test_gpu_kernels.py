@@ -677,24 +677,38 @@ def test_winograd_at_the_bench_batch_size_agrees_with_direct_and_is_linear(h, c,
 
 
 def test_winograd_filter_pack_device_vs_host():
-    """egn_wino_pack_weight_f32 == engine.pack_wino_weight (the float64 host transform the inference
-    programs use), forward and data-gradient filters."""
-    from egonet_amd import _lib, engine
+    """egn_wino_pack_weight_f32 and the F(2x2,3x3) entries of the one-launch packer (egn_pack_conv_weights_batch_f32:
+    what a training step runs) == engine.pack_wino_weight (the float64 host transform the inference programs use),
+    forward and data-gradient filters.  The two device paths share their code: the host transform is the oracle."""
+    from egonet_amd import _lib, engine, filters
+    from egonet_amd.train_common import PackedFilters
     L = _lib.lib()
+    st = _lib.current_stream()
     g = torch.Generator().manual_seed(5)
+    pf = PackedFilters(torch.device('cuda', torch.cuda.current_device()))
+    cases = []
     for cout, cin in ((48, 48), (96, 32), (144, 192), (64, 64), (32, 128)):
         wt = torch.randn(cout, cin, 3, 3, generator=g)
+        wd = wt.cuda()
         for dgrad in (0, 1):
             if L.egn_wino_weight_floats(cout, cin, dgrad) == 0:
                 continue
             dst = torch.empty(L.egn_wino_weight_floats(cout, cin, dgrad), device='cuda')
-            _lib.check(L.egn_wino_pack_weight_f32(_lib.ptr(wt.cuda()), cout, cin, dgrad, _lib.ptr(dst),
-                                                  _lib.current_stream()))
+            _lib.check(L.egn_wino_pack_weight_f32(_lib.ptr(wd), cout, cin, dgrad, _lib.ptr(dst), st))
             src = wt.flip(2, 3).permute(1, 0, 2, 3).contiguous() if dgrad else wt
             want = engine.pack_wino_weight(src)
             assert dst.numel() == want.numel()
             d = (dst.cpu() - want).abs().max().item()
             assert d <= 2e-7 * wt.abs().max().item(), (cout, cin, dgrad, d)
+            cases.append((wt, wd, dgrad, want, pf.get(wd, dgrad, st, kind=filters.WINO2)))
+    assert len(cases) == 10
+    pf.finalize()
+    for case in cases:
+        case[4].fill_(float('nan'))                           # an element the batch launch leaves unwritten fails
+    assert pf.pack_all(st) is True
+    for wt, wd, dgrad, want, got in cases:
+        d = (got.cpu() - want).abs().max().item()             # NaN compares False
+        assert d <= 2e-7 * wt.abs().max().item(), (tuple(wt.shape), dgrad, d)
 
 
 @pytest.mark.parametrize('n,h,w,res,act', [

@@ -195,7 +195,7 @@ def test_step_with_winograd_forward_and_data_gradient_convs_vs_oracle(monkeypatc
     Winograd kernels (csrc/conv_wino.hip; filters transformed on the device by the step's batched
     pack).  Loss, maps and gradients against the CPU training oracle, and the second step (the
     batched pack of direct + Winograd filters in one launch) against the oracle's second step."""
-    from egonet_amd import _lib
+    from egonet_amd import _lib, filters
     monkeypatch.setenv('EGONET_AMD_WINO', '1')
     cfg = configs.tiny_config('coordinates', width=48)
     net, sd = _tiny_model(cfg, seed=7)
@@ -215,23 +215,23 @@ def test_step_with_winograd_forward_and_data_gradient_convs_vs_oracle(monkeypatc
             np.testing.assert_allclose(tr.last_maps.cpu().numpy(), want_maps.numpy(), rtol=0, atol=3e-4)
             gl2, cos, med = gradient_agreement(dict(net.named_parameters()), orc.grads())
             assert cos > 0.9999 and gl2 < 1e-2 and med < 5e-3, (gl2, cos, med)
-    kinds = {code for (_, code) in tr.packs.entries}
-    assert kinds == {0, 1, 2, 3}                 # direct + Winograd filters, forward + data gradient
+    kinds = {(kind, dgrad) for (_, kind, dgrad) in tr.packs.entries}
+    assert kinds == {(filters.DIRECT, 0), (filters.DIRECT, 1), (filters.WINO2, 0), (filters.WINO2, 1)}   # forward + data gradient
     assert tr.packs.table is not None            # the second step packed them all in one launch
-    n_wino = sum(1 for (_, code) in tr.packs.entries if code & 2)
+    n_wino = sum(1 for (_, kind, _) in tr.packs.entries if kind == filters.WINO2)
     assert n_wino >= 2 * 16                      # 2 x (4 + 3 + 2 + ... ) 3x3 s1 convs of the branches / head
     # the one-launch pack of every filter == the single-filter entry points, bit for bit
     L = _lib.lib()
     st = _lib.current_stream()
     assert tr.packs.pack_all(st)
-    for (_, code), (w, wp) in tr.packs.entries.items():
+    for (_, kind, dgrad), (w, wp) in tr.packs.entries.items():
         one = torch.full_like(wp, float('nan'))
         cout, cin, kh, kw = w.shape
-        if code & 2:
-            _lib.check(L.egn_wino_pack_weight_f32(_lib.ptr(w), cout, cin, code & 1, _lib.ptr(one), st))
+        if kind == filters.WINO2:
+            _lib.check(L.egn_wino_pack_weight_f32(_lib.ptr(w), cout, cin, dgrad, _lib.ptr(one), st))
         else:
-            _lib.check(L.egn_pack_conv_weight_f32(_lib.ptr(w), cout, cin, kh, kw, code & 1, _lib.ptr(one), st))
-        assert torch.equal(one, wp), (tuple(w.shape), code)
+            _lib.check(L.egn_pack_conv_weight_f32(_lib.ptr(w), cout, cin, kh, kw, dgrad, _lib.ptr(one), st))
+        assert torch.equal(one, wp), (tuple(w.shape), kind, dgrad)
 
 
 def test_frozen_prefix_gets_no_gradient_and_no_update():

@@ -412,6 +412,50 @@ def test_conv_wgrad_refuses_unsupported():
                                   _lib.ptr(a), 256, _st()) != 0                       # cs_in % 4
 
 
+def test_direct_filter_pack_device_vs_host():
+    """The direct layout is a permutation plus zero padding: egn_pack_conv_weight_f32 and the one-launch packer ==
+    filters.pack_conv_weight (the host packer of the inference engine) element for element, forward and data-gradient
+    filters; padded output channels, a ragged last K chunk, 1 / 9 / 16 taps.  The device entries share their code:
+    the host packer is the oracle."""
+    from egonet_amd import filters
+    from egonet_amd.train_common import PackedFilters
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(21)
+    pf = PackedFilters(torch.device('cuda', torch.cuda.current_device()))
+    cases = []
+    for shape in ((33, 48, 1, 1), (66, 35, 3, 3), (66, 66, 4, 4), (48, 48, 3, 3)):
+        wt = torch.randn(*shape, generator=g)
+        wd = wt.cuda()
+        for dgrad in (0, 1):
+            want = filters.pack_conv_weight(wt.permute(1, 0, 2, 3).flip(2, 3) if dgrad else wt)
+            nfl = L.egn_packed_weight_floats(*shape, dgrad)
+            assert nfl == want.numel()
+            one = torch.full((nfl,), float('nan'), device='cuda')
+            _lib.check(L.egn_pack_conv_weight_f32(_lib.ptr(wd), *shape, dgrad, _lib.ptr(one), _st()))
+            assert torch.equal(one.cpu(), want), (shape, dgrad)
+            cases.append((shape, dgrad, want, pf.get(wd, dgrad, _st())))
+    pf.finalize()
+    for case in cases:
+        case[3].fill_(float('nan'))
+    assert pf.pack_all(_st()) is True
+    for shape, dgrad, want, got in cases:
+        assert torch.equal(got.cpu(), want), (shape, dgrad)
+
+
+@pytest.mark.parametrize('transpose', [0, 1])
+def test_strided_matrix_pack_device_vs_host(transpose):
+    """egn_pack_matrix_f32 with ld > the row length == filters.pack_conv_weight of the [cout, cin, 1, 1] view."""
+    from egonet_amd import filters
+    L = _lib.lib()
+    cout, cin, ld = 40, 70, 77
+    src = torch.randn(cin if transpose else cout, ld, generator=torch.Generator().manual_seed(22))
+    view = src[:, :cout].t() if transpose else src[:, :cin]
+    want = filters.pack_conv_weight(view.reshape(cout, cin, 1, 1))
+    sd, dst = src.cuda(), torch.full((want.numel(),), float('nan'), device='cuda')
+    _lib.check(L.egn_pack_matrix_f32(_lib.ptr(sd), ld, cout, cin, transpose, _lib.ptr(dst), _st()))
+    assert torch.equal(dst.cpu(), want)
+
+
 def test_all_filters_packed_in_one_launch_equal_the_single_packs():
     from egonet_amd.train_hrnet import PackedFilters
     L = _lib.lib()
@@ -440,7 +484,7 @@ def test_f43_filters_in_the_one_launch_packer_equal_the_single_packs():
     """[round 5] descriptor code 4 (+ dgrad): the F(4x4,3x3) filter of conv_wino4.hip packed with all the others
     (egn_pack_conv_weights_batch_f32) == egn_wino4_pack_weight_f32 bit for bit (and engine.pack_wino4_weight, the host
     transform the inference engine uses, to the last fp32 bit or two), beside direct and F(2x2,3x3) entries of the same table."""
-    from egonet_amd import engine
+    from egonet_amd import engine, filters
     from egonet_amd.train_hrnet import PackedFilters
     L = _lib.lib()
     g = torch.Generator().manual_seed(12)
@@ -450,8 +494,8 @@ def test_f43_filters_in_the_one_launch_packer_equal_the_single_packs():
         for dgrad in (0, 1):
             cout, cin = w.shape[:2]
             if L.egn_wino4_pack_weight_floats(cout, cin, dgrad) > 0:
-                pf.get(w, dgrad, _st(), wino=3)
-            pf.get(w, dgrad, _st(), wino=True)
+                pf.get(w, dgrad, _st(), kind=filters.WINO4)
+            pf.get(w, dgrad, _st(), kind=filters.WINO2)
             pf.get(w, dgrad, _st())
     pf.finalize()
     for w in ws:
@@ -469,7 +513,7 @@ def test_f43_filters_in_the_one_launch_packer_equal_the_single_packs():
             n43 += 1
             want = torch.full((nfl,), float('nan'), device='cuda')
             _lib.check(L.egn_wino4_pack_weight_f32(_lib.ptr(w), cout, cin, dgrad, _lib.ptr(want), _st()))
-            got = pf.get(w, dgrad, _st(), wino=3)
+            got = pf.get(w, dgrad, _st(), kind=filters.WINO4)
             assert not torch.isnan(got).any() and torch.equal(got, want)
             if not dgrad:       # the host transform (einsum with G in float64) rounds the last bit differently here and there
                 np.testing.assert_allclose(got.cpu().numpy(), engine.pack_wino4_weight(w.cpu()).reshape(-1).numpy(),
@@ -477,7 +521,7 @@ def test_f43_filters_in_the_one_launch_packer_equal_the_single_packs():
             nf2 = L.egn_wino_weight_floats(cout, cin, dgrad)
             want2 = torch.zeros(nf2, device='cuda')
             _lib.check(L.egn_wino_pack_weight_f32(_lib.ptr(w), cout, cin, dgrad, _lib.ptr(want2), _st()))
-            assert torch.equal(pf.get(w, dgrad, _st(), wino=True), want2)
+            assert torch.equal(pf.get(w, dgrad, _st(), kind=filters.WINO2), want2)
     assert n43 >= 6
 
 

@@ -458,9 +458,9 @@ def test_wino4b_reads_the_same_filter_pack_in_k_group_pairs():
 
 
 def test_device_filter_transform_addresses_the_register_feed_layout():
-    """wino4_pack_weight_kernel (egn_wino4_pack_weight_f32) restated: thread (o, i) writes U[pt] = (G g G^T)[pt // 6][pt % 6]
+    """w4p_pack_pair (csrc/wino4_pack.h: egn_wino4_pack_weight_f32) restated: the unit (o, i) writes U[pt] = (G g G^T)[pt // 6][pt % 6]
     to ((ct * (n_in / 4) + i / 4) * 9216 + wave * 768 + (p / 4) * 256 + (16 (i % 4) + o % 16) * 4 + p % 4 with wave = pt / 3,
-    p = 3 (pt % 3) + nt, nt = (o % 48) / 16; the thread with nt = 0 zeroes values 9..11.  dgrad swaps the channels and
+    p = 3 (pt % 3) + nt, nt = (o % 48) / 16; the unit with nt = 0 zeroes values 9..11.  dgrad swaps the channels and
     rotates the taps.  Must equal engine.pack_wino4_weight (the layout the kernels are tested with) element for element."""
     from egonet_amd import engine
     rng = np.random.default_rng(0)
