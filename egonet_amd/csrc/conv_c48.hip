@@ -28,31 +28,13 @@
 // rows 2w and 2w+1 (MT = 2) x all 48 output channels (NT = 3).
 #include "conv_common.h"
 
-typedef __attribute__((address_space(3))) void* lds_ptr_c48_t;
-
+// The filter load, once per block, through the builtin: the compiler's s_waitcnt vmcnt(0) in front of the next ds_read
+// is what that load needs.  The per-tile halo DMA is egn_lds_dma16 (conv_common.h), the same instruction as raw ISA:
+// there the compiler's wait -- in front of a ds_read of the OTHER buffer -- would expose the latency of the very
+// prefetch this kernel exists for; completion is enforced by hand (s_waitcnt vmcnt(24) + s_barrier at the top of the
+// tile loop).
 __device__ __forceinline__ void c48_dma16(__amdgpu_buffer_rsrc_t r, float4* dst, unsigned voff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_c48_t)dst, 16, voff, 0, 0, 0);
-}
-// The per-tile halo DMA as raw ISA.  Through the builtin the compiler knows that the
-// instruction writes LDS and puts an s_waitcnt vmcnt(0) in front of the next ds_read --
-// of the OTHER buffer -- which would expose the latency of the very prefetch this kernel
-// exists for.  The asm is invisible to the waitcnt insertion pass; completion is
-// enforced by hand (s_waitcnt vmcnt(24) + s_barrier at the top of the tile loop).
-// lds_addr: wave-uniform LDS byte address of the wave's 64 x 16 B destination.
-__device__ __forceinline__ void c48_dma16_raw(u32x4 rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(rsrc)
-               : "m0");
-}
-__device__ __forceinline__ unsigned c48_lds_addr(const void* p) {
-  return (unsigned)(__UINTPTR_TYPE__)(lds_ptr_c48_t) const_cast<void*>(p);  // LDS pointers are 32-bit offsets
-}
-__device__ __forceinline__ float c48_load4(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
-}
-__device__ __forceinline__ void c48_store4(__amdgpu_buffer_rsrc_t r, unsigned voff, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, 0, 0);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (egn_lds_ptr_t)dst, 16, voff, 0, 0, 0);
 }
 
 namespace {
@@ -87,18 +69,15 @@ __device__ __forceinline__ void c48_body(const ConvArgs& a) {
   const int li = lane & 15;
   const int kq = lane >> 4;
 
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x), 0, (unsigned)((size_t)a.N * a.H * a.W * C48 * 4), 0x00020000);
-  // the same descriptor as raw words for the inline-asm DMA: base, stride 0, bytes, flags
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const u32x4 rxv = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu, (unsigned)((size_t)a.N * a.H * a.W * C48 * 4),
-                     0x00020000u};
+  const unsigned in_bytes = (unsigned)((size_t)a.N * a.H * a.W * C48 * 4);
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, in_bytes, EGN_RSRC_WORD3);
+  const u32x4 rxv = egn_rsrc(a.x, in_bytes);   // the same descriptor as raw words for the inline-asm DMA
   const __amdgpu_buffer_rsrc_t rw =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (unsigned)(W_SLOTS * 16), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (unsigned)(W_SLOTS * 16), EGN_RSRC_WORD3);
   const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * C48 * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
   // the filter, once (W_SLOTS is a multiple of 64: whole waves)
   for (int base = wave * 64; base < W_SLOTS; base += NTH) c48_dma16(rw, sW + base, (unsigned)(base + lane) * 16u);
@@ -150,10 +129,10 @@ __device__ __forceinline__ void c48_body(const ConvArgs& a) {
 #define C48_ISSUE(B, OFF)                                                                            \
   {                                                                                                  \
     float4* dst_ = sA + (B)*HALO_SLOTS + wave * 64;                                                  \
-    const unsigned lds_ = c48_lds_addr(dst_);                                                        \
+    const unsigned lds_ = egn_lds_addr(dst_);                                                        \
     _Pragma("unroll") for (int it = 0; it < A_IT; ++it)                                              \
       if (it * NTH + wave * 64 < HALO_SLOTS) /* wave-uniform */                                      \
-        c48_dma16_raw(rxv, lds_ + it * NTH * 16, OFF[it]);                                           \
+        egn_lds_dma16(rxv, lds_ + it * NTH * 16, OFF[it]);                                           \
   }
 // byte offsets of this lane's MT x 4 output pixels (channel li of the first 16; + nt*64 for the
 // others), EGN_OOB = masked.  EGN_OOB + 128 is still out of range: no select per access.
@@ -247,7 +226,7 @@ __device__ __forceinline__ void c48_body(const ConvArgs& a) {
       for (int r = 0; r < 4; ++r) {
         const unsigned ro = has_res ? voff[mt][r] : EGN_OOB;
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) rv[mt][nt][r] = c48_load4(rr, ro + nt * 64u);
+        for (int nt = 0; nt < NT; ++nt) rv[mt][nt][r] = egn_buf_load4(rr, ro + nt * 64u);
       }
     // address arithmetic of the tiles to come (computed in pieces between the MFMA steps below)
     unsigned doff_n[A_IT], voff_n[MT][4];
@@ -333,7 +312,7 @@ __device__ __forceinline__ void c48_body(const ConvArgs& a) {
           if (!res_after) v += rv[mt][nt][r];
           v = egn_act(v, act);
           if (res_after) v = rv[mt][nt][r] + v;
-          c48_store4(ry, voff[mt][r] + nt * 64u, v);
+          egn_buf_store4(ry, voff[mt][r] + nt * 64u, v);
         }
     buf ^= 1;
 #pragma unroll
@@ -402,15 +381,13 @@ __global__ __launch_bounds__(T_NTH, 1) void conv_c48t_kernel(ConvArgs a) {
   const int li = lane & 15;
   const int kq = lane >> 4;
 
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const u32x4 rxv = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu, (unsigned)((size_t)a.N * a.H * a.W * C48 * 4),
-                     0x00020000u};
+  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C48 * 4);
   const __amdgpu_buffer_rsrc_t rw =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (unsigned)(W_SLOTS * 16), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (unsigned)(W_SLOTS * 16), EGN_RSRC_WORD3);
   const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * C48 * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
   for (int base = wave * 64; base < W_SLOTS; base += T_NTH) c48_dma16(rw, sW + base, (unsigned)(base + lane) * 16u);
 
@@ -445,10 +422,10 @@ __global__ __launch_bounds__(T_NTH, 1) void conv_c48t_kernel(ConvArgs a) {
 // chunk C of the tile whose chunk-0 offsets are OFF, into ring buffer C (EGN_OOB + 128 stays OOB)
 #define T_ISSUE(C, OFF)                                                                              \
   {                                                                                                  \
-    const unsigned lds_ = c48_lds_addr(sA + (C)*T_CHUNK_SLOTS + wave * 64);                          \
+    const unsigned lds_ = egn_lds_addr(sA + (C)*T_CHUNK_SLOTS + wave * 64);                          \
     _Pragma("unroll") for (int it = 0; it < T_IT; ++it)                                              \
       if (it * T_NTH + wave * 64 < T_CHUNK_SLOTS) /* wave-uniform */                                 \
-        c48_dma16_raw(rxv, lds_ + it * T_NTH * 16, OFF[it] + (C)*64u);                               \
+        egn_lds_dma16(rxv, lds_ + it * T_NTH * 16, OFF[it] + (C)*64u);                               \
   }
 #define T_VOFF1(N_, TY_, TX_, OUT)                                                                   \
   {                                                                                                  \
@@ -518,7 +495,7 @@ __global__ __launch_bounds__(T_NTH, 1) void conv_c48t_kernel(ConvArgs a) {
       for (int r = 0; r < 4; ++r) {
         const unsigned ro = has_res ? voff[mt][r] : EGN_OOB;
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) rv[mt][nt][r] = c48_load4(rr, ro + nt * 64u);
+        for (int nt = 0; nt < NT; ++nt) rv[mt][nt][r] = egn_buf_load4(rr, ro + nt * 64u);
       }
     unsigned doff_nn[T_IT], voff_n[T_MT][4];
     int dn_ = 0, dty_ = 0, dtx_ = 0, vn_ = 0, vty_ = 0, vtx_ = 0;
@@ -609,7 +586,7 @@ __global__ __launch_bounds__(T_NTH, 1) void conv_c48t_kernel(ConvArgs a) {
           if (!res_after) v += rv[mt][nt][r];
           v = egn_act(v, act);
           if (res_after) v = rv[mt][nt][r] + v;
-          c48_store4(ry, voff[mt][r] + nt * 64u, v);
+          egn_buf_store4(ry, voff[mt][r] + nt * 64u, v);
         }
 #pragma unroll
     for (int it = 0; it < T_IT; ++it) {
@@ -635,32 +612,19 @@ __global__ __launch_bounds__(T_NTH, 1) void conv_c48t_kernel(ConvArgs a) {
 template <int WAVES>
 static int c48_launch(const ConvArgs& a, size_t lds, int grid, hipStream_t stream) {
   static bool raised[EGN_MAX_DEVICES];  // per instantiation and device
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_c48_kernel<WAVES>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(&conv_c48_kernel<WAVES>, EGN_BIG_LDS_BYTES, raised));
   hipLaunchKernelGGL((conv_c48_kernel<WAVES>), dim3(grid), dim3(64 * WAVES), lds, stream, a);
   return (int)hipGetLastError();
 }
 
 int egn_conv_launch_c48(const ConvArgs& a, size_t lds, C48Kernel k, hipStream_t stream) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
+  const int cus = egn_device_cus();
   const int ntiles = a.tiles_x * a.tiles_y * a.N;
   const int grid = ntiles < cus ? ntiles : cus;
   switch (k) {
     case C48_Ring: {  // 16 x 16 tile, halo as a ring of chunks
       static bool raised_t[EGN_MAX_DEVICES];
-      if (egn_first_use_on_device(raised_t)) {
-        EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_c48t_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-      }
+      EGN_CHECK_HIP(egn_allow_big_lds(&conv_c48t_kernel, EGN_BIG_LDS_BYTES, raised_t));
       hipLaunchKernelGGL(conv_c48t_kernel, dim3(grid), dim3(512), lds, stream, a);
       return (int)hipGetLastError();
     }
@@ -668,10 +632,7 @@ int egn_conv_launch_c48(const ConvArgs& a, size_t lds, C48Kernel k, hipStream_t 
 #ifdef EGN_PROBES
     case C48_RegFilter: {  // register-resident filter
       static bool raised[EGN_MAX_DEVICES];
-      if (egn_first_use_on_device(raised)) {
-        EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_c48r_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-      }
+      EGN_CHECK_HIP(egn_allow_big_lds(&conv_c48r_kernel, EGN_BIG_LDS_BYTES, raised));
       hipLaunchKernelGGL(conv_c48r_kernel, dim3(grid), dim3(256), lds, stream, a);
       return (int)hipGetLastError();
     }

@@ -1,5 +1,6 @@
-// conv_common.h -- device helpers shared by the conv kernel families
-// (conv_mfma.hip: register-staged pipeline, conv_dma.hip: LDS-DMA pipeline).
+// conv_common.h -- device helpers shared by every MFMA kernel of the library (the conv families, gemm.hip, the
+// weight-gradient kernels): LDS addresses, buffer descriptors, the LDS-DMA instruction, the buffer load / store
+// wrappers, the multiply-high division -- and the NHWC / NCHW epilogues of conv_mfma.hip and conv_dma.hip.
 #pragma once
 #include "egn_internal.h"
 
@@ -7,6 +8,53 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr unsigned EGN_OOB = 0xF0000000u;  // byte offset beyond any tensor the planner accepts
+
+// LDS byte address of p (LDS pointers are 32-bit offsets)
+typedef __attribute__((address_space(3))) void* egn_lds_ptr_t;
+__device__ __forceinline__ unsigned egn_lds_addr(const void* p) {
+  return (unsigned)(__UINTPTR_TYPE__)(egn_lds_ptr_t) const_cast<void*>(p);
+}
+
+// Raw buffer descriptor of `bytes` bytes at p as four words: base, stride 0, bytes, flags -- what the inline-asm
+// buffer instructions take; __builtin_amdgcn_make_buffer_rsrc builds the same from (p, 0, bytes, EGN_RSRC_WORD3).
+constexpr unsigned EGN_RSRC_WORD3 = 0x00020000u;  // descriptor word 3: raw buffer, out-of-range loads give 0, stores drop
+// egn_rsrc(p, bytes): p converts to the two address words where the call names it, before `bytes` is evaluated (and
+// `bytes` is narrowed there, not in here) -- the order of the brace initialisers this replaced, which the compiled
+// kernels depend on down to their instruction schedule (profiles/shared_prims_isa.txt).
+struct egn_base48 {   // descriptor words 0 and 1: the 48-bit base address
+  unsigned lo, hi;
+  __device__ __forceinline__ egn_base48(const void* p)
+      : lo((unsigned)reinterpret_cast<unsigned long long>(p)),
+        hi((unsigned)(reinterpret_cast<unsigned long long>(p) >> 32) & 0xffffu) {}
+};
+__device__ __forceinline__ u32x4 egn_rsrc(egn_base48 p, unsigned bytes) {
+  return u32x4{p.lo, p.hi, bytes, EGN_RSRC_WORD3};
+}
+
+// One LDS-DMA instruction as raw ISA: 16 B per lane from buffer r at byte offset voff (+ the scalar soff) to LDS at
+// lds_addr + lane * 16.  m0 holds the WAVE-UNIFORM LDS byte address of the wave's 64 x 16 B destination, and the
+// s_nop between the m0 write and its use by the vector-memory instruction is required.
+// Raw ISA, not __builtin_amdgcn_raw_ptr_buffer_load_lds: the compiler knows that the builtin writes LDS and puts
+// `s_waitcnt vmcnt(0)` in front of the next ds_read -- which in a double-buffered kernel belongs to the OTHER buffer
+// -- so the prefetch would have to land before the work it is meant to hide under may start (measured in
+// conv_dma.hip: that wait sat in front of every stage's first fragment read).  The asm is invisible to the waitcnt
+// insertion: the CALLER waits, by an explicit s_waitcnt vmcnt(n) in front of the barrier that publishes the data.
+// MEM adds a "memory" clobber (conv_pw.hip, conv_s2r.hip: the compiler moves no memory access across the issue).
+#define EGN_LDS_DMA16_ISA(SOFF) "s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, " SOFF " offen lds"
+template <bool MEM = false>
+__device__ __forceinline__ void egn_lds_dma16(u32x4 r, unsigned lds_addr, unsigned voff, unsigned soff) {
+  if constexpr (MEM) asm volatile(EGN_LDS_DMA16_ISA("%3") : : "s"(lds_addr), "v"(voff), "s"(r), "s"(soff) : "m0", "memory");
+  else asm volatile(EGN_LDS_DMA16_ISA("%3") : : "s"(lds_addr), "v"(voff), "s"(r), "s"(soff) : "m0");
+}
+template <bool MEM = false>
+__device__ __forceinline__ void egn_lds_dma16(u32x4 r, unsigned lds_addr, unsigned voff) {
+  if constexpr (MEM) asm volatile(EGN_LDS_DMA16_ISA("0") : : "s"(lds_addr), "v"(voff), "s"(r) : "m0", "memory");
+  else asm volatile(EGN_LDS_DMA16_ISA("0") : : "s"(lds_addr), "v"(voff), "s"(r) : "m0");
+}
+#undef EGN_LDS_DMA16_ISA
+
+// x / d by one multiply-high with magic = egn_magic_u32(d) (0: d is 1) -- exact while x * d < 2^32
+__device__ __forceinline__ unsigned egn_udiv_magic(unsigned x, unsigned magic) { return magic ? __umulhi(x, magic) : x; }
 
 __device__ __forceinline__ float egn_act(float v, int act) {
   switch (act) {
@@ -24,6 +72,16 @@ __device__ __forceinline__ f32x4 egn_buf_load16(__amdgpu_buffer_rsrc_t r, unsign
 }
 __device__ __forceinline__ void egn_buf_store16(__amdgpu_buffer_rsrc_t r, unsigned voff, f32x4 v) {
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, 0, 0);
+}
+// one dword per lane at voff (+ the scalar soff)
+__device__ __forceinline__ float egn_buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff = 0) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
+}
+__device__ __forceinline__ void egn_buf_store4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float v) {
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
+}
+__device__ __forceinline__ void egn_buf_store4(__amdgpu_buffer_rsrc_t r, unsigned voff, float v) {
+  egn_buf_store4(r, voff, 0u, v);
 }
 
 // ---------------------------------------------------------------------------
@@ -77,7 +135,7 @@ __device__ __forceinline__ void conv_epi_prefetch(const ConvArgs& a, const float
   const int* sPix = reinterpret_cast<const int*>(smem + a.spix_off);
   const int cbase = n0 + wn * TNW;
   const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.res ? a.res : a.y), 0, (unsigned)((size_t)a.N * a.Ho * a.Wo * a.cs_out * 4), 0x00020000);
+      const_cast<float*>(a.res ? a.res : a.y), 0, (unsigned)((size_t)a.N * a.Ho * a.Wo * a.cs_out * 4), EGN_RSRC_WORD3);
 #pragma unroll
   for (int it = 0; it < MT * NT; ++it) {
     const int idx = it * 64 + lane;
@@ -110,7 +168,7 @@ __device__ __forceinline__ void conv_epi_finish(const ConvArgs& a, f32x4 (&acc)[
   const int act = a.act & EGN_ACT_MASK;
   const bool res_after = (a.act & EGN_ACT_RES_AFTER) != 0;
   const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-      a.y, 0, (unsigned)((size_t)a.N * a.Ho * a.Wo * a.cs_out * 4), 0x00020000);
+      a.y, 0, (unsigned)((size_t)a.N * a.Ho * a.Wo * a.cs_out * 4), EGN_RSRC_WORD3);
 
   __syncthreads();  // main-loop LDS reads are done
   float* sC = reinterpret_cast<float*>(smem) + (size_t)wave * (MT * 16) * SC_LD;

@@ -20,32 +20,18 @@
 
 #include "conv_common.h"
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// One LDS-DMA instruction: 16 B per lane from buffer `r` at voff (+ SGPR soff)
-// to LDS at wave-uniform `dst` + lane*16.  Kept out of the kernel template: a
-// call to the target builtin with template-dependent operands makes clang drop
-// the host-side stub of the kernel without a diagnostic (ROCm 7.2).
-//
-// Issued as raw ISA, not through __builtin_amdgcn_raw_ptr_buffer_load_lds: the compiler
-// knows the builtin writes LDS and puts `s_waitcnt vmcnt(0)` in front of the next
-// ds_read -- which here belongs to the OTHER stage buffer -- so the DMA of stage s+1
-// would have to land before the MFMA loop of stage s may start (measured: that wait sat
-// in front of every stage's first fragment read).  The asm is invisible to the waitcnt
-// insertion; completion is enforced by the explicit vmcnt(0) in front of the stage
-// barrier, one whole MFMA loop after the issue.
+// One LDS-DMA instruction (egn_lds_dma16, conv_common.h: raw ISA, the kernel waits by its explicit vmcnt(0) in front of
+// the stage barrier, one whole MFMA loop after the issue) to LDS at wave-uniform `dst` + lane*16.  Kept out of the
+// kernel template: a call to the target builtin with template-dependent operands makes clang drop the host-side stub
+// of the kernel without a diagnostic (ROCm 7.2).
 __device__ __forceinline__ void egn_dma16(u32x4 r, float4* dst, unsigned voff, int soff) {
 #ifdef EGN_DMA_VIA_BUILTIN  // A/B switch for tools/conv_probe.py builds only (-DEGN_DMA_VIA_BUILTIN)
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
       reinterpret_cast<void*>(((unsigned long long)(r[1] & 0xffffu) << 32) | r[0]), 0, r[2], r[3]);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)dst, 16, voff, soff, 0, 0);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (egn_lds_ptr_t)dst, 16, voff, soff, 0, 0);
   return;
 #endif
-  const unsigned lds = (unsigned)(__UINTPTR_TYPE__)(lds_ptr_t)dst;  // wave-uniform LDS byte address
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds), "v"(voff), "s"(r), "s"(soff)
-               : "m0");
+  egn_lds_dma16(r, egn_lds_addr(dst), voff, (unsigned)soff);
 }
 
 // ABL != 0 are timing ablations (wrong results by construction, never planned):
@@ -84,12 +70,8 @@ __global__ __launch_bounds__(256, 2) void conv_dma_kernel(ConvArgs a) {
 
   constexpr unsigned OOB = 0xF0000000u;
   // buffer descriptors as raw words (base, stride 0, bytes, flags) for the inline-asm DMA
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const unsigned long long waddr = reinterpret_cast<unsigned long long>(a.w);
-  const u32x4 rx = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu,
-                    (unsigned)((size_t)a.N * a.H * a.W * a.cs_in * 4), 0x00020000u};
-  const u32x4 rw = {(unsigned)waddr, (unsigned)(waddr >> 32) & 0xffffu,
-                    (unsigned)((size_t)a.nchunk * a.taps * CKQ * a.CoutP * 16), 0x00020000u};
+  const u32x4 rx = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * a.cs_in * 4);
+  const u32x4 rw = egn_rsrc(a.w, (size_t)a.nchunk * a.taps * CKQ * a.CoutP * 16);
 
   // halo element e = tid + it*256 -> LDS slot e = pixel p * 4 + quad q
   const int q = tid & 3;
@@ -277,10 +259,7 @@ __global__ __launch_bounds__(256, 2) void conv_dma_kernel(ConvArgs a) {
 template <int WM, int WN, int MT, int NT, int ABL>
 static int launch_abl(const ConvArgs& a, size_t lds, hipStream_t stream) {
   static bool raised[EGN_MAX_DEVICES];  // per instantiation and device
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_kernel<WM, WN, MT, NT, 8, 8, ABL>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(&conv_dma_kernel<WM, WN, MT, NT, 8, 8, ABL>, EGN_BIG_LDS_BYTES, raised));
   const int tiles_b = (a.N + a.TNB - 1) / a.TNB;
   dim3 grid(a.tiles_x * a.tiles_y * tiles_b, (a.CoutP + WN * NT * 16 - 1) / (WN * NT * 16));
   hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 8, 8, ABL>), grid, dim3(256), lds, stream, a);
@@ -290,10 +269,7 @@ static int launch_abl(const ConvArgs& a, size_t lds, hipStream_t stream) {
 template <int WM, int WN, int MT, int NT>
 static int launch_one(const ConvArgs& a, size_t lds, hipStream_t stream) {
   static bool raised[EGN_MAX_DEVICES];  // per instantiation and device
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_kernel<WM, WN, MT, NT, 8, 8>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(&conv_dma_kernel<WM, WN, MT, NT, 8, 8>, EGN_BIG_LDS_BYTES, raised));
   const int tiles_b = (a.N + a.TNB - 1) / a.TNB;
   dim3 grid(a.tiles_x * a.tiles_y * tiles_b, (a.CoutP + WN * NT * 16 - 1) / (WN * NT * 16));
   hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 8, 8>), grid, dim3(256), lds, stream, a);

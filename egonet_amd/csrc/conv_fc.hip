@@ -25,9 +25,9 @@ __global__ __launch_bounds__(256, 2) void conv_fc_kernel(ConvArgs a) {
   const int rows = a.N * a.H * a.W;
 
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x), 0, (unsigned)((size_t)rows * a.cs_in * 4), 0x00020000);
+      const_cast<float*>(a.x), 0, (unsigned)((size_t)rows * a.cs_in * 4), EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.w), 0, (unsigned)((size_t)nchunk * EGN_CKQ * a.CoutP * 16), 0x00020000);
+      const_cast<float*>(a.w), 0, (unsigned)((size_t)nchunk * EGN_CKQ * a.CoutP * 16), EGN_RSRC_WORD3);
   // lane (row m0 + li, k lanes 4 kq .. 4 kq + 3 of a chunk) / lane (channel n0 + li, the same k lanes)
   const unsigned xo = (unsigned)(((m0 + li) * a.cs_in + 4 * kq) * 4);
   const unsigned wo = (unsigned)((kq * a.CoutP + n0 + li) * 16);

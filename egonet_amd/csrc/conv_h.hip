@@ -111,12 +111,12 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
     for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x), 0, (unsigned)((size_t)a.N * a.H * a.W * a.Cin * 4), 0x00020000);
+      const_cast<float*>(a.x), 0, (unsigned)((size_t)a.N * a.H * a.W * a.Cin * 4), EGN_RSRC_WORD3);
   const int nchunk = a.Cin / H_CK;
   const int nstage = a.npix * (H_CK / 4);   // float4 items of a chunk's halo tile
   // B fragments: [cout tile][chunk][step][lane] x 16 bytes -- one lane offset in a register, the rest is wave-uniform
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(a.w), 0, (unsigned)((a.Cout / 16) * nchunk * (H_KS * 1024)), 0x00020000);
+      const_cast<void*>(a.w), 0, (unsigned)((a.Cout / 16) * nchunk * (H_KS * 1024)), EGN_RSRC_WORD3);
   const unsigned wlane = lane * 16;
   int wb[NT];      // byte offset of (cout tile, chunk 0, step 0)
 #pragma unroll
@@ -202,9 +202,9 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
   }
   __syncthreads();
   const unsigned ybytes = (unsigned)((size_t)a.N * a.H * a.W * a.Cout * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, ybytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, ybytes, EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, ybytes, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, ybytes, EGN_RSRC_WORD3);
   constexpr int C4 = NT * 4;   // float4 per slab row
 #pragma unroll
   for (int it = 0; it < MT * NT; ++it) {

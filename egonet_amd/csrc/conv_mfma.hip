@@ -70,9 +70,9 @@ __global__ __launch_bounds__(256, 3) void conv_mfma_kernel(ConvArgs a) {
   // padding of the convolution.
   constexpr unsigned OOB = 0xF0000000u;  // > any tensor size accepted by the planner
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x), 0, (unsigned)((size_t)a.N * a.H * a.W * a.cs_in * 4), 0x00020000);
+      const_cast<float*>(a.x), 0, (unsigned)((size_t)a.N * a.H * a.W * a.cs_in * 4), EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.w), 0, (unsigned)((size_t)a.nchunk * a.taps * CKQ * a.CoutP * 16), 0x00020000);
+      const_cast<float*>(a.w), 0, (unsigned)((size_t)a.nchunk * a.taps * CKQ * a.CoutP * 16), EGN_RSRC_WORD3);
   // halo tile: element e = tid + it*256 -> quad q = tid & 3, pixel p = (tid>>2) + it*64
   const int q = tid & 3;
   const int p0 = tid >> 2;

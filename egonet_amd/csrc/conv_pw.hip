@@ -30,8 +30,6 @@
 
 #include "conv_common.h"
 
-typedef __attribute__((address_space(3))) void* lds_ptr_pw_t;
-
 namespace {
 
 constexpr int PW_C1 = 64, PW_C2 = 256, PW_C3 = 64;   // h -> out -> h'
@@ -55,19 +53,13 @@ struct PwArgs {
   int M, relu1;
 };
 
-__device__ __forceinline__ void pw_dma16(u32x4 r, unsigned lds_addr, unsigned voff, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(r), "s"(soff)
-               : "m0", "memory");
-}
 // byte offset of (row, quad) inside a slab (gemm.hip: kc_off)
 __device__ __forceinline__ unsigned pw_off(int row, int quad) { return (unsigned)row * 128u + (unsigned)((quad ^ ((row >> 1) & 7)) << 4); }
 
 template <bool FUSED>
 __global__ __launch_bounds__(PW_NTH, 2) void conv_pw_kernel(PwArgs g) {
   extern __shared__ float4 pw_smem[];
-  const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)(lds_ptr_pw_t)pw_smem;
+  const unsigned lds0 = egn_lds_addr(pw_smem);
   char* smc = reinterpret_cast<char*>(pw_smem);
   const unsigned ldsR = lds0 + 2u * PW_A_BYTES;
   char* sR = smc + 2 * PW_A_BYTES;
@@ -77,14 +69,12 @@ __global__ __launch_bounds__(PW_NTH, 2) void conv_pw_kernel(PwArgs g) {
   const int li = lane & 15, kq = lane >> 4;
   const bool has_res = g.res != nullptr;
 
-  const unsigned long long haddr = reinterpret_cast<unsigned long long>(g.h);
-  const unsigned long long raddr = reinterpret_cast<unsigned long long>(has_res ? g.res : g.h);
-  const u32x4 rh = {(unsigned)haddr, (unsigned)(haddr >> 32) & 0xffffu, (unsigned)((size_t)g.M * PW_C1 * 4), 0x00020000u};
-  const u32x4 rr = {(unsigned)raddr, (unsigned)(raddr >> 32) & 0xffffu,
-                    (unsigned)((size_t)g.M * (has_res ? PW_C2 : PW_C1) * 4), 0x00020000u};
-  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(g.out, 0, (unsigned)((size_t)g.M * PW_C2 * 4), 0x00020000);
+  const float* rsrc = has_res ? g.res : g.h;   // (no residual: the descriptor of h, never read)
+  const u32x4 rh = egn_rsrc(g.h, (size_t)g.M * PW_C1 * 4);
+  const u32x4 rr = egn_rsrc(rsrc, (size_t)g.M * (has_res ? PW_C2 : PW_C1) * 4);
+  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(g.out, 0, (unsigned)((size_t)g.M * PW_C2 * 4), EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(FUSED ? g.hn : g.out, 0,
-                                                                     (unsigned)((size_t)g.M * (FUSED ? PW_C3 : PW_C2) * 4), 0x00020000);
+                                                                     (unsigned)((size_t)g.M * (FUSED ? PW_C3 : PW_C2) * 4), EGN_RSRC_WORD3);
 
   // ---- the filters: registers for the whole kernel
   f32x4 b1[4][4];
@@ -143,7 +133,7 @@ __global__ __launch_bounds__(PW_NTH, 2) void conv_pw_kernel(PwArgs g) {
   if (t >= ntiles) return;
   // prologue: h of the first tile
 #pragma unroll
-  for (int j = 0; j < 2; ++j) pw_dma16(rh, lds0 + aldst[j], avoff[j], (unsigned)t * (PW_TP * PW_C1 * 4));
+  for (int j = 0; j < 2; ++j) egn_lds_dma16<true>(rh, lds0 + aldst[j], avoff[j], (unsigned)t * (PW_TP * PW_C1 * 4));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   int par = 0;
   for (; t < ntiles; t += gsz) {
@@ -155,14 +145,14 @@ __global__ __launch_bounds__(PW_NTH, 2) void conv_pw_kernel(PwArgs g) {
     if (has_res) {
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        pw_dma16(rr, ldsR + (unsigned)((8 * wave + j) * 1024), rvoff[j & 3],
+        egn_lds_dma16<true>(rr, ldsR + (unsigned)((8 * wave + j) * 1024), rvoff[j & 3],
                  pix0 * (PW_C2 * 4) + (unsigned)((2 * wave + (j >> 2)) * 128));
     }
     const int tn = t + gsz;
     if (tn < ntiles) {
 #pragma unroll
       for (int j = 0; j < 2; ++j)
-        pw_dma16(rh, lds0 + (unsigned)((par ^ 1) * PW_A_BYTES) + aldst[j], avoff[j], (unsigned)tn * (PW_TP * PW_C1 * 4));
+        egn_lds_dma16<true>(rh, lds0 + (unsigned)((par ^ 1) * PW_A_BYTES) + aldst[j], avoff[j], (unsigned)tn * (PW_TP * PW_C1 * 4));
     }
     // ---- GEMM 1
     f32x4 acc1[2][4];
@@ -245,16 +235,9 @@ __global__ __launch_bounds__(PW_NTH, 2) void conv_pw_kernel(PwArgs g) {
 template <bool FUSED>
 static int pw_launch(const PwArgs& g, hipStream_t st) {
   static bool raised[EGN_MAX_DEVICES];
-  static int cus = 0;
   auto k = &conv_pw_kernel<FUSED>;
-  if (egn_first_use_on_device(raised))
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, PW_LDS));
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(k, PW_LDS, raised));
+  const int cus = egn_device_cus();
   const int ntiles = g.M / PW_TP;
   const int grid = ntiles < 2 * cus ? ntiles : 2 * cus;
   hipLaunchKernelGGL(k, dim3(grid), dim3(PW_NTH), PW_LDS, st, g);

@@ -30,8 +30,6 @@
 
 #include "conv_common.h"
 
-typedef __attribute__((address_space(3))) void* lds_ptr_s2r_t;
-
 namespace {
 constexpr int S2_NW = 3, S2_NTH = 64 * S2_NW;
 constexpr int S2_CIN = 48, S2_CG = 48;         // input channels; output channels per block (3 n-tiles)
@@ -40,16 +38,9 @@ constexpr int S2_NSLAB = 27;                   // (tap, 16-channel chunk)
 constexpr int S2_LDS = S2_NSLAB * 1024;
 }  // namespace
 
-__device__ __forceinline__ void s2r_dma16(u32x4 r, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(r)
-               : "m0", "memory");
-}
-
 __global__ __launch_bounds__(S2_NTH, 4) void conv_s2r_kernel(ConvArgs a) {
   extern __shared__ float4 s2_smem[];
-  const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)(lds_ptr_s2r_t)s2_smem;
+  const unsigned lds0 = egn_lds_addr(s2_smem);
   const char* smc = reinterpret_cast<const char*>(s2_smem);
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -64,11 +55,9 @@ __global__ __launch_bounds__(S2_NTH, 4) void conv_s2r_kernel(ConvArgs a) {
   const int cg = (int)blockIdx.x % ncg;
   const int co = cg * S2_CG + 16 * wave + li;      // this lane's output channel
 
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const u32x4 rx = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu, (unsigned)((size_t)a.N * a.H * a.W * S2_CIN * 4),
-                    0x00020000u};
+  const u32x4 rx = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * S2_CIN * 4);
   const __amdgpu_buffer_rsrc_t ry =
-      __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4), EGN_RSRC_WORD3);
 
   // ---- the filter slice of this wave: b[tap][chunk], element s = input channel 16 chunk + 4 kq + s of output channel co
   f32x4 b[9][3];
@@ -105,7 +94,7 @@ __global__ __launch_bounds__(S2_NTH, 4) void conv_s2r_kernel(ConvArgs a) {
       const int ky = tap / 3, kx = tap - 3 * ky;
       const bool ok = (unsigned)(iy0 + ky) < (unsigned)a.H && (unsigned)(ix0 + kx) < (unsigned)a.W;
       const unsigned voff = ok ? (unsigned)(pixoff + ((ky * a.W + kx) * S2_CIN + 16 * ch) * 4) : EGN_OOB;
-      s2r_dma16(rx, lds0 + (unsigned)p * 1024u, voff);
+      egn_lds_dma16<true>(rx, lds0 + (unsigned)p * 1024u, voff);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces (and the previous tile's stores)
     __builtin_amdgcn_s_barrier();                          // ... everyone's
@@ -141,16 +130,8 @@ size_t egn_conv_s2r_lds_bytes() { return S2_LDS; }
 int egn_conv_launch_s2r(const ConvArgs& a, hipStream_t stream) {
   if (!egn_conv_s2r_applies(a)) return EGN_E_BADARG;
   static bool raised[EGN_MAX_DEVICES];
-  static int cus = 0;
-  if (egn_first_use_on_device(raised))
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_s2r_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      S2_LDS));
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(&conv_s2r_kernel, S2_LDS, raised));
+  const int cus = egn_device_cus();
   const int ncg = a.Cout / S2_CG;
   const int nitem = a.N * (a.Ho / S2_TH) * (a.Wo / S2_TW) * ncg;
   // five blocks per CU (128 VGPRs: four waves per SIMD; 5 x 27 KB of LDS), a multiple of the co-groups

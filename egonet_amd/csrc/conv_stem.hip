@@ -18,8 +18,6 @@
 // Numerics: the same fp32 fmaf chain per output as the general kernels, in (tap, channel) order.
 #include "conv_common.h"
 
-typedef __attribute__((address_space(3))) void* lds_ptr_stem_t;
-
 namespace {
 constexpr int ST_T = 16;                  // output tile edge
 constexpr int ST_H = 2 * ST_T + 1;        // input halo edge: 33
@@ -28,21 +26,16 @@ constexpr int ST_IT = (ST_SLOTS + 255) / 256;   // DMA instructions per lane and
 constexpr int ST_BUF = ST_IT * 256;       // float4 slots per halo buffer
 }  // namespace
 
-__device__ __forceinline__ void stem_dma16(u32x4 rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" : : "s"(lds_addr), "v"(voff), "s"(rsrc) : "m0");
-}
-
 __global__ __launch_bounds__(256, 2) void conv_stem_kernel(ConvArgs a) {
   extern __shared__ float4 smem[];   // [2][ST_BUF]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, kq = lane >> 4;
-  const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)(lds_ptr_stem_t)smem;
+  const unsigned lds0 = egn_lds_addr(smem);
 
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const u32x4 rx = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu, (unsigned)((size_t)a.N * a.H * a.W * 16), 0x00020000u};
+  const u32x4 rx = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * 16);
   const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * 64 * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
 
   // the filter: 9 taps x 4 co sub-tiles, one register each, for the whole kernel
   float wf[9][4];
@@ -78,7 +71,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(ConvArgs a) {
       if (it * 256 + wave * 64 < ST_SLOTS) {                                                            \
         const unsigned iy_ = (unsigned)(iy0_ + (hyx[it] >> 8)), ix_ = (unsigned)(ix0_ + (hyx[it] & 255)); \
         const bool in_ = hyx[it] >= 0 && iy_ < (unsigned)a.H && ix_ < (unsigned)a.W;                    \
-        stem_dma16(rx, lds0 + (unsigned)(((P)*ST_BUF + it * 256 + wave * 64) * 16),                     \
+        egn_lds_dma16(rx, lds0 + (unsigned)(((P)*ST_BUF + it * 256 + wave * 64) * 16),                  \
                    in_ ? (unsigned)(((n_ * a.H + (int)iy_) * a.W + (int)ix_) * 16) : EGN_OOB);          \
       }                                                                                                 \
     }                                                                                                   \
@@ -141,13 +134,7 @@ size_t egn_conv_stem_lds_bytes() { return (size_t)2 * ST_BUF * 16; }
 
 int egn_conv_launch_stem(const ConvArgs& a, size_t lds, hipStream_t stream) {
   if (!egn_conv_stem_applies(a) || a.stats) return EGN_E_BADARG;
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
+  const int cus = egn_device_cus();
   const int ntile = a.tiles_x * a.tiles_y * a.N;
   const int grid = ntile < 2 * cus ? ntile : 2 * cus;     // two 35 KB blocks per CU
   hipLaunchKernelGGL(conv_stem_kernel, dim3(grid), dim3(256), lds, stream, a);

@@ -44,8 +44,6 @@
 #include "conv_common.h"
 #include "conv_wgrad.h"
 
-typedef __attribute__((address_space(3))) void* lds_ptr_wgw_t;
-
 template <int TW_, int TNB_>
 struct WgwGeom {
   static constexpr int TH = 8, TW = TW_, TNB = TNB_;
@@ -62,13 +60,6 @@ struct WgwGeom {
   static_assert(DPX == 128 && DPX * PXQ % 64 == 0, "32 Winograd tiles = 8 K steps per stage");
   static_assert(2 * STAGE * 16 <= EGN_WGW_LDS_BYTES, "two stages fit");
 };
-
-__device__ __forceinline__ void wgw_dma16(u32x4 rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(rsrc)
-               : "m0");
-}
 
 // The eight K steps of a stage for one wave.  Its frequency row i and column pair jb enter only through
 // WHICH patch rows / columns it reads (uniform LDS offsets) and three signs:
@@ -177,13 +168,9 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino_kernel(WgradArgs a) {
   const int cot = blockIdx.x % a.co_tiles, cit = blockIdx.x / a.co_tiles;
   const int co0 = cot * 48, ci0 = cit * 48;
 
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const unsigned long long daddr = reinterpret_cast<unsigned long long>(a.dy);
-  const u32x4 rx = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu,
-                    (unsigned)((size_t)a.N * a.H * a.W * a.Cin * 4), 0x00020000u};
-  const u32x4 rd = {(unsigned)daddr, (unsigned)(daddr >> 32) & 0xffffu,
-                    (unsigned)((size_t)a.N * a.H * a.W * a.Cout * 4), 0x00020000u};
-  const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)(lds_ptr_wgw_t)wgw_smem;
+  const u32x4 rx = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * a.Cin * 4);
+  const u32x4 rd = egn_rsrc(a.dy, (size_t)a.N * a.H * a.W * a.Cout * 4);
+  const unsigned lds0 = egn_lds_addr(wgw_smem);
 
   // DMA slot of this lane in instruction i = wave + 8k: image dn, row dy, column dx of the stage's halo (x) or
   // dy tile and the channel quad.  Per lane and instruction, ONCE: the byte offset relative to the tile's first
@@ -248,7 +235,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_wino_kernel(WgradArgs a) {
 #define WGW_ISSUE(K, P, OFF)                                                                             \
   {                                                                                                      \
     const int i_ = wave + 8 * (K);                                                                       \
-    if (i_ < G::NI) wgw_dma16(i_ < G::NHI ? rx : rd, lds0 + (unsigned)(((P)*G::STAGE + i_ * 64) * 16), OFF[K]); \
+    if (i_ < G::NI) egn_lds_dma16(i_ < G::NHI ? rx : rd, lds0 + (unsigned)(((P)*G::STAGE + i_ * 64) * 16), OFF[K]); \
   }
 
   const int t_begin = blockIdx.y * a.tiles_per_split;
@@ -405,9 +392,7 @@ template <int TW, int TNB, int ABL = 0>
 static int wgw_launch(const WgradArgs& a, hipStream_t stream) {
   auto k = conv_wgrad_wino_kernel<TW, TNB, ABL>;
   static bool raised[EGN_MAX_DEVICES];
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(k, EGN_BIG_LDS_BYTES, raised));
   hipLaunchKernelGGL(k, dim3(a.co_tiles * a.ci_tiles, a.nsplit), dim3(512), EGN_WGW_LDS_BYTES, stream, a);
   return (int)hipGetLastError();
 }

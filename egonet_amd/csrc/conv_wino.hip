@@ -42,8 +42,6 @@
 // kernels -- the parity bar is the reference's (1e-3 px on key-points, arg-max indices exact).
 #include "conv_common.h"
 
-typedef __attribute__((address_space(3))) void* lds_ptr_wino_t;
-
 // Output channels per block (co-tile, egn_wino_cot in egn_internal.h): 48 (NT = 3 MFMA column tiles)
 // where Cout allows -- the widths of HRNet-W48 (48 / 96 / 192 / 384) -- else 32 (NT = 2): the W32 /
 // Pedestrian widths (32 / 64 / 128 / 256) and the 64-channel stem layers.  The SAME rule in the filter
@@ -159,22 +157,6 @@ struct WinoDims {
   static_assert(TNB * (TH / 2) * (TW / 2) == 64 || TNB * (TH / 2) * (TW / 2) == 32, "m-tiles of 16 Winograd tiles");
 };
 
-__device__ __forceinline__ void wino_dma16(u32x4 rsrc, unsigned lds_addr, unsigned voff, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff)
-               : "m0");
-}
-__device__ __forceinline__ unsigned wino_lds_addr(const void* p) {
-  return (unsigned)(__UINTPTR_TYPE__)(lds_ptr_wino_t) const_cast<void*>(p);
-}
-__device__ __forceinline__ float wino_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ void wino_store4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
-}
-
 // ABL != 0 are timing ablations (wrong results by construction; cfg ids 47..50, tools/wino_probe.py only):
 //   bit 0 no DMA after the prologue, bit 1 no patch reads / input transform, bit 2 no residual loads /
 //   output stores, bit 3 no barrier / waitcnt at the step tops
@@ -199,16 +181,12 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
   const int nct = Co / WN_CO;
   const int nchunk = a.nchunk;
 
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const unsigned long long uaddr = reinterpret_cast<unsigned long long>(a.w);
-  const u32x4 rxv = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu,
-                     (unsigned)((size_t)a.N * a.H * a.W * C * 4), 0x00020000u};
-  const u32x4 ruv = {(unsigned)uaddr, (unsigned)(uaddr >> 32) & 0xffffu,
-                     (unsigned)((size_t)nct * nchunk * WN_USLOTS * 16), 0x00020000u};
+  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C * 4);
+  const u32x4 ruv = egn_rsrc(a.w, (size_t)nct * nchunk * WN_USLOTS * 16);
   const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
   // halo slot e = it*256 + tid -> (quad plane, pixel slot) -> (image b, hy, hx); item independent
   int hmeta[IT];  // b << 16 | hy << 8 | hx, -1 = pad slot;  the quad is e / PLANE
@@ -262,10 +240,10 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
 #define WINO_PIECE(K, P, OFF, CT, CH)                                                                \
   {                                                                                                  \
     if ((K) < IT) {                                                                                  \
-      wino_dma16(rxv, wino_lds_addr(sH + (P)*D::BUF + wave * 64) + (K)*WN_NTH * 16, OFF[(K) < IT ? (K) : 0], \
+      egn_lds_dma16(rxv, egn_lds_addr(sH + (P)*D::BUF + wave * 64) + (K)*WN_NTH * 16, OFF[(K) < IT ? (K) : 0], \
                  (unsigned)(CH)*64u);                                                                \
     } else {                                                                                         \
-      wino_dma16(ruv, wino_lds_addr(sU + (P)*WN_USLOTS + wave * 64) + ((K)-IT) * WN_NTH * 16, (unsigned)tid * 16u, \
+      egn_lds_dma16(ruv, egn_lds_addr(sU + (P)*WN_USLOTS + wave * 64) + ((K)-IT) * WN_NTH * 16, (unsigned)tid * 16u, \
                  (unsigned)(((CT)*nchunk + (CH)) * WN_USLOTS) * 16u + ((K)-IT) * WN_NTH * 16);       \
     }                                                                                                \
   }
@@ -430,7 +408,7 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
             for (int pb = 0; pb < 2; ++pb)
 #pragma unroll
               for (int nt = 0; nt < WN_NT; ++nt)
-                rv[r][pa][pb][nt] = wino_load4(rr, ro, pa * rowpitch + pb * colpitch + nt * 64u);
+                rv[r][pa][pb][nt] = egn_buf_load4(rr, ro, pa * rowpitch + pb * colpitch + nt * 64u);
         }
       }
       par ^= 1;
@@ -457,7 +435,7 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
           for (int pa = 0; pa < 2; ++pa) {
             float v = (pa == 0 ? y0 : y1) * sc[nt] + sh[nt] + rv[r][pa][pb][nt];
             v = fmaxf(v, act_lo);
-            wino_store4(ry, ((ABL & 4) && v != 12345.678f) ? EGN_OOB : voff[r], pa * rowpitch + pb * colpitch + nt * 64u, v);
+            egn_buf_store4(ry, ((ABL & 4) && v != 12345.678f) ? EGN_OOB : voff[r], pa * rowpitch + pb * colpitch + nt * 64u, v);
           }
         }
       }
@@ -536,16 +514,12 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
   const int nct = Co / CO_T;
   const int nchunk = a.nchunk;
 
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const unsigned long long uaddr = reinterpret_cast<unsigned long long>(a.w);
-  const u32x4 rxv = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu,
-                     (unsigned)((size_t)a.N * a.H * a.W * C * 4), 0x00020000u};
-  const u32x4 ruv = {(unsigned)uaddr, (unsigned)(uaddr >> 32) & 0xffffu,
-                     (unsigned)((size_t)nct * nchunk * USL * 16), 0x00020000u};
+  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C * 4);
+  const u32x4 ruv = egn_rsrc(a.w, (size_t)nct * nchunk * USL * 16);
   const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
   int hmeta[IT];
   unsigned hq[IT];
@@ -596,10 +570,10 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
   {                                                                                                  \
     if ((K) < IT) {                                                                                  \
       if ((K)*NTH + wave * 64 < SLOTS)                                                               \
-        wino_dma16(rxv, wino_lds_addr(sH + (P)*BUF + wave * 64) + (K)*NTH * 16, OFF[(K) < IT ? (K) : 0], \
+        egn_lds_dma16(rxv, egn_lds_addr(sH + (P)*BUF + wave * 64) + (K)*NTH * 16, OFF[(K) < IT ? (K) : 0], \
                    (unsigned)(CH)*64u);                                                              \
     } else {                                                                                         \
-      wino_dma16(ruv, wino_lds_addr(sU + (P)*USL + wave * 64) + ((K)-IT) * NTH * 16, (unsigned)tid * 16u, \
+      egn_lds_dma16(ruv, egn_lds_addr(sU + (P)*USL + wave * 64) + ((K)-IT) * NTH * 16, (unsigned)tid * 16u, \
                  (unsigned)(((CT)*nchunk + (CH)) * USL) * 16u + ((K)-IT) * NTH * 16);          \
     }                                                                                                \
   }
@@ -758,7 +732,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
 #pragma unroll
           for (int pb = 0; pb < 2; ++pb)
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) rv[r][pb][nt] = wino_load4(rr, ro, pb * colpitch + nt * 64u);
+            for (int nt = 0; nt < NT; ++nt) rv[r][pb][nt] = egn_buf_load4(rr, ro, pb * colpitch + nt * 64u);
         }
       }
       par ^= 1;
@@ -829,7 +803,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
         for (int pb = 0; pb < 2; ++pb) {
           float v = keep[nt][r][pb] * sc[nt] + sh[nt] + rv[r][pb][nt];
           v = fmaxf(v, act_lo);
-          wino_store4(ry, ((ABL & 4) && v != 12345.678f) ? EGN_OOB : voff[r], pb * colpitch + nt * 64u, v);
+          egn_buf_store4(ry, ((ABL & 4) && v != 12345.678f) ? EGN_OOB : voff[r], pb * colpitch + nt * 64u, v);
           if (voff[r] != EGN_OOB) { st1[nt] += v; st2[nt] += v * v; }
         }
     if (a.stats != nullptr) {
@@ -918,7 +892,6 @@ __device__ __forceinline__ float wn_max(float a, float b) { float r; asm("v_max_
 __device__ __forceinline__ f32x4 wn_sub4(f32x4 a, f32x4 b) { return f32x4{wn_sub(a[0], b[0]), wn_sub(a[1], b[1]), wn_sub(a[2], b[2]), wn_sub(a[3], b[3])}; }
 __device__ __forceinline__ f32x4 wn_add4(f32x4 a, f32x4 b) { return f32x4{wn_add(a[0], b[0]), wn_add(a[1], b[1]), wn_add(a[2], b[2]), wn_add(a[3], b[3])}; }
 __device__ __forceinline__ f32x4 wn_fma4_s(float s, f32x4 b, f32x4 c) { return f32x4{wn_fma_s(s, b[0], c[0]), wn_fma_s(s, b[1], c[1]), wn_fma_s(s, b[2], c[2]), wn_fma_s(s, b[3], c[3])}; }
-__device__ __forceinline__ unsigned wn_udiv(unsigned x, unsigned magic) { return magic ? __umulhi(x, magic) : x; }
 
 // KQ = channel quads per K stage: 4 (a whole 16-channel chunk of the packed filter, one 140 KB block per CU) or
 // 2 (half a chunk: 8-channel stages, 68 KB of LDS -- TWO 4-wave blocks per CU, one wave of each on every SIMD.
@@ -979,16 +952,12 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
   const int nct = Co / CO_T;
   const int nchunk = a.nchunk;
 
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const unsigned long long uaddr = reinterpret_cast<unsigned long long>(a.w);
-  const u32x4 rxv = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu,
-                     (unsigned)((size_t)a.N * a.H * a.W * C * 4), 0x00020000u};
-  const u32x4 ruv = {(unsigned)uaddr, (unsigned)(uaddr >> 32) & 0xffffu,
-                     (unsigned)((size_t)nct * nchunk * UCH * 16), 0x00020000u};
+  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C * 4);
+  const u32x4 ruv = egn_rsrc(a.w, (size_t)nct * nchunk * UCH * 16);
   const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
   // ---- per-lane, item-independent: halo slot -> (image, hy, hx) and its byte offset relative to the tile's
   // origin pixel (n0, iy0, ix0); the tile origin is a wave-uniform base added per item
@@ -1041,12 +1010,12 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
   {                                                                              \
     const unsigned wi_ = (unsigned)__builtin_amdgcn_readfirstlane((int)(Wi));    \
     const unsigned x_ = wi_ & 7u, q_ = wi_ >> 3;                                 \
-    const unsigned qq_ = wn_udiv(q_, a.mg_nct);                                  \
+    const unsigned qq_ = egn_udiv_magic(q_, a.mg_nct);                           \
     TILE_ = (int)(qq_ * 8u + x_);                                                \
     CT_ = (int)(q_ - qq_ * (unsigned)nct);                                       \
-    const unsigned tb_ = wn_udiv((unsigned)TILE_, a.mg_txy);                     \
+    const unsigned tb_ = egn_udiv_magic((unsigned)TILE_, a.mg_txy);              \
     const unsigned r_ = (unsigned)TILE_ - tb_ * (unsigned)tiles_xy;              \
-    const unsigned ty_ = wn_udiv(r_, a.mg_tx);                                   \
+    const unsigned ty_ = egn_udiv_magic(r_, a.mg_tx);                            \
     TB_ = (int)tb_; TY_ = (int)ty_; TX_ = (int)(r_ - ty_ * (unsigned)a.tiles_x); \
   }
   // halo DMA byte offsets (chunk 0) of a tile: uniform base + per-lane relative offset; pad slots and
@@ -1068,14 +1037,14 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
   {                                                                                                  \
     if ((K) < IT) {                                                                                  \
       if ((K)*NTH + wave * 64 < SLOTS)                                                               \
-        wino_dma16(rxv, wino_lds_addr(sH + (P)*BUF + wave * 64) + (K)*NTH * 16, OFF[(K) < IT ? (K) : 0], \
+        egn_lds_dma16(rxv, egn_lds_addr(sH + (P)*BUF + wave * 64) + (K)*NTH * 16, OFF[(K) < IT ? (K) : 0], \
                    (unsigned)(CH) * (KQ * 16u));                                                     \
     } else if constexpr (KQ == EGN_CKQ) {                                                            \
-      wino_dma16(ruv, wino_lds_addr(sU + (P)*USL + wave * 64) + ((K)-IT) * NTH * 16, (unsigned)tid * 16u, \
+      egn_lds_dma16(ruv, egn_lds_addr(sU + (P)*USL + wave * 64) + ((K)-IT) * NTH * 16, (unsigned)tid * 16u, \
                  (unsigned)(((CT)*nchunk + (CH)) * USL) * 16u + ((K)-IT) * NTH * 16);                \
     } else {                                                                                         \
       const unsigned ch_ = (unsigned)(CH) / HS, hs_ = (unsigned)(CH) - ch_ * HS;                     \
-      wino_dma16(ruv, wino_lds_addr(sU + (P)*USL + wave * 64) + ((K)-IT) * NTH * 16, urel[(K) >= IT ? (K)-IT : 0], \
+      egn_lds_dma16(ruv, egn_lds_addr(sU + (P)*USL + wave * 64) + ((K)-IT) * NTH * 16, urel[(K) >= IT ? (K)-IT : 0], \
                  (((unsigned)(CT)*nchunk + ch_) * UCH + hs_ * (KQ * CO_T)) * 16u);                   \
     }                                                                                                \
   }
@@ -1237,7 +1206,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
 #pragma unroll
           for (int pb = 0; pb < 2; ++pb)
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) rv[r][pb][nt] = wino_load4(rr, ro, pb * colpitch + nt * 64u);
+            for (int nt = 0; nt < NT; ++nt) rv[r][pb][nt] = egn_buf_load4(rr, ro, pb * colpitch + nt * 64u);
         }
       }
       par ^= 1;
@@ -1301,7 +1270,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
 #pragma unroll
         for (int pb = 0; pb < 2; ++pb) {
           float v = fmaxf(keep[nt][r][pb] * sc[nt] + sh[nt] + rv[r][pb][nt], act_lo);
-          wino_store4(ry, voff[r], pb * colpitch + nt * 64u, v);
+          egn_buf_store4(ry, voff[r], pb * colpitch + nt * 64u, v);
           if (a.stats != nullptr && voff[r] != EGN_OOB) { st1[nt] += v; st2[nt] += v * v; }
         }
     if (a.stats != nullptr) {
@@ -1353,20 +1322,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
 template <int TH, int TW, int TNB, int ABL = 0>
 static int wino_launch(const ConvArgs& a, size_t lds, hipStream_t stream) {
   static bool raised[EGN_MAX_DEVICES];
-  static int cus = 0;
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_kernel<TH, TW, TNB, ABL>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-  }
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-    cus &= ~7;  // whole XCD rounds
-    if (cus <= 0) cus = 8;
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(&conv_wino_kernel<TH, TW, TNB, ABL>, EGN_BIG_LDS_BYTES, raised));
+  int cus = egn_device_cus() & ~7;  // whole XCD rounds
+  if (cus <= 0) cus = 8;
   const int ntile = a.tiles_x * a.tiles_y * ((a.N + TNB - 1) / TNB);
   const int nwork = ((ntile + 7) / 8) * 8 * (a.Cout / WN_CO);
   const int grid = nwork < cus ? nwork : cus;
@@ -1379,29 +1337,16 @@ static int wino_launch(const ConvArgs& a, size_t lds, hipStream_t stream) {
 // (ct = (w >> 3) % nct and w advances by the grid size) -- its BatchNorm partial row covers one co-tile
 static int wino8_grid(const ConvArgs& a, int tnb, int blocks_per_cu = 1) {
   const int cot = egn_wino_cot(a.Cout);
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
   const int nct = a.Cout / (cot ? cot : 48);
   const int ntile = a.tiles_x * a.tiles_y * ((a.N + tnb - 1) / tnb);
   const int nwork = ((ntile + 7) / 8) * 8 * nct;
-  int cap = blocks_per_cu * cus / (8 * nct) * (8 * nct);
-  if (cap <= 0) cap = 8 * nct;
-  return nwork < cap ? nwork : cap;
+  return egn_persistent_grid(nwork, 8 * nct, blocks_per_cu);
 }
 
 template <int TH, int TW, int TNB, int ABL, int NW, int NT>
 static int wino8_launch_nt(const ConvArgs& a, size_t lds, hipStream_t stream) {
   static bool raised[EGN_MAX_DEVICES];
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino8_kernel<TH, TW, TNB, ABL, NW, NT>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(&conv_wino8_kernel<TH, TW, TNB, ABL, NW, NT>, EGN_BIG_LDS_BYTES, raised));
   const int grid = wino8_grid(a, TNB);
   hipLaunchKernelGGL((conv_wino8_kernel<TH, TW, TNB, ABL, NW, NT>), dim3(grid), dim3(64 * NW), lds, stream, a);
   return (int)hipGetLastError();
@@ -1467,7 +1412,7 @@ template <int CLK = 0>
 __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
   extern __shared__ float4 smem[];
   float* sm = reinterpret_cast<float*>(smem);
-  const unsigned lds0 = wino_lds_addr(smem);
+  const unsigned lds0 = egn_lds_addr(smem);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1478,13 +1423,11 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
   const int C = a.Cin, Co = a.Cout;
   const int nct = Co / 48;
   const int nsteps = C / 4;
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const unsigned long long uaddr = reinterpret_cast<unsigned long long>(a.w);
-  const u32x4 rxv = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu, (unsigned)((size_t)a.N * a.H * a.W * C * 4), 0x00020000u};
-  const u32x4 ruv = {(unsigned)uaddr, (unsigned)(uaddr >> 32) & 0xffffu, (unsigned)((size_t)nct * nsteps * W43_UF * 4), 0x00020000u};
+  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C * 4);
+  const u32x4 ruv = egn_rsrc(a.w, (size_t)nct * nsteps * W43_UF * 4);
   const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
+  const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
   // ---- halo pieces of this wave: k = 0 -> p = wave (all 12 are halo pieces), k = 1 -> p = 12 + wave (waves 0, 1) ----
   int hyx[2], hrel[2], hmt[2];
@@ -1542,15 +1485,15 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
   {                                                                              \
     const unsigned wi_ = (unsigned)__builtin_amdgcn_readfirstlane((int)(Wi));    \
     const unsigned x_ = wi_ & 7u, q_ = wi_ >> 3;                                 \
-    const unsigned qq_ = wn_udiv(q_, a.mg_nct);                                  \
+    const unsigned qq_ = egn_udiv_magic(q_, a.mg_nct);                           \
     PAIR_ = (int)(qq_ * 8u + x_);                                                \
     CT_ = (int)(q_ - qq_ * (unsigned)nct);                                       \
   }
 #define W43_TILE(TILE_, N_, TY_, TX_)                                            \
   {                                                                              \
-    const unsigned tbq_ = wn_udiv((unsigned)(TILE_), a.mg_txy);                  \
+    const unsigned tbq_ = egn_udiv_magic((unsigned)(TILE_), a.mg_txy);           \
     const unsigned rq_ = (unsigned)(TILE_)-tbq_ * (unsigned)tiles_xy;            \
-    const unsigned tyq_ = wn_udiv(rq_, a.mg_tx);                                 \
+    const unsigned tyq_ = egn_udiv_magic(rq_, a.mg_tx);                          \
     N_ = (int)tbq_; TY_ = (int)tyq_; TX_ = (int)(rq_ - tyq_ * (unsigned)a.tiles_x); \
   }
 // halo DMA byte offsets (K step 0) of this wave's halo pieces for tile pair PAIR_
@@ -1572,9 +1515,9 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
   {                                                                                                          \
     const int p_ = (K)*W43_NW + wave;                                                                        \
     if (p_ < W43_MT * W43_HP) {                                                                              \
-      wino_dma16(rxv, lds0 + (unsigned)((P)*W43_STAGE * 4 + p_ * 1024), OFF[(K) < 2 ? (K) : 0], (unsigned)(STEP)*16u); \
+      egn_lds_dma16(rxv, lds0 + (unsigned)((P)*W43_STAGE * 4 + p_ * 1024), OFF[(K) < 2 ? (K) : 0], (unsigned)(STEP)*16u); \
     } else if (p_ < W43_NP) {                                                                                \
-      wino_dma16(ruv, lds0 + (unsigned)((P)*W43_STAGE * 4 + W43_MT * W43_HF * 4 + (p_ - W43_MT * W43_HP) * 1024), \
+      egn_lds_dma16(ruv, lds0 + (unsigned)((P)*W43_STAGE * 4 + W43_MT * W43_HF * 4 + (p_ - W43_MT * W43_HP) * 1024), \
                  (unsigned)lane * 16u, (unsigned)((((CT)*nsteps + (STEP)) * W43_UP + (p_ - W43_MT * W43_HP)) * 1024)); \
     }                                                                                                        \
   }
@@ -1723,7 +1666,7 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
 #pragma unroll
       for (int b = 0; b < 4; ++b)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) rv[0][b][r] = wino_load4(rr, has_res ? vbase : EGN_OOB, (unsigned)(4 * r + b) * colpitch);
+        for (int r = 0; r < 4; ++r) rv[0][b][r] = egn_buf_load4(rr, has_res ? vbase : EGN_OOB, (unsigned)(4 * r + b) * colpitch);
     }
 #pragma unroll
     for (int nt = 0; nt < 3; ++nt) {
@@ -1743,7 +1686,7 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
           for (int b = 0; b < 4; ++b)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-              rv[(nt + 1) & 1][b][r] = wino_load4(rr, has_res ? vbase : EGN_OOB, (unsigned)(4 * r + b) * colpitch + (nt + 1) * 64u);
+              rv[(nt + 1) & 1][b][r] = egn_buf_load4(rr, has_res ? vbase : EGN_OOB, (unsigned)(4 * r + b) * colpitch + (nt + 1) * 64u);
         }
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
@@ -1759,7 +1702,7 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float v = fmaxf(y[r] * sc[nt] + sh[nt] + rv[nt & 1][b][r], act_lo);
-            wino_store4(ry, vbase, (unsigned)(4 * r + b) * colpitch + nt * 64u, v);
+            egn_buf_store4(ry, vbase, (unsigned)(4 * r + b) * colpitch + nt * 64u, v);
           }
         }
       }
@@ -1784,15 +1727,10 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
 
 size_t egn_conv_wino43_lds_bytes(int clk) { return (size_t)W43_RING * W43_STAGE * 4 + (clk ? W43_NW * 48 * 8 : 0); }
 
-static unsigned wino_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
-
 template <int TH, int TW, int TNB, int NW, int NT, int CLK = 0, int KQ = EGN_CKQ>
 static int wino9_launch_nt(ConvArgs a, size_t lds, hipStream_t stream) {
   static bool raised[EGN_MAX_DEVICES];
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino9_kernel<TH, TW, TNB, NW, NT, CLK, KQ>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(&conv_wino9_kernel<TH, TW, TNB, NW, NT, CLK, KQ>, EGN_BIG_LDS_BYTES, raised));
   // the kernel divides its item / tile indices by nct, tiles_x * tiles_y and tiles_x with ONE multiply-high by
   // ceil(2^32 / d): exact while dividend * d < 2^32.  Dividends stay below (tiles + 8) * nct; shapes beyond that bound
   // (far outside the 2 GB tensor guards for any HRNet map, but a legal call) are refused, not mis-decoded
@@ -1802,9 +1740,9 @@ static int wino9_launch_nt(ConvArgs a, size_t lds, hipStream_t stream) {
     if (ntile_ * nct_ * nct_ >= 0x100000000ull || ntile_ * (unsigned long long)(a.tiles_x * a.tiles_y) >= 0x100000000ull)
       return EGN_E_BADARG;
   }
-  a.mg_nct = wino_magic(a.Cout / (16 * NT));
-  a.mg_txy = wino_magic(a.tiles_x * a.tiles_y);
-  a.mg_tx = wino_magic(a.tiles_x);
+  a.mg_nct = egn_magic_u32(a.Cout / (16 * NT));
+  a.mg_txy = egn_magic_u32(a.tiles_x * a.tiles_y);
+  a.mg_tx = egn_magic_u32(a.tiles_x);
   const int grid = wino8_grid(a, TNB, KQ == EGN_CKQ ? 1 : 2);     // half-chunk stages: two blocks per CU
   hipLaunchKernelGGL((conv_wino9_kernel<TH, TW, TNB, NW, NT, CLK, KQ>), dim3(grid), dim3(64 * NW), lds, stream, a);
   return (int)hipGetLastError();
@@ -1819,27 +1757,15 @@ static int wino9_launch(const ConvArgs& a, size_t lds, hipStream_t stream) {
 template <int CLK>
 static int wino43_launch(ConvArgs a, size_t lds, hipStream_t stream) {
   static bool raised[EGN_MAX_DEVICES];
-  static int cus = 0;
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino43_kernel<CLK>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512));
-  }
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(&conv_wino43_kernel<CLK>, EGN_BIG_LDS_BYTES, raised));
   const int nct = a.Cout / 48;
-  a.mg_nct = wino_magic(nct);
-  a.mg_txy = wino_magic(a.tiles_x * a.tiles_y);
-  a.mg_tx = wino_magic(a.tiles_x);
+  a.mg_nct = egn_magic_u32(nct);
+  a.mg_txy = egn_magic_u32(a.tiles_x * a.tiles_y);
+  a.mg_tx = egn_magic_u32(a.tiles_x);
   const int ntile = a.tiles_x * a.tiles_y * a.N;
   const int npair = (ntile + 1) / 2;
   const int nwork = ((npair + 7) / 8) * 8 * nct;
-  int cap = cus / (8 * nct) * (8 * nct);              // one 126 KB block per CU, whole XCD rounds
-  if (cap <= 0) cap = 8 * nct;
-  const int grid = nwork < cap ? nwork : cap;
+  const int grid = egn_persistent_grid(nwork, 8 * nct);   // one 126 KB block per CU, whole XCD rounds
   hipLaunchKernelGGL((conv_wino43_kernel<CLK>), dim3(grid), dim3(W43_NTH), lds, stream, a);
   return (int)hipGetLastError();
 }

@@ -1,15 +1,14 @@
 // conv_wino4.h -- device helpers shared by the F(4x4,3x3) kernel bodies: conv_wino4.hip (12 waves: 16 x 32 / 16 x 16 regions,
 // four 8 x 8 images; one 48-channel co-tile per item) and conv_wino4w.hip (round 6: 96 output channels per item).
 // Geometry constants of the bank-conflict-free halo order, the raw-ISA load / LDS wrappers whose waits the kernels
-// place themselves, the 1-D transforms and the input transform of a wave's third (V = B^T d B).
+// place themselves, the item order with the launchers' item set-up (w4_item_setup), the 1-D transforms and the input
+// transform of a wave's third (V = B^T d B).
 // Reference: the 3x3 stride-1 convolutions of libs/model/heatmapModel/hrnet.py:49-76.
 #pragma once
 #include <stdlib.h>
 
 #include "conv_common.h"
 #include "wino4_pack.h"
-
-typedef __attribute__((address_space(3))) void* lds_ptr_w4_t;
 
 namespace {
 constexpr int W4_NW = 12, W4_NTH = 64 * W4_NW;
@@ -72,7 +71,7 @@ static_assert(W4G<0>::QPP * W4G<0>::RH * W4G<0>::RWP <= W4G<0>::NP * W4_NW * 64 
                   W4G<1>::QPP * W4G<1>::RH * W4G<1>::RWP <= W4G<1>::NP * W4_NW * 64 &&
                   W4G<2>::QPP * W4G<2>::NIMG * W4G<2>::RH * W4G<2>::RWP <= W4G<2>::NP * W4_NW * 64,
               "the load pieces of the waves cover the halo");
-static_assert(W4G<2>::imgbase(3) + W4G<2>::RH * W4G<2>::XD <= W4G<2>::PLANE && w4_lds_bytes<2>() + 12 * 96 * 8 <= 160 * 1024 - 512,
+static_assert(W4G<2>::imgbase(3) + W4G<2>::RH * W4G<2>::XD <= W4G<2>::PLANE && w4_lds_bytes<2>() + 12 * 96 * 8 <= EGN_BIG_LDS_BYTES,
               "GEO 2: four images fit a plane, the buffers fit the CU");
 constexpr int W4_UKG = W4_NW * 3 * 64 * 4;            // filter floats of one (co-tile, stage, k-group): 9216 (9 of 12 used)
 static_assert(W4_UKG == W4P_UKG && W4_CO == W4P_CO, "wino4_pack.h packs this kernel's layout");
@@ -140,7 +139,6 @@ __device__ __forceinline__ float w4_xrd(unsigned xr0, unsigned xr1) {
   if constexpr (PT < 18) return w4_lds<PT * 3072>(xr0);
   else return w4_lds<(PT - 18) * 3072>(xr1);
 }
-__device__ __forceinline__ unsigned w4_udiv(unsigned x, unsigned magic) { return magic ? __umulhi(x, magic) : x; }
 
 // Item order: what the XCD of a block (block index mod 8 -- blocks w, w + 8, ... stay on one XCD; a matter of speed only)
 // owns.  The transformed filter is 36 x 4 bytes per (ci, co): 21 MB at 384 -> 384 channels, 5.3 MB at 192 -> 192 -- more
@@ -166,6 +164,20 @@ __host__ __device__ inline int w4_item_count(int mode, int nreg, int nct, int ks
   if (mode == 2) return nreg * nct * ks;
   if (mode == 1) return 8 * ((nreg * ks + 8 / nct - 1) / (8 / nct));
   return ((nreg + 7) >> 3) * nct * ks * 8;
+}
+// Host: the item set-up of a launcher (a: planned) for nreg regions x nct co-tiles (wide items: co-tile pairs) x ks K
+// halves.  Sets the multipliers of the kernels' item index divisions -- one multiply-high each, exact while x * d < 2^32
+// (x = the dividend's range) -- and returns the item count, or EGN_E_BADARG where a division would not be exact.
+static inline int w4_item_setup(ConvArgs& a, int nct, int ks, int nreg) {
+  const int nck = nct * ks, imode = w4_item_mode(nct);
+  const int nwork = w4_item_count(imode, nreg, nct, ks);
+  if ((unsigned long long)nwork * (unsigned)(8 * nck) >= 0x100000000ull ||
+      (unsigned long long)(nreg + 8) * (unsigned)(a.tiles_x * a.tiles_y) >= 0x100000000ull)
+    return EGN_E_BADARG;
+  a.mg_nct = imode == 1 ? 0u : egn_magic_u32(imode == 2 ? nct / 8 : nck);
+  a.mg_txy = egn_magic_u32(a.tiles_x * a.tiles_y);
+  a.mg_tx = egn_magic_u32(a.tiles_x);
+  return nwork;
 }
 
 // 1-D input transform of six values (12 instructions)

@@ -65,7 +65,7 @@ template <int ABL, int GEO, int KS = 1, bool ST = false>
 __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
   typedef W4G<GEO> Q;
   extern __shared__ float4 w4_smem[];
-  const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)(lds_ptr_w4_t)w4_smem;
+  const unsigned lds0 = egn_lds_addr(w4_smem);
   const float* smf = reinterpret_cast<const float*>(w4_smem);
 
   const int tid = threadIdx.x;
@@ -79,16 +79,12 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
   const int nct = Co / W4_CO;
   const int S = C / (4 * Q::QPP * KS);     // stages of 8 (GEO 0) / 16 (GEO 1, 2) channels of an item (KS: its half of Cin)
 
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const unsigned long long uaddr = reinterpret_cast<unsigned long long>(a.w);
-  const u32x4 rxv = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu, (unsigned)((size_t)a.N * a.H * a.W * C * 4),
-                     0x00020000u};
-  const u32x4 ruv = {(unsigned)uaddr, (unsigned)(uaddr >> 32) & 0xffffu, (unsigned)((size_t)nct * (C >> 2) * W4_UKG * 4),
-                     0x00020000u};
+  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C * 4);
+  const u32x4 ruv = egn_rsrc(a.w, (size_t)nct * (C >> 2) * W4_UKG * 4);
   const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
   // ---- halo loads: this wave's pieces wave, wave + 12 (, wave + 24); element e -> (pixel = e / QPP, channel quad e % QPP)
   int hyx[Q::NP];
@@ -171,7 +167,7 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
     const unsigned wi = (unsigned)__builtin_amdgcn_readfirstlane(w);
     const unsigned xq = wi & 7u, q_ = wi >> 3;
     // (mg_nct: the multiplier of nct * KS (mode 0) or of nct / 8 (mode 2); KS is a power of two)
-    const unsigned qq = w4_udiv(q_, a.mg_nct);
+    const unsigned qq = egn_udiv_magic(q_, a.mg_nct);
     int reg, ct, ks;
     if (imode == 0) {
       const int cs_ = (int)(q_ - qq * (unsigned)(nct * KS));
@@ -185,9 +181,9 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
     }
     if (reg >= nreg) continue;                         // (uniform) padding of the last round of the XCDs
     ct_blk = ct;
-    const unsigned n_ = w4_udiv((unsigned)reg, a.mg_txy);
+    const unsigned n_ = egn_udiv_magic((unsigned)reg, a.mg_txy);
     const unsigned r_ = (unsigned)reg - n_ * (unsigned)regs_xy;
-    const unsigned ry_ = w4_udiv(r_, a.mg_tx);
+    const unsigned ry_ = egn_udiv_magic(r_, a.mg_tx);
     // (GEO 2: the region is the four images n .. n + 3; images past N load zeros and store nothing)
     const int n = (int)n_ * Q::NIMG, y0 = (int)ry_ * Q::RGH, x0 = (int)(r_ - ry_ * (unsigned)regs_x) * Q::RGW;
 
@@ -639,9 +635,7 @@ bool egn_conv_wino4_applies(const ConvArgs& a, Wino4Kernel k) {
   }
   // (K split: whole 16-channel stages per half; the residual is read after y was zeroed -- it must be another buffer)
   if (w4_ksplit(k) && (a.Cin % 32 || (a.res && a.res == a.y))) return false;
-  return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin % 16 == 0 && a.cs_in == a.Cin &&
-         a.Cout % W4_CO == 0 && a.cs_out == a.Cout && !a.out_nchw && map_ok && !(a.act & EGN_ACT_RES_AFTER) &&
-         ((a.act & EGN_ACT_MASK) == EGN_ACT_NONE || (a.act & EGN_ACT_MASK) == EGN_ACT_RELU);
+  return egn_plain_3x3_s1(a) && a.Cin % 16 == 0 && a.Cout % W4_CO == 0 && map_ok;
 }
 // ticket words a K-split launch wants (zeroed once; every launch leaves them zero): the error word (index 0) + one per
 // (region, co-tile); 0 = none
@@ -671,25 +665,9 @@ extern "C" long long egn_wino4_weight_floats(int cout, int cin) {
   return (long long)(cout / W4_CO) * (cin / 8) * 2 * W4_UKG;
 }
 
-static unsigned w4_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
-
-static int w4_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
 // persistent grid: one block per CU in whole XCD rounds of (co-tile, K half) -- a multiple of 8 nct KS, so that the
 // items w, w + grid, ... of a block share the co-tile (and the K half): its BatchNorm partial row covers one co-tile
-static int w4_grid(int nwork, int nck) {
-  int cap = w4_cus() / (8 * nck) * (8 * nck);
-  if (cap <= 0) cap = 8 * nck;
-  return nwork < cap ? nwork : cap;
-}
+static int w4_grid(int nwork, int nck) { return egn_persistent_grid(nwork, 8 * nck); }
 // rows of the BatchNorm partial table a launch with ConvArgs::stats writes (a: planned): one per block; 0 = none
 int egn_conv_wino4_stats_rows(const ConvArgs& a, Wino4Kernel k) {
   switch (k) {
@@ -716,22 +694,12 @@ static int wino4_launch(ConvArgs a, size_t lds, hipStream_t stream) {
   void (*kern)(ConvArgs);
   if constexpr (ST) kern = &conv_wino4s_kernel<GEO, KS>;
   else kern = GEO == 2 ? &conv_wino4c_kernel<ABL, KS> : (GEO == 0 ? &conv_wino4_kernel<ABL> : (KS > 1 ? &conv_wino4bk_kernel<ABL> : &conv_wino4b_kernel<ABL>));
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      160 * 1024 - 512));
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(kern, EGN_BIG_LDS_BYTES, raised));
   if (ST && KS > 1 && !a.tickets) return EGN_E_BADARG;   // (the three-launch form applies the epilogue in another kernel)
   const int nct = a.Cout / W4_CO, nck = nct * KS;
   const int nreg = a.tiles_x * a.tiles_y * ((a.N + W4G<GEO>::NIMG - 1) / W4G<GEO>::NIMG);
-  const int imode = w4_item_mode(nct);
-  const int nwork = w4_item_count(imode, nreg, nct, KS);
-  // the item index divisions run as one multiply-high each: exact while x * d < 2^32 (x = the dividend's range)
-  if ((unsigned long long)nwork * (unsigned)(8 * nck) >= 0x100000000ull ||
-      (unsigned long long)(nreg + 8) * (unsigned)(a.tiles_x * a.tiles_y) >= 0x100000000ull)
-    return EGN_E_BADARG;
-  a.mg_nct = imode == 1 ? 0u : w4_magic(imode == 2 ? nct / 8 : nck);
-  a.mg_txy = w4_magic(a.tiles_x * a.tiles_y);
-  a.mg_tx = w4_magic(a.tiles_x);
+  const int nwork = w4_item_setup(a, nct, KS, nreg);
+  if (nwork < 0) return nwork;
   const int grid = w4_grid(nwork, nck);               // one block per CU, whole XCD rounds
   if (KS > 1 && !a.tickets) {
     const size_t n = (size_t)a.N * a.Ho * a.Wo * a.Cout;
@@ -838,22 +806,19 @@ int egn_conv_pair_plan(const ConvArgs* a, const ConvArgs* b, int cus, int* block
 // cus <= 0: the device's CU count (a test may cap the grid to make the persistent loops iterate)
 int egn_conv_launch_wino4_pair(ConvArgs a, ConvArgs b, int cus, hipStream_t stream) {
   int ga = 0, gb = 0;
-  const int rc = egn_conv_pair_plan(&a, &b, cus > 0 ? cus : w4_cus(), &ga, &gb);
+  const int rc = egn_conv_pair_plan(&a, &b, cus > 0 ? cus : egn_device_cus(), &ga, &gb);
   if (rc) return rc;
   static bool raised[EGN_MAX_DEVICES];
   void (*kern)(ConvArgs, ConvArgs, int) = &conv_wino4_pair_kernel;
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      160 * 1024 - 512));
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(kern, EGN_BIG_LDS_BYTES, raised));
   const int ncp = a.Cout / (2 * W4_CO), nct = b.Cout / W4_CO;
   const int ma = w4_item_mode(ncp), mb = w4_item_mode(nct);
-  a.mg_nct = ma == 1 ? 0u : w4_magic(ma == 2 ? ncp / 8 : ncp);
-  a.mg_txy = w4_magic(a.tiles_x * a.tiles_y);
-  a.mg_tx = w4_magic(a.tiles_x);
-  b.mg_nct = mb == 1 ? 0u : w4_magic(mb == 2 ? nct / 8 : nct);
-  b.mg_txy = w4_magic(b.tiles_x * b.tiles_y);
-  b.mg_tx = w4_magic(b.tiles_x);
+  a.mg_nct = ma == 1 ? 0u : egn_magic_u32(ma == 2 ? ncp / 8 : ncp);
+  a.mg_txy = egn_magic_u32(a.tiles_x * a.tiles_y);
+  a.mg_tx = egn_magic_u32(a.tiles_x);
+  b.mg_nct = mb == 1 ? 0u : egn_magic_u32(mb == 2 ? nct / 8 : nct);
+  b.mg_txy = egn_magic_u32(b.tiles_x * b.tiles_y);
+  b.mg_tx = egn_magic_u32(b.tiles_x);
   const size_t lds = egn_conv_wino4_lds_bytes(Wino4c);      // the larger of the two bodies' (GEO 2), + the stamp area
   hipLaunchKernelGGL(kern, dim3(ga + gb), dim3(W4_NTH), lds, stream, a, b, ga);
   return (int)hipGetLastError();

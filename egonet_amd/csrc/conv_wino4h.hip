@@ -104,7 +104,7 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
   const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = DUAL ? (wave_all >= W4H_NW ? 1 : 0) : 0;
   const int wave = wave_all - W4H_NW * half;
-  const unsigned lds_wg = (unsigned)(__UINTPTR_TYPE__)(lds_ptr_w4_t)w4_smem;
+  const unsigned lds_wg = egn_lds_addr(w4_smem);
   const unsigned lds0 = lds_wg + (unsigned)(half * W4H_LDS);
   const float* smf = reinterpret_cast<const float*>(w4_smem) + half * (W4H_LDS / 4);
   // the halves' barrier counters (monotonic; zeroed below) behind the two LDS images
@@ -123,16 +123,12 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
   const int nct = Co / W4_CO;
   const int S = C / 8;                     // stages of 8 channels
 
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const unsigned long long uaddr = reinterpret_cast<unsigned long long>(a.w);
-  const u32x4 rxv = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu, (unsigned)((size_t)a.N * a.H * a.W * C * 4),
-                     0x00020000u};
-  const u32x4 ruv = {(unsigned)uaddr, (unsigned)(uaddr >> 32) & 0xffffu, (unsigned)((size_t)nct * (C >> 2) * W4_UKG * 4),
-                     0x00020000u};
+  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C * 4);
+  const u32x4 ruv = egn_rsrc(a.w, (size_t)nct * (C >> 2) * W4_UKG * 4);
   const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
   // ---- halo loads: pieces wave, wave + 6; element e -> (pixel e / 2, channel quad e % 2).  Every lane stores to the
   // NATURAL slot of its element: the padded columns 18 / 19 fall on slots (x & 3) in {2, 3}, x >> 2 = 4 and the rows 18 / 19
@@ -189,7 +185,7 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
   for (int w = blockIdx.x + half * gsz; w < nwork; w += (DUAL ? 2 : 1) * gsz) {
     const unsigned wi = (unsigned)__builtin_amdgcn_readfirstlane(w);
     const unsigned xq = wi & 7u, q_ = wi >> 3;
-    const unsigned qq = w4_udiv(q_, a.mg_nct);
+    const unsigned qq = egn_udiv_magic(q_, a.mg_nct);
     int reg, ct;
     if (imode == 0) {
       ct = (int)(q_ - qq * (unsigned)nct);
@@ -201,9 +197,9 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
       reg = (int)qq; ct = (int)((q_ - qq * ((unsigned)nct >> 3)) * 8u + xq);
     }
     if (reg >= nreg) continue;
-    const unsigned n_ = w4_udiv((unsigned)reg, a.mg_txy);
+    const unsigned n_ = egn_udiv_magic((unsigned)reg, a.mg_txy);
     const unsigned r_ = (unsigned)reg - n_ * (unsigned)regs_xy;
-    const unsigned ry_ = w4_udiv(r_, a.mg_tx);
+    const unsigned ry_ = egn_udiv_magic(r_, a.mg_tx);
     const int n = (int)n_, y0 = (int)ry_ * Q::RGH, x0 = (int)(r_ - ry_ * (unsigned)regs_x) * Q::RGW;
 
     // halo offsets of the item: recomputed from the lane id per item (not kept over the K loop: registers)
@@ -445,16 +441,12 @@ template <int ABL>
 __global__ __launch_bounds__(2 * W4H_NTH, 1) void conv_wino4d_kernel(ConvArgs a) { w4h_body<ABL, true>(a); }
 
 bool egn_conv_wino4h_applies(const ConvArgs& a) {
-  return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin % 16 == 0 && a.cs_in == a.Cin &&
-         a.Cout % W4_CO == 0 && a.cs_out == a.Cout && !a.out_nchw && a.Ho % 16 == 0 && a.Wo % 16 == 0 &&
-         !(a.act & EGN_ACT_RES_AFTER) &&
-         ((a.act & EGN_ACT_MASK) == EGN_ACT_NONE || (a.act & EGN_ACT_MASK) == EGN_ACT_RELU);
+  return egn_plain_3x3_s1(a) && a.Cin % 16 == 0 && a.Cout % W4_CO == 0 && a.Ho % 16 == 0 && a.Wo % 16 == 0;
 }
 // (+ the stamp area of the ABL & 64 build); dual: both halves' images + their barrier counters
 size_t egn_conv_wino4h_lds_bytes(int dual) { return dual ? 2 * W4H_LDS + 64 + 12 * 128 * 8 : W4H_LDS + 6 * 128 * 8; }
 
 #ifdef EGN_PROBES
-static unsigned w4h_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 // start delay of a CU's second block in units of 64 cycles (EGN_W4H_SKEW overrides: probes)
 static int w4h_default_skew() {
   static int skew = -1;
@@ -472,34 +464,15 @@ template <int ABL, bool DUAL>
 static int wino4h_launch(ConvArgs a, size_t lds, hipStream_t stream) {
   static bool raised[EGN_MAX_DEVICES];
   void (*kern)(ConvArgs) = DUAL ? &conv_wino4d_kernel<ABL> : &conv_wino4h_kernel<ABL>;
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      DUAL ? 160 * 1024 - 512 : 80 * 1024));
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(kern, DUAL ? EGN_BIG_LDS_BYTES : 80 * 1024, raised));
   const int nct = a.Cout / W4_CO;
-  const int nreg = a.tiles_x * a.tiles_y * a.N;
-  const int imode = w4_item_mode(nct);
-  const int nwork = w4_item_count(imode, nreg, nct, 1);
-  if ((unsigned long long)nwork * (unsigned)(8 * nct) >= 0x100000000ull ||
-      (unsigned long long)(nreg + 8) * (unsigned)(a.tiles_x * a.tiles_y) >= 0x100000000ull)
-    return EGN_E_BADARG;
-  a.mg_nct = imode == 1 ? 0u : w4h_magic(imode == 2 ? nct / 8 : nct);
-  a.mg_txy = w4h_magic(a.tiles_x * a.tiles_y);
-  a.mg_tx = w4h_magic(a.tiles_x);
+  const int nwork = w4_item_setup(a, nct, 1, a.tiles_x * a.tiles_y * a.N);
+  if (nwork < 0) return nwork;
   a.spix_off = w4h_default_skew();
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  // blocks per CU: two 6-wave workgroups, or one 12-wave workgroup with two halves; whole XCD rounds of co-tiles
-  int cap = (DUAL ? 1 : 2) * cus / (8 * nct) * (8 * nct);
-  if (cap <= 0) cap = 8 * nct;
   // (DUAL: a workgroup's halves take items w and w + grid: half as many workgroups as items fill both halves)
   const int want = DUAL ? (nwork / 2 + 8 * nct - 1) / (8 * nct) * (8 * nct) : nwork;
-  const int grid = want < cap ? want : cap;
+  // blocks per CU: two 6-wave workgroups, or one 12-wave workgroup with two halves; whole XCD rounds of co-tiles
+  const int grid = egn_persistent_grid(want, 8 * nct, DUAL ? 1 : 2);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(DUAL ? 2 * W4H_NTH : W4H_NTH), lds, stream, a);
   return (int)hipGetLastError();
 }

@@ -34,7 +34,7 @@ constexpr unsigned W4R_KGB = W4_UKG * 4u;                 // filter bytes of one
 constexpr int W4R_XWAVE = 12 * 1024;                     // exchange bytes of a writer wave: [nt 3][b 4][lane 64] float4
 constexpr int W4R_XBYTES = 12 * W4R_XWAVE;               // 147 456 B
 constexpr int W4R_LDS = W4R_XBYTES > w4_lds_bytes<0>() ? W4R_XBYTES : w4_lds_bytes<0>();
-static_assert(W4R_LDS + 12 * 96 * 8 <= 160 * 1024 - 512, "the one-round exchange (and the stamp area) fit the CU");
+static_assert(W4R_LDS + 12 * 96 * 8 <= EGN_BIG_LDS_BYTES, "the one-round exchange (and the stamp area) fit the CU");
 static_assert(5 * W4R_XWAVE + 3 * 1024 < 65536, "ds_read_b32 immediates of a pass");
 
 struct W4RB {
@@ -84,7 +84,7 @@ template <int ABL>
 __device__ __forceinline__ void w4r_body(const ConvArgs& a) {
   typedef QR Q;
   extern __shared__ float4 w4_smem[];
-  const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)(lds_ptr_w4_t)w4_smem;
+  const unsigned lds0 = egn_lds_addr(w4_smem);
   const float* smf = reinterpret_cast<const float*>(w4_smem);
 
   const int tid = threadIdx.x;
@@ -100,16 +100,12 @@ __device__ __forceinline__ void w4r_body(const ConvArgs& a) {
   const int nct = Co / W4_CO;
   const int S = C / 8;                     // stages of 8 channels
 
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const unsigned long long uaddr = reinterpret_cast<unsigned long long>(a.w);
-  const u32x4 rxv = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu, (unsigned)((size_t)a.N * a.H * a.W * C * 4),
-                     0x00020000u};
-  const u32x4 ruv = {(unsigned)uaddr, (unsigned)(uaddr >> 32) & 0xffffu, (unsigned)((size_t)nct * (C >> 2) * W4_UKG * 4),
-                     0x00020000u};
+  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C * 4);
+  const u32x4 ruv = egn_rsrc(a.w, (size_t)nct * (C >> 2) * W4_UKG * 4);
   const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
   // ---- halo loads (conv_wino4.hip, geometry 0): pieces wave, wave + 12; element e -> (pixel e / 2, channel quad e % 2);
   // the 96 elements past the halo (rows 18 / 19) park their zeros in the unused tail of the buffer
@@ -154,7 +150,7 @@ __device__ __forceinline__ void w4r_body(const ConvArgs& a) {
   for (int w = blockIdx.x; w < nwork; w += gsz) {
     const unsigned wi = (unsigned)__builtin_amdgcn_readfirstlane(w);
     const unsigned xq = wi & 7u, q_ = wi >> 3;
-    const unsigned qq = w4_udiv(q_, a.mg_nct);
+    const unsigned qq = egn_udiv_magic(q_, a.mg_nct);
     int reg, ct;
     if (imode == 0) {
       ct = (int)(q_ - qq * (unsigned)nct);
@@ -166,9 +162,9 @@ __device__ __forceinline__ void w4r_body(const ConvArgs& a) {
       reg = (int)qq; ct = (int)((q_ - qq * ((unsigned)nct >> 3)) * 8u + xq);
     }
     if (reg >= nreg) continue;
-    const unsigned n_ = w4_udiv((unsigned)reg, a.mg_txy);
+    const unsigned n_ = egn_udiv_magic((unsigned)reg, a.mg_txy);
     const unsigned r_ = (unsigned)reg - n_ * (unsigned)regs_xy;
-    const unsigned ry_ = w4_udiv(r_, a.mg_tx);
+    const unsigned ry_ = egn_udiv_magic(r_, a.mg_tx);
     const int n = (int)n_, y0 = (int)ry_ * Q::RGH, x0 = (int)(r_ - ry_ * (unsigned)regs_x) * Q::RGW;
 
     // halo offsets of the item: recomputed from the lane id per item (not kept over the K loop: registers)
@@ -394,44 +390,20 @@ template <int ABL>
 __global__ __launch_bounds__(W4_NTH, 1) void conv_wino4r_kernel(ConvArgs a) { w4r_body<ABL>(a); }
 
 bool egn_conv_wino4r_applies(const ConvArgs& a) {
-  return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin % 16 == 0 && a.cs_in == a.Cin &&
-         a.Cout % W4_CO == 0 && a.cs_out == a.Cout && !a.out_nchw && a.Ho % 16 == 0 && a.Wo % 32 == 0 &&
-         !(a.act & EGN_ACT_RES_AFTER) &&
-         ((a.act & EGN_ACT_MASK) == EGN_ACT_NONE || (a.act & EGN_ACT_MASK) == EGN_ACT_RELU);
+  return egn_plain_3x3_s1(a) && a.Cin % 16 == 0 && a.Cout % W4_CO == 0 && a.Ho % 16 == 0 && a.Wo % 32 == 0;
 }
 size_t egn_conv_wino4r_lds_bytes() { return W4R_LDS + 12 * 96 * 8; }      // (+ the stamp area of the ABL & 64 build)
 
 #ifdef EGN_PROBES
-static unsigned w4r_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
-
 template <int ABL>
 static int wino4r_launch(ConvArgs a, size_t lds, hipStream_t stream) {
   static bool raised[EGN_MAX_DEVICES];
   void (*kern)(ConvArgs) = &conv_wino4r_kernel<ABL>;
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      160 * 1024 - 512));
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(kern, EGN_BIG_LDS_BYTES, raised));
   const int nct = a.Cout / W4_CO;
-  const int nreg = a.tiles_x * a.tiles_y * a.N;
-  const int imode = w4_item_mode(nct);
-  const int nwork = w4_item_count(imode, nreg, nct, 1);
-  if ((unsigned long long)nwork * (unsigned)(8 * nct) >= 0x100000000ull ||
-      (unsigned long long)(nreg + 8) * (unsigned)(a.tiles_x * a.tiles_y) >= 0x100000000ull)
-    return EGN_E_BADARG;
-  a.mg_nct = imode == 1 ? 0u : w4r_magic(imode == 2 ? nct / 8 : nct);
-  a.mg_txy = w4r_magic(a.tiles_x * a.tiles_y);
-  a.mg_tx = w4r_magic(a.tiles_x);
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  int cap = cus / (8 * nct) * (8 * nct);
-  if (cap <= 0) cap = 8 * nct;
-  const int grid = nwork < cap ? nwork : cap;               // one block per CU, whole XCD rounds
+  const int nwork = w4_item_setup(a, nct, 1, a.tiles_x * a.tiles_y * a.N);
+  if (nwork < 0) return nwork;
+  const int grid = egn_persistent_grid(nwork, 8 * nct);     // one block per CU, whole XCD rounds
   hipLaunchKernelGGL(kern, dim3(grid), dim3(W4_NTH), lds, stream, a);
   return (int)hipGetLastError();
 }

@@ -27,42 +27,19 @@ template <int ABL>
 __global__ __launch_bounds__(W4_NTH, 1) void conv_wino4w_kernel(ConvArgs a) { w4w_body<ABL>(a, (int)blockIdx.x, (int)gridDim.x); }
 
 bool egn_conv_wino4w_applies(const ConvArgs& a) {
-  return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin % 16 == 0 && a.Cin >= 32 && a.cs_in == a.Cin &&
-         a.Cout % (2 * W4_CO) == 0 && a.cs_out == a.Cout && !a.out_nchw && a.Ho % 16 == 0 && a.Wo % 16 == 0 &&
-         !(a.act & EGN_ACT_RES_AFTER) &&
-         ((a.act & EGN_ACT_MASK) == EGN_ACT_NONE || (a.act & EGN_ACT_MASK) == EGN_ACT_RELU);
+  return egn_plain_3x3_s1(a) && a.Cin % 16 == 0 && a.Cin >= 32 && a.Cout % (2 * W4_CO) == 0 && a.Ho % 16 == 0 &&
+         a.Wo % 16 == 0;
 }
-
-static unsigned w4w_magic(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
 
 template <int ABL>
 static int wino4w_launch(ConvArgs a, size_t lds, hipStream_t stream) {
   static bool raised[EGN_MAX_DEVICES];
   void (*kern)(ConvArgs) = &conv_wino4w_kernel<ABL>;
-  if (egn_first_use_on_device(raised)) {
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      160 * 1024 - 512));
-  }
+  EGN_CHECK_HIP(egn_allow_big_lds(kern, EGN_BIG_LDS_BYTES, raised));
   const int ncp = a.Cout / (2 * W4_CO);
-  const int nreg = a.tiles_x * a.tiles_y * a.N;
-  const int imode = w4_item_mode(ncp);
-  const int nwork = w4_item_count(imode, nreg, ncp, 1);
-  if ((unsigned long long)nwork * (unsigned)(8 * ncp) >= 0x100000000ull ||
-      (unsigned long long)(nreg + 8) * (unsigned)(a.tiles_x * a.tiles_y) >= 0x100000000ull)
-    return EGN_E_BADARG;
-  a.mg_nct = imode == 1 ? 0u : w4w_magic(imode == 2 ? ncp / 8 : ncp);
-  a.mg_txy = w4w_magic(a.tiles_x * a.tiles_y);
-  a.mg_tx = w4w_magic(a.tiles_x);
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  int cap = cus / (8 * ncp) * (8 * ncp);
-  if (cap <= 0) cap = 8 * ncp;
-  const int grid = nwork < cap ? nwork : cap;               // one block per CU, whole XCD rounds
+  const int nwork = w4_item_setup(a, ncp, 1, a.tiles_x * a.tiles_y * a.N);
+  if (nwork < 0) return nwork;
+  const int grid = egn_persistent_grid(nwork, 8 * ncp);     // one block per CU, whole XCD rounds
   hipLaunchKernelGGL(kern, dim3(grid), dim3(W4_NTH), lds, stream, a);
   return (int)hipGetLastError();
 }

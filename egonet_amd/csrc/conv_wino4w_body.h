@@ -34,7 +34,7 @@ template <int ABL>
 __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
   typedef QW Q;
   extern __shared__ float4 w4_smem[];
-  const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)(lds_ptr_w4_t)w4_smem;
+  const unsigned lds0 = egn_lds_addr(w4_smem);
   const float* smf = reinterpret_cast<const float*>(w4_smem);
 
   const int tid = threadIdx.x;
@@ -48,16 +48,12 @@ __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
   const int nct = Co / W4_CO, ncp = nct >> 1;        // co-tiles, co-tile pairs
   const int S = C / 16;                    // stages of 16 channels
 
-  const unsigned long long xaddr = reinterpret_cast<unsigned long long>(a.x);
-  const unsigned long long uaddr = reinterpret_cast<unsigned long long>(a.w);
-  const u32x4 rxv = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu, (unsigned)((size_t)a.N * a.H * a.W * C * 4),
-                     0x00020000u};
-  const u32x4 ruv = {(unsigned)uaddr, (unsigned)(uaddr >> 32) & 0xffffu, (unsigned)((size_t)nct * (C >> 2) * W4_UKG * 4),
-                     0x00020000u};
+  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C * 4);
+  const u32x4 ruv = egn_rsrc(a.w, (size_t)nct * (C >> 2) * W4_UKG * 4);
   const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
   // ---- halo loads (conv_wino4.hip, geometry 1): pieces wave, wave + 12; element e -> (pixel e / 4, channel quad e % 4).
   // Every lane stores to the NATURAL slot of its element: the padded columns 18 / 19 of a row fall on slots (x & 3) in
@@ -104,7 +100,7 @@ __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
   for (int w = blk; w < nwork; w += gsz) {
     const unsigned wi = (unsigned)__builtin_amdgcn_readfirstlane(w);
     const unsigned xq = wi & 7u, q_ = wi >> 3;
-    const unsigned qq = w4_udiv(q_, a.mg_nct);
+    const unsigned qq = egn_udiv_magic(q_, a.mg_nct);
     int reg, cp;
     if (imode == 0) {
       cp = (int)(q_ - qq * (unsigned)ncp);
@@ -117,9 +113,9 @@ __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
     }
     if (reg >= nreg) continue;
     const int ct0 = 2 * cp;
-    const unsigned n_ = w4_udiv((unsigned)reg, a.mg_txy);
+    const unsigned n_ = egn_udiv_magic((unsigned)reg, a.mg_txy);
     const unsigned r_ = (unsigned)reg - n_ * (unsigned)regs_xy;
-    const unsigned ry_ = w4_udiv(r_, a.mg_tx);
+    const unsigned ry_ = egn_udiv_magic(r_, a.mg_tx);
     const int n = (int)n_, y0 = (int)ry_ * Q::RGH, x0 = (int)(r_ - ry_ * (unsigned)regs_x) * Q::RGW;
 
     // halo offsets of the item: recomputed from the lane id per item (not kept over the K loop: registers)

@@ -21,6 +21,37 @@ static inline bool egn_first_use_on_device(bool* seen) {
     if (_e != hipSuccess) return (int)_e;        \
   } while (0)
 
+// A kernel whose dynamic LDS exceeds 64 KB is allowed `bytes` of it on the first launch on each device (`raised`: the
+// launcher's own static bool[EGN_MAX_DEVICES]).  EGN_BIG_LDS_BYTES: all a workgroup can have on the 160 KB CU.
+constexpr int EGN_BIG_LDS_BYTES = 160 * 1024 - 512;
+template <class Kernel>
+static inline hipError_t egn_allow_big_lds(Kernel kernel, int bytes, bool* raised) {
+  if (!egn_first_use_on_device(raised)) return hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
+// CUs of the CURRENT device, looked up once per device; 256 where no device answers
+inline int egn_device_cus() {
+  static int cus[EGN_MAX_DEVICES];
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= EGN_MAX_DEVICES) return 256;
+  if (!cus[d]) {
+    hipDeviceProp_t prop;
+    cus[d] = hipGetDeviceProperties(&prop, d) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  }
+  return cus[d];
+}
+// Grid of a persistent kernel: all nwork items if they fit blocks_per_cu blocks on every CU, else whole rounds of
+// `round` blocks (8 XCDs x the co-tiles: the items w, w + grid, ... of a block then share their co-tile), at least one
+static inline int egn_persistent_grid(int nwork, int round, int blocks_per_cu = 1) {
+  int cap = blocks_per_cu * egn_device_cus() / round * round;
+  if (cap <= 0) cap = round;
+  return nwork < cap ? nwork : cap;
+}
+
+// ceil(2^32 / d) for egn_udiv_magic (conv_common.h); 0 = the divisor is 1
+static inline unsigned egn_magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d); }
+
 // conv chunking constants (the packed-weight format depends on them)
 constexpr int EGN_CK = 16;          // input channels per K chunk
 constexpr int EGN_CKQ = EGN_CK / 4; // float4 planes per chunk
@@ -53,6 +84,14 @@ struct ConvArgs {
   // both blocks add into it and conv_wino4_finish_kernel applies the epilogue (three launches instead of one).
   unsigned* tickets;
 };
+
+// the shared opening of the F(4x4,3x3) `applies` predicates: 3x3, stride 1, pad 1, NHWC with unpadded channel
+// strides, activation none / ReLU applied after the residual
+static inline bool egn_plain_3x3_s1(const ConvArgs& a) {
+  return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.cs_in == a.Cin && a.cs_out == a.Cout && !a.out_nchw &&
+         !(a.act & EGN_ACT_RES_AFTER) &&
+         ((a.act & EGN_ACT_MASK) == EGN_ACT_NONE || (a.act & EGN_ACT_MASK) == EGN_ACT_RELU);
+}
 
 // One row of kConfigs (conv_plan.hip) says everything about a config id: which family launches it, which of the
 // family's kernels, on which tile, with which filter packing, in which build.  Nothing is decoded from it elsewhere.

@@ -40,8 +40,6 @@
 
 #include "conv_common.h"
 
-typedef __attribute__((address_space(3))) void* lds_ptr_gemm_t;
-
 namespace {
 
 constexpr int GK = 32;  // k per stage
@@ -61,13 +59,6 @@ struct GemmArgs {
   int raster;         // block -> (split, tile) order, see the kernel (EGONET_AMD_GEMM_RASTER=0: round 4's order)
   size_t a_bytes, b_bytes;
 };
-
-__device__ __forceinline__ void gemm_dma16(u32x4 r, unsigned lds_addr, unsigned voff, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(r), "s"(soff)
-               : "m0");
-}
 
 template <int N>
 __device__ __forceinline__ void gemm_wait_vm() {
@@ -101,7 +92,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 4) void gemm_kernel(GemmA
   static_assert(P % NW == 0, "whole DMA pieces per wave");
   constexpr int PW = P / NW;
   extern __shared__ float4 smem[];
-  const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)(lds_ptr_gemm_t)smem;
+  const unsigned lds0 = egn_lds_addr(smem);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -135,9 +126,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 4) void gemm_kernel(GemmA
   const int m0 = tm * BM, n0 = tn * BN;
   const int kbeg = split * g.K;
 
-  const unsigned long long aaddr = reinterpret_cast<unsigned long long>(g.A), baddr = reinterpret_cast<unsigned long long>(g.B);
-  const u32x4 ra = {(unsigned)aaddr, (unsigned)(aaddr >> 32) & 0xffffu, (unsigned)g.a_bytes, 0x00020000u};
-  const u32x4 rb = {(unsigned)baddr, (unsigned)(baddr >> 32) & 0xffffu, (unsigned)g.b_bytes, 0x00020000u};
+  const u32x4 ra = egn_rsrc(g.A, g.a_bytes);
+  const u32x4 rb = egn_rsrc(g.B, g.b_bytes);
 
   // this wave's DMA pieces of a stage: piece p = j * NW + wave; p < PA: A tile, else B tile
   unsigned pvoff[PW];
@@ -169,7 +159,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 4) void gemm_kernel(GemmA
     _Pragma("unroll") for (int j = 0; j < PW; ++j) {                                                         \
       const int p = j * NW + wave;                                                                           \
       const bool isA = p < PA;                                                                               \
-      gemm_dma16(isA ? ra : rb, lds0 + (unsigned)(STG)*ST_BYTES + (unsigned)p * 1024u, pvoff[j],             \
+      egn_lds_dma16(isA ? ra : rb, lds0 + (unsigned)(STG)*ST_BYTES + (unsigned)p * 1024u, pvoff[j],          \
                  (unsigned)(KS) * (isA ? a_kstep : b_kstep));                                                \
     }                                                                                                        \
   }
@@ -368,8 +358,7 @@ int gemm_launch(GemmArgs g, hipStream_t st) {
   static bool raised[EGN_MAX_DEVICES];
   constexpr size_t lds = (size_t)STAGES * (BM + BN) * GK * 4;
   auto k = &gemm_kernel<AKC, BKC, BM, BN, WM, WN, STAGES>;
-  if (egn_first_use_on_device(raised))
-    EGN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  EGN_CHECK_HIP(egn_allow_big_lds(k, (int)lds, raised));
   g.tiles_m = g.M / BM;
   g.tiles_n = g.N / BN;
   static const int raster = [] { const char* e = getenv("EGONET_AMD_GEMM_RASTER"); return e && e[0] == '0' ? 0 : 1; }();

@@ -243,3 +243,20 @@ def test_winograd_frequency_halves_kernel_design_vs_torch():
     # 32-channel co-tiles (NT = 2): the W32 / Pedestrian widths and the 64-channel layers
     assert wino_emulator.conv_case8(1, 16, 16, 32, 64, 16, 16, 1, seed=5) < 2e-5
     assert wino_emulator.conv_case8(3, 8, 8, 16, 32, 8, 8, 2, seed=6) < 2e-5
+
+
+def test_shared_primitives_are_stated_once():
+    """The hazard-sensitive primitives every MFMA kernel file shares live in ONE place each: the LDS-DMA instruction,
+    the LDS address-space typedef (csrc/conv_common.h), the CU count of a device, the large-LDS opt-in and the
+    multiply-high divisor (csrc/egn_internal.h).  A second copy is a second place to fix the m0 / s_nop sequence,
+    the per-device caches or the rounding."""
+    import glob
+    import os
+    csrc = os.path.join(os.path.dirname(os.path.abspath(engine.__file__)), 'csrc')
+    files = sorted(p for ext in ('*.hip', '*.h', '*.cpp') for p in glob.glob(os.path.join(csrc, ext)))
+    assert len(files) > 40
+    text = {os.path.basename(p): open(p, encoding='utf-8').read() for p in files}
+    for pattern in ('offen lds', 'hipGetDeviceProperties', 'hipFuncAttributeMaxDynamicSharedMemorySize',
+                    '0x100000000ull +', 'address_space(3)'):
+        hits = [name for name, t in text.items() if pattern in t]
+        assert len(hits) == 1, (pattern, hits)
