@@ -87,25 +87,20 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
   // ---- halo loads: this wave's pieces wave, wave + 12 (, wave + 24); element e -> (pixel = e / QPP, channel quad e % QPP)
+  // in conv_wino4.h's load and slot order
   int hyx[Q::NP];
-  unsigned hrel[Q::NP], hws[Q::NP], hws2[Q::NP];
+  unsigned hrel[Q::NP];
+  W4HaloParked<Q::NP> hws;       // (parked: the lanes past the last pixel, conv_wino4.h)
 #pragma unroll
   for (int k = 0; k < Q::NP; ++k) {
-    // LOAD order pixel-major, the channel quads of a pixel in neighbouring lanes (32 / 64 contiguous bytes: 32 or
-    // 16 cache lines per instruction instead of 64); the lane stores its 16 bytes to the pixel's slots of the
-    // bank-conflict-free order above
-    const int e = (wave + W4_NW * k) * 64 + lane;
-    const int px = e / Q::QPP, hq = e % Q::QPP;
-    const int hya = px / Q::RWP, hx = px - hya * Q::RWP;        // (rows padded to whole store groups)
+    W4_HALO_ELEM(W4_NW, k, lane)
     const int img = hya / Q::RH, hy = hya - img * Q::RH;        // (GEO 2: the rows of the region's images follow each other)
     const bool ok = img < Q::NIMG && hx < Q::RW;
     hyx[k] = ok ? ((img << 24) | (hy << 16) | hx) : -1;
     hrel[k] = ok ? (unsigned)((((img * a.H + hy) * a.W + hx) * C + 4 * hq) * 4) : 0u;
-    // (lanes past the last pixel park their zeros in the unused tail of the buffer)
-    // channels 4 hq, 4 hq + 1 -> pair plane 2 hq, channels 4 hq + 2, + 3 -> pair plane 2 hq + 1
     const int slot = 2 * hq * Q::PAIR + (hx & 3) * Q::PLANE + Q::imgbase(img) + hy * Q::XD + (hx >> 2);
-    hws[k] = lds0 + (unsigned)(W4_H0 + (ok ? slot * 8 : Q::HSLOT * 8 + lane * 8));
-    hws2[k] = lds0 + (unsigned)(W4_H0 + (ok ? (slot + Q::PAIR) * 8 : Q::HSLOT * 8 + 512 + lane * 8));
+    hws.a[k] = lds0 + (unsigned)(W4_H0 + (ok ? slot * 8 : Q::HSLOT * 8 + lane * 8));
+    hws.b[k] = lds0 + (unsigned)(W4_H0 + (ok ? (slot + Q::PAIR) * 8 : Q::HSLOT * 8 + 512 + lane * 8));
   }
   // ---- transform share of this wave: lane (tile li of its m-tile, channel 4 g + kq of the stage)
   unsigned hb0, vw0;
@@ -120,10 +115,7 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
   const unsigned uvo = (unsigned)lane * 16u;
   // ---- exchange + output: this lane finishes tile 4 (wave & 3) + (lane >> 4) of the m-tile, co 16 (wave >> 2) + li
   const int ont = wave >> 2, okq = wave & 3;
-  // exchange [point][co sub-tile][writer lane] float4 (the C fragment: tiles 4 kq_w .. + 3 of channel li_w).  The reader
-  // takes ONE dword of 16 writer slots (li = 0..15): a stride of 4 dwords puts li and li + 8 on one bank (2-way conflict
-  // on all 36 reads of a round).  So writers with li >= 8 store their float4 rotated by two dwords (two ds_write_b64
-  // with swapped offsets -- no extra instruction), and the reader looks at dword (kq + 2 (li >> 3)) & 3.
+  // (exchange [point][co sub-tile][writer lane] float4; li >= 8 writes rotated by two dwords: w4_xw, conv_wino4.h)
   const unsigned xhi = (unsigned)(li >> 3);
   const unsigned xw0 = lds0 + (unsigned)((3 * wave) * 3 * 1024 + lane * 16);
   const unsigned xwa = xw0 + 8u * xhi, xwb = xw0 + 8u - 8u * xhi;           // elements (0, 1) / (2, 3) of the fragment
@@ -142,17 +134,8 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
   const unsigned rowpitch = (unsigned)(a.Wo * Co) * 4u, colpitch = (unsigned)Co * 4u;
 
   // ABL & 64 (tools/wino4_clk.py): s_memtime stamps of every wave into the LDS above the stage buffers, dumped into
-  // `res` at the end ([block][1 + 12 x 96] u64)
-  constexpr int W4_NTK = 96;
-  unsigned long long* sT = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(w4_smem) + w4_lds_bytes<GEO>());
-  int ntk = 0;
-#define W4_CLK()                                                                        \
-  {                                                                                     \
-    if constexpr ((ABL & 64) != 0) {                                                    \
-      if (lane == 0 && ntk < W4_NTK) sT[wave * W4_NTK + ntk] = __builtin_readcyclecounter(); \
-      ++ntk;                                                                            \
-    }                                                                                   \
-  }
+  // `res` at the end ([block][1 + 12 x 96] u64): conv_wino4.h
+  W4_STAMPS(96, w4_lds_bytes<GEO>(), wave)
   W4_CLK()
   // ST: per-(wave, statistic, channel li) sums in doubles above the stage buffers (the stamp area of the ABL & 64 build);
   // slot (wave, ., li) is written by the wave's lanes kq == 0 only; zeroed here, read after the last item (barriers between)
@@ -165,30 +148,15 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
   for (int w = blk; w < nwork; w += gsz) {
     // item -> (region, co-tile): blocks w, w + 8, ... stay on one XCD (conv_wino.hip: wino8_grid)
     const unsigned wi = (unsigned)__builtin_amdgcn_readfirstlane(w);
-    const unsigned xq = wi & 7u, q_ = wi >> 3;
-    // (mg_nct: the multiplier of nct * KS (mode 0) or of nct / 8 (mode 2); KS is a power of two)
-    const unsigned qq = egn_udiv_magic(q_, a.mg_nct);
-    int reg, ct, ks;
-    if (imode == 0) {
-      const int cs_ = (int)(q_ - qq * (unsigned)(nct * KS));
-      reg = (int)(qq * 8u + xq); ct = cs_ / KS; ks = cs_ % KS;
-    } else if (imode == 1) {
-      const unsigned lg = (unsigned)nct >> 1;          // log2 of 2 / 4
-      const int cs_ = (int)(q_ * (8u >> lg) + (xq >> lg));
-      reg = cs_ / KS; ct = (int)(xq & ((unsigned)nct - 1u)); ks = cs_ % KS;
-    } else {
-      reg = (int)qq / KS; ct = (int)((q_ - qq * ((unsigned)nct >> 3)) * 8u + xq); ks = (int)qq % KS;
-    }
+    W4_ITEM_DECODE(wi, KS, nct, reg, ct, ks)
     if (reg >= nreg) continue;                         // (uniform) padding of the last round of the XCDs
     ct_blk = ct;
-    const unsigned n_ = egn_udiv_magic((unsigned)reg, a.mg_txy);
-    const unsigned r_ = (unsigned)reg - n_ * (unsigned)regs_xy;
-    const unsigned ry_ = egn_udiv_magic(r_, a.mg_tx);
     // (GEO 2: the region is the four images n .. n + 3; images past N load zeros and store nothing)
-    const int n = (int)n_ * Q::NIMG, y0 = (int)ry_ * Q::RGH, x0 = (int)(r_ - ry_ * (unsigned)regs_x) * Q::RGW;
+    const W4Region rg_ = w4_item_region<GEO>(a, reg, regs_x, regs_xy);
+    const int n = rg_.n, y0 = rg_.y0, x0 = rg_.x0;
 
     // halo offsets of the item (stage 0): uniform base + per-lane relative offset, zero padding by OOB offsets
-    unsigned doff[Q::NP];
+    W4HaloOffs<Q::NP> doff;
     {
       // (KS: the item's half of the input channels starts ks * S stages into the pixel)
       const int base = ((n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * C * 4 + ks * S * Q::SBYTES;
@@ -196,22 +164,9 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
       for (int k = 0; k < Q::NP; ++k) {
         const unsigned iy = (unsigned)(y0 - 1 + ((hyx[k] >> 16) & 0xff)), ix = (unsigned)(x0 - 1 + (hyx[k] & 0xffff));
         const bool in = hyx[k] >= 0 && iy < (unsigned)a.H && ix < (unsigned)a.W && n + (hyx[k] >> 24) < a.N;
-        doff[k] = in ? (unsigned)base + hrel[k] : EGN_OOB;
+        doff.v[k] = in ? (unsigned)base + hrel[k] : EGN_OOB;
       }
     }
-  // The halo goes through REGISTERS (buffer_load_dwordx4 -> ds_write_b64), not LDS-DMA, and every vector-memory
-  // wait of the kernel is vmcnt(0): see the note in front of W4_STAGE.
-#define W4_HLOAD(K, STAGE) /* piece K of this wave; STAGE: byte offset of the stage's channels, W4_PAST = none */ \
-  if constexpr ((ABL & 16) == 0) hreg[K] = w4_gld4<0>(rxv, doff[K], (unsigned)(STAGE));                        \
-  else hreg[K] = f32x4{1.f, 2.f, 3.f, (float)lane};
-#define W4_HLOADS(STAGE) W4_HLOAD(0, STAGE) W4_HLOAD(1, STAGE) if constexpr (Q::NP == 3) { W4_HLOAD(Q::NP - 1, STAGE) }
-#define W4_HSTORE(P)                                                                                           \
-  {                                                                                                            \
-    _Pragma("unroll") for (int k_ = 0; k_ < Q::NP; ++k_) {                                                     \
-      w4_xwr2<(P)*Q::HBYTES>(hws[k_], hreg[k_][0], hreg[k_][1]);                                               \
-      w4_xwr2<(P)*Q::HBYTES>(hws2[k_], hreg[k_][2], hreg[k_][3]);                                              \
-    }                                                                                                          \
-  }
     // filter of this wave: k-group h (4 channels) = [co-tile][h][wave][3 x dwordx4 per lane] (engine.pack_wino4_weight);
     // a wait group is one k-group (GEO 0: x 2 m-tiles) or two consecutive ones (GEO 1).  Raw ISA -- the waits are
     // mine (tools/check_wino4_isa.py checks that no load's destination is touched before its wait)
@@ -232,32 +187,7 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
     constexpr unsigned WGB = (unsigned)Q::NKK * W4_UKG * 4u;       // filter bytes between consecutive wait groups
     f32x4 b0[Q::NKK][3], b1[Q::NKK][3];       // value p = 3 pl + nt of a k-group = b[kk][p >> 2][p & 3]
     f32x4 hreg[Q::NP];
-    W4_HLOADS(0u)
-    W4_LOADB(b0, ubase)
-    W4_CLK()      /* item top: halo + filter loads issued */
-    w4_vm_landedH(hreg);                                // stage 0's pieces (and the first filter wait group)
-    W4_HSTORE(0)
-    W4_HLOADS((unsigned)Q::SBYTES)                      // stage 1's pieces fly during the first transform
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    W4_CLK()      /* own pieces of stage 0 in LDS */
-    __builtin_amdgcn_s_barrier();
-    W4_CLK()      /* everyone's */
-    asm volatile("" ::: "memory");
-    if constexpr ((ABL & 1) == 0) {
-      if (tpart == 0) w4_transform<0, 0, GEO>(hb0, vw0);
-      else if (tpart == 1) w4_transform<0, 1, GEO>(hb0, vw0);
-      else w4_transform<0, 2, GEO>(hb0, vw0);
-    }
-    asm volatile("" ::: "memory");
-    // this wave's pieces of stage 1 (and the filter loads before them) have landed: into LDS with them -- the
-    // first third transforms stage 1 right behind the barrier
-    w4_vm_landedH(hreg);
-    W4_HSTORE(1)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    W4_CLK()      /* stage 0 transformed */
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    W4_CLK()      /* K loop starts */
+    W4_PROLOGUE(W4_LOADB(b0, ubase), __builtin_amdgcn_s_barrier();)
 
     f32x4 acc[3][3][Q::NMT];
 #pragma unroll
@@ -307,14 +237,6 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
   // registers are written asynchronously behind the compiler's back: the destination of a load must reach its
   // s_waitcnt without being copied -- tools/check_wino4_isa.py asserts that on the compiled ISA
   // (tests/test_wino4_design_cpu.py).
-  // raised priority: at equal priority the SIMD's arbiter hands the transforming wave one VALU issue per MFMA of
-  // the two multiplying waves -- 48 instructions took 1 500-2 000 cycles (profiles/r3_wino4_timeline_v2.txt)
-#define W4_TRANS(P, PART)                                                                                      \
-  if ((ABL & 1) == 0 && s_ + 1 < S && tpart == (PART)) {                                                       \
-    __builtin_amdgcn_s_setprio(3);                                                                             \
-    w4_transform<1 - (P), PART, GEO>(hb0, vw0 + (unsigned)((1 - (P)) * W4_VBYTES));                            \
-    __builtin_amdgcn_s_setprio(0);                                                                             \
-  }
   // the transform of stage s + 1 sits at a different point of the stage for each third of the waves: two of a
   // SIMD's three waves always have MFMAs to issue
 #define W4_STAGE(P, SI)                                                                                        \
@@ -359,12 +281,8 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
     w4_vm_landedH(hreg);
     W4_CLK()      /* K loop done */
 #undef W4_STAGE
-#undef W4_TRANS
 #undef W4_MUL
 #undef W4_MUL6
-#undef W4_HLOAD
-#undef W4_HLOADS
-#undef W4_HSTORE
 #undef W4_LOADB
 
     // ---- item end: per m-tile, accumulators -> LDS -> one (tile, co) per lane -> Y = A^T M A -> epilogue
@@ -392,63 +310,30 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
                                                        ct * W4_CO + ont * 16 + li) * 4)
                                          : EGN_OOB;
       float rv[4][4];
-#pragma unroll
-      for (int oa = 0; oa < 4; ++oa)
-#pragma unroll
-        for (int ob = 0; ob < 4; ++ob)
-          rv[oa][ob] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                     rr, has_res ? vo : EGN_OOB, oa * rowpitch + ob * colpitch, 0));
-#define W4_XW(SL, V) w4_xwr2<(SL)*1024>(xwa, (V)[0], (V)[1]); w4_xwr2<(SL)*1024>(xwb, (V)[2], (V)[3]);
-      W4_XW(0, acc[0][0][mt]) W4_XW(1, acc[0][1][mt]) W4_XW(2, acc[0][2][mt])
-      W4_XW(3, acc[1][0][mt]) W4_XW(4, acc[1][1][mt]) W4_XW(5, acc[1][2][mt])
-      W4_XW(6, acc[2][0][mt]) W4_XW(7, acc[2][1][mt]) W4_XW(8, acc[2][2][mt])
-#undef W4_XW
+      W4_RES_LOAD(rv, has_res ? vo : EGN_OOB)
+      w4_xw<0 * 1024>(xwa, xwb, acc[0][0][mt]); w4_xw<1 * 1024>(xwa, xwb, acc[0][1][mt]); w4_xw<2 * 1024>(xwa, xwb, acc[0][2][mt]);
+      w4_xw<3 * 1024>(xwa, xwb, acc[1][0][mt]); w4_xw<4 * 1024>(xwa, xwb, acc[1][1][mt]); w4_xw<5 * 1024>(xwa, xwb, acc[1][2][mt]);
+      w4_xw<6 * 1024>(xwa, xwb, acc[2][0][mt]); w4_xw<7 * 1024>(xwa, xwb, acc[2][1][mt]); w4_xw<8 * 1024>(xwa, xwb, acc[2][2][mt]);
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_waitcnt(0xC07F);
       W4_CLK()    /* round: accumulators written */
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       W4_CLK()    /* round: exchange barrier passed */
-      // M[i][j] = X[6 i + j]: two columns per batch (12 reads), column pass A^T right away: 24 values stay
       float yc[4][6];
-#define W4_M(I, J) w4_xrd<(I)*6 + (J)>(xr0, xr1)
-#define W4_COLS(J0)                                                                                     \
-  {                                                                                                     \
-    float ca_[6], cb_[6], ya_[4], yb_[4];                                                               \
-    ca_[0] = W4_M(0, J0); ca_[1] = W4_M(1, J0); ca_[2] = W4_M(2, J0); ca_[3] = W4_M(3, J0); ca_[4] = W4_M(4, J0);  \
-    ca_[5] = W4_M(5, J0);                                                                               \
-    cb_[0] = W4_M(0, J0 + 1); cb_[1] = W4_M(1, J0 + 1); cb_[2] = W4_M(2, J0 + 1); cb_[3] = W4_M(3, J0 + 1);        \
-    cb_[4] = W4_M(4, J0 + 1); cb_[5] = W4_M(5, J0 + 1);                                                 \
-    w4_landed6(ca_, cb_);                                                                               \
-    w4_at(ca_, ya_);                                                                                    \
-    w4_at(cb_, yb_);                                                                                    \
-    _Pragma("unroll") for (int oa = 0; oa < 4; ++oa) { yc[oa][J0] = ya_[oa]; yc[oa][J0 + 1] = yb_[oa]; } \
-  }
-      const unsigned xr1 = xr0 + 18u * 3072u;
-      W4_COLS(0)
-      W4_COLS(2)
-      W4_COLS(4)
-#undef W4_COLS
-#undef W4_M
+      W4_XREAD_COLS(3072)
       double st1 = 0.0, st2 = 0.0;       // ST: this lane's 16 stored values of the round (one channel), in doubles from the
                                          // first add (a mean far above the deviation loses the variance's digits in fp32: ADVICE r5)
+      if constexpr (KS == 1) {
+        W4_ROWS_STORE(if constexpr (ST) { st1 += (double)v; st2 = __builtin_fma((double)v, (double)v, st2); })
+      } else {
 #pragma unroll
-      for (int oa = 0; oa < 4; ++oa) {
-        float yo[4];
-        w4_at(yc[oa], yo);
-        if constexpr (KS > 1) {
+        for (int oa = 0; oa < 4; ++oa) {
+          float yo[4];
+          w4_at(yc[oa], yo);
 #pragma unroll
           for (int ob = 0; ob < 4; ++ob) yc[oa][ob] = yo[ob];      // (the column values of this row are spent)
-        } else {
-#pragma unroll
-          for (int ob = 0; ob < 4; ++ob) {
-            const float v = fmaxf(__builtin_fmaf(yo[ob], sc, sh) + rv[oa][ob], act_lo);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, vo, oa * rowpitch + ob * colpitch, 0);
-            if constexpr (ST) { st1 += (double)v; st2 = __builtin_fma((double)v, (double)v, st2); }
-          }
         }
-      }
-      if constexpr (KS > 1) {
         // yc[oa][ob]: this item's share of the output sum (its half of the input channels)
         if (!tk) {      // no ticket word: add into the zeroed y; conv_wino4_finish_kernel does the rest
 #pragma unroll
@@ -552,14 +437,7 @@ __device__ __forceinline__ void w4_body(const ConvArgs& a, int blk, int nblk) {
       row[e] = v;
     }
   }
-  if constexpr ((ABL & 64) != 0) {
-    __syncthreads();
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res)) +
-                              (size_t)blockIdx.x * (W4_NW * W4_NTK + 1);
-    for (int e = tid; e < W4_NW * W4_NTK; e += W4_NTH) out[1 + e] = sT[e];
-    if (tid == 0) out[0] = (unsigned long long)ntk;
-  }
-#undef W4_CLK
+  if constexpr ((ABL & 64) != 0) w4_stamp_dump<W4_NW, W4_NTK, 1>(a, sT, ntk, tid);
 }
 
 template <int ABL>

@@ -42,36 +42,12 @@ constexpr int W4H_LDS = W4H_H0 + 2 * QH::HBYTES;               // 62 KB
 constexpr int W4H_XPT = 6 * 256;                               // exchange bytes per point and round
 static_assert(36 * W4H_XPT <= W4H_LDS, "the exchange reuses the stage buffers");
 static_assert(QH::QPP * QH::RH * QH::RWP <= QH::NP * W4H_NW * 64, "the load pieces of the waves cover the halo");
-static_assert(QH::RH * QH::XD + 2 * QH::XD <= QH::PLANE && 3 * QH::PAIR + 3 * QH::PLANE + 20 * QH::XD <= QH::HSLOT &&
-                  QH::HSLOT * 8 <= QH::HBYTES,
-              "every load lane stores to the natural slot of its element (no parking area)");
 constexpr unsigned W4H_KGB = W4_UKG * 4u;                      // filter bytes of one (co-tile, k-group)
-
-struct W4HB {
-  f32x4 q[4];       // [2 o + (p >> 2)][p & 3], p < 8: slice o of the 12-wave layout (points 6w + 3o .. + 2)
-  float s[2];       // value 8 of slice o
-};
 }  // namespace
 
-__device__ __forceinline__ void w4h_vm_landedB(W4HB& b) {
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(b.q[0]), "+v"(b.q[1]), "+v"(b.q[2]), "+v"(b.q[3]), "+v"(b.s[0]), "+v"(b.s[1]));
-}
-template <int OFF>
-__device__ __forceinline__ float w4h_gld1(u32x4 rsrc, unsigned voff, unsigned soff) {
-  float v;
-  asm volatile("buffer_load_dword %0, %1, %2, %3 offen offset:%4" : "=v"(v) : "v"(voff), "s"(rsrc), "s"(soff), "n"(OFF));
-  return v;
-}
 // value of point pl (0..5) and co sub-tile nt: slice o = pl / 3, p = 3 (pl % 3) + nt
-__device__ __forceinline__ float w4h_bval(const W4HB& b, int pl, int nt) {
-  const int o = pl / 3, p = 3 * (pl % 3) + nt;
-  return p < 8 ? b.q[2 * o + (p >> 2)][p & 3] : b.s[o];
-}
-template <int PT>
-__device__ __forceinline__ float w4h_xrd(unsigned xr0, unsigned xr1) {
-  if constexpr (PT < 18) return w4_lds<PT * W4H_XPT>(xr0);
-  else return w4_lds<(PT - 18) * W4H_XPT>(xr1);
-}
+// (W4B9, conv_wino4.h: slice o = the 12-wave layout's points 6w + 3o .. + 2)
+__device__ __forceinline__ float w4h_bval(const W4B9& b, int pl, int nt) { return b.val(pl / 3, 3 * (pl % 3) + nt); }
 
 // Barrier of the six waves of a half (DUAL): arrive = one ds_add on the half's counter, wait = poll it.  The LDS serves a
 // wave's operations in order, so the wave's earlier LDS writes (and reads) are done when its add is; a wave that has seen
@@ -130,18 +106,9 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
   const __amdgpu_buffer_rsrc_t rr =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
-  // ---- halo loads: pieces wave, wave + 6; element e -> (pixel e / 2, channel quad e % 2).  Every lane stores to the
-  // NATURAL slot of its element: the padded columns 18 / 19 fall on slots (x & 3) in {2, 3}, x >> 2 = 4 and the rows 18 / 19
-  // on slots 90 .. 99 of a plane (PLANE = 100) -- never read by the transform; OOB offsets load zeros.
-  unsigned hws[Q::NP];
-#pragma unroll
-  for (int k = 0; k < Q::NP; ++k) {
-    const int e = (wave + W4H_NW * k) * 64 + lane;
-    const int px = e / Q::QPP, hq = e % Q::QPP;
-    const int hy = px / Q::RWP, hx = px - hy * Q::RWP;
-    const int slot = 2 * hq * Q::PAIR + (hx & 3) * Q::PLANE + hy * Q::XD + (hx >> 2);
-    hws[k] = lds0 + (unsigned)(W4H_H0 + slot * 8);
-  }
+  // ---- halo loads: pieces wave, wave + 6; element e -> (pixel e / 2, channel quad e % 2), every lane to the natural slot
+  // of its element (conv_wino4.h; PLANE = 100: the rows 18 / 19 fall on slots 90 .. 99); OOB offsets load zeros
+  W4_HALO_SLOTS_NATURAL(W4H_NW, W4H_H0)
   // ---- transform share: lane (tile li, channel 4 tg + kq of the stage)
   const unsigned hb0 = lds0 + (unsigned)(W4H_H0 + ((2 * tg + (kq >> 1)) * Q::PAIR + Q::tileslot(li, 0)) * 8 + (kq & 1) * 4);
   const unsigned vw0 = lds0 + (unsigned)(W4H_V0 + tg * 256 + lane * 4);         // V[pt][g][lane]
@@ -158,16 +125,7 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
   const bool has_res = (ABL & 64) ? false : a.res != nullptr;
   const unsigned rowpitch = (unsigned)(a.Wo * Co) * 4u, colpitch = (unsigned)Co * 4u;
 
-  constexpr int W4_NTK = 128;
-  unsigned long long* sT = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(w4_smem) + (DUAL ? 2 * W4H_LDS + 64 : W4H_LDS));
-  int ntk = 0;
-#define W4_CLK()                                                                        \
-  {                                                                                     \
-    if constexpr ((ABL & 64) != 0) {                                                    \
-      if (lane == 0 && ntk < W4_NTK) sT[wave_all * W4_NTK + ntk] = __builtin_readcyclecounter(); \
-      ++ntk;                                                                            \
-    }                                                                                   \
-  }
+  W4_STAMPS(128, DUAL ? 2 * W4H_LDS + 64 : W4H_LDS, wave_all)
   W4_CLK()
   // ---- phase skew: the block whose LDS allocation does not start at 0 shares its CU with an older block
   const unsigned lds_base = __builtin_amdgcn_s_getreg((12 - 1) << 11 | 0 << 6 | 6) & 0xfffu;      // HW_REG_LDS_ALLOC: LDS_BASE
@@ -184,83 +142,19 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
   // DUAL: the second halves are blocks gsz .. 2 gsz - 1 of a virtual grid (gsz is a multiple of 8: the same XCD)
   for (int w = blockIdx.x + half * gsz; w < nwork; w += (DUAL ? 2 : 1) * gsz) {
     const unsigned wi = (unsigned)__builtin_amdgcn_readfirstlane(w);
-    const unsigned xq = wi & 7u, q_ = wi >> 3;
-    const unsigned qq = egn_udiv_magic(q_, a.mg_nct);
-    int reg, ct;
-    if (imode == 0) {
-      ct = (int)(q_ - qq * (unsigned)nct);
-      reg = (int)(qq * 8u + xq);
-    } else if (imode == 1) {
-      const unsigned lg = (unsigned)nct >> 1;
-      reg = (int)(q_ * (8u >> lg) + (xq >> lg)); ct = (int)(xq & ((unsigned)nct - 1u));
-    } else {
-      reg = (int)qq; ct = (int)((q_ - qq * ((unsigned)nct >> 3)) * 8u + xq);
-    }
+    W4_ITEM_DECODE(wi, 1, nct, reg, ct, ks_)
     if (reg >= nreg) continue;
-    const unsigned n_ = egn_udiv_magic((unsigned)reg, a.mg_txy);
-    const unsigned r_ = (unsigned)reg - n_ * (unsigned)regs_xy;
-    const unsigned ry_ = egn_udiv_magic(r_, a.mg_tx);
-    const int n = (int)n_, y0 = (int)ry_ * Q::RGH, x0 = (int)(r_ - ry_ * (unsigned)regs_x) * Q::RGW;
-
+    const W4Region rg_ = w4_item_region<3>(a, reg, regs_x, regs_xy);
+    const int n = rg_.n, y0 = rg_.y0, x0 = rg_.x0;
     // halo offsets of the item: recomputed from the lane id per item (not kept over the K loop: registers)
-    unsigned doff[Q::NP];
-    {
-      int lane_t = lane;
-      asm volatile("" : "+v"(lane_t));
-      const int base = ((n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * C * 4;
-#pragma unroll
-      for (int k = 0; k < Q::NP; ++k) {
-        const int e = (wave + W4H_NW * k) * 64 + lane_t;
-        const int px = e / Q::QPP, hq = e % Q::QPP;
-        const int hy = px / Q::RWP, hx = px - hy * Q::RWP;
-        const unsigned iy = (unsigned)(y0 - 1 + hy), ix = (unsigned)(x0 - 1 + hx);
-        const bool in = hy < Q::RH && hx < Q::RW && iy < (unsigned)a.H && ix < (unsigned)a.W;
-        doff[k] = in ? (unsigned)(base + ((hy * a.W + hx) * C + 4 * hq) * 4) : EGN_OOB;
-      }
-    }
-#define W4_HLOAD(K, STAGE) hreg[K] = w4_gld4<0>(rxv, doff[K], (unsigned)(STAGE));
-#define W4_HLOADS(STAGE) W4_HLOAD(0, STAGE) W4_HLOAD(1, STAGE)
-#define W4_HSTORE(P)                                                                                           \
-  {                                                                                                            \
-    _Pragma("unroll") for (int k_ = 0; k_ < Q::NP; ++k_) {                                                     \
-      w4_xwr2<(P)*Q::HBYTES>(hws[k_], hreg[k_][0], hreg[k_][1]);                                               \
-      w4_xwr2<(P)*Q::HBYTES + Q::PAIR * 8>(hws[k_], hreg[k_][2], hreg[k_][3]);                                 \
-    }                                                                                                          \
-  }
+    W4_HALO_DOFF(W4H_NW)
     // filter of this wave: k-group h = [ct][h][12-wave slice 2w, 2w + 1][3 x dwordx4 per lane] -- 6 KB in a row.
     // Raw ISA: the waits are mine (tools/check_wino4_isa.py)
     const unsigned ubase = (unsigned)(ct * (C >> 2)) * W4H_KGB + (unsigned)wave * (6u * 64u * 16u);
-#define W4_LOADB(DST, HS)                                                                                      \
-  {                                                                                                            \
-    const unsigned so_ = (HS);        /* byte offset of the k-group, W4_PAST = none */                         \
-    const unsigned so1_ = so_ + 3072u; /* the second slice (the immediate offset of a buffer instruction has 12 bits) */ \
-    DST.q[0] = w4_gld4<0>(ruv, uvo, so_); DST.q[1] = w4_gld4<1024>(ruv, uvo, so_); DST.s[0] = w4h_gld1<2048>(ruv, uvo, so_);     \
-    DST.q[2] = w4_gld4<0>(ruv, uvo, so1_); DST.q[3] = w4_gld4<1024>(ruv, uvo, so1_); DST.s[1] = w4h_gld1<2048>(ruv, uvo, so1_);  \
-  }
-    W4HB b0, b1;
+#define W4_LOADB(DST, HS) w4_loadB(DST, ruv, uvo, HS, 3072u);   /* HS: byte offset of the k-group, W4_PAST = none */
+    W4B9 b0, b1;
     f32x4 hreg[Q::NP];
-    W4_HLOADS(0u)
-    W4_LOADB(b0, ubase)
-    W4_CLK()      /* item top: halo + filter loads issued */
-    w4_vm_landedH(hreg);
-    W4_HSTORE(0)
-    W4_HLOADS((unsigned)Q::SBYTES)                      // stage 1's pieces fly during the first transform
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    W4_CLK()      /* own pieces of stage 0 in LDS */
-    W4H_BAR()
-    W4_CLK()      /* everyone's */
-    asm volatile("" ::: "memory");
-    if (tpart == 0) w4_transform<0, 0, 3>(hb0, vw0);
-    else if (tpart == 1) w4_transform<0, 1, 3>(hb0, vw0);
-    else w4_transform<0, 2, 3>(hb0, vw0);
-    asm volatile("" ::: "memory");
-    w4_vm_landedH(hreg);
-    W4_HSTORE(1)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    W4_CLK()      /* stage 0 transformed */
-    W4H_BAR()
-    asm volatile("" ::: "memory");
-    W4_CLK()      /* K loop starts */
+    W4_PROLOGUE(W4_LOADB(b0, ubase), W4H_BAR())
 
     f32x4 acc[6][3];
 #pragma unroll
@@ -283,12 +177,6 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
     W4_MUL6(1, B) __builtin_amdgcn_sched_barrier(0); H1 __builtin_amdgcn_sched_barrier(0);                     \
     W4_MUL6(2, B) __builtin_amdgcn_sched_barrier(0); H2 __builtin_amdgcn_sched_barrier(0);                     \
   }
-#define W4_TRANS(P, PART)                                                                                      \
-  if (s_ + 1 < S && tpart == (PART)) {                                                                         \
-    __builtin_amdgcn_s_setprio(3);                                                                             \
-    w4_transform<1 - (P), PART, 3>(hb0, vw0 + (unsigned)((1 - (P)) * W4H_VBYTES));                             \
-    __builtin_amdgcn_s_setprio(0);                                                                             \
-  }
     // Stage s (parity P): k-groups 2s, 2s+1 (conv_wino4.hip's GEO 0 stage with one m-tile and six points per wave)
 #define W4_STAGE(P, SI)                                                                                        \
   {                                                                                                            \
@@ -296,14 +184,14 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
     const unsigned dst_ = s_ + 2 < S ? (unsigned)(s_ + 2) * (unsigned)Q::SBYTES : W4_PAST;                     \
     const unsigned u0_ = ubase + (unsigned)(2 * s_) * W4H_KGB;                                                 \
     const unsigned bn_ = s_ + 1 < S ? u0_ + 2u * W4H_KGB : W4_PAST;                                            \
-    w4h_vm_landedB(b0);                                                                                        \
+    w4_vm_landedB(b0);                                                                                        \
     W4_CLK() /* 0: k-group 2s landed */                                                                        \
     W4_TRANS(P, 0)                                                                                             \
     W4_LOADB(b1, u0_ + W4H_KGB)                                                                                \
     W4_CLK() /* 1: (transform third 0 +) loads issued */                                                       \
     W4_MUL(P, 0, b0, , , )                                                                                     \
     W4_CLK() /* 2: k-group 0 multiplies issued */                                                              \
-    w4h_vm_landedB(b1);                                                                                        \
+    w4_vm_landedB(b1);                                                                                        \
     W4_CLK() /* 3: k-group 2s+1 landed */                                                                      \
     W4_TRANS(P, 1)                                                                                             \
     W4_LOADB(b0, bn_)                                                                                          \
@@ -323,17 +211,13 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
       W4_STAGE(1, s + 1)
     }
     // the loads past the end: tied to the wait (conv_wino4.hip)
-    w4h_vm_landedB(b0);
-    w4h_vm_landedB(b1);
+    w4_vm_landedB(b0);
+    w4_vm_landedB(b1);
     w4_vm_landedH(hreg);
     W4_CLK()      /* K loop done */
 #undef W4_STAGE
-#undef W4_TRANS
 #undef W4_MUL
 #undef W4_MUL6
-#undef W4_HLOAD
-#undef W4_HLOADS
-#undef W4_HSTORE
 #undef W4_LOADB
 
     // ---- item end.  Unit U = 4 nt + kq (a quarter C fragment: tiles 4 kq .. 4 kq + 3 x 16 channels of sub-tile nt);
@@ -343,7 +227,7 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
     asm volatile("" : "+v"(lane_e));
     const int li_e = lane_e & 15, kq_e = lane_e >> 4;
     const unsigned xhi = (unsigned)(li_e >> 3);
-    // writer: slot of (nt, kq) in its round; li >= 8 stores its float4 rotated by two dwords (conv_wino4.hip: the reader
+    // writer: slot of (nt, kq) in its round; li >= 8 stores its float4 rotated by two dwords (conv_wino4.h: the reader
     // takes one dword of 16 writer slots -- li and li + 8 would share a bank)
     const unsigned xw_ = lds0 + (unsigned)((6 * wave) * W4H_XPT + li_e * 16);
     const unsigned xw_n0 = xw_ + (unsigned)(kq_e * 256);                              // nt 0: round 0, units 0..3
@@ -361,15 +245,10 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
       const unsigned vo = (unsigned)((((n * a.Ho + y0 + 4 * ty) * a.Wo + x0 + 4 * tx) * Co + cch) * 4);
       const unsigned xr0 = lds0 + (unsigned)(wave * 256 + li_e * 16) + (((unsigned)kq_e + 2u * xhi) & 3u) * 4u;
       float rv[4][4];
-#pragma unroll
-      for (int oa = 0; oa < 4; ++oa)
-#pragma unroll
-        for (int ob = 0; ob < 4; ++ob)
-          rv[oa][ob] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                     rr, has_res ? vo : EGN_OOB, oa * rowpitch + ob * colpitch, 0));
-#define W4_XW(ADDR, PL, V) w4_xwr2<(PL)*W4H_XPT>((ADDR) + 8u * xhi, (V)[0], (V)[1]); w4_xwr2<(PL)*W4H_XPT>((ADDR) + 8u - 8u * xhi, (V)[2], (V)[3]);
-#define W4_XW6(ADDR, NT) W4_XW(ADDR, 0, acc[0][NT]) W4_XW(ADDR, 1, acc[1][NT]) W4_XW(ADDR, 2, acc[2][NT])    \
-                         W4_XW(ADDR, 3, acc[3][NT]) W4_XW(ADDR, 4, acc[4][NT]) W4_XW(ADDR, 5, acc[5][NT])
+      W4_RES_LOAD(rv, has_res ? vo : EGN_OOB)
+#define W4_XWH(ADDR, PL, V) w4_xw<(PL)*W4H_XPT>((ADDR) + 8u * xhi, (ADDR) + 8u - 8u * xhi, V);
+#define W4_XW6(ADDR, NT) W4_XWH(ADDR, 0, acc[0][NT]) W4_XWH(ADDR, 1, acc[1][NT]) W4_XWH(ADDR, 2, acc[2][NT])    \
+                         W4_XWH(ADDR, 3, acc[3][NT]) W4_XWH(ADDR, 4, acc[4][NT]) W4_XWH(ADDR, 5, acc[5][NT])
       if (r == 0) {
         W4_XW6(xw_n0, 0)
         if (kq_e < 2) { W4_XW6(xw_n1, 1) }
@@ -378,7 +257,7 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
         W4_XW6(xw_n2, 2)
       }
 #undef W4_XW6
-#undef W4_XW
+#undef W4_XWH
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_waitcnt(0xC07F);
       W4_CLK()    /* round: accumulators written */
@@ -386,35 +265,8 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
       asm volatile("" ::: "memory");
       W4_CLK()    /* round: exchange barrier passed */
       float yc[4][6];
-#define W4_M(I, J) w4h_xrd<(I)*6 + (J)>(xr0, xr1)
-#define W4_COLS(J0)                                                                                     \
-  {                                                                                                     \
-    float ca_[6], cb_[6], ya_[4], yb_[4];                                                               \
-    ca_[0] = W4_M(0, J0); ca_[1] = W4_M(1, J0); ca_[2] = W4_M(2, J0); ca_[3] = W4_M(3, J0); ca_[4] = W4_M(4, J0);  \
-    ca_[5] = W4_M(5, J0);                                                                               \
-    cb_[0] = W4_M(0, J0 + 1); cb_[1] = W4_M(1, J0 + 1); cb_[2] = W4_M(2, J0 + 1); cb_[3] = W4_M(3, J0 + 1);        \
-    cb_[4] = W4_M(4, J0 + 1); cb_[5] = W4_M(5, J0 + 1);                                                 \
-    w4_landed6(ca_, cb_);                                                                               \
-    w4_at(ca_, ya_);                                                                                    \
-    w4_at(cb_, yb_);                                                                                    \
-    _Pragma("unroll") for (int oa = 0; oa < 4; ++oa) { yc[oa][J0] = ya_[oa]; yc[oa][J0 + 1] = yb_[oa]; } \
-  }
-      const unsigned xr1 = xr0 + 18u * (unsigned)W4H_XPT;
-      W4_COLS(0)
-      W4_COLS(2)
-      W4_COLS(4)
-#undef W4_COLS
-#undef W4_M
-#pragma unroll
-      for (int oa = 0; oa < 4; ++oa) {
-        float yo[4];
-        w4_at(yc[oa], yo);
-#pragma unroll
-        for (int ob = 0; ob < 4; ++ob) {
-          const float v = fmaxf(__builtin_fmaf(yo[ob], sc, sh) + rv[oa][ob], act_lo);
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, vo, oa * rowpitch + ob * colpitch, 0);
-        }
-      }
+      W4_XREAD_COLS(W4H_XPT)
+      W4_ROWS_STORE()
       asm volatile("" ::: "memory");
       W4_CLK()    /* round: output transform done, stores issued */
       W4H_BAR()      // the exchange buffer is free again (next round / next item's halo)
@@ -423,15 +275,10 @@ __device__ __forceinline__ void w4h_body(const ConvArgs& a) {
     }
   }
   if constexpr ((ABL & 64) != 0) {
-    __syncthreads();
-    constexpr int NWA = DUAL ? 2 * W4H_NW : W4H_NW;
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res)) +
-                              (size_t)blockIdx.x * (NWA * W4_NTK + 2);
-    for (int e = tid; e < NWA * W4_NTK; e += NWA * 64) out[2 + e] = sT[e];
-    if (tid == 0) { out[0] = (unsigned long long)ntk; out[1] = ((unsigned long long)lds_base << 32) | ((unsigned long long)(__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 0xfu) << 16) |
-                             (__builtin_amdgcn_s_getreg((16 - 1) << 11 | 0 << 6 | 4) & 0xffffu); }      /* LDS base | XCC_ID | HW_ID */
+    unsigned long long* out = w4_stamp_dump<(DUAL ? 2 * W4H_NW : W4H_NW), W4_NTK, 2>(a, sT, ntk, tid);
+    if (tid == 0) out[1] = ((unsigned long long)lds_base << 32) | ((unsigned long long)(__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 0xfu) << 16) |
+                           (__builtin_amdgcn_s_getreg((16 - 1) << 11 | 0 << 6 | 4) & 0xffffu);      /* LDS base | XCC_ID | HW_ID */
   }
-#undef W4_CLK
 #undef W4H_BAR
 }
 

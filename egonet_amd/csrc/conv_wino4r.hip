@@ -37,27 +37,11 @@ constexpr int W4R_LDS = W4R_XBYTES > w4_lds_bytes<0>() ? W4R_XBYTES : w4_lds_byt
 static_assert(W4R_LDS + 12 * 96 * 8 <= EGN_BIG_LDS_BYTES, "the one-round exchange (and the stamp area) fit the CU");
 static_assert(5 * W4R_XWAVE + 3 * 1024 < 65536, "ds_read_b32 immediates of a pass");
 
-struct W4RB {
-  f32x4 q[4];       // [2 o + (p >> 2)][p & 3], p < 8: slice o of the 12-wave layout (points 6 row + 3 o .. + 2)
-  float s[2];       // value 8 of slice o
-};
 }  // namespace
 
-__device__ __forceinline__ void w4r_vm_landedB(W4RB& b) {
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(b.q[0]), "+v"(b.q[1]), "+v"(b.q[2]), "+v"(b.q[3]), "+v"(b.s[0]), "+v"(b.s[1]));
-}
-template <int OFF>
-__device__ __forceinline__ float w4r_gld1(u32x4 rsrc, unsigned voff, unsigned soff) {
-  static_assert(OFF >= 0 && OFF < 4096, "12-bit immediate");
-  float v;
-  asm volatile("buffer_load_dword %0, %1, %2, %3 offen offset:%4" : "=v"(v) : "v"(voff), "s"(rsrc), "s"(soff), "n"(OFF));
-  return v;
-}
 // value of column j (0..5) of the wave's row and co sub-tile nt: slice o = j / 3, p = 3 (j % 3) + nt
-__device__ __forceinline__ float w4r_bval(const W4RB& b, int j, int nt) {
-  const int o = j / 3, p = 3 * (j % 3) + nt;
-  return p < 8 ? b.q[2 * o + (p >> 2)][p & 3] : b.s[o];
-}
+// (W4B9, conv_wino4.h: slice o = the 12-wave layout's points 6 row + 3 o .. + 2)
+__device__ __forceinline__ float w4r_bval(const W4B9& b, int j, int nt) { return b.val(j / 3, 3 * (j % 3) + nt); }
 
 // Row pass of the output transform for co sub-tile NT, in the wave's own accumulators, and its four exchange slots:
 // R[b] = sum_j acc[j][NT][e] A^T[b][j] for the four tile elements e of the C fragment (10 instructions each).
@@ -107,18 +91,17 @@ __device__ __forceinline__ void w4r_body(const ConvArgs& a) {
   const __amdgpu_buffer_rsrc_t rr =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
-  // ---- halo loads (conv_wino4.hip, geometry 0): pieces wave, wave + 12; element e -> (pixel e / 2, channel quad e % 2);
-  // the 96 elements past the halo (rows 18 / 19) park their zeros in the unused tail of the buffer
-  unsigned hws[Q::NP], hws2[Q::NP];
+  // ---- halo loads (geometry 0): pieces wave, wave + 12; element e -> (pixel e / 2, channel quad e % 2); the 96 elements
+  // past the halo (rows 18 / 19) park their zeros in the unused tail of the buffer (W4HaloParked, conv_wino4.h)
+  W4HaloParked<Q::NP> hws;
 #pragma unroll
   for (int k = 0; k < Q::NP; ++k) {
-    const int e = (wave + W4_NW * k) * 64 + lane;
-    const int px = e / Q::QPP, hq = e % Q::QPP;
-    const int hy = px / Q::RWP, hx = px - hy * Q::RWP;
+    W4_HALO_ELEM(W4_NW, k, lane)
+    const int hy = hya;
     const bool ok = hy < Q::RH && hx < Q::RW;
     const int slot = 2 * hq * Q::PAIR + (hx & 3) * Q::PLANE + hy * Q::XD + (hx >> 2);
-    hws[k] = lds0 + (unsigned)(W4_H0 + (ok ? slot * 8 : Q::HSLOT * 8 + lane * 8));
-    hws2[k] = lds0 + (unsigned)(W4_H0 + (ok ? (slot + Q::PAIR) * 8 : Q::HSLOT * 8 + 512 + lane * 8));
+    hws.a[k] = lds0 + (unsigned)(W4_H0 + (ok ? slot * 8 : Q::HSLOT * 8 + lane * 8));
+    hws.b[k] = lds0 + (unsigned)(W4_H0 + (ok ? (slot + Q::PAIR) * 8 : Q::HSLOT * 8 + 512 + lane * 8));
   }
   // ---- transform share: lane (tile li of m-tile tw >> 1, channel 4 (tw & 1) + kq of the stage)
   const unsigned hb0 = lds0 + (unsigned)(W4_H0 + ((2 * (tw & 1) + (kq >> 1)) * Q::PAIR + Q::tileslot(li, tw)) * 8 + (kq & 1) * 4);
@@ -136,96 +119,22 @@ __device__ __forceinline__ void w4r_body(const ConvArgs& a) {
   const bool has_res = (ABL & 64) ? false : a.res != nullptr;
   const unsigned rowpitch = (unsigned)(a.Wo * Co) * 4u, colpitch = (unsigned)Co * 4u;
 
-  constexpr int W4_NTK = 96;
-  unsigned long long* sT = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(w4_smem) + W4R_LDS);
-  int ntk = 0;
-#define W4_CLK()                                                                        \
-  {                                                                                     \
-    if constexpr ((ABL & 64) != 0) {                                                    \
-      if (lane == 0 && ntk < W4_NTK) sT[wave * W4_NTK + ntk] = __builtin_readcyclecounter(); \
-      ++ntk;                                                                            \
-    }                                                                                   \
-  }
+  W4_STAMPS(96, W4R_LDS, wave)
   W4_CLK()
   for (int w = blockIdx.x; w < nwork; w += gsz) {
     const unsigned wi = (unsigned)__builtin_amdgcn_readfirstlane(w);
-    const unsigned xq = wi & 7u, q_ = wi >> 3;
-    const unsigned qq = egn_udiv_magic(q_, a.mg_nct);
-    int reg, ct;
-    if (imode == 0) {
-      ct = (int)(q_ - qq * (unsigned)nct);
-      reg = (int)(qq * 8u + xq);
-    } else if (imode == 1) {
-      const unsigned lg = (unsigned)nct >> 1;
-      reg = (int)(q_ * (8u >> lg) + (xq >> lg)); ct = (int)(xq & ((unsigned)nct - 1u));
-    } else {
-      reg = (int)qq; ct = (int)((q_ - qq * ((unsigned)nct >> 3)) * 8u + xq);
-    }
+    W4_ITEM_DECODE(wi, 1, nct, reg, ct, ks_)
     if (reg >= nreg) continue;
-    const unsigned n_ = egn_udiv_magic((unsigned)reg, a.mg_txy);
-    const unsigned r_ = (unsigned)reg - n_ * (unsigned)regs_xy;
-    const unsigned ry_ = egn_udiv_magic(r_, a.mg_tx);
-    const int n = (int)n_, y0 = (int)ry_ * Q::RGH, x0 = (int)(r_ - ry_ * (unsigned)regs_x) * Q::RGW;
-
-    // halo offsets of the item: recomputed from the lane id per item (not kept over the K loop: registers)
-    unsigned doff[Q::NP];
-    {
-      int lane_t = lane;
-      asm volatile("" : "+v"(lane_t));
-      const int base = ((n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * C * 4;
-#pragma unroll
-      for (int k = 0; k < Q::NP; ++k) {
-        const int e = (wave + W4_NW * k) * 64 + lane_t;
-        const int px = e / Q::QPP, hq = e % Q::QPP;
-        const int hy = px / Q::RWP, hx = px - hy * Q::RWP;
-        const unsigned iy = (unsigned)(y0 - 1 + hy), ix = (unsigned)(x0 - 1 + hx);
-        const bool in = hy < Q::RH && hx < Q::RW && iy < (unsigned)a.H && ix < (unsigned)a.W;
-        doff[k] = in ? (unsigned)(base + ((hy * a.W + hx) * C + 4 * hq) * 4) : EGN_OOB;
-      }
-    }
-#define W4_HLOAD(K, STAGE) hreg[K] = w4_gld4<0>(rxv, doff[K], (unsigned)(STAGE));
-#define W4_HLOADS(STAGE) W4_HLOAD(0, STAGE) W4_HLOAD(1, STAGE)
-#define W4_HSTORE(P)                                                                                           \
-  {                                                                                                            \
-    _Pragma("unroll") for (int k_ = 0; k_ < Q::NP; ++k_) {                                                     \
-      w4_xwr2<(P)*Q::HBYTES>(hws[k_], hreg[k_][0], hreg[k_][1]);                                               \
-      w4_xwr2<(P)*Q::HBYTES>(hws2[k_], hreg[k_][2], hreg[k_][3]);                                              \
-    }                                                                                                          \
-  }
+    const W4Region rg_ = w4_item_region<0>(a, reg, regs_x, regs_xy);
+    const int n = rg_.n, y0 = rg_.y0, x0 = rg_.x0;
+    W4_HALO_DOFF(W4_NW)
     // filter of this wave: k-group h = [ct][h][12-wave slices 2 row, 2 row + 1][3 x dwordx4 per lane] -- 6 KB in a row.
     // Raw ISA: the waits are mine (tools/check_wino4_isa.py)
     const unsigned ubase = (unsigned)(ct * (C >> 2)) * W4R_KGB + (unsigned)row * (6u * 64u * 16u);
-#define W4_LOADB(DST, HS)                                                                                      \
-  {                                                                                                            \
-    const unsigned so_ = (HS);        /* byte offset of the k-group, W4_PAST = none */                         \
-    const unsigned so1_ = so_ + 3072u; /* the second slice (12-bit immediates) */                              \
-    DST.q[0] = w4_gld4<0>(ruv, uvo, so_); DST.q[1] = w4_gld4<1024>(ruv, uvo, so_); DST.s[0] = w4r_gld1<2048>(ruv, uvo, so_);     \
-    DST.q[2] = w4_gld4<0>(ruv, uvo, so1_); DST.q[3] = w4_gld4<1024>(ruv, uvo, so1_); DST.s[1] = w4r_gld1<2048>(ruv, uvo, so1_);  \
-  }
-    W4RB b0, b1;
+#define W4_LOADB(DST, HS) w4_loadB(DST, ruv, uvo, HS, 3072u);   /* HS: byte offset of the k-group, W4_PAST = none */
+    W4B9 b0, b1;
     f32x4 hreg[Q::NP];
-    W4_HLOADS(0u)
-    W4_LOADB(b0, ubase)
-    W4_CLK()      /* item top: halo + filter loads issued */
-    w4_vm_landedH(hreg);
-    W4_HSTORE(0)
-    W4_HLOADS((unsigned)Q::SBYTES)                      // stage 1's pieces fly during the first transform
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    W4_CLK()      /* own pieces of stage 0 in LDS */
-    __builtin_amdgcn_s_barrier();
-    W4_CLK()      /* everyone's */
-    asm volatile("" ::: "memory");
-    if (tpart == 0) w4_transform<0, 0, 0>(hb0, vw0);
-    else if (tpart == 1) w4_transform<0, 1, 0>(hb0, vw0);
-    else w4_transform<0, 2, 0>(hb0, vw0);
-    asm volatile("" ::: "memory");
-    w4_vm_landedH(hreg);
-    W4_HSTORE(1)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    W4_CLK()      /* stage 0 transformed */
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    W4_CLK()      /* K loop starts */
+    W4_PROLOGUE(W4_LOADB(b0, ubase), __builtin_amdgcn_s_barrier();)
 
     f32x4 acc[6][3];
 #pragma unroll
@@ -247,12 +156,6 @@ __device__ __forceinline__ void w4r_body(const ConvArgs& a) {
     W4_MUL6(1, B) __builtin_amdgcn_sched_barrier(0); H1 __builtin_amdgcn_sched_barrier(0);                     \
     W4_MUL6(2, B) __builtin_amdgcn_sched_barrier(0); H2 __builtin_amdgcn_sched_barrier(0);                     \
   }
-#define W4_TRANS(P, PART)                                                                                      \
-  if (s_ + 1 < S && tpart == (PART)) {                                                                         \
-    __builtin_amdgcn_s_setprio(3);                                                                             \
-    w4_transform<1 - (P), PART, 0>(hb0, vw0 + (unsigned)((1 - (P)) * W4_VBYTES));                              \
-    __builtin_amdgcn_s_setprio(0);                                                                             \
-  }
     // Stage s (parity P): k-groups 2s, 2s+1 -- conv_wino4.hip's stage; each transform third where one filter buffer is live
 #define W4_STAGE(P, SI)                                                                                        \
   {                                                                                                            \
@@ -260,14 +163,14 @@ __device__ __forceinline__ void w4r_body(const ConvArgs& a) {
     const unsigned dst_ = s_ + 2 < S ? (unsigned)(s_ + 2) * (unsigned)Q::SBYTES : W4_PAST;                     \
     const unsigned u0_ = ubase + (unsigned)(2 * s_) * W4R_KGB;                                                 \
     const unsigned bn_ = s_ + 1 < S ? u0_ + 2u * W4R_KGB : W4_PAST;                                            \
-    w4r_vm_landedB(b0);                                                                                        \
+    w4_vm_landedB(b0);                                                                                        \
     W4_CLK() /* 0: k-group 2s landed */                                                                        \
     W4_TRANS(P, 0)                                                                                             \
     W4_LOADB(b1, u0_ + W4R_KGB)                                                                                \
     W4_CLK() /* 1: (transform third 0 +) loads issued */                                                       \
     W4_MUL(P, 0, b0, , , )                                                                                     \
     W4_CLK() /* 2: k-group 0 multiplies issued */                                                              \
-    w4r_vm_landedB(b1);                                                                                        \
+    w4_vm_landedB(b1);                                                                                        \
     W4_CLK() /* 3: k-group 2s+1 landed */                                                                      \
     W4_TRANS(P, 1)                                                                                             \
     W4_TRANS(P, 2)                                                                                             \
@@ -287,17 +190,13 @@ __device__ __forceinline__ void w4r_body(const ConvArgs& a) {
       W4_STAGE(1, s + 1)
     }
     // the loads past the end: tied to the wait (conv_wino4.hip)
-    w4r_vm_landedB(b0);
-    w4r_vm_landedB(b1);
+    w4_vm_landedB(b0);
+    w4_vm_landedB(b1);
     w4_vm_landedH(hreg);
     W4_CLK()      /* K loop done */
 #undef W4_STAGE
-#undef W4_TRANS
 #undef W4_MUL
 #undef W4_MUL6
-#undef W4_HLOAD
-#undef W4_HLOADS
-#undef W4_HSTORE
 #undef W4_LOADB
 
     // ---- item end, ONE round.  Row pass in registers: for co sub-tile nt and tile element e of the C fragment,
@@ -308,7 +207,7 @@ __device__ __forceinline__ void w4r_body(const ConvArgs& a) {
     const int li_e = lane_e & 15, kq_e = lane_e >> 4;
     const unsigned xhi = (unsigned)(li_e >> 3);
     // (writers with li >= 8 store their float4 rotated by two dwords: the reader takes one dword of 16 writer slots,
-    // li and li + 8 would share a bank -- conv_wino4.hip)
+    // li and li + 8 would share a bank -- w4_xw, conv_wino4.h)
     const unsigned xw0 = lds0 + (unsigned)(wave * W4R_XWAVE + lane_e * 16);
     const unsigned xwa = xw0 + 8u * xhi, xwb = xw0 + 8u - 8u * xhi;
     w4r_row_pass<0>(acc, xwa, xwb);
@@ -326,12 +225,7 @@ __device__ __forceinline__ void w4r_body(const ConvArgs& a) {
     for (int mt = 0; mt < 2; ++mt) {
       const int ty = 2 * mt + (tile >> 3), tx = tile & 7;
       vo[mt] = (unsigned)((((n * a.Ho + y0 + 4 * ty) * a.Wo + x0 + 4 * tx) * Co + cch) * 4);
-#pragma unroll
-      for (int oa = 0; oa < 4; ++oa)
-#pragma unroll
-        for (int ob = 0; ob < 4; ++ob)
-          rv[mt][oa][ob] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                         rr, has_res ? vo[mt] : EGN_OOB, oa * rowpitch + ob * colpitch, 0));
+      W4_RES_LOAD(rv[mt], has_res ? vo[mt] : EGN_OOB)
     }
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0): the exchange writes (the residual loads stay in flight)
@@ -376,14 +270,7 @@ __device__ __forceinline__ void w4r_body(const ConvArgs& a) {
     asm volatile("" ::: "memory");
     W4_CLK()    /* item end */
   }
-  if constexpr ((ABL & 64) != 0) {
-    __syncthreads();
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res)) +
-                              (size_t)blockIdx.x * (W4_NW * W4_NTK + 1);
-    for (int e = tid; e < W4_NW * W4_NTK; e += W4_NTH) out[1 + e] = sT[e];
-    if (tid == 0) out[0] = (unsigned long long)ntk;
-  }
-#undef W4_CLK
+  if constexpr ((ABL & 64) != 0) w4_stamp_dump<W4_NW, W4_NTK, 1>(a, sT, ntk, tid);
 }
 
 template <int ABL>

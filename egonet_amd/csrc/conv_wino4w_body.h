@@ -10,22 +10,8 @@ constexpr int W4W_NT = 6;                          // co sub-tiles of an item: t
 constexpr unsigned W4W_KGB = W4_UKG * 4u;          // filter bytes of one (co-tile, k-group)
 }  // namespace
 
-// The filter registers of a k-group: the 9 used values (p = 3 pl + nt') of the 12 per (wave, lane, co-tile) slot --
-// values 0 .. 7 as two dwordx4, value 8 as one dword (18 registers per buffer instead of 24: the budget)
-struct W4WB {
-  f32x4 q[4];       // [2 c + (p >> 2)][p & 3], p < 8
-  float s[2];       // value 8 of co-tile c
-};
-__device__ __forceinline__ void w4w_vm_landedB(W4WB& b) {
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(b.q[0]), "+v"(b.q[1]), "+v"(b.q[2]), "+v"(b.q[3]), "+v"(b.s[0]), "+v"(b.s[1]));
-}
-template <int OFF>
-__device__ __forceinline__ float w4w_gld1(u32x4 rsrc, unsigned voff, unsigned soff) {
-  float v;
-  asm volatile("buffer_load_dword %0, %1, %2, %3 offen offset:%4" : "=v"(v) : "v"(voff), "s"(rsrc), "s"(soff), "n"(OFF));
-  return v;
-}
-__device__ __forceinline__ float w4w_bval(const W4WB& b, int c, int p) { return p < 8 ? b.q[2 * c + (p >> 2)][p & 3] : b.s[c]; }
+// value p = 3 pl + nt' of co-tile c of the pair: the slices of the filter registers (W4B9, conv_wino4.h) are the co-tiles
+__device__ __forceinline__ float w4w_bval(const W4B9& b, int c, int p) { return b.val(c, p); }
 
 // ABL (probe builds): bit 6 s_memtime stamps of every wave (tools/wino4_clk.py), dumped into `res`.
 // blk / nblk: the block's index in its launch share and the share's size -- blockIdx.x / gridDim.x in conv_wino4w_kernel,
@@ -55,21 +41,9 @@ __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
   const __amdgpu_buffer_rsrc_t rr =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
 
-  // ---- halo loads (conv_wino4.hip, geometry 1): pieces wave, wave + 12; element e -> (pixel e / 4, channel quad e % 4).
-  // Every lane stores to the NATURAL slot of its element: the padded columns 18 / 19 of a row fall on slots (x & 3) in
-  // {2, 3}, x >> 2 = 4 and the rows 18 / 19 past the halo on slots 90 .. 95 of a plane -- none of them is read by the
-  // transform (rows 0 .. 17 x (x >> 2) 0 .. 4 of the planes of x = 0 .. 17), so the idle lanes need no parking area and
-  // the second channel pair of a lane sits at a constant + PAIR slots (one address register per piece).
-  static_assert(Q::RH * Q::XD + 5 < Q::PLANE && 7 * Q::PAIR + 3 * Q::PLANE + 19 * Q::XD + 5 <= Q::HSLOT, "natural slots of the idle lanes");
-  unsigned hws[Q::NP];
-#pragma unroll
-  for (int k = 0; k < Q::NP; ++k) {
-    const int e = (wave + W4_NW * k) * 64 + lane;
-    const int px = e / Q::QPP, hq = e % Q::QPP;
-    const int hy = px / Q::RWP, hx = px - hy * Q::RWP;
-    const int slot = 2 * hq * Q::PAIR + (hx & 3) * Q::PLANE + hy * Q::XD + (hx >> 2);
-    hws[k] = lds0 + (unsigned)(W4_H0 + slot * 8);
-  }
+  // ---- halo loads (geometry 1): pieces wave, wave + 12; element e -> (pixel e / 4, channel quad e % 4), every lane to
+  // the natural slot of its element (conv_wino4.h: the rows 18 / 19 fall on slots 90 .. 95 of a plane)
+  W4_HALO_SLOTS_NATURAL(W4_NW, W4_H0)
   // ---- transform share: lane (tile li, channel 4 tw + kq of the stage)
   const unsigned hb0 = lds0 + (unsigned)(W4_H0 + ((2 * tw + (kq >> 1)) * Q::PAIR + Q::tileslot(li, tw)) * 8 + (kq & 1) * 4);
   const unsigned vw0 = lds0 + (unsigned)(W4_V0 + tw * 256 + lane * 4);        // V[pt][g][lane]
@@ -86,96 +60,22 @@ __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
   const unsigned rowpitch = (unsigned)(a.Wo * Co) * 4u, colpitch = (unsigned)Co * 4u;
   const unsigned ctstride = (unsigned)(C >> 2) * W4W_KGB;        // filter bytes of a co-tile
 
-  constexpr int W4_NTK = 96;
-  unsigned long long* sT = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(w4_smem) + w4_lds_bytes<1>());
-  int ntk = 0;
-#define W4_CLK()                                                                        \
-  {                                                                                     \
-    if constexpr ((ABL & 64) != 0) {                                                    \
-      if (lane == 0 && ntk < W4_NTK) sT[wave * W4_NTK + ntk] = __builtin_readcyclecounter(); \
-      ++ntk;                                                                            \
-    }                                                                                   \
-  }
+  W4_STAMPS(96, w4_lds_bytes<1>(), wave)
   W4_CLK()
   for (int w = blk; w < nwork; w += gsz) {
     const unsigned wi = (unsigned)__builtin_amdgcn_readfirstlane(w);
-    const unsigned xq = wi & 7u, q_ = wi >> 3;
-    const unsigned qq = egn_udiv_magic(q_, a.mg_nct);
-    int reg, cp;
-    if (imode == 0) {
-      cp = (int)(q_ - qq * (unsigned)ncp);
-      reg = (int)(qq * 8u + xq);
-    } else if (imode == 1) {
-      const unsigned lg = (unsigned)ncp >> 1;
-      reg = (int)(q_ * (8u >> lg) + (xq >> lg)); cp = (int)(xq & ((unsigned)ncp - 1u));
-    } else {
-      reg = (int)qq; cp = (int)((q_ - qq * ((unsigned)ncp >> 3)) * 8u + xq);
-    }
+    W4_ITEM_DECODE(wi, 1, ncp, reg, cp, ks_)
     if (reg >= nreg) continue;
     const int ct0 = 2 * cp;
-    const unsigned n_ = egn_udiv_magic((unsigned)reg, a.mg_txy);
-    const unsigned r_ = (unsigned)reg - n_ * (unsigned)regs_xy;
-    const unsigned ry_ = egn_udiv_magic(r_, a.mg_tx);
-    const int n = (int)n_, y0 = (int)ry_ * Q::RGH, x0 = (int)(r_ - ry_ * (unsigned)regs_x) * Q::RGW;
-
-    // halo offsets of the item: recomputed from the lane id per item (not kept over the K loop: registers)
-    unsigned doff[Q::NP];
-    {
-      int lane_t = lane;
-      asm volatile("" : "+v"(lane_t));
-      const int base = ((n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * C * 4;
-#pragma unroll
-      for (int k = 0; k < Q::NP; ++k) {
-        const int e = (wave + W4_NW * k) * 64 + lane_t;
-        const int px = e / Q::QPP, hq = e % Q::QPP;
-        const int hy = px / Q::RWP, hx = px - hy * Q::RWP;
-        const unsigned iy = (unsigned)(y0 - 1 + hy), ix = (unsigned)(x0 - 1 + hx);
-        const bool in = hy < Q::RH && hx < Q::RW && iy < (unsigned)a.H && ix < (unsigned)a.W;
-        doff[k] = in ? (unsigned)(base + ((hy * a.W + hx) * C + 4 * hq) * 4) : EGN_OOB;
-      }
-    }
-#define W4_HLOAD(K, STAGE) hreg[K] = w4_gld4<0>(rxv, doff[K], (unsigned)(STAGE));
-#define W4_HLOADS(STAGE) W4_HLOAD(0, STAGE) W4_HLOAD(1, STAGE)
-#define W4_HSTORE(P)                                                                                           \
-  {                                                                                                            \
-    _Pragma("unroll") for (int k_ = 0; k_ < Q::NP; ++k_) {                                                     \
-      w4_xwr2<(P)*Q::HBYTES>(hws[k_], hreg[k_][0], hreg[k_][1]);                                               \
-      w4_xwr2<(P)*Q::HBYTES + Q::PAIR * 8>(hws[k_], hreg[k_][2], hreg[k_][3]);                                 \
-    }                                                                                                          \
-  }
+    const W4Region rg_ = w4_item_region<1>(a, reg, regs_x, regs_xy);
+    const int n = rg_.n, y0 = rg_.y0, x0 = rg_.x0;
+    W4_HALO_DOFF(W4_NW)
     // filter of this wave: k-group h of co-tile ct = [ct][h][wave][3 x dwordx4 per lane], co-tiles ct0 and ct0 + 1.  Raw ISA: the waits are mine (tools/check_wino4_isa.py)
     const unsigned ubase = (unsigned)(ct0 * (C >> 2)) * W4W_KGB + (unsigned)wave * (3u * 64u * 16u);
-#define W4_LOADB(DST, HS)                                                                                      \
-  {                                                                                                            \
-    const unsigned so_ = (HS);        /* byte offset of the k-group in co-tile ct0, W4_PAST = none */          \
-    const unsigned so1_ = so_ + ctstride;                                                                      \
-    DST.q[0] = w4_gld4<0>(ruv, uvo, so_); DST.q[1] = w4_gld4<1024>(ruv, uvo, so_); DST.s[0] = w4w_gld1<2048>(ruv, uvo, so_);     \
-    DST.q[2] = w4_gld4<0>(ruv, uvo, so1_); DST.q[3] = w4_gld4<1024>(ruv, uvo, so1_); DST.s[1] = w4w_gld1<2048>(ruv, uvo, so1_);  \
-  }
-    W4WB b0, b1;
+#define W4_LOADB(DST, HS) w4_loadB(DST, ruv, uvo, HS, ctstride);   /* HS: byte offset of the k-group in co-tile ct0, W4_PAST = none */
+    W4B9 b0, b1;
     f32x4 hreg[Q::NP];
-    W4_HLOADS(0u)
-    W4_LOADB(b0, ubase)
-    W4_CLK()      /* item top: halo + filter loads issued */
-    w4_vm_landedH(hreg);
-    W4_HSTORE(0)
-    W4_HLOADS((unsigned)Q::SBYTES)                      // stage 1's pieces fly during the first transform
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    W4_CLK()      /* own pieces of stage 0 in LDS */
-    __builtin_amdgcn_s_barrier();
-    W4_CLK()      /* everyone's */
-    asm volatile("" ::: "memory");
-    if (tpart == 0) w4_transform<0, 0, 1>(hb0, vw0);
-    else if (tpart == 1) w4_transform<0, 1, 1>(hb0, vw0);
-    else w4_transform<0, 2, 1>(hb0, vw0);
-    asm volatile("" ::: "memory");
-    w4_vm_landedH(hreg);
-    W4_HSTORE(1)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    W4_CLK()      /* stage 0 transformed */
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    W4_CLK()      /* K loop starts */
+    W4_PROLOGUE(W4_LOADB(b0, ubase), __builtin_amdgcn_s_barrier();)
 
     f32x4 acc[3][W4W_NT];
 #pragma unroll
@@ -184,7 +84,7 @@ __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
       for (int nt = 0; nt < W4W_NT; ++nt) acc[pl][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // 18 MFMAs of a k-group in three groups of 6 (one frequency point each); H0 / H1 / H2: the vector-memory
-    // instruction issued behind each group (conv_wino4.hip: spread, not a burst behind the barrier)
+    // instruction issued behind each group (w4_body, conv_wino4.hip: spread, not a burst behind the barrier)
 #define W4_MUL6(PL, B)                                                                                         \
   _Pragma("unroll") for (int nt = 0; nt < W4W_NT; ++nt)                                                        \
       acc[PL][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av_[PL], w4w_bval(B, nt / 3, (PL)*3 + nt % 3),             \
@@ -199,12 +99,6 @@ __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
   }
     // the transform of stage s + 1, one third of the waves at each of three points of the stage -- each point where
     // only ONE filter buffer is live (the other's multiplies are issued, its next load is not): the register budget
-#define W4_TRANS(P, PART)                                                                                      \
-  if (s_ + 1 < S && tpart == (PART)) {                                                                         \
-    __builtin_amdgcn_s_setprio(3);                                                                             \
-    w4_transform<1 - (P), PART, 1>(hb0, vw0 + (unsigned)((1 - (P)) * W4_VBYTES));                              \
-    __builtin_amdgcn_s_setprio(0);                                                                             \
-  }
     // Stage s (parity P): k-groups 4s .. 4s+3.  Wait group h is issued one multiply (18 MFMAs) before it is awaited,
     // alone in the queue -- except the last wait of the stage, which also retires the halo pieces of stage s + 2
     // issued behind the first MFMA groups of k-group 3: no wait needs a count.
@@ -214,24 +108,24 @@ __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
     const unsigned dst_ = s_ + 2 < S ? (unsigned)(s_ + 2) * (unsigned)Q::SBYTES : W4_PAST;                     \
     const unsigned u0_ = ubase + (unsigned)(4 * s_) * W4W_KGB;                                                 \
     const unsigned bn_ = s_ + 1 < S ? u0_ + 4u * W4W_KGB : W4_PAST;                                            \
-    w4w_vm_landedB(b0);                                                                                        \
+    w4_vm_landedB(b0);                                                                                        \
     W4_CLK() /* 0: k-group 4s landed */                                                                        \
     W4_TRANS(P, 0)                                                                                             \
     W4_LOADB(b1, u0_ + W4W_KGB)                                                                                \
     W4_CLK() /* 1: (transform third 0 +) loads issued */                                                       \
     W4_MUL(P, 0, b0, , , )                                                                                     \
     W4_CLK() /* 2: k-group 0 multiplies issued */                                                              \
-    w4w_vm_landedB(b1);                                                                                        \
+    w4_vm_landedB(b1);                                                                                        \
     W4_CLK() /* 3: k-group 4s+1 landed */                                                                      \
     W4_TRANS(P, 1)                                                                                             \
     W4_LOADB(b0, u0_ + 2u * W4W_KGB)                                                                           \
     W4_MUL(P, 1, b1, , , )                                                                                     \
     W4_CLK() /* 4: (transform third 1 +) k-group 1 multiplies issued */                                        \
-    w4w_vm_landedB(b0);                                                                                        \
+    w4_vm_landedB(b0);                                                                                        \
     W4_LOADB(b1, u0_ + 3u * W4W_KGB)                                                                           \
     W4_MUL(P, 2, b0, , , )                                                                                     \
     W4_CLK() /* 5: k-group 2 multiplies issued */                                                              \
-    w4w_vm_landedB(b1);                                                                                        \
+    w4_vm_landedB(b1);                                                                                        \
     W4_TRANS(P, 2)                                                                                             \
     W4_LOADB(b0, bn_)                                                                                          \
     W4_MUL(P, 3, b1, W4_HLOAD(0, dst_), W4_HLOAD(1, dst_), )                                                   \
@@ -249,22 +143,18 @@ __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
       W4_STAGE(1, s + 1)
     }
     if (S & 1) W4_STAGE(0, S - 1)            // (every item starts at parity 0)
-    // the loads past the end: tied to the wait (conv_wino4.hip)
-    w4w_vm_landedB(b0);
-    w4w_vm_landedB(b1);
+    // the loads past the end: tied to the wait (w4_body, conv_wino4.hip)
+    w4_vm_landedB(b0);
+    w4_vm_landedB(b1);
     w4_vm_landedH(hreg);
     W4_CLK()      /* K loop done */
 #undef W4_STAGE
-#undef W4_TRANS
 #undef W4_MUL
 #undef W4_MUL6
-#undef W4_HLOAD
-#undef W4_HLOADS
-#undef W4_HSTORE
 #undef W4_LOADB
 
     // ---- item end: per co-tile, accumulators -> LDS -> one (tile, co) per lane -> Y = A^T M A -> epilogue
-    // exchange + output (conv_wino4.hip): this lane finishes tile 4 (wave & 3) + (lane >> 4), co 16 (wave >> 2) + li.
+    // exchange + output (the rotated write and the round's pieces: conv_wino4.h): this lane finishes tile 4 (wave & 3) + (lane >> 4), co 16 (wave >> 2) + li.
     // Addresses from an opaque copy of the lane id: computed here, not held in registers over the K loop.
     int lane_e = lane;
     asm volatile("" : "+v"(lane_e));
@@ -283,17 +173,10 @@ __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
       const float sh = a.shift[cch];
       const unsigned vo = (unsigned)((((n * a.Ho + y0 + 4 * ty) * a.Wo + x0 + 4 * tx) * Co + cch) * 4);
       float rv[4][4];
-#pragma unroll
-      for (int oa = 0; oa < 4; ++oa)
-#pragma unroll
-        for (int ob = 0; ob < 4; ++ob)
-          rv[oa][ob] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                     rr, has_res ? vo : EGN_OOB, oa * rowpitch + ob * colpitch, 0));
-#define W4_XW(SL, V) w4_xwr2<(SL)*1024>(xwa, (V)[0], (V)[1]); w4_xwr2<(SL)*1024>(xwb, (V)[2], (V)[3]);
-      W4_XW(0, acc[0][3 * r + 0]) W4_XW(1, acc[0][3 * r + 1]) W4_XW(2, acc[0][3 * r + 2])
-      W4_XW(3, acc[1][3 * r + 0]) W4_XW(4, acc[1][3 * r + 1]) W4_XW(5, acc[1][3 * r + 2])
-      W4_XW(6, acc[2][3 * r + 0]) W4_XW(7, acc[2][3 * r + 1]) W4_XW(8, acc[2][3 * r + 2])
-#undef W4_XW
+      W4_RES_LOAD(rv, has_res ? vo : EGN_OOB)
+      w4_xw<0 * 1024>(xwa, xwb, acc[0][3 * r + 0]); w4_xw<1 * 1024>(xwa, xwb, acc[0][3 * r + 1]); w4_xw<2 * 1024>(xwa, xwb, acc[0][3 * r + 2]);
+      w4_xw<3 * 1024>(xwa, xwb, acc[1][3 * r + 0]); w4_xw<4 * 1024>(xwa, xwb, acc[1][3 * r + 1]); w4_xw<5 * 1024>(xwa, xwb, acc[1][3 * r + 2]);
+      w4_xw<6 * 1024>(xwa, xwb, acc[2][3 * r + 0]); w4_xw<7 * 1024>(xwa, xwb, acc[2][3 * r + 1]); w4_xw<8 * 1024>(xwa, xwb, acc[2][3 * r + 2]);
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_waitcnt(0xC07F);
       W4_CLK()    /* round: accumulators written */
@@ -301,35 +184,8 @@ __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
       asm volatile("" ::: "memory");
       W4_CLK()    /* round: exchange barrier passed */
       float yc[4][6];
-#define W4_M(I, J) w4_xrd<(I)*6 + (J)>(xr0, xr1)
-#define W4_COLS(J0)                                                                                     \
-  {                                                                                                     \
-    float ca_[6], cb_[6], ya_[4], yb_[4];                                                               \
-    ca_[0] = W4_M(0, J0); ca_[1] = W4_M(1, J0); ca_[2] = W4_M(2, J0); ca_[3] = W4_M(3, J0); ca_[4] = W4_M(4, J0);  \
-    ca_[5] = W4_M(5, J0);                                                                               \
-    cb_[0] = W4_M(0, J0 + 1); cb_[1] = W4_M(1, J0 + 1); cb_[2] = W4_M(2, J0 + 1); cb_[3] = W4_M(3, J0 + 1);        \
-    cb_[4] = W4_M(4, J0 + 1); cb_[5] = W4_M(5, J0 + 1);                                                 \
-    w4_landed6(ca_, cb_);                                                                               \
-    w4_at(ca_, ya_);                                                                                    \
-    w4_at(cb_, yb_);                                                                                    \
-    _Pragma("unroll") for (int oa = 0; oa < 4; ++oa) { yc[oa][J0] = ya_[oa]; yc[oa][J0 + 1] = yb_[oa]; } \
-  }
-      const unsigned xr1 = xr0 + 18u * 3072u;
-      W4_COLS(0)
-      W4_COLS(2)
-      W4_COLS(4)
-#undef W4_COLS
-#undef W4_M
-#pragma unroll
-      for (int oa = 0; oa < 4; ++oa) {
-        float yo[4];
-        w4_at(yc[oa], yo);
-#pragma unroll
-        for (int ob = 0; ob < 4; ++ob) {
-          const float v = fmaxf(__builtin_fmaf(yo[ob], sc, sh) + rv[oa][ob], act_lo);
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, vo, oa * rowpitch + ob * colpitch, 0);
-        }
-      }
+      W4_XREAD_COLS(3072)
+      W4_ROWS_STORE()
       asm volatile("" ::: "memory");
       W4_CLK()    /* round: output transform done, stores issued */
       __builtin_amdgcn_s_barrier();      // the exchange buffer is free again (next round / next item's halo)
@@ -337,12 +193,5 @@ __device__ __forceinline__ void w4w_body(const ConvArgs& a, int blk, int nblk) {
       W4_CLK()    /* round: end */
     }
   }
-  if constexpr ((ABL & 64) != 0) {
-    __syncthreads();
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res)) +
-                              (size_t)blockIdx.x * (W4_NW * W4_NTK + 1);
-    for (int e = tid; e < W4_NW * W4_NTK; e += W4_NTH) out[1 + e] = sT[e];
-    if (tid == 0) out[0] = (unsigned long long)ntk;
-  }
-#undef W4_CLK
+  if constexpr ((ABL & 64) != 0) w4_stamp_dump<W4_NW, W4_NTK, 1>(a, sT, ntk, tid);
 }

@@ -260,3 +260,30 @@ def test_shared_primitives_are_stated_once():
                     '0x100000000ull +', 'address_space(3)'):
         hits = [name for name, t in text.items() if pattern in t]
         assert len(hits) == 1, (pattern, hits)
+
+
+def test_wino4_item_pipeline_is_stated_once():
+    """The four F(4x4,3x3) bodies (w4_body, w4w_body, w4h_body, w4r_body) share ONE definition of each part of the item
+    pipeline -- stamps, halo pieces, item decode, prologue, transform thirds, the exchange round and the one-dword filter
+    load (csrc/conv_wino4.h) -- so a hazard fix (the vmcnt(0) ties, the opaque lane copy, the natural halo slots, the
+    rotated exchange write) is made once.  W4_XW became the function w4_xw; no body defines a macro of that name."""
+    import glob
+    import os
+    csrc = os.path.join(os.path.dirname(os.path.abspath(engine.__file__)), 'csrc')
+    files = sorted(p for ext in ('*.hip', '*.h', '*.cpp') for p in glob.glob(os.path.join(csrc, ext)))
+    text = {os.path.basename(p): open(p, encoding='utf-8').read() for p in files}
+    for pattern in ('#define W4_CLK(', '#define W4_HLOAD(', '#define W4_HSTORE(', 'void w4_xw(', '#define W4_COLS(',
+                    'buffer_load_dword %0', '#define W4_STAMPS(', 'w4_stamp_dump(const', '#define W4_HLOADS(',
+                    '#define W4_HALO_ELEM(', '#define W4_HALO_SLOTS_NATURAL(', '#define W4_HALO_DOFF(',
+                    '#define W4_ITEM_DECODE(', 'w4_item_region(const', '#define W4_PROLOGUE(', '#define W4_TRANS(',
+                    '#define W4_RES_LOAD(', '#define W4_ROWS_STORE(', 'struct W4B9', 'void w4_vm_landedB(W4B9'):
+        hits = [name for name, t in text.items() if pattern in t]
+        assert hits == ['conv_wino4.h'], (pattern, hits)
+    for pattern in ('#define W4_XW(', '#define W4_M('):
+        hits = [name for name, t in text.items() if pattern in t and name != 'conv_wino4.h']
+        assert not hits, (pattern, hits)
+    # every body goes through the shared parts
+    for name in ('conv_wino4.hip', 'conv_wino4w_body.h', 'conv_wino4h.hip', 'conv_wino4r.hip'):
+        for use in ('W4_STAMPS(', 'W4_ITEM_DECODE(', 'w4_item_region<', 'W4_PROLOGUE(', 'W4_TRANS(', 'W4_HSTORE(',
+                    'W4_RES_LOAD(', 'w4_stamp_dump<'):
+            assert use in text[name], (name, use)
