@@ -174,6 +174,13 @@ SIGNATURES = {
     'egn_overlay_tile_capacity': (_i, []),
     'egn_overlay_draw_u8': (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _i, _i, _p]),
     'egn_overlay_draw_host_u8': (_i, [_p, _p, _i, _p, _p, _i, _i]),
+    'egn_debug_range_ws_bytes': (C.c_long, [_i, _i, _i]),
+    'egn_debug_range_f32': (_i, [_p, _i, _i, _i, _i, _p, C.c_long, _p, _p]),
+    'egn_debug_range_host_f32': (_i, [_p, _i, _i, _i, _i, _p]),
+    'egn_debug_grid_u8': (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, C.c_long, _p]),
+    'egn_debug_grid_host_u8': (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, C.c_long]),
+    'egn_debug_mosaic_u8': (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p, C.c_long, _p]),
+    'egn_debug_mosaic_host_u8': (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p, C.c_long]),
     'egn_program_op_info':(_i,[_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), C.c_char_p, _i]),
 }
 

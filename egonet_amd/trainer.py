@@ -18,8 +18,9 @@ executed: the loss weights come from ``loss_func.comp_dict`` when it has one
 ``cfgs['heatmapModel']['loss_weight_list']``; the learning rate of every epoch is
 read from ``optim.param_groups`` after ``sche.step()``.  For the 'angleregression' head
 (exp_type baselinealpha / baselinetheta) the criterion's class name -- ``MSELoss1D`` / ``SmoothL1Loss1D``,
-function.py:204-228 -- or ``cfgs['heatmapModel']['loss_type']`` selects the native step's ``angle_type``.  Plotting and debug-image
-dumps of the reference are not reproduced.
+function.py:204-228 -- or ``cfgs['heatmapModel']['loss_type']`` selects the native step's ``angle_type``.  The reference's
+debug pictures (``save_debug``, trainer.py:223-234 and :450-466) are composed on the device and written by a background
+thread (``visualization/debug.py``); its loss-curve plotting is not reproduced.
 """
 import gc
 import os
@@ -33,6 +34,7 @@ from .model import FCmodel
 from .model.heatmapModel.hrnet import PoseHighResolutionNet
 from .train_hrnet import HRNetTrainStep
 from .train_lifter import LifterTrainStep
+from .visualization import debug as debug_pictures
 
 
 def get_loader(dataset, cfgs, split, collate_fn=None):
@@ -247,7 +249,21 @@ def evaluate(eval_dataset, model, loss_func, cfgs, logger, evaluator, save=False
     An evaluator with ``device_update = True`` (``metric.criterions.Evaluator`` over the lifter's 3-D metrics) gets
     the CUDA prediction / target as they are -- with ``testing_settings.unnormalize`` also the set's ``statistics``,
     its kernel unnormalises -- instead of the ``.cpu().numpy()`` copies and the host unnormalise.
+    ``testing_settings.save_debug`` with ``exp_type == 'instanceto2d'`` writes the debug pictures of every batch like
+    trainer.py:450-466 (epoch 0, split 'validation'; rank 0 only).
     Returns the mean validation loss (None without ``loss_func``)."""
+    ts = cfgs['testing_settings']
+    writer = debug_pictures.DebugPictureWriter() if ts.get('save_debug', False) and \
+        cfgs.get('exp_type') == 'instanceto2d' and _rank() == 0 else None
+    try:
+        return _evaluate(eval_dataset, model, loss_func, cfgs, logger, evaluator, save, save_path, collate_fn, epoch,
+                         writer)
+    finally:
+        if writer is not None:
+            writer.close()
+
+
+def _evaluate(eval_dataset, model, loss_func, cfgs, logger, evaluator, save, save_path, collate_fn, epoch, writer):
     ts = cfgs['testing_settings']
     unnorm = bool(ts.get('unnormalize', False))
     stats = eval_dataset.statistics if unnorm else None
@@ -269,6 +285,10 @@ def evaluate(eval_dataset, model, loss_func, cfgs, logger, evaluator, save=False
             data, target = data.cuda(), target.cuda()
             weights = weights.cuda() if torch.is_tensor(weights) else weights
         prediction = model(data)
+        if writer is not None:
+            debug_pictures.save_debug_images(0, batch_idx, cfgs, data, meta, target, None, prediction, 'validation',
+                                             writer=writer)
+            logger.info('Saved batch {:d}'.format(batch_idx))
         if loss_func is not None:
             with torch.no_grad():
                 loss = loss_func(prediction, target, weights, meta)
@@ -319,7 +339,12 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
     A mixed batch (``cfgs['ss']``, car_instance.py:1368-1380) passes through as it is: ``data`` holds ``N`` crops, the
     labelled ones first, ``target`` and ``meta['transformed_joints']`` their ``n_fs <= N`` rows; the step takes the
     heat-map and coordinate terms over the labelled prefix and the cross-ratio term over all crops, a metric sees the
-    ``N`` predictions and the ``n_fs`` meta rows, and the logged samples/s counts ``N``."""
+    ``N`` predictions and the ``n_fs`` meta rows, and the logged samples/s counts ``N``.
+    ``save_debug``: on report batches, where the loss is read back, the reference's three debug pictures
+    (``visualization.debug.save_debug_images``, gated by ``training_settings.debug``) are composed on the device and
+    handed to a ``DebugPictureWriter``, closed when the loop ends; heat-map and coordinate heads on rank 0 only -- the
+    angle head and the lifter have no maps and skip silently.  Off (the default), no writer is made and the step's
+    launches are unchanged."""
     ts = cfgs['training_settings']
     total_epochs, report_every = ts['total_epochs'], ts['report_every']
     eval_during = bool(ts.get('eval_during', False)) and valid_dataset is not None
@@ -344,6 +369,7 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
     metric_on_device = metric_func is not None and hasattr(metric_func, 'accumulate')
     x_buffer, y_buffer = [], []
     frozen = False
+    writer = debug_pictures.DebugPictureWriter() if save_debug and is_hc and not is_angle and _rank() == 0 else None
     if eval_during:
         _make_host_group()      # all ranks are here together: the group exists before anyone has to wait in it
     try:
@@ -380,6 +406,7 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
                 # the optional metric runs on EVERY batch and accumulates, like the reference
                 # (trainer.py:200-205); a plain callable decodes on the device and returns a host number, a meter
                 # only launches and is read back where the loss is
+                others = None
                 if metric_func is not None and prediction is not None:
                     if metric_on_device:
                         metric_func.accumulate(prediction, meta, cfgs)
@@ -405,6 +432,9 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
                             logger.info('          metric %.6f (running mean over %d)' % (run_mean, run_cnt))
                     elif acc.count:
                         logger.info('          metric %.6f (running mean over %d)' % (acc.avg, acc.count))
+                    if writer is not None:
+                        debug_pictures.save_debug_images(epoch, batch_idx, cfgs, data, meta, target, others, prediction,
+                                                         'train', writer=writer)
                     x_buffer.append(total_batches * (epoch - 1) + batch_idx)
                     y_buffer.append(lv)
                 if eval_during and epoch > eval_start and batch_idx and eval_every and batch_idx % eval_every == 0:
@@ -434,6 +464,8 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
     finally:
         if frozen:
             gc.unfreeze()
+        if writer is not None:
+            writer.close()
     logger.info('Training finished.')
     return {'model': model, 'batch_idx': x_buffer, 'loss': y_buffer}
 

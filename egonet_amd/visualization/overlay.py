@@ -5,8 +5,8 @@ is a disc -- and csrc/overlay.hip rasterises a whole batch of frames in one laun
     prims  float32 [P, 6]   x0 y0 x1 y1 r a, drawn in list order
     colors uint32  [P]      R | G << 8 | B << 16
 
-Not drawn: text labels (there is no font), dash-dot line styles (the ground-truth cuboid is solid green), the
-matplotlib 3-D scene and the training-time heat-map mosaics.
+Not drawn: text labels (there is no font; the debug pictures' joint numbers are seven-segment capsules,
+visualization/debug.py), dash-dot line styles (the ground-truth cuboid is solid green) and the matplotlib 3-D scene.
 """
 import math
 

@@ -942,6 +942,43 @@ int egn_overlay_draw_u8(void* base, const int64_t* frames_dev, int n_frames, int
 int egn_overlay_draw_host_u8(void* base, const int64_t* frames, int n_frames, const float* prims,
                              const uint32_t* colors, int n_prims, int antialias);
 
+/* ------------------------------------------------------------------------
+ * Training debug pictures (csrc/debug_pictures.hip, definition in csrc/debug_pictures_math.h): the grid of crops and
+ * the heat-map mosaic of libs/visualization/debug.py:51-149, composed into caller-allocated uint8 RGB pictures.  The
+ * pictures are pinned on the header's definition (no cv2 / torchvision pixel parity); markers are drawn afterwards
+ * with the overlay rasteriser above.
+ *
+ * Range: lohi[0] / lohi[1] = minimum / maximum of x [n][c][hw] f32 over the first c_used channels, NaNs ignored, -0
+ *   stored as +0, 0 0 when every value is a NaN.  Two launches (block partials with plain stores, one block folds
+ *   them); min / max are exact, so equal inputs give equal bits.  ws: the ws_bytes query's bytes (-1: bad sizes).
+ *   n * c_used * hw == 0 is a no-op that leaves lohi alone.
+ * Crop value -> grey level: q = trunc(min(255, max(0, 255 (x - lo) / (hi - lo + 1e-5)))) in float64, 0 for a NaN.
+ * Grid (make_grid(img[:, :3], nrow, pad, normalize=True)): out [ymaps (H + pad) + pad][xmaps (W + pad) + pad][3] with
+ *   xmaps = min(nrow, N), ymaps = ceil(N / xmaps); crop k at row (k / xmaps)(H + pad) + pad, column
+ *   (k % xmaps)(W + pad) + pad; padding and empty cells are zeros.  img [N][C][H][W] f32, C >= 3.
+ * Mosaic: out [n h][(J + 1) w][3]; row block i is crop i; tile 0 is the crop's thumbnail (the quantised crop resized
+ *   to w x h, bilinear on the uint8 values with half-pixel centres, rounded half up), tile j + 1 is
+ *   (7 lut[q(maps[i][j])] + 3 thumbnail) / 10 in integers with q(m) = trunc(min(255, max(0, 255 m))), 0 for a NaN.
+ *   maps [n][J][h][w] f32, img holds at least n crops, lut [256][3] u8 (egonet_amd.visualization.debug.jet_lut()).
+ * out rows are `stride` bytes apart; bytes past 3 * width of a row are not touched.  lohi is read on the device.
+ * A zero N / n, crop or map size is a successful no-op; a negative size, C < 3, nrow < 1, a NULL required pointer, a
+ * stride below 3 * width or a picture size past 2^31 - 1: EGN_E_BADARG.  One launch each, added to the launch
+ * counter; no allocation, no synchronisation.  The _host_ entries run the same header as plain loops over HOST
+ * pointers and give the same bytes; they are never used for device tensors.
+ * ---------------------------------------------------------------------- */
+long egn_debug_range_ws_bytes(int n, int c_used, int hw);
+int egn_debug_range_f32(const float* x, int n, int c, int c_used, int hw, void* ws, long ws_bytes, float* lohi,
+                        void* stream);
+int egn_debug_range_host_f32(const float* x, int n, int c, int c_used, int hw, float* lohi);
+int egn_debug_grid_u8(const float* img, int N, int C, int H, int W, int nrow, int pad, const float* lohi,
+                      uint8_t* out, long stride, void* stream);
+int egn_debug_grid_host_u8(const float* img, int N, int C, int H, int W, int nrow, int pad, const float* lohi,
+                           uint8_t* out, long stride);
+int egn_debug_mosaic_u8(const float* img, int C, int H, int W, const float* maps, int n, int J, int h, int w,
+                        const float* lohi, const uint8_t* lut, uint8_t* out, long stride, void* stream);
+int egn_debug_mosaic_host_u8(const float* img, int C, int H, int W, const float* maps, int n, int J, int h, int w,
+                             const float* lohi, const uint8_t* lut, uint8_t* out, long stride);
+
 #ifdef __cplusplus
 }
 #endif

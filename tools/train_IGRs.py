@@ -5,7 +5,7 @@
         [--valid-split-file <stems>] --out <dir> [--epochs 45] [--batch-frames 8] [--eval-every N] [--seed S]
         [--tiny] [--max-steps N] [--workers 4] [--report-every 30] [--lr 1e-3]
         [--exp-type instanceto2d|baselinealpha|baselinetheta] [--loss-type MSELoss1D|SmoothL1Loss1D]
-        [--cr-weight W] [--ss-record FILE --ss-img-root DIR [--ss-max-per-img 6]]
+        [--cr-weight W] [--ss-record FILE --ss-img-root DIR [--ss-max-per-img 6]] [--no-debug-pictures]
 
 Labels + calibration -> ``PoseAnnotBuilder`` (the 2-D pose annotations, built on the device:
 egonet_amd.common.pose_annot) -> ``PoseFrames`` -> ``DataLoader(collate_fn=collate_frames)`` (frames decoded in the
@@ -34,6 +34,12 @@ holds the images under their basenames.  Every labelled frame with fewer than ``
 crops of one random unlabelled frame (``MixedFrames``); the heat-map and coordinate terms see the labelled crops, the
 cross-ratio term and BatchNorm all of them.  ``--cr-weight W`` is the third entry of ``loss_weight_list`` ('None' in the
 shipped file): the weight of the cross-ratio term, which counts from the second epoch on.  The mix needs it.
+
+Like the shipped config (``training_settings.debug``: ``save`` and its three ``save_*`` keys, all True) the key-point
+run writes the reference's debug pictures on every report batch -- ``<out>/intermediate_results/train/
+<epoch>_<batch>_{keypoints,hm_gt,hm_pred}.jpg``, composed on the device and encoded on a background thread
+(egonet_amd/visualization/debug.py); ``--no-debug-pictures`` sets ``debug.save`` to False.  The angle baselines have
+no maps and write none (train_IGRs.py:83-88).
 """
 import argparse
 import json
@@ -82,11 +88,15 @@ def igr_cfgs(a):
                training_settings={'total_epochs': a.epochs, 'batch_size': a.batch_frames, 'num_threads': a.workers,
                                   'shuffle': True, 'use_target_weight': False, 'report_every': a.report_every,
                                   'eval_every': a.eval_every, 'eval_during': a.eval_every > 0,
-                                  'eval_metrics': [metric], 'plot_loss': False},
+                                  'eval_metrics': [metric], 'plot_loss': False,
+                                  'debug': {'save': not getattr(a, 'no_debug_pictures', False), 'save_images_kpts': True,
+                                            'save_hms_gt': True, 'save_hms_pred': True}},
                # the validation batches are built by a device front end inside collate_fn: no worker processes
                testing_settings={'batch_size': a.batch_frames, 'num_threads': 0, 'shuffle': False,
                                  'apply_dropout': False, 'unnormalize': False, 'arg_max': 'hard',
                                  'eval_metrics': [metric], 'alpha_mode': 'proj'})
+    if getattr(a, 'out', None):
+        cfg['dirs'] = {'output': a.out}
     if getattr(a, 'ss_record', None):
         cfg['ss'] = {'flag': True, 'record_path': a.ss_record, 'img_root': a.ss_img_root,
                      'max_per_img': a.ss_max_per_img}
@@ -182,6 +192,8 @@ def main(argv=None):
     ap.add_argument('--ss-img-root', default=None, metavar='DIR', help='directory of the unlabelled images')
     ap.add_argument('--ss-max-per-img', type=int, default=6,
                     help='a labelled frame with fewer cars is filled up to this many crops from an unlabelled frame')
+    ap.add_argument('--no-debug-pictures', action='store_true',
+                    help='training_settings.debug.save = False: no key-point / heat-map pictures on report batches')
     a = ap.parse_args(argv)
     if bool(a.ss_record) != bool(a.ss_img_root):
         ap.error('--ss-record and --ss-img-root go together')
@@ -232,9 +244,11 @@ def main(argv=None):
                                     epoch=epoch)
 
     optim, sche = trainer.prepare_optim(model, cfgs)
+    # train_IGRs.py:83-88: the angle baselines save no debug pictures, the key-point model what its config says
+    save_debug = False if angle else bool(cfgs['training_settings']['debug']['save'])
     record = trainer.train(train_set, model, loss_func, optim, sche, cfgs, logger,
                            metric_func=AngleErrorMeter(cfgs) if angle else DistanceSrcMeter(cfgs),
-                           valid_dataset=valid_frames, evaluate_fn=evaluate_fn,
+                           valid_dataset=valid_frames, evaluate_fn=evaluate_fn, save_debug=save_debug,
                            sample_builder=train_samples.TrainSampleBuilder(cfgs, split='train', target=target))
     if a.valid_split_file:                                  # trainer.py:395-513 over the validation split
         evaluate_fn(valid_frames, model, None)
