@@ -18,6 +18,22 @@
 // Epilogue (the project's): acc * scale + shift, + residual, ReLU / none, through LDS to float4 along the channel axis,
 // 16-byte buffer stores; out-of-range pixels get the OOB offset (loads 0, drops the store), as conv_common.h does.
 // No BatchNorm statistics, no ticket words, no K split.
+//
+// STRIDE 2 (precision = 'f16s2', egn_conv3x3s2_h_applies) is the same kernel with S = 2: the same filter pack (its layout
+// does not know the stride), the same chunks, K steps, staging and epilogue (no residual: no stride-2 layer has one).  A
+// TH x TW output tile (8 x 8, 64 pixels, for both channel tiles; at least 2 x 2) brings a (2 TH + 1) x (2 TW + 1) halo, 1.13x
+// its input pixels at 8 x 8, and the A fragment of output pixel (oy, ox) and tap (ky, kx) is halo pixel (2 oy + ky, 2 ox + kx).
+// Bank arithmetic (ds_read_b128: a 16-byte quad q = (address / 16) % 16, the 16 rows of a fragment read must hit 16 quads;
+// a pixel is 7 quads).  Stride 1: row li of a fragment is pixel x = li, quad 7 li: 16 different ones.  Stride 2 read the
+// same way: halo pixel 2 li, quad 14 li -- even quads only, every one twice.  So
+//   1. a halo row is stored SPLIT BY COLUMN PARITY: the TW + 1 even columns, then the TW odd ones.  Tap kx of output
+//      column x is then entry (kx & 1) (TW + 1) + (kx >> 1) + x of the row: consecutive x are consecutive entries, 7 quads
+//      apart, as at stride 1 (x = 0..7: quads 0 7 14 5 12 3 10 1);
+//   2. the two tile rows inside a 16-row fragment (TW = 8) are y and y + TH / 2, not y and y + 1 (h_tile_row): 2 * 4 halo
+//      rows x 17 pixels x 7 quads = 952 = 8 (mod 16), the other eight quads (8 15 6 13 4 11 2 9).  Rows y and y + 1 would be
+//      2 x 17 x 7 = 238 = 14 (mod 16) apart and collide on six of the eight.
+// Both hold for the tiles HRNet-W48 has (outputs of 8 x 8 and more); smaller tiles are correct, not conflict-free.  (The
+// arithmetic is per channel group, as at stride 1: the hardware's 16-lane groups of a ds_read_b128 mix two of them.)
 #include <string.h>
 
 #include <atomic>
@@ -46,13 +62,24 @@ struct ConvHTile {
   static constexpr int SB = 5;
   // the next chunk's batch 0 in flight during the products: not for the 48-output-channel tile, whose layers in HRNet have
   // one chunk (48 -> 48) and whose staging registers, live across the products, would cost it a wave per SIMD
-  static constexpr bool PREFETCH = TM != 128;
+  // (the same holds for the stride-2 64 x 48 tile)
+  static constexpr bool PREFETCH = TN == 96;
 };
 
-template <int WM, int WN, int MT, int NT>
+// Stride 2: the row bits of a tile row index, rotated right by one.  The 16 rows of an A fragment are then 8 columns of
+// the tile rows y and y + TH / 2 instead of y and y + 1 (the bank arithmetic in the header); a bijection on [0, TH).
+template <int S>
+__device__ __forceinline__ int h_tile_row(int r, int lth) {
+  return S == 1 || lth == 0 ? r : (r >> 1) | ((r & 1) << (lth - 1));
+}
+
+template <int S, int WM, int WN, int MT, int NT>
 __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
   using T = ConvHTile<WM, WN, MT, NT>;
   static_assert(WM * WN == 4, "four waves");
+  // stride 2: the 289-pixel halo of an 8 x 8 tile is 13.5 float4 per thread: two batches of 7 (two round trips to memory,
+  // not three; one batch of 14 spills)
+  constexpr int SB = S == 1 ? T::SB : 7;
   extern __shared__ float4 smem_f4[];
   char* smem = reinterpret_cast<char*>(smem_f4);
   unsigned* sOff = reinterpret_cast<unsigned*>(smem);        // [npix] byte offset of halo pixel (channel 0) in x, or EGN_OOB
@@ -78,8 +105,9 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
     const int b = p / (a.HH * a.HW);
     const int rem = p - b * (a.HH * a.HW);
     const int hy = rem / a.HW;
-    const int hx = rem - hy * a.HW;
-    const int n = n_base + b, iy = oy0 + hy - 1, ix = ox0 + hx - 1;
+    const int col = rem - hy * a.HW;
+    const int hx = S == 1 ? col : (col <= a.TW ? 2 * col : 2 * (col - a.TW) - 1);   // stride 2: even columns first
+    const int n = n_base + b, iy = S * oy0 + hy - 1, ix = S * ox0 + hx - 1;
     const bool ok = n < a.N && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
     sOff[p] = ok ? (unsigned)((n * a.H + iy) * a.W + ix) * (unsigned)(a.Cin * 4) : EGN_OOB;
   }
@@ -91,8 +119,8 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
     const int m = (wm * MT + mt) * 16 + li;
     const int b = m >> (a.lth + a.ltw);
     const int rem = m & px_mask;
-    const int y = rem >> a.ltw, x = rem & (a.TW - 1);
-    abase[mt] = a.tab_bytes + ((b * a.HH + y) * a.HW + x) * H_PIXB;      // from smem
+    const int y = h_tile_row<S>(rem >> a.ltw, a.lth), x = rem & (a.TW - 1);
+    abase[mt] = a.tab_bytes + ((b * a.HH + S * y) * a.HW + x) * H_PIXB;      // from smem
   }
   // sKoff[4 ks + g]: LDS byte offset of the 8 channels a lane of group g reads at K step ks (tap and channel group of
   // k = 8 (4 ks + g)); -1 past k = 432.  A table in LDS, not 14 registers per lane: the kernel keeps 4 waves per SIMD.
@@ -101,7 +129,8 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
   if (tid < H_KS * 4) {
     const int tap = tid / 6, c8 = tid - tap * 6;
     const int ky = tap / 3, kx = tap - ky * 3;
-    sKoff[tid] = tid < 54 ? (ky * a.HW + kx) * H_PIXB + c8 * 16 : -1;
+    const int kcol = S == 1 ? kx : (kx & 1) * (a.TW + 1) + (kx >> 1);   // stride 2: halo column 2 x + kx of the split row
+    sKoff[tid] = tid < 54 ? (ky * a.HW + kcol) * H_PIXB + c8 * 16 : -1;
   }
 
   f32x4 acc[MT][NT];
@@ -122,14 +151,14 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) wb[nt] = (ct * (T::TN / 16) + wn * NT + nt) * nchunk * (H_KS * 1024);
 
-  // Staging of a chunk's halo tile, T::SB float4 per thread and batch: all loads of a batch are issued before the first
+  // Staging of a chunk's halo tile, SB float4 per thread and batch: all loads of a batch are issued before the first
   // is converted, and (T::PREFETCH) batch 0 of the NEXT chunk is issued before the current chunk's products, so its HBM latency
   // hides behind them (an 8 x 8 tile is one batch, 8 x 16 two; tiles of many tiny images have more).
-  f32x4 sv[T::SB];
+  f32x4 sv[SB];
   auto stage_load = [&](int chunk, int batch) {
 #pragma unroll
-    for (int j = 0; j < T::SB; ++j) {
-      const int idx = (batch * T::SB + j) * 256 + tid;
+    for (int j = 0; j < SB; ++j) {
+      const int idx = (batch * SB + j) * 256 + tid;
       const int p = idx / (H_CK / 4);
       const int c4 = idx - p * (H_CK / 4);
       const unsigned off = idx < nstage ? sOff[p] : EGN_OOB;
@@ -138,8 +167,8 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
   };
   auto stage_store = [&](int batch) {
 #pragma unroll
-    for (int j = 0; j < T::SB; ++j) {
-      const int idx = (batch * T::SB + j) * 256 + tid;
+    for (int j = 0; j < SB; ++j) {
+      const int idx = (batch * SB + j) * 256 + tid;
       const int p = idx / (H_CK / 4);
       const int c4 = idx - p * (H_CK / 4);
       const f32x4 v = sv[j];
@@ -151,10 +180,22 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
       if (idx < nstage) *reinterpret_cast<f16x4*>(slab + p * H_PIXB + c4 * 8) = h;
     }
   };
-  const int nbatch = (nstage + T::SB * 256 - 1) / (T::SB * 256);
+  const int nbatch = (nstage + SB * 256 - 1) / (SB * 256);
   __syncthreads();   // sOff is written
   if (T::PREFETCH) stage_load(0, 0);
+  // Filter fragments in flight: two K steps; FOUR for the stride-2 64 x 48 tile, whose 3 MFMAs per step hide nothing of an
+  // L2 round trip -- its layers (48 -> 48, one chunk, small grids) are bound by the block's latency, so the first ones are
+  // also issued before the halo is staged and travel beside it.
+  constexpr int BD = S == 2 && MT == 1 ? 4 : 2;
   for (int chunk = 0; chunk < nchunk; ++chunk) {
+    f16x8 bf[BD][NT];
+    auto b_preload = [&]() {
+#pragma unroll
+      for (int d = 0; d < BD - 1; ++d)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) bf[d][nt] = h_load_b(rw, wlane, wb[nt] + chunk * (H_KS * 1024) + d * 1024);
+    };
+    if (BD > 2) b_preload();
     if (chunk) __syncthreads();   // the previous chunk's fragment reads are done
     if (!T::PREFETCH) stage_load(chunk, 0);
     stage_store(0);
@@ -165,15 +206,13 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
     __syncthreads();
     if (T::PREFETCH && chunk + 1 < nchunk) stage_load(chunk + 1, 0);
 
-    f16x8 bf[2][NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) bf[0][nt] = h_load_b(rw, wlane, wb[nt] + chunk * (H_KS * 1024));
+    if (BD == 2) b_preload();
 #pragma unroll
     for (int ks = 0; ks < H_KS; ++ks) {
-      if (ks + 1 < H_KS) {
+      if (ks + BD - 1 < H_KS) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
-          bf[(ks + 1) & 1][nt] = h_load_b(rw, wlane, wb[nt] + chunk * (H_KS * 1024) + (ks + 1) * 1024);
+          bf[(ks + BD - 1) % BD][nt] = h_load_b(rw, wlane, wb[nt] + chunk * (H_KS * 1024) + (ks + BD - 1) * 1024);
       }
       f16x8 af[MT];
       const int koff = sKoff[ks * 4 + g];
@@ -183,7 +222,7 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt], bf[ks & 1][nt], acc[mt][nt], 0, 0, 0);
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt], bf[ks % BD][nt], acc[mt][nt], 0, 0, 0);
     }
   }
 
@@ -201,7 +240,7 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
       for (int r = 0; r < 4; ++r) sC[(mt * 16 + g * 4 + r) * T::SC_LD + nt * 16 + li] = acc[mt][nt][r] * sc + sh;
   }
   __syncthreads();
-  const unsigned ybytes = (unsigned)((size_t)a.N * a.H * a.W * a.Cout * 4);
+  const unsigned ybytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * a.Cout * 4);
   const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, ybytes, EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rr =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, ybytes, EGN_RSRC_WORD3);
@@ -214,9 +253,9 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
     const int m = wm * MT * 16 + row;
     const int b = m >> (a.lth + a.ltw);
     const int rem = m & px_mask;
-    const int n = n_base + b, oy = oy0 + (rem >> a.ltw), ox = ox0 + (rem & (a.TW - 1));
-    const bool ok = n < a.N && oy < a.H && ox < a.W;
-    const unsigned voff = ok ? (unsigned)(((n * a.H + oy) * a.W + ox) * a.Cout + cbase + c4 * 4) * 4u : EGN_OOB;
+    const int n = n_base + b, oy = oy0 + h_tile_row<S>(rem >> a.ltw, a.lth), ox = ox0 + (rem & (a.TW - 1));
+    const bool ok = n < a.N && oy < a.Ho && ox < a.Wo;
+    const unsigned voff = ok ? (unsigned)(((n * a.Ho + oy) * a.Wo + ox) * a.Cout + cbase + c4 * 4) * 4u : EGN_OOB;
     f32x4 v = *reinterpret_cast<const f32x4*>(&sC[row * T::SC_LD + c4 * 4]);
     if (a.res) v += egn_buf_load16(rr, voff);
     if (a.act == EGN_ACT_RELU) {
@@ -250,22 +289,38 @@ extern "C" long egn_conv3x3_h_wpack_bytes(int Cin, int Cout) {
   return (long)(Cout / 16) * (Cin / H_CK) * H_KS * 64 * 16;
 }
 
-int egn_conv_h_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act) {
-  if (!egn_conv3x3_h_applies(N, H, W, Cin, Cin, Cout, Cout, has_res, act)) return EGN_E_BADARG;
+// Host-only: 1 where the family runs the layer at STRIDE 2 (input N x H x W, output (H - 1) / 2 + 1 x (W - 1) / 2 + 1).  As
+// above without a residual: no stride-2 layer of HRNet has one.  256 -> 96 (transition1) is refused like 256 -> 48.
+extern "C" int egn_conv3x3s2_h_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int act) {
+  if (N < 1 || H < 2 || W < 2 || !h_width(Cin) || !h_width(Cout) || cs_in != Cin || cs_out != Cout) return 0;
+  if (act != EGN_ACT_NONE && act != EGN_ACT_RELU) return 0;
+  const long long pxo = (long long)N * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1);
+  if ((long long)N * H * W * Cin * 4 >= (1ll << 31) || pxo * Cout * 4 >= (1ll << 31)) return 0;
+  return 1;
+}
+
+int egn_conv_h_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act, int stride) {
+  if (stride == 1 ? !egn_conv3x3_h_applies(N, H, W, Cin, Cin, Cout, Cout, has_res, act)
+                  : stride != 2 || has_res || !egn_conv3x3s2_h_applies(N, H, W, Cin, Cin, Cout, Cout, act))
+    return EGN_E_BADARG;
   memset(&a, 0, sizeof(a));
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.act = act;
-  a.wide = Cout % 96 == 0;                           // 64 pixels x 96 channels, else 128 pixels x 48 channels
-  const int TM = a.wide ? 64 : 128;
-  a.TH = h_pow2_ceil(H) < 8 ? h_pow2_ceil(H) : 8;
-  a.TW = h_pow2_ceil(W) < TM / 8 ? h_pow2_ceil(W) : TM / 8;
+  a.stride = stride; a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1;
+  a.wide = Cout % 96 == 0;                           // 64 pixels x 96 channels, else 128 (stride 2: 64) pixels x 48 channels
+  const int TM = a.wide || stride == 2 ? 64 : 128;
+  // stride 2: at least 2 x 2, so that the 64 images of a tile of 1 x 1 outputs do not bring 64 3 x 3 halos (65 KiB)
+  const int th = h_pow2_ceil(a.Ho) < stride ? stride : h_pow2_ceil(a.Ho), tw = h_pow2_ceil(a.Wo) < stride ? stride : h_pow2_ceil(a.Wo);
+  a.TH = th < 8 ? th : 8;
+  a.TW = tw < TM / 8 ? tw : TM / 8;
   a.TNB = TM / (a.TH * a.TW);
   a.lth = h_log2(a.TH); a.ltw = h_log2(a.TW);
-  a.HH = a.TH + 2; a.HW = a.TW + 2;
+  a.HH = stride * a.TH + 3 - stride; a.HW = stride * a.TW + 3 - stride;
   a.npix = a.TNB * a.HH * a.HW;
-  a.tiles_x = (W + a.TW - 1) / a.TW;
-  a.tiles_y = (H + a.TH - 1) / a.TH;
+  a.tiles_x = (a.Wo + a.TW - 1) / a.TW;
+  a.tiles_y = (a.Ho + a.TH - 1) / a.TH;
   a.tab_bytes = (a.npix * 4 + 15) / 16 * 16 + 16 + H_KS * 4 * 4;   // halo offsets, 16 zero bytes, the K-step offsets (224 bytes)
-  const int epi = a.wide ? ConvHTile<2, 2, 2, 3>::EPI_BYTES : ConvHTile<4, 1, 2, 3>::EPI_BYTES;
+  const int epi = a.wide ? ConvHTile<2, 2, 2, 3>::EPI_BYTES
+                         : (stride == 2 ? ConvHTile<4, 1, 1, 3>::EPI_BYTES : ConvHTile<4, 1, 2, 3>::EPI_BYTES);
   const int halo = a.npix * H_PIXB;
   a.lds_bytes = a.tab_bytes + (halo > epi ? halo : epi);
   const long long blocks = (long long)a.tiles_x * a.tiles_y * ((N + a.TNB - 1) / a.TNB) * (Cout / (a.wide ? 96 : 48));
@@ -276,10 +331,14 @@ int egn_conv_h_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int ha
 
 int egn_conv_h_launch(const ConvHArgs& a, hipStream_t stream) {
   if (!a.x || !a.w || !a.scale || !a.shift || !a.y) return EGN_E_BADARG;
-  if (a.wide)
-    hipLaunchKernelGGL((conv_h_kernel<2, 2, 2, 3>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);
+  if (a.stride == 2 && a.wide)
+    hipLaunchKernelGGL((conv_h_kernel<2, 2, 2, 2, 3>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);
+  else if (a.stride == 2)
+    hipLaunchKernelGGL((conv_h_kernel<2, 4, 1, 1, 3>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);
+  else if (a.wide)
+    hipLaunchKernelGGL((conv_h_kernel<1, 2, 2, 2, 3>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);
   else
-    hipLaunchKernelGGL((conv_h_kernel<4, 1, 2, 3>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);
+    hipLaunchKernelGGL((conv_h_kernel<1, 4, 1, 2, 3>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);
   EGN_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -291,8 +350,18 @@ extern "C" int egn_conv3x3_h_f32(const float* x, const void* wpack_f16, const fl
                                  void* stream) {
   g_egn_direct_convs.fetch_add(1, std::memory_order_relaxed);
   ConvHArgs a;
-  int rc = egn_conv_h_plan(a, N, H, W, Cin, Cout, res != nullptr, act);
+  int rc = egn_conv_h_plan(a, N, H, W, Cin, Cout, res != nullptr, act, 1);
   if (rc) return rc;
   a.x = x; a.w = wpack_f16; a.scale = scale; a.shift = shift; a.res = res; a.y = y;
+  return egn_conv_h_launch(a, (hipStream_t)stream);
+}
+
+extern "C" int egn_conv3x3s2_h_f32(const float* x, const void* wpack_f16, const float* scale, const float* shift, float* y,
+                                   int N, int H, int W, int Cin, int Cout, int act, void* stream) {
+  g_egn_direct_convs.fetch_add(1, std::memory_order_relaxed);
+  ConvHArgs a;
+  int rc = egn_conv_h_plan(a, N, H, W, Cin, Cout, 0, act, 2);
+  if (rc) return rc;
+  a.x = x; a.w = wpack_f16; a.scale = scale; a.shift = shift; a.y = y;
   return egn_conv_h_launch(a, (hipStream_t)stream);
 }

@@ -178,23 +178,26 @@ constexpr int EGN_PAIR_CFG_A = 86, EGN_PAIR_CFG_B = 82;
 int egn_conv_pair_plan(const ConvArgs* a, const ConvArgs* b, int cus, int* blocks_a, int* blocks_b);
 int egn_conv_launch_wino4_pair(ConvArgs a, ConvArgs b, int cus, hipStream_t stream);   // cus <= 0: the device's
 
-// The f16-operand 3x3 / stride 1 / pad 1 family (conv_h.hip): beside the config table, planned by its own predicate.
+// The f16-operand 3x3 / pad 1 family (conv_h.hip), stride 1 and stride 2: beside the config table, planned by its own
+// predicates.
 struct ConvHArgs {
   const float* x;
   const void* w;       // engine.pack_conv_weight_f16
   const float* scale;
   const float* shift;
-  const float* res;
+  const float* res;    // stride 1 only
   float* y;
   int N, H, W, Cin, Cout, act;
-  int wide;            // 1: 64 pixels x 96 channels per block, 0: 128 pixels x 48 channels
+  int stride;          // 1 or 2
+  int Ho, Wo;          // output size: (H - 1) / stride + 1, (W - 1) / stride + 1
+  int wide;            // 1: 64 pixels x 96 channels per block, 0: 128 (stride 2: 64) pixels x 48 channels
   int TH, TW, TNB;     // output tile (powers of two): TNB images x TH rows x TW cols
   int lth, ltw;        // log2 of TH / TW
-  int HH, HW, npix;    // halo tile per image, halo pixels per block
+  int HH, HW, npix;    // halo tile per image (stride * T + 3 - stride a side), halo pixels per block
   int tiles_x, tiles_y;
   int tab_bytes, lds_bytes, blocks;
 };
-int egn_conv_h_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act);   // host-only
+int egn_conv_h_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act, int stride);   // host-only
 int egn_conv_h_launch(const ConvHArgs& a, hipStream_t stream);
 
 // adds n to egn_launch_count() (program.hip): entry points outside programs that want their launches provable

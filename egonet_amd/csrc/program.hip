@@ -161,7 +161,7 @@ extern "C" int egn_conv_plan_query(int N, int H, int W, int Cin, int cs_in, int 
 // programs
 // ---------------------------------------------------------------------------
 enum OpKind { OP_CONV = 1, OP_FUSE = 2, OP_NCHW2NHWC = 3, OP_NHWC2NCHW = 4, OP_RAMPS = 5, OP_DECODE = 6,
-              OP_FORK = 7, OP_JOIN = 8, OP_PIXSHUF = 9, OP_PWPAIR = 10, OP_CONVPAIR = 11, OP_CONVH = 12 };
+              OP_FORK = 7, OP_JOIN = 8, OP_PIXSHUF = 9, OP_PWPAIR = 10, OP_CONVPAIR = 11, OP_CONVH = 12, OP_CONVH2 = 13 };
 constexpr int kMaxLanes = 4;  // concurrent launch lanes (HRNet has at most 4 branches)
 
 struct Op {
@@ -170,7 +170,7 @@ struct Op {
   // conv
   ConvArgs conv;
   ConvArgs conv2;  // OP_CONVPAIR: the second convolution (refs r[6..11])
-  ConvHArgs convh; // OP_CONVH (conv_h.hip)
+  ConvHArgs convh; // OP_CONVH, OP_CONVH2 (conv_h.hip)
   int cfg;
   egn_ref r[12];  // pointer refs, meaning depends on kind
   // generic ints
@@ -421,7 +421,7 @@ extern "C" int egn_program_add_conv3x3_h(egn_program* p, egn_ref x, egn_ref wpac
   if (!p) return EGN_E_BADARG;
   Op op;
   op.kind = OP_CONVH;
-  int rc = egn_conv_h_plan(op.convh, N, H, W, Cin, Cout, res.slot >= 0, act);
+  int rc = egn_conv_h_plan(op.convh, N, H, W, Cin, Cout, res.slot >= 0, act, 1);
   if (rc) return rc;
   op.cfg = 0;
   const egn_ref refs[6] = {x, wpack, scale, shift, res, y};
@@ -431,6 +431,28 @@ extern "C" int egn_program_add_conv3x3_h(egn_program* p, egn_ref x, egn_ref wpac
   }
   op.flops = 2.0 * 9.0 * N * H * W * (double)Cout * Cin;
   op.bytes = 4.0 * N * H * W * (Cin + Cout * (res.slot >= 0 ? 2.0 : 1.0)) + 2.0 * 9.0 * Cout * Cin;
+  op.lane = p->cur_lane;
+  p->ops.push_back(op);
+  return 0;
+}
+
+// its stride-2 sibling (egn_conv3x3s2_h_f32) as one op; H, W are the input size; no residual
+extern "C" int egn_program_add_conv3x3s2_h(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
+                                           egn_ref y, int N, int H, int W, int Cin, int Cout, int act) {
+  if (!p) return EGN_E_BADARG;
+  Op op;
+  op.kind = OP_CONVH2;
+  int rc = egn_conv_h_plan(op.convh, N, H, W, Cin, Cout, 0, act, 2);
+  if (rc) return rc;
+  op.cfg = 0;
+  const egn_ref refs[6] = {x, wpack, scale, shift, egn_ref{-1, 0}, y};
+  for (int k = 0; k < 6; ++k) {
+    if (k != 4 && (!ref_ok(p, refs[k]) || refs[k].slot < 0)) return EGN_E_BADARG;
+    op.r[k] = refs[k];
+  }
+  const double pxo = (double)N * op.convh.Ho * op.convh.Wo;
+  op.flops = 2.0 * 9.0 * pxo * Cout * Cin;
+  op.bytes = 4.0 * ((double)N * H * W * Cin + pxo * Cout) + 2.0 * 9.0 * Cout * Cin;
   op.lane = p->cur_lane;
   p->ops.push_back(op);
   return 0;
@@ -596,7 +618,8 @@ static int launch_op(egn_program* p, Op& op, hipStream_t s) {
       a.y = (float*)resolve(p, op.r[5]);   b.y = (float*)resolve(p, op.r[11]);
       return egn_conv_launch_wino4_pair(a, b, op.i[0], s);
     }
-    case OP_CONVH: {
+    case OP_CONVH:
+    case OP_CONVH2: {
       ConvHArgs a = op.convh;
       a.x = (const float*)resolve(p, op.r[0]);
       a.w = resolve(p, op.r[1]);

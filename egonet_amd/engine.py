@@ -31,7 +31,13 @@ from .filters import (CK, H_CK, H_KS, _round_up, pack_conv_weight, wino_cot, pac
 ACT_RES_AFTER = 0x10
 BN_EPS_DEFAULT = 1e-5
 SLOT_ARENA, SLOT_WEIGHTS, SLOT_USER0 = 0, 1, 2
-PRECISIONS = ('f32', 'f16')
+PRECISIONS = ('f32', 'f16', 'f16s2')
+# (cin, cout) classes of 3x3 stride-2 layers that precision = 'f16s2' leaves on their fp32 kernels because the f16-operand
+# op was measured not to win on them (tools/precision_bench.py --s2); empty unless a measurement fills it.
+#   48 -> 48: faster at 64 crops (64^2 input 35.7 -> 19.0 us, 32^2 input 14.7 -> 9.9 us) but SLOWER beyond the spread at 16
+#   crops on the 32^2 input: fp32 (cfg 85) 7.8 us (spread 0.9), f16-operand op 8.9 us (spread 0.7) -- 64 blocks, the
+#   latency of one block.  (64^2 input at 16 crops: 14.7 -> 9.6 us.)
+F16S2_FP32_CLASSES = ((48, 48),)
 
 
 def _h_applies(n, h, w, cin, cs_in, cout, cs_out, has_res, act):
@@ -53,18 +59,40 @@ def f16_eligible(conv, n, h, w):
     return _h_applies(n, h, w, cin, cin, cout, cout, False, ACT_RELU)
 
 
+def _h2_applies(n, h, w, cin, cs_in, cout, cs_out, act):
+    return (cin, cout) not in F16S2_FP32_CLASSES and \
+        bool(_lib.lib().egn_conv3x3s2_h_applies(n, h, w, cin, cs_in, cout, cs_out, act))
+
+
+def f16s2_eligible(conv, n, h, w):
+    """THE rule for which layers precision = 'f16s2' moves to the f16-operand kernel BESIDE those ``f16_eligible`` names:
+    ``conv`` is a 3x3 / stride 2 / pad 1 nn.Conv2d without bias, groups or dilation, the host-only predicate
+    egn_conv3x3s2_h_applies takes its [n, Cin, h, w] input, and its class is not in ``F16S2_FP32_CLASSES``."""
+    if not isinstance(conv, nn.Conv2d):
+        return False
+    if (tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation), conv.groups) != \
+            ((3, 3), (2, 2), (1, 1), (1, 1), 1) or conv.bias is not None or conv.padding_mode != 'zeros':
+        return False
+    cin, cout = conv.in_channels, conv.out_channels
+    return _h2_applies(n, h, w, cin, cin, cout, cout, ACT_RELU)
+
+
 class f16_emulation(object):
     """Context manager: the torch graph of ``model`` computing what precision = 'f16' computes, up to the fp32 summation
     order -- every ``f16_eligible`` convolution sees its input as f16(clamp(x, +-65504)) and its filter as f16(w), both
     round-to-nearest-even and widened back to fp32.  The measuring stick of the mode's network-level error (CPU or any
-    device; tests/golden/make_f16_bounds.py, tools/precision_bench.py), never a way to run the network."""
+    device; tests/golden/make_f16_bounds.py, tools/precision_bench.py), never a way to run the network.
+    ``precision='f16s2'`` also rounds the operands of the ``f16s2_eligible`` convolutions."""
 
-    def __init__(self, model):
-        self.model, self.handles, self.saved, self.hit = model, [], {}, []
+    def __init__(self, model, precision='f16'):
+        if precision not in PRECISIONS[1:]:
+            raise ValueError("f16_emulation: precision must be 'f16' or 'f16s2', got %r" % (precision,))
+        self.model, self.handles, self.saved, self.hit, self.s2 = model, [], {}, [], precision == 'f16s2'
 
     def _pre(self, mod, args):
         x = args[0]
-        if x.dim() != 4 or not f16_eligible(mod, x.shape[0], x.shape[2], x.shape[3]):
+        if x.dim() != 4 or not (f16_eligible(mod, x.shape[0], x.shape[2], x.shape[3]) or
+                                (self.s2 and f16s2_eligible(mod, x.shape[0], x.shape[2], x.shape[3]))):
             return None
         self.saved[mod] = mod.weight.data
         mod.weight.data = mod.weight.data.half().float()
@@ -153,6 +181,7 @@ class _Recorder(object):
         self.region = 0        # fork/join regions are totally ordered
         self.cur_lane = 0      # launch lane inside the current region
         self.f16 = False       # precision = 'f16': eligible 3x3 convs are recorded as 'convh' ops (csrc/conv_h.hip)
+        self.f16s2 = False     # precision = 'f16s2': ... and eligible 3x3 stride-2 convs as 'convh2' ops
 
     def _push(self, kind, op):
         op['region'], op['lane'] = self.region, self.cur_lane
@@ -221,6 +250,13 @@ class _Recorder(object):
             self._touch(x, res, dst)
             self._push('convh', op)
             return dst
+        if self.f16s2 and self.takes_f16s2(x, weight, bias, act, res, stride, pad, out_nchw, cout_cs, dst_given):
+            scale, shift = fold_scale_shift(cout, None, bn)
+            op = dict(x=x, w=self.weight(pack_conv_weight_f16(weight)), scale=self.weight(scale), shift=self.weight(shift),
+                      y=dst, cin=cin, cout=cout, act=act, tag=tag)
+            self._touch(x, dst)
+            self._push('convh2', op)
+            return dst
         scale, shift = fold_scale_shift(cout, bias, bn)
         # the filter is packed when the program is built: the layout depends on the tile
         # configuration the tuner picks for the shape (direct vs Winograd kernels)
@@ -238,6 +274,15 @@ class _Recorder(object):
         if (kh, kw, stride, pad) != (3, 3, 1, 1) or bias is not None or out_nchw or cout_cs is not None or dst_given:
             return False
         return _h_applies(x.n, x.h, x.w, cin, x.cs, cout, _round_up(cout, 4), res is not None, act)
+
+    @staticmethod
+    def takes_f16s2(x, weight, bias, act, res, stride, pad, out_nchw=False, cout_cs=None, dst_given=False):
+        """``f16s2_eligible`` on a recorded layer: its C predicate, asked with the layer's own epilogue."""
+        cout, cin, kh, kw = weight.shape
+        if (kh, kw, stride, pad) != (3, 3, 2, 1) or bias is not None or res is not None or out_nchw or \
+                cout_cs is not None or dst_given:
+            return False
+        return _h2_applies(x.n, x.h, x.w, cin, x.cs, cout, _round_up(cout, 4), act)
 
     def conv_pair(self, xa, conv_a, bn_a, act_a, res_a, xb, conv_b, bn_b, act_b, res_b, tag=''):
         """Two independent 3x3 / stride 1 / pad 1 convolutions (+ folded BatchNorm, residual, ReLU) as ONE launch
@@ -464,6 +509,13 @@ class Program(object):
             flops = 2.0 * m * op['cout'] * op['cin'] * 9
             nbytes = 4.0 * m * (op['cin'] + op['cout'] * (2 if op['res'] is not None else 1)) + 2.0 * op['cout'] * op['cin'] * 9
             klass = 'conv3x3h %d->%d@%dx%d' % (op['cin'], op['cout'], x.h, x.w)
+        elif kind == 'convh2':
+            x, y = op['x'], op['y']
+            _lib.check(L.egn_program_add_conv3x3s2_h(h, x.ref(), op['w'], op['scale'], op['shift'], y.ref(),
+                                                     x.n, x.h, x.w, op['cin'], op['cout'], op['act']), op['tag'])
+            flops = 2.0 * y.n * y.h * y.w * op['cout'] * op['cin'] * 9
+            nbytes = 4.0 * (x.n * x.h * x.w * op['cin'] + y.n * y.h * y.w * op['cout']) + 2.0 * op['cout'] * op['cin'] * 9
+            klass = 'conv3x3s2h %d->%d@%dx%d' % (op['cin'], op['cout'], y.h, y.w)
         elif kind == 'convpair':
             args, klass = [], []
             for half in (op['a'], op['b']):
@@ -625,16 +677,16 @@ class HRNetEngine(object):
         self.fuse_layer1 = os.environ.get('EGONET_AMD_PW_FUSE', '1') != '0'      # layer1's 1x1 pairs on csrc/conv_pw.hip
         # fuse output i -> branch i of the next module on the same lane, no join in between
         self.chain_regions = os.environ.get('EGONET_AMD_CHAIN', '1') != '0'
-        self.last_f16_ops = []    # tags of the layers the last recording lowered to the f16-operand op (precision = 'f16')
+        self.last_f16_ops = []    # tags of the layers the last recording lowered to the f16-operand ops (precision = 'f16' / 'f16s2')
 
     @property
     def precision(self):
-        """The model's ``precision`` attribute ('f32', the default, or 'f16'): read at every forward, part of the
-        program key.  'f16' moves the layers ``f16_eligible`` names to csrc/conv_h.hip; everything else, and the
-        training tape, is recorded exactly as in 'f32'."""
+        """The model's ``precision`` attribute ('f32', the default, 'f16' or 'f16s2'): read at every forward, part of the
+        program key.  'f16' moves the layers ``f16_eligible`` names to csrc/conv_h.hip, 'f16s2' those and the layers
+        ``f16s2_eligible`` names; everything else, and the training tape, is recorded exactly as in 'f32'."""
         prec = getattr(self.model, 'precision', 'f32')
         if prec not in PRECISIONS:
-            raise ValueError("precision must be 'f32' or 'f16', got %r" % (prec,))
+            raise ValueError("precision must be 'f32', 'f16' or 'f16s2', got %r" % (prec,))
         return prec
 
     # -- recording ---------------------------------------------------------
@@ -816,7 +868,8 @@ class HRNetEngine(object):
         own = r is None
         if own:
             r = _Recorder()
-            r.f16 = self.precision == 'f16'     # (the training tape brings its own recorder: the switch is not its)
+            r.f16 = self.precision in ('f16', 'f16s2')     # (the training tape brings its own recorder: the switch is not its)
+            r.f16s2 = self.precision == 'f16s2'
         x = r.nchw_to_nhwc(Ref(SLOT_USER0, 0), n, cin, h, w, tag='input')
         t = r.conv(x, m.conv1.weight, None, m.bn1, ACT_RELU, None, 2, 1, tag='conv1')
         t = r.conv(t, m.conv2.weight, None, m.bn2, ACT_RELU, None, 2, 1, tag='conv2')
@@ -917,7 +970,7 @@ class HRNetEngine(object):
             out_shapes['decode_slot'] = SLOT_USER0 + nslots
             nslots += 3
         if own:
-            self.last_f16_ops = [op['tag'] for kind, op in r.ops if kind == 'convh']
+            self.last_f16_ops = [op['tag'] for kind, op in r.ops if kind in ('convh', 'convh2')]
         return r, nslots, out_shapes
 
     def program(self, x, decode_mode=None, slot=0):

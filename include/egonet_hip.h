@@ -710,6 +710,20 @@ int egn_conv3x3_h_f32(const float* x, const void* wpack_f16, const float* scale,
 /* the same as a program op (fork / join lanes, egn_program_run_timed, egn_program_op_info, capture / replay); res may be NULL */
 int egn_program_add_conv3x3_h(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
                               egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act);
+/* The same family at STRIDE 2 (3x3 / stride 2 / pad 1; PoseHighResolutionNet.precision = 'f16s2'): x [N][H][W][Cin],
+ * y [N][Ho][Wo][Cout] with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1 -- H, W are the INPUT size everywhere.  The same
+ * kernel, rounding and filter pack (engine.pack_conv_weight_f16: its layout does not depend on the stride) as above:
+ *     y = act(conv_s2(f16(x), f16(w)) * scale + shift),    act = EGN_ACT_NONE or EGN_ACT_RELU;    no residual.
+ * egn_conv3x3s2_h_applies is its one predicate, host-only: 1 where Cin, Cout in {48, 96, 192, 384} with cs == C, N >= 1,
+ * H, W >= 2, input and output below 2 GiB, act none / ReLU -- else 0 (256 -> 96, the stem's 3 -> 64 and 64 -> 64 are
+ * refused); the other entry points return EGN_E_BADARG where it says 0.  The reference runs these layers as fp32 torch
+ * calls (libs/model/heatmapModel/hrnet.py, the transition and fuse layers). */
+int egn_conv3x3s2_h_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int act);
+int egn_conv3x3s2_h_f32(const float* x, const void* wpack_f16, const float* scale, const float* shift, float* y,
+                        int N, int H, int W, int Cin, int Cout, int act, void* stream);
+/* as a program op with a kind id of its own (13; egn_program_op_info: flops = 2 * 9 * N * Ho * Wo * Cout * Cin) */
+int egn_program_add_conv3x3s2_h(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift, egn_ref y,
+                                int N, int H, int W, int Cin, int Cout, int act);
 /* number of kernel launches issued through egn_program_run / _run_timed / _replay
  * since the library was loaded (process wide, all devices).  Test hook: a caller
  * can prove that a forward went through this library's kernels. */
