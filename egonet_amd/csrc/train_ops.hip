@@ -442,10 +442,16 @@ extern "C" int egn_bn_act_fwd_drop_f32(const float* z, const float* mean, const 
   return (int)hipGetLastError();
 }
 
+// The backward kernels know 0 (none), 1 (ReLU) and 2 (LeakyReLU) and read every other non-zero value as ReLU: a forward
+// flag with EGN_ACT_RES_AFTER set (0x12) would silently give ReLU gradients, so the entry points refuse it.  (The
+// residual-after form has no gate on res: its gradient is dy itself, and the caller passes the plain flag.)
+static inline bool bn_bwd_flag_ok(int relu) { return relu >= 0 && relu <= 2; }
+
 extern "C" int egn_bn_bwd_sums_f32(const float* dy, const float* z, const float* mask, float keep_scale,
                                    const float* mean, const float* invstd, const float* gamma, const float* beta,
                                    int relu, const float* res, int rows, int cols, int ld, float* dbeta,
                                    float* dgamma, void* ws, void* stream) {
+  if (!bn_bwd_flag_ok(relu)) return EGN_E_BADARG;
   ColArgs p = {};
   p.res = res;
   p.a = z; p.dy = dy; p.mask = mask; p.keep_scale = keep_scale; p.mean = mean; p.invstd = invstd;
@@ -458,7 +464,7 @@ extern "C" int egn_bn_bwd_sums_drop_f32(const float* dy, const float* z, float p
                                         const int* step_dev, int layer, const float* mean, const float* invstd,
                                         const float* gamma, const float* beta, int relu, const float* res, int rows,
                                         int cols, int ld, float* dbeta, float* dgamma, void* ws, void* stream) {
-  if (!(p >= 0.f && p < 1.f) || (p > 0.f && !step_dev)) return EGN_E_BADARG;
+  if (!bn_bwd_flag_ok(relu) || !(p >= 0.f && p < 1.f) || (p > 0.f && !step_dev)) return EGN_E_BADARG;
   ColArgs q = {};
   q.drop = make_drop(p, seed, step_dev, layer);
   q.res = res;
@@ -539,7 +545,7 @@ extern "C" int egn_bn_bwd_dz_f32(const float* dy, const float* z, const float* m
                                  const float* mean, const float* invstd, const float* gamma, const float* beta,
                                  int relu, const float* res, const float* dbeta, const float* dgamma, float* dz,
                                  float* dres, int rows, int cols, int ld, void* stream) {
-  if (rows <= 0 || cols <= 0 || ld % 4 || ld < cols) return EGN_E_BADARG;
+  if (!bn_bwd_flag_ok(relu) || rows <= 0 || cols <= 0 || ld % 4 || ld < cols) return EGN_E_BADARG;
   hipLaunchKernelGGL(bn_bwd_dz_kernel, rowstream_grid(rows, ld), dim3(256), 0, (hipStream_t)stream, dy, z, mask,
                      keep_scale, mean, invstd, gamma, beta, relu, res, dbeta, dgamma, dz, dres, rows, cols, ld,
                      DropArgs{});
@@ -550,7 +556,9 @@ extern "C" int egn_bn_bwd_dz_drop_f32(const float* dy, const float* z, float p, 
                                       const float* gamma, const float* beta, int relu, const float* res,
                                       const float* dbeta, const float* dgamma, float* dz, float* dres, int rows,
                                       int cols, int ld, void* stream) {
-  if (rows <= 0 || cols <= 0 || ld % 4 || ld < cols || !(p >= 0.f && p < 1.f) || (p > 0.f && !step_dev)) return EGN_E_BADARG;
+  if (!bn_bwd_flag_ok(relu) || rows <= 0 || cols <= 0 || ld % 4 || ld < cols || !(p >= 0.f && p < 1.f) ||
+      (p > 0.f && !step_dev))
+    return EGN_E_BADARG;
   hipLaunchKernelGGL(bn_bwd_dz_kernel, rowstream_grid(rows, ld), dim3(256), 0, (hipStream_t)stream, dy, z,
                      (const float*)nullptr, 1.0f / (1.0f - p), mean, invstd, gamma, beta, relu, res, dbeta, dgamma, dz,
                      dres, rows, cols, ld, make_drop(p, seed, step_dev, layer));

@@ -439,7 +439,10 @@ int egn_bn_stats_finalize_f32(const double* partials, long nrows, int rows, int 
                               float* var_unbiased, float* running_mean,
                               float* running_var, float momentum, void* stream);
 /* relu: 0 none, 1 nn.ReLU, 2 nn.LeakyReLU() (slope 0.01, FCmodel.py:19-22) -- here and in the two
- * backward entry points below.
+ * backward entry points below.  The forward entry points also take relu | EGN_ACT_RES_AFTER (0x11, 0x12):
+ * y = res + dropout(act(bn(z))) instead of act(bn(z) + res).  The backward entry points (and their _drop forms) take
+ * 0, 1 and 2 only and refuse anything else with EGN_E_BADARG: the residual-after form puts no gate on res (its
+ * gradient is dy itself), so its backward is the plain flag without res.
  * y = relu?(gamma*(z-mean)*invstd + beta + res?) * (mask ? mask*keep_scale : 1)
  * (BatchNorm on batch statistics + residual + ReLU + inverted dropout) */
 int egn_bn_act_fwd_f32(const float* z, const float* mean, const float* invstd,

@@ -171,33 +171,54 @@ def tape_requests(device='cuda'):
     return reqs
 
 
-def _tape_steps(device, g):
+def hrnet_run(cfg, n, device, g, update=False, **step_kw):
+    """Builds an ``HRNetTrainStep`` of ``cfg`` and its batch of ``n`` crops; returns (step object, step()): one native
+    iteration per call."""
     from egonet_amd.model.heatmapModel import hrnet
-    from egonet_amd.model import FCmodel
     from egonet_amd.train_hrnet import HRNetTrainStep
+    net = hrnet.get_pose_net(cfg, is_train=False).to(device).train()
+    iw, ih = cfg['heatmapModel']['input_size']
+    hw, hh = cfg['heatmapModel']['heatmap_size']
+    J = cfg['heatmapModel']['num_joints']
+    x = torch.randn(n, 3, ih, iw, generator=g).to(device)
+    tgt = torch.rand(n, J, hh, hw, generator=g).to(device)
+    jxy = (torch.rand(n, J, 2, generator=g) * iw).to(device)
+    tr = HRNetTrainStep(net, lr=1e-3, w_coor=0.0 if net.head_type == 'heatmap' else 0.1, **step_kw)
+    return tr, lambda: tr.step(x, tgt, None if net.pixel_shuffle else jxy, update=update)
+
+
+def lifter_run(rows, device, g, update=False, leaky=False, **step_kw):
+    """The same for the lifter (66 -> 96) at ``rows`` rows."""
+    from egonet_amd.model import FCmodel
     from egonet_amd.train_lifter import LifterTrainStep
+    cfg = configs.w48_config()
+    cfg['FCModel'] = dict(cfg['FCModel'], leaky=leaky)
+    lifter = FCmodel.get_fc_model(1, cfg, 66, 96).to(device).train()
+    tr = LifterTrainStep(lifter, lr=1e-3, **step_kw)
+    x, t = torch.randn(rows, 66, generator=g).to(device), torch.randn(rows, 96, generator=g).to(device)
+    return tr, lambda: tr.step(x, t, update=update)
+
+
+# The recorded training steps, ONE list for the conv sweep and the training-ops sweep (tests/train_ops_sweep.py):
+# (where it is seen, make(device, g) -> (step object, step())).  W48 'coordinates' at 3 crops, the pedestrian model at
+# 2, the pixel-shuffle head at 2; the lifter at a ragged 30 rows.
+TAPE_STEPS = [
+    ('train-w48/b3', lambda device, g: hrnet_run(configs.w48_config('coordinates'), 3, device, g)),
+    ('train-ped/b2', lambda device, g: hrnet_run(configs.ped_config(), 2, device, g)),
+    ('train-pixshuf/b2', lambda device, g: hrnet_run(_pixshuf_config(2), 2, device, g)),
+    ('train-lifter/b30', lambda device, g: lifter_run(30, device, g)),
+]
+
+
+def _tape_steps(device, g):
     reqs = []
-    for name, cfg, n in (('train-w48', configs.w48_config('coordinates'), 3), ('train-ped', configs.ped_config(), 2),
-                         ('train-pixshuf', _pixshuf_config(2), 2)):
-        net = hrnet.get_pose_net(cfg, is_train=False).to(device).train()
-        iw, ih = cfg['heatmapModel']['input_size']
-        hw, hh = cfg['heatmapModel']['heatmap_size']
-        J = cfg['heatmapModel']['num_joints']
-        x = torch.randn(n, 3, ih, iw, generator=g).to(device)
-        tgt = torch.rand(n, J, hh, hw, generator=g).to(device)
-        jxy = (torch.rand(n, J, 2, generator=g) * iw).to(device)
-        tr = HRNetTrainStep(net, lr=1e-3, w_coor=0.0 if net.head_type == 'heatmap' else 0.1)
-        with TapeRecorder('%s/b%d' % (name, n)) as rec:
-            tr.step(x, tgt, None if net.pixel_shuffle else jxy, update=False)
+    for src, make in TAPE_STEPS:
+        tr, step = make(device, g)
+        with TapeRecorder(src) as rec:
+            step()
         torch.cuda.synchronize()
         reqs += rec.reqs
-        del tr, net
-    lifter = FCmodel.get_fc_model(1, configs.w48_config(), 66, 96).to(device).train()
-    tr = LifterTrainStep(lifter, lr=1e-3)
-    with TapeRecorder('train-lifter/b30') as rec:
-        tr.step(torch.randn(30, 66, generator=g).to(device), torch.randn(30, 96, generator=g).to(device), update=False)
-    torch.cuda.synchronize()
-    reqs += rec.reqs
+        del tr, step
     return reqs
 
 

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from egonet_amd import _lib
+from train_ops_sweep import philox4 as _philox4     # the numpy Philox4x32-10 the training-ops sweep shares
 
 pytestmark = pytest.mark.gpu
 
@@ -53,19 +54,6 @@ def test_gemm_forms_vs_float64(form, M, N, K, variants):
     # shapes the kernels do not take are refused (the callers keep the conv-kernel route for them)
     assert L.egn_gemm_supported(form, M + 1, N, K, A.shape[1], B.shape[1], N) == 0
     assert L.egn_gemm_supported(form, M, N, K + 4, A.shape[1] + 4, B.shape[1] + 4, N) == 0
-
-
-def _philox4(k0, k1, c):
-    """numpy Philox4x32-10 (Salmon et al.): c = uint32 [n, 4] counters -> [n, 4] draws."""
-    M0, M1, W0, W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), 0x9E3779B9, 0xBB67AE85
-    c = c.astype(np.uint64)
-    k0, k1 = int(k0), int(k1)
-    for _ in range(10):
-        p0, p1 = M0 * c[:, 0], M1 * c[:, 2]
-        hi0, lo0, hi1, lo1 = p0 >> np.uint64(32), p0 & np.uint64(0xffffffff), p1 >> np.uint64(32), p1 & np.uint64(0xffffffff)
-        c = np.stack([hi1 ^ c[:, 1] ^ np.uint64(k0), lo1, hi0 ^ c[:, 3] ^ np.uint64(k1), lo0], axis=1)
-        k0, k1 = (k0 + W0) & 0xffffffff, (k1 + W1) & 0xffffffff
-    return c.astype(np.uint32)
 
 
 def test_in_kernel_dropout_is_philox_and_forward_backward_agree():

@@ -594,6 +594,19 @@ def test_bad_arguments_are_refused():
     assert L.egn_adam_step_f32(_lib.ptr(a), _lib.ptr(a), _lib.ptr(a), _lib.ptr(a), 16, 1e-3, 0.9, 0.999, 1e-8, 0,
                                _st()) != 0                                                 # step counts from 1
     assert L.egn_colsum_f32(_lib.ptr(a), 4, 4, 4, _lib.ptr(a), None, _st()) != 0          # no workspace
+    ws = torch.zeros(L.egn_colreduce_ws_bytes(4) // 4, device='cuda')
+    for flag in (0x11, 0x12, 3, -1):          # the backward entry points take 0, 1, 2: no residual-after form, no other bit
+        assert L.egn_bn_bwd_sums_f32(_lib.ptr(a), _lib.ptr(a), None, 1.0, _lib.ptr(a), _lib.ptr(a), _lib.ptr(a), _lib.ptr(a),
+                                     flag, None, 4, 4, 4, _lib.ptr(a), _lib.ptr(a), _lib.ptr(ws), _st()) == -1
+        assert L.egn_bn_bwd_dz_f32(_lib.ptr(a), _lib.ptr(a), None, 1.0, _lib.ptr(a), _lib.ptr(a), _lib.ptr(a), _lib.ptr(a),
+                                   flag, None, _lib.ptr(a), _lib.ptr(a), _lib.ptr(a), None, 4, 4, 4, _st()) == -1
+        step = torch.zeros(1, dtype=torch.int32, device='cuda')
+        assert L.egn_bn_bwd_sums_drop_f32(_lib.ptr(a), _lib.ptr(a), 0.5, 1, _lib.ptr(step), 0, _lib.ptr(a), _lib.ptr(a),
+                                          _lib.ptr(a), _lib.ptr(a), flag, None, 4, 4, 4, _lib.ptr(a), _lib.ptr(a),
+                                          _lib.ptr(ws), _st()) == -1
+        assert L.egn_bn_bwd_dz_drop_f32(_lib.ptr(a), _lib.ptr(a), 0.5, 1, _lib.ptr(step), 0, _lib.ptr(a), _lib.ptr(a),
+                                        _lib.ptr(a), _lib.ptr(a), flag, None, _lib.ptr(a), _lib.ptr(a), _lib.ptr(a), None,
+                                        4, 4, 4, _st()) == -1
 
 
 @pytest.mark.parametrize('tag', ['s1', 's2', 'rect'])
