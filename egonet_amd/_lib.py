@@ -134,6 +134,10 @@ SIGNATURES = {
     'egn_conv3x3s2_h_applies': (_i, [_i] * 8),
     'egn_conv3x3s2_h_f32': (_i, [_p] * 5 + [_i] * 6 + [_p]),
     'egn_program_add_conv3x3s2_h': (_i, [_p] + [Ref] * 5 + [_i] * 6),
+    'egn_conv3x3_hx_applies': (_i, [_i] * 10),
+    'egn_conv3x3_hx_wpack_bytes': (C.c_long, [_i, _i]),
+    'egn_conv3x3_hx_f32': (_i, [_p] * 6 + [_i] * 7 + [_p]),
+    'egn_program_add_conv3x3_hx': (_i, [_p] + [Ref] * 6 + [_i] * 7),
     'egn_pw_pair_f32': (_i, [_p] * 8 + [_i, _i, _p]),
     'egn_program_add_ramps': (_i, [_p, Ref, _i, _i, _i, _i, _i]),
     'egn_program_add_decode': (_i, [_p, Ref, _i, _i, _i, _i, _i, Ref, Ref, Ref]),

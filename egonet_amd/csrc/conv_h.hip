@@ -34,6 +34,15 @@
 //      2 x 17 x 7 = 238 = 14 (mod 16) apart and collide on six of the eight.
 // Both hold for the tiles HRNet-W48 has (outputs of 8 x 8 and more); smaller tiles are correct, not conflict-free.  (The
 // arithmetic is per channel group, as at stride 1: the hardware's 16-lane groups of a ds_read_b128 mix two of them.)
+//
+// CHUNKS OF 32 (precision = 'f16x', egn_conv3x3_hx_applies; template parameter CK = 32) run the widths 48 does not
+// divide: Cin in {32, 64, 128, 256}, either stride.  K per chunk is 9 * 32 = 288 = 9 steps of 32 exactly: K step ks IS tap
+// ks and lane group g IS channel group g, so there is no K-step table, no padding branch and no zero bytes; the filter
+// pack is engine.pack_conv_weight_f16x: [Cout/16][Cin/32][9 taps][64 lanes][8] f16.  A halo pixel is 64 bytes of f16
+// stored with an 80-byte stride, 5 quads, and the arguments above carry over: stride 1, fragment row li reads quad
+// 5 li mod 16 (0 5 10 15 4 9 14 3 8 13 2 7 12 1 6 11); stride 2 with the parity-split row, x = 0..7: quads 0 5 10 15 4 9 14 3,
+// and tile row y + TH / 2 is 8 * 17 * 5 = 680 = 8 (mod 16) away: the other eight.  Output-channel tiles: 64 (Cout = 64 /
+// 128 / 256, 2 x 2 waves on 64 pixels) and 32 (4 x 1 waves on 128 pixels, stride 2: 64), beside 96 / 48 for 256 -> 96 / 48.
 #include <string.h>
 
 #include <atomic>
@@ -43,9 +52,17 @@
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
-constexpr int H_CK = 48;      // input channels per chunk
-constexpr int H_KS = 14;      // MFMA K steps per chunk (432 -> 448)
-constexpr int H_PIXB = 112;   // LDS bytes per halo pixel: 96 + 16 (28-dword stride: 16 neighbouring pixels hit 16 bank quads)
+// What follows from the input-channel chunk CK (48: the W48 widths; 32: the 32-multiple widths, 'f16x').
+template <int CK>
+struct ConvHChunk {
+  static_assert(CK == 48 || CK == 32, "chunks of 48 or 32 input channels");
+  static constexpr int KS = (9 * CK + 31) / 32;   // MFMA K steps per chunk: 14 (432 -> 448) or 9 (288, no padding)
+  static constexpr int PIXB = 2 * CK + 16;        // LDS bytes per halo pixel: 112 / 80 (a 7- / 5-quad stride: 16 neighbouring
+                                                  // pixels hit 16 bank quads)
+  static constexpr int TAB = CK == 48 ? 16 + KS * 4 * 4 : 0;   // CK = 48: 16 zero bytes and the K-step offsets behind sOff
+};
+constexpr int H_CK = 48;      // input channels per chunk of the 'f16' / 'f16s2' instances
+constexpr int H_KS = ConvHChunk<48>::KS;
 constexpr float H_F16_MAX = 65504.0f;
 
 // a 16-byte B fragment: lane offset in a VGPR, wave-uniform offset in an SGPR (non-template wrapper, as conv_common.h's)
@@ -63,7 +80,8 @@ struct ConvHTile {
   // the next chunk's batch 0 in flight during the products: not for the 48-output-channel tile, whose layers in HRNet have
   // one chunk (48 -> 48) and whose staging registers, live across the products, would cost it a wave per SIMD
   // (the same holds for the stride-2 64 x 48 tile)
-  static constexpr bool PREFETCH = TN == 96;
+  // (CK = 32: the 64-channel tile prefetches too; the 32-channel tile's layers have one chunk)
+  static constexpr bool PREFETCH = TN == 96 || TN == 64;
 };
 
 // Stride 2: the row bits of a tile row index, rotated right by one.  The 16 rows of an A fragment are then 8 columns of
@@ -73,9 +91,10 @@ __device__ __forceinline__ int h_tile_row(int r, int lth) {
   return S == 1 || lth == 0 ? r : (r >> 1) | ((r & 1) << (lth - 1));
 }
 
-template <int S, int WM, int WN, int MT, int NT>
+template <int CK, int S, int WM, int WN, int MT, int NT>
 __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
   using T = ConvHTile<WM, WN, MT, NT>;
+  constexpr int H_CK = CK, H_KS = ConvHChunk<CK>::KS, H_PIXB = ConvHChunk<CK>::PIXB;
   static_assert(WM * WN == 4, "four waves");
   // stride 2: the 289-pixel halo of an 8 x 8 tile is 13.5 float4 per thread: two batches of 7 (two round trips to memory,
   // not three; one batch of 14 spills)
@@ -83,7 +102,7 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
   extern __shared__ float4 smem_f4[];
   char* smem = reinterpret_cast<char*>(smem_f4);
   unsigned* sOff = reinterpret_cast<unsigned*>(smem);        // [npix] byte offset of halo pixel (channel 0) in x, or EGN_OOB
-  int* sKoff = reinterpret_cast<int*>(smem + a.tab_bytes - H_KS * 4 * 4);   // the last 224 bytes of the table region
+  int* sKoff = reinterpret_cast<int*>(smem + a.tab_bytes - H_KS * 4 * 4);   // CK = 48: the last 224 bytes of the table region
   char* slab = smem + a.tab_bytes;                            // [npix][H_PIXB] f16 halo tile; later the epilogue slabs
 
   const int tid = threadIdx.x;
@@ -124,13 +143,19 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
   }
   // sKoff[4 ks + g]: LDS byte offset of the 8 channels a lane of group g reads at K step ks (tap and channel group of
   // k = 8 (4 ks + g)); -1 past k = 432.  A table in LDS, not 14 registers per lane: the kernel keeps 4 waves per SIMD.
+  // CK = 32: K step ks IS tap ks and lane group g IS channel group g -- no table, nothing past K, no zero bytes.
   const int zoff = a.tab_bytes - H_KS * 4 * 4 - 16;   // 16 zero bytes: the A fragment of the padding steps, read without a branch
-  if (tid < 4) reinterpret_cast<int*>(smem + zoff)[tid] = 0;
-  if (tid < H_KS * 4) {
-    const int tap = tid / 6, c8 = tid - tap * 6;
-    const int ky = tap / 3, kx = tap - ky * 3;
-    const int kcol = S == 1 ? kx : (kx & 1) * (a.TW + 1) + (kx >> 1);   // stride 2: halo column 2 x + kx of the split row
-    sKoff[tid] = tid < 54 ? (ky * a.HW + kcol) * H_PIXB + c8 * 16 : -1;
+  if constexpr (CK == 48) {
+    if (tid < 4) reinterpret_cast<int*>(smem + zoff)[tid] = 0;
+    if (tid < H_KS * 4) {
+      const int tap = tid / 6, c8 = tid - tap * 6;
+      const int ky = tap / 3, kx = tap - ky * 3;
+      const int kcol = S == 1 ? kx : (kx & 1) * (a.TW + 1) + (kx >> 1);   // stride 2: halo column 2 x + kx of the split row
+      sKoff[tid] = tid < 54 ? (ky * a.HW + kcol) * H_PIXB + c8 * 16 : -1;
+    }
+  } else {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) abase[mt] += g * 16;
   }
 
   f32x4 acc[MT][NT];
@@ -215,9 +240,17 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
           bf[(ks + BD - 1) % BD][nt] = h_load_b(rw, wlane, wb[nt] + chunk * (H_KS * 1024) + (ks + BD - 1) * 1024);
       }
       f16x8 af[MT];
-      const int koff = sKoff[ks * 4 + g];
+      if constexpr (CK == 48) {
+        const int koff = sKoff[ks * 4 + g];
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) af[mt] = *reinterpret_cast<const f16x8*>(smem + (koff >= 0 ? abase[mt] + koff : zoff));
+        for (int mt = 0; mt < MT; ++mt) af[mt] = *reinterpret_cast<const f16x8*>(smem + (koff >= 0 ? abase[mt] + koff : zoff));
+      } else {
+        const int ky = ks / 3, kx = ks - ky * 3;     // compile-time; the offset is wave-uniform
+        const int kcol = S == 1 ? kx : (kx & 1) * (a.TW + 1) + (kx >> 1);
+        const int koff = (ky * a.HW + kcol) * H_PIXB;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) af[mt] = *reinterpret_cast<const f16x8*>(smem + abase[mt] + koff);
+      }
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -274,7 +307,8 @@ static int h_log2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 // Host-only: 1 where the family runs the layer.  The W48 widths with unpadded channel strides, a plain epilogue (scale /
 // shift, optional residual added before the activation, ReLU or none), tensors below 2 GiB (32-bit buffer offsets).  The
-// Pedestrian widths (32 / 64 / 128 / 256) and 256 -> 48 are REFUSED: 48-channel chunks do not divide them.
+// Pedestrian widths (32 / 64 / 128 / 256) and 256 -> 48 are REFUSED: 48-channel chunks do not divide them
+// (egn_conv3x3_hx_applies below takes them, in chunks of 32).
 extern "C" int egn_conv3x3_h_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act) {
   if (N < 1 || H < 2 || W < 2 || !h_width(Cin) || !h_width(Cout) || cs_in != Cin || cs_out != Cout) return 0;
   if (act != EGN_ACT_NONE && act != EGN_ACT_RELU) return 0;     // (sigmoid, leaky and RES_AFTER stay on the fp32 kernels)
@@ -299,15 +333,38 @@ extern "C" int egn_conv3x3s2_h_applies(int N, int H, int W, int Cin, int cs_in, 
   return 1;
 }
 
-int egn_conv_h_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act, int stride) {
-  if (stride == 1 ? !egn_conv3x3_h_applies(N, H, W, Cin, Cin, Cout, Cout, has_res, act)
-                  : stride != 2 || has_res || !egn_conv3x3s2_h_applies(N, H, W, Cin, Cin, Cout, Cout, act))
-    return EGN_E_BADARG;
+// 'f16x': the 32-multiple widths, walked in chunks of 32 (K step = tap, lane group = channel group; the header).
+static bool hx_cin(int c) { return c == 32 || c == 64 || c == 128 || c == 256; }
+static bool hx_cout(int c) { return hx_cin(c) || c == 48 || c == 96; }
+
+// Host-only: 1 where the CK = 32 instances run the layer -- Cin in {32, 64, 128, 256}, Cout in those or {48, 96}
+// (transition1's 256 -> 48 / 256 -> 96), stride 1 or 2 (stride 2: no residual); the rest as the two predicates above.
+extern "C" int egn_conv3x3_hx_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act,
+                                      int stride) {
+  if (N < 1 || H < 2 || W < 2 || !hx_cin(Cin) || !hx_cout(Cout) || cs_in != Cin || cs_out != Cout) return 0;
+  if (act != EGN_ACT_NONE && act != EGN_ACT_RELU) return 0;
+  if (stride != 1 && stride != 2) return 0;
+  if (has_res != 0 && (has_res != 1 || stride == 2)) return 0;
+  const long long pxo = (long long)N * ((H - 1) / stride + 1) * ((W - 1) / stride + 1);
+  if ((long long)N * H * W * Cin * 4 >= (1ll << 31) || pxo * Cout * 4 >= (1ll << 31)) return 0;
+  return 1;
+}
+
+extern "C" long egn_conv3x3_hx_wpack_bytes(int Cin, int Cout) {
+  if (!hx_cin(Cin) || !hx_cout(Cout)) return 0;
+  return (long)(Cout / 16) * (Cin / 32) * ConvHChunk<32>::KS * 64 * 16;
+}
+
+// the tile geometry of a layer its predicate has taken (ck: the chunk)
+static int h_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int act, int stride, int ck) {
   memset(&a, 0, sizeof(a));
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.act = act;
   a.stride = stride; a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1;
-  a.wide = Cout % 96 == 0;                           // 64 pixels x 96 channels, else 128 (stride 2: 64) pixels x 48 channels
-  const int TM = a.wide || stride == 2 ? 64 : 128;
+  a.ck = ck;
+  // output channels per block: 96 / 48 as the widths allow; CK = 32 also 64 (Cout = 64 / 128 / 256) and 32
+  a.tn = Cout % 96 == 0 ? 96 : (Cout % 48 == 0 ? 48 : (Cout % 64 == 0 ? 64 : 32));
+  const bool wide = a.tn == 96 || a.tn == 64;        // 2 x 2 waves on 64 pixels, else 4 x 1 on 128 (stride 2: 64) pixels
+  const int TM = wide || stride == 2 ? 64 : 128;
   // stride 2: at least 2 x 2, so that the 64 images of a tile of 1 x 1 outputs do not bring 64 3 x 3 halos (65 KiB)
   const int th = h_pow2_ceil(a.Ho) < stride ? stride : h_pow2_ceil(a.Ho), tw = h_pow2_ceil(a.Wo) < stride ? stride : h_pow2_ceil(a.Wo);
   a.TH = th < 8 ? th : 8;
@@ -318,30 +375,53 @@ int egn_conv_h_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int ha
   a.npix = a.TNB * a.HH * a.HW;
   a.tiles_x = (a.Wo + a.TW - 1) / a.TW;
   a.tiles_y = (a.Ho + a.TH - 1) / a.TH;
-  a.tab_bytes = (a.npix * 4 + 15) / 16 * 16 + 16 + H_KS * 4 * 4;   // halo offsets, 16 zero bytes, the K-step offsets (224 bytes)
-  const int epi = a.wide ? ConvHTile<2, 2, 2, 3>::EPI_BYTES
-                         : (stride == 2 ? ConvHTile<4, 1, 1, 3>::EPI_BYTES : ConvHTile<4, 1, 2, 3>::EPI_BYTES);
-  const int halo = a.npix * H_PIXB;
+  // halo offsets; CK = 48: 16 zero bytes and the K-step offsets (224 bytes)
+  a.tab_bytes = (a.npix * 4 + 15) / 16 * 16 + (ck == 48 ? ConvHChunk<48>::TAB : ConvHChunk<32>::TAB);
+  const int wn = wide ? 2 : 1;
+  const int epi = TM * wn * (a.tn / wn + 4) * 4;      // ConvHTile::EPI_BYTES of the instance egn_conv_h_launch picks
+  const int halo = a.npix * (ck == 48 ? ConvHChunk<48>::PIXB : ConvHChunk<32>::PIXB);
   a.lds_bytes = a.tab_bytes + (halo > epi ? halo : epi);
-  const long long blocks = (long long)a.tiles_x * a.tiles_y * ((N + a.TNB - 1) / a.TNB) * (Cout / (a.wide ? 96 : 48));
+  const long long blocks = (long long)a.tiles_x * a.tiles_y * ((N + a.TNB - 1) / a.TNB) * (Cout / a.tn);
   if (a.lds_bytes > 64 * 1024 || blocks > 0x7fffffffll) return EGN_E_BADARG;
   a.blocks = (int)blocks;
   return 0;
 }
 
+int egn_conv_h_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act, int stride) {
+  if (stride == 1 ? !egn_conv3x3_h_applies(N, H, W, Cin, Cin, Cout, Cout, has_res, act)
+                  : stride != 2 || has_res || !egn_conv3x3s2_h_applies(N, H, W, Cin, Cin, Cout, Cout, act))
+    return EGN_E_BADARG;
+  return h_plan(a, N, H, W, Cin, Cout, act, stride, 48);
+}
+
+int egn_conv_hx_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act, int stride) {
+  if (!egn_conv3x3_hx_applies(N, H, W, Cin, Cin, Cout, Cout, has_res, act, stride)) return EGN_E_BADARG;
+  return h_plan(a, N, H, W, Cin, Cout, act, stride, 32);
+}
+
+#define EGN_H_LAUNCH(CK, S, WM, WN, MT, NT) \
+  hipLaunchKernelGGL((conv_h_kernel<CK, S, WM, WN, MT, NT>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a)
+
 int egn_conv_h_launch(const ConvHArgs& a, hipStream_t stream) {
   if (!a.x || !a.w || !a.scale || !a.shift || !a.y) return EGN_E_BADARG;
-  if (a.stride == 2 && a.wide)
-    hipLaunchKernelGGL((conv_h_kernel<2, 2, 2, 2, 3>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);
-  else if (a.stride == 2)
-    hipLaunchKernelGGL((conv_h_kernel<2, 4, 1, 1, 3>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);
-  else if (a.wide)
-    hipLaunchKernelGGL((conv_h_kernel<1, 2, 2, 2, 3>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);
-  else
-    hipLaunchKernelGGL((conv_h_kernel<1, 4, 1, 2, 3>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);
+  const int s = a.stride;
+  if (a.ck == 48) {
+    if (a.tn == 96) { if (s == 2) EGN_H_LAUNCH(48, 2, 2, 2, 2, 3); else EGN_H_LAUNCH(48, 1, 2, 2, 2, 3); }
+    else if (a.tn == 48) { if (s == 2) EGN_H_LAUNCH(48, 2, 4, 1, 1, 3); else EGN_H_LAUNCH(48, 1, 4, 1, 2, 3); }
+    else return EGN_E_BADARG;
+  } else if (a.ck == 32) {
+    if (a.tn == 96) { if (s == 2) EGN_H_LAUNCH(32, 2, 2, 2, 2, 3); else EGN_H_LAUNCH(32, 1, 2, 2, 2, 3); }
+    else if (a.tn == 48) { if (s == 2) EGN_H_LAUNCH(32, 2, 4, 1, 1, 3); else EGN_H_LAUNCH(32, 1, 4, 1, 2, 3); }
+    else if (a.tn == 64) { if (s == 2) EGN_H_LAUNCH(32, 2, 2, 2, 2, 2); else EGN_H_LAUNCH(32, 1, 2, 2, 2, 2); }
+    else if (a.tn == 32) { if (s == 2) EGN_H_LAUNCH(32, 2, 4, 1, 1, 2); else EGN_H_LAUNCH(32, 1, 4, 1, 2, 2); }
+    else return EGN_E_BADARG;
+  } else {
+    return EGN_E_BADARG;
+  }
   EGN_CHECK_HIP(hipGetLastError());
   return 0;
 }
+#undef EGN_H_LAUNCH
 
 extern std::atomic<long> g_egn_direct_convs;
 
@@ -363,5 +443,16 @@ extern "C" int egn_conv3x3s2_h_f32(const float* x, const void* wpack_f16, const 
   int rc = egn_conv_h_plan(a, N, H, W, Cin, Cout, 0, act, 2);
   if (rc) return rc;
   a.x = x; a.w = wpack_f16; a.scale = scale; a.shift = shift; a.y = y;
+  return egn_conv_h_launch(a, (hipStream_t)stream);
+}
+
+extern "C" int egn_conv3x3_hx_f32(const float* x, const void* wpack_f16, const float* scale, const float* shift,
+                                  const float* res, float* y, int N, int H, int W, int Cin, int Cout, int act, int stride,
+                                  void* stream) {
+  g_egn_direct_convs.fetch_add(1, std::memory_order_relaxed);
+  ConvHArgs a;
+  int rc = egn_conv_hx_plan(a, N, H, W, Cin, Cout, res != nullptr, act, stride);
+  if (rc) return rc;
+  a.x = x; a.w = wpack_f16; a.scale = scale; a.shift = shift; a.res = res; a.y = y;
   return egn_conv_h_launch(a, (hipStream_t)stream);
 }

@@ -182,7 +182,7 @@ int egn_conv_launch_wino4_pair(ConvArgs a, ConvArgs b, int cus, hipStream_t stre
 // predicates.
 struct ConvHArgs {
   const float* x;
-  const void* w;       // engine.pack_conv_weight_f16
+  const void* w;       // engine.pack_conv_weight_f16 (ck = 48) / pack_conv_weight_f16x (ck = 32)
   const float* scale;
   const float* shift;
   const float* res;    // stride 1 only
@@ -190,7 +190,8 @@ struct ConvHArgs {
   int N, H, W, Cin, Cout, act;
   int stride;          // 1 or 2
   int Ho, Wo;          // output size: (H - 1) / stride + 1, (W - 1) / stride + 1
-  int wide;            // 1: 64 pixels x 96 channels per block, 0: 128 (stride 2: 64) pixels x 48 channels
+  int ck;              // input channels per chunk: 48 (egn_conv_h_plan) or 32 (egn_conv_hx_plan)
+  int tn;              // output channels per block: 96 / 64 on 64 pixels, 48 / 32 on 128 (stride 2: 64) pixels
   int TH, TW, TNB;     // output tile (powers of two): TNB images x TH rows x TW cols
   int lth, ltw;        // log2 of TH / TW
   int HH, HW, npix;    // halo tile per image (stride * T + 3 - stride a side), halo pixels per block
@@ -198,6 +199,8 @@ struct ConvHArgs {
   int tab_bytes, lds_bytes, blocks;
 };
 int egn_conv_h_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act, int stride);   // host-only
+// the 32-multiple widths in chunks of 32 (egn_conv3x3_hx_applies; precision = 'f16x'), either stride
+int egn_conv_hx_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act, int stride);  // host-only
 int egn_conv_h_launch(const ConvHArgs& a, hipStream_t stream);
 
 // adds n to egn_launch_count() (program.hip): entry points outside programs that want their launches provable

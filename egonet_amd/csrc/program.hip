@@ -161,7 +161,8 @@ extern "C" int egn_conv_plan_query(int N, int H, int W, int Cin, int cs_in, int 
 // programs
 // ---------------------------------------------------------------------------
 enum OpKind { OP_CONV = 1, OP_FUSE = 2, OP_NCHW2NHWC = 3, OP_NHWC2NCHW = 4, OP_RAMPS = 5, OP_DECODE = 6,
-              OP_FORK = 7, OP_JOIN = 8, OP_PIXSHUF = 9, OP_PWPAIR = 10, OP_CONVPAIR = 11, OP_CONVH = 12, OP_CONVH2 = 13 };
+              OP_FORK = 7, OP_JOIN = 8, OP_PIXSHUF = 9, OP_PWPAIR = 10, OP_CONVPAIR = 11, OP_CONVH = 12, OP_CONVH2 = 13,
+              OP_CONVHX = 14 };
 constexpr int kMaxLanes = 4;  // concurrent launch lanes (HRNet has at most 4 branches)
 
 struct Op {
@@ -170,7 +171,7 @@ struct Op {
   // conv
   ConvArgs conv;
   ConvArgs conv2;  // OP_CONVPAIR: the second convolution (refs r[6..11])
-  ConvHArgs convh; // OP_CONVH, OP_CONVH2 (conv_h.hip)
+  ConvHArgs convh; // OP_CONVH, OP_CONVH2, OP_CONVHX (conv_h.hip)
   int cfg;
   egn_ref r[12];  // pointer refs, meaning depends on kind
   // generic ints
@@ -458,6 +459,29 @@ extern "C" int egn_program_add_conv3x3s2_h(egn_program* p, egn_ref x, egn_ref wp
   return 0;
 }
 
+// the 32-multiple widths (egn_conv3x3_hx_f32) as one op, either stride; H, W are the input size; res may be NULL at stride 1
+extern "C" int egn_program_add_conv3x3_hx(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
+                                          egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act,
+                                          int stride) {
+  if (!p) return EGN_E_BADARG;
+  Op op;
+  op.kind = OP_CONVHX;
+  int rc = egn_conv_hx_plan(op.convh, N, H, W, Cin, Cout, res.slot >= 0, act, stride);
+  if (rc) return rc;
+  op.cfg = 0;
+  const egn_ref refs[6] = {x, wpack, scale, shift, res, y};
+  for (int k = 0; k < 6; ++k) {
+    if (!ref_ok(p, refs[k]) || (refs[k].slot < 0 && k != 4)) return EGN_E_BADARG;    // (only the residual may be NULL)
+    op.r[k] = refs[k];
+  }
+  const double pxo = (double)N * op.convh.Ho * op.convh.Wo;
+  op.flops = 2.0 * 9.0 * pxo * Cout * Cin;
+  op.bytes = 4.0 * ((double)N * H * W * Cin + pxo * Cout * (res.slot >= 0 ? 2.0 : 1.0)) + 2.0 * 9.0 * Cout * Cin;
+  op.lane = p->cur_lane;
+  p->ops.push_back(op);
+  return 0;
+}
+
 extern "C" int egn_program_add_fuse(egn_program* p, egn_ref y, int N, int H, int W, int C, int cs, int nterms,
                                     const egn_ref* terms, const int* shifts, int relu) {
   if (!p || nterms < 1 || nterms > 4 || cs % 4 || C > cs) return EGN_E_BADARG;
@@ -619,7 +643,8 @@ static int launch_op(egn_program* p, Op& op, hipStream_t s) {
       return egn_conv_launch_wino4_pair(a, b, op.i[0], s);
     }
     case OP_CONVH:
-    case OP_CONVH2: {
+    case OP_CONVH2:
+    case OP_CONVHX: {
       ConvHArgs a = op.convh;
       a.x = (const float*)resolve(p, op.r[0]);
       a.w = resolve(p, op.r[1]);

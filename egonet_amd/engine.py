@@ -26,7 +26,8 @@ import torch.nn as nn
 from . import _lib, tuner
 from ._lib import Ref, NULL_REF, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_LEAKY
 from .filters import (CK, H_CK, H_KS, _round_up, pack_conv_weight, wino_cot, pack_wino_weight,   # noqa: F401
-                      pack_wino43_weight, pack_wino4_weight, pack_conv_weight_f16, unpack_conv_weight_f16, pack_for_kind)
+                      pack_wino43_weight, pack_wino4_weight, pack_conv_weight_f16, unpack_conv_weight_f16,
+                      pack_conv_weight_f16x, unpack_conv_weight_f16x, pack_for_kind)
 
 ACT_RES_AFTER = 0x10
 BN_EPS_DEFAULT = 1e-5
@@ -38,6 +39,16 @@ PRECISIONS = ('f32', 'f16', 'f16s2')
 #   crops on the 32^2 input: fp32 (cfg 85) 7.8 us (spread 0.9), f16-operand op 8.9 us (spread 0.7) -- 64 blocks, the
 #   latency of one block.  (64^2 input at 16 crops: 14.7 -> 9.6 us.)
 F16S2_FP32_CLASSES = ((48, 48),)
+# Every value the switch takes.  'f16x' lowers what 'f16s2' lowers (the same kernel instances, the same bits) plus the 3x3 /
+# pad 1 layers of the 32-MULTIPLE widths, stride 1 or 2 (``f16x_eligible``): HRNet-W32's stages, and in every width
+# layer1's 64 -> 64, the stem's second convolution and transition1.  (PRECISIONS keeps its three values and its last entry.)
+ALL_PRECISIONS = PRECISIONS + ('f16x',)
+_PRECISION_TEXT = "'f32', 'f16', 'f16s2' or 'f16x'"
+# (cin, cout, stride) classes that precision = 'f16x' leaves on their fp32 kernels because the f16-operand op was measured
+# not to win on them (tools/precision_bench.py --x); empty unless a measurement fills it.
+#   Empty: all sixteen classes of W32 at 192 x 256 and of W48's seven layers are faster beyond the spread at 64 crops
+#   (1.6-4.0x) and at 16 (1.2-5.7x; the smallest win is 256 -> 48 stride 1 at 16 crops, 55.3 -> 45.9 us, spreads 2.2 / 1.2).
+F16X_FP32_CLASSES = ()
 
 
 def _h_applies(n, h, w, cin, cs_in, cout, cs_out, has_res, act):
@@ -77,22 +88,44 @@ def f16s2_eligible(conv, n, h, w):
     return _h2_applies(n, h, w, cin, cin, cout, cout, ACT_RELU)
 
 
+def _hx_applies(n, h, w, cin, cs_in, cout, cs_out, has_res, act, stride):
+    return (cin, cout, stride) not in F16X_FP32_CLASSES and \
+        bool(_lib.lib().egn_conv3x3_hx_applies(n, h, w, cin, cs_in, cout, cs_out, int(has_res), act, stride))
+
+
+def f16x_eligible(conv, n, h, w):
+    """THE rule for which layers precision = 'f16x' moves to the f16-operand kernel BESIDE those ``f16_eligible`` and
+    ``f16s2_eligible`` name: ``conv`` is a 3x3 / pad 1 nn.Conv2d of stride 1 or 2 without bias, groups or dilation, the
+    host-only predicate egn_conv3x3_hx_applies takes its [n, Cin, h, w] input, and its (cin, cout, stride) class is not in
+    ``F16X_FP32_CLASSES``."""
+    if not isinstance(conv, nn.Conv2d):
+        return False
+    if (tuple(conv.kernel_size), tuple(conv.padding), tuple(conv.dilation), conv.groups) != ((3, 3), (1, 1), (1, 1), 1) \
+            or tuple(conv.stride) not in ((1, 1), (2, 2)) or conv.bias is not None or conv.padding_mode != 'zeros':
+        return False
+    cin, cout = conv.in_channels, conv.out_channels
+    return _hx_applies(n, h, w, cin, cin, cout, cout, False, ACT_RELU, conv.stride[0])
+
+
 class f16_emulation(object):
     """Context manager: the torch graph of ``model`` computing what precision = 'f16' computes, up to the fp32 summation
     order -- every ``f16_eligible`` convolution sees its input as f16(clamp(x, +-65504)) and its filter as f16(w), both
     round-to-nearest-even and widened back to fp32.  The measuring stick of the mode's network-level error (CPU or any
     device; tests/golden/make_f16_bounds.py, tools/precision_bench.py), never a way to run the network.
-    ``precision='f16s2'`` also rounds the operands of the ``f16s2_eligible`` convolutions."""
+    ``precision='f16s2'`` also rounds the operands of the ``f16s2_eligible`` convolutions, ``precision='f16x'`` those and
+    the ``f16x_eligible`` ones."""
 
     def __init__(self, model, precision='f16'):
-        if precision not in PRECISIONS[1:]:
-            raise ValueError("f16_emulation: precision must be 'f16' or 'f16s2', got %r" % (precision,))
-        self.model, self.handles, self.saved, self.hit, self.s2 = model, [], {}, [], precision == 'f16s2'
+        if precision not in ALL_PRECISIONS[1:]:
+            raise ValueError("f16_emulation: precision must be 'f16', 'f16s2' or 'f16x', got %r" % (precision,))
+        self.model, self.handles, self.saved, self.hit = model, [], {}, []
+        self.s2, self.x = precision in ('f16s2', 'f16x'), precision == 'f16x'
 
     def _pre(self, mod, args):
         x = args[0]
         if x.dim() != 4 or not (f16_eligible(mod, x.shape[0], x.shape[2], x.shape[3]) or
-                                (self.s2 and f16s2_eligible(mod, x.shape[0], x.shape[2], x.shape[3]))):
+                                (self.s2 and f16s2_eligible(mod, x.shape[0], x.shape[2], x.shape[3])) or
+                                (self.x and f16x_eligible(mod, x.shape[0], x.shape[2], x.shape[3]))):
             return None
         self.saved[mod] = mod.weight.data
         mod.weight.data = mod.weight.data.half().float()
@@ -182,6 +215,7 @@ class _Recorder(object):
         self.cur_lane = 0      # launch lane inside the current region
         self.f16 = False       # precision = 'f16': eligible 3x3 convs are recorded as 'convh' ops (csrc/conv_h.hip)
         self.f16s2 = False     # precision = 'f16s2': ... and eligible 3x3 stride-2 convs as 'convh2' ops
+        self.f16x = False      # precision = 'f16x': ... and the 3x3 convs of the 32-multiple widths as 'convhx' ops
 
     def _push(self, kind, op):
         op['region'], op['lane'] = self.region, self.cur_lane
@@ -257,6 +291,13 @@ class _Recorder(object):
             self._touch(x, dst)
             self._push('convh2', op)
             return dst
+        if self.f16x and self.takes_f16x(x, weight, bias, act, res, stride, pad, out_nchw, cout_cs, dst_given):
+            scale, shift = fold_scale_shift(cout, None, bn)
+            op = dict(x=x, w=self.weight(pack_conv_weight_f16x(weight)), scale=self.weight(scale), shift=self.weight(shift),
+                      res=res, y=dst, cin=cin, cout=cout, act=act, stride=stride, tag=tag)
+            self._touch(x, res, dst)
+            self._push('convhx', op)
+            return dst
         scale, shift = fold_scale_shift(cout, bias, bn)
         # the filter is packed when the program is built: the layout depends on the tile
         # configuration the tuner picks for the shape (direct vs Winograd kernels)
@@ -283,6 +324,15 @@ class _Recorder(object):
                 cout_cs is not None or dst_given:
             return False
         return _h2_applies(x.n, x.h, x.w, cin, x.cs, cout, _round_up(cout, 4), act)
+
+    @staticmethod
+    def takes_f16x(x, weight, bias, act, res, stride, pad, out_nchw=False, cout_cs=None, dst_given=False):
+        """``f16x_eligible`` on a recorded layer: its C predicate, asked with the layer's own epilogue."""
+        cout, cin, kh, kw = weight.shape
+        if (kh, kw, pad) != (3, 3, 1) or stride not in (1, 2) or bias is not None or out_nchw or cout_cs is not None or \
+                dst_given:
+            return False
+        return _hx_applies(x.n, x.h, x.w, cin, x.cs, cout, _round_up(cout, 4), res is not None, act, stride)
 
     def conv_pair(self, xa, conv_a, bn_a, act_a, res_a, xb, conv_b, bn_b, act_b, res_b, tag=''):
         """Two independent 3x3 / stride 1 / pad 1 convolutions (+ folded BatchNorm, residual, ReLU) as ONE launch
@@ -516,6 +566,15 @@ class Program(object):
             flops = 2.0 * y.n * y.h * y.w * op['cout'] * op['cin'] * 9
             nbytes = 4.0 * (x.n * x.h * x.w * op['cin'] + y.n * y.h * y.w * op['cout']) + 2.0 * op['cout'] * op['cin'] * 9
             klass = 'conv3x3s2h %d->%d@%dx%d' % (op['cin'], op['cout'], y.h, y.w)
+        elif kind == 'convhx':
+            x, y = op['x'], op['y']
+            res = op['res'].ref() if op['res'] is not None else NULL_REF
+            _lib.check(L.egn_program_add_conv3x3_hx(h, x.ref(), op['w'], op['scale'], op['shift'], res, y.ref(),
+                                                    x.n, x.h, x.w, op['cin'], op['cout'], op['act'], op['stride']), op['tag'])
+            flops = 2.0 * y.n * y.h * y.w * op['cout'] * op['cin'] * 9
+            nbytes = 4.0 * (x.n * x.h * x.w * op['cin'] + y.n * y.h * y.w * op['cout'] * (2 if op['res'] is not None else 1)) + \
+                2.0 * op['cout'] * op['cin'] * 9
+            klass = 'conv3x3hx%s %d->%d@%dx%d' % ('s2' if op['stride'] == 2 else '', op['cin'], op['cout'], y.h, y.w)
         elif kind == 'convpair':
             args, klass = [], []
             for half in (op['a'], op['b']):
@@ -677,16 +736,17 @@ class HRNetEngine(object):
         self.fuse_layer1 = os.environ.get('EGONET_AMD_PW_FUSE', '1') != '0'      # layer1's 1x1 pairs on csrc/conv_pw.hip
         # fuse output i -> branch i of the next module on the same lane, no join in between
         self.chain_regions = os.environ.get('EGONET_AMD_CHAIN', '1') != '0'
-        self.last_f16_ops = []    # tags of the layers the last recording lowered to the f16-operand ops (precision = 'f16' / 'f16s2')
+        self.last_f16_ops = []    # tags of the layers the last recording lowered to the f16-operand ops (precision = 'f16' / 'f16s2' / 'f16x')
 
     @property
     def precision(self):
-        """The model's ``precision`` attribute ('f32', the default, 'f16' or 'f16s2'): read at every forward, part of the
-        program key.  'f16' moves the layers ``f16_eligible`` names to csrc/conv_h.hip, 'f16s2' those and the layers
-        ``f16s2_eligible`` names; everything else, and the training tape, is recorded exactly as in 'f32'."""
+        """The model's ``precision`` attribute ('f32', the default, 'f16', 'f16s2' or 'f16x'): read at every forward, part of
+        the program key.  'f16' moves the layers ``f16_eligible`` names to csrc/conv_h.hip, 'f16s2' those and the layers
+        ``f16s2_eligible`` names, 'f16x' those and the layers ``f16x_eligible`` names; everything else, and the training
+        tape, is recorded exactly as in 'f32'."""
         prec = getattr(self.model, 'precision', 'f32')
-        if prec not in PRECISIONS:
-            raise ValueError("precision must be 'f32', 'f16' or 'f16s2', got %r" % (prec,))
+        if prec not in ALL_PRECISIONS:
+            raise ValueError("precision must be %s, got %r" % (_PRECISION_TEXT, prec))
         return prec
 
     # -- recording ---------------------------------------------------------
@@ -771,7 +831,9 @@ class HRNetEngine(object):
             return None
         lowered = [False] * mod.num_branches        # precision = 'f16': a layer the f16-operand op takes is never half of a pair
         if getattr(r, 'f16', False):
-            lowered = [any(r.takes_f16(x, conv.weight, conv.bias, ACT_RELU, None, conv.stride[0], conv.padding[0])
+            lowered = [any(r.takes_f16(x, conv.weight, conv.bias, ACT_RELU, None, conv.stride[0], conv.padding[0]) or
+                           (getattr(r, 'f16x', False) and
+                            r.takes_f16x(x, conv.weight, conv.bias, ACT_RELU, None, conv.stride[0], conv.padding[0]))
                            for blk in b for conv in (blk.conv1, blk.conv2) if getattr(blk, 'depth', 0) == 2)
                        for b, x in zip(mod.branches, xs)]
 
@@ -868,8 +930,9 @@ class HRNetEngine(object):
         own = r is None
         if own:
             r = _Recorder()
-            r.f16 = self.precision in ('f16', 'f16s2')     # (the training tape brings its own recorder: the switch is not its)
-            r.f16s2 = self.precision == 'f16s2'
+            r.f16 = self.precision in ('f16', 'f16s2', 'f16x')     # (the training tape brings its own recorder: the switch is not its)
+            r.f16s2 = self.precision in ('f16s2', 'f16x')
+            r.f16x = self.precision == 'f16x'
         x = r.nchw_to_nhwc(Ref(SLOT_USER0, 0), n, cin, h, w, tag='input')
         t = r.conv(x, m.conv1.weight, None, m.bn1, ACT_RELU, None, 2, 1, tag='conv1')
         t = r.conv(t, m.conv2.weight, None, m.bn2, ACT_RELU, None, 2, 1, tag='conv2')
@@ -970,7 +1033,7 @@ class HRNetEngine(object):
             out_shapes['decode_slot'] = SLOT_USER0 + nslots
             nslots += 3
         if own:
-            self.last_f16_ops = [op['tag'] for kind, op in r.ops if kind in ('convh', 'convh2')]
+            self.last_f16_ops = [op['tag'] for kind, op in r.ops if kind in ('convh', 'convh2', 'convhx')]
         return r, nslots, out_shapes
 
     def program(self, x, decode_mode=None, slot=0):

@@ -14,6 +14,7 @@ DIRECT, WINO2, WINO43, WINO4 = 0, 1, 2, 3
 
 CK = 16                 # input channels per K chunk (EGN_CK in csrc/egn_internal.h)
 H_CK, H_KS = 48, 14     # csrc/conv_h.hip: input channels per chunk, MFMA K steps of 32 per chunk (9 * 48 = 432 -> 448)
+HX_CK = 32              # ... of its CK = 32 instances ('f16x'): 9 * 32 = 288, nine K steps, one per tap
 
 
 def _round_up(v, m):
@@ -118,6 +119,26 @@ def unpack_conv_weight_f16(packed, cout, cin):
     u = packed.view(torch.float16).reshape(ct, nch, H_KS, 4, 16, 8).permute(0, 1, 2, 3, 5, 4)            # ... g j li
     u = u.reshape(ct, nch, H_KS * 32, 16)[:, :, :9 * H_CK].reshape(ct, nch, 9, H_CK, 16)
     return u.permute(0, 4, 1, 3, 2).reshape(cout, cin, 3, 3).contiguous()
+
+
+def pack_conv_weight_f16x(w):
+    """[Cout,Cin,3,3] -> the filter rounded ONCE to f16 (round-to-nearest-even) in the layout the CK = 32 instances of
+    csrc/conv_h.hip load (precision = 'f16x'): flat f16 [co-tile = Cout/16][chunk = Cin/32][tap 0..8][lane = 16 g + li][j 0..7]
+    holding W[16 ct + li][32 chunk + 8 g + j][tap] -- K step = tap, lane group = channel group, no padding.  Returned as a
+    flat fp32 VIEW of those bytes; ``unpack_conv_weight_f16x`` is the inverse."""
+    w = w.detach().to(torch.float32).cpu()
+    cout, cin, kh, kw = w.shape
+    assert (kh, kw) == (3, 3) and cout % 16 == 0 and cin % HX_CK == 0, w.shape
+    ct, nch = cout // 16, cin // HX_CK
+    u = w.half().reshape(ct, 16, nch, 4, 8, 9).permute(0, 2, 5, 3, 1, 4).contiguous()     # ct chunk tap g li j
+    return u.reshape(-1).view(torch.float32)
+
+
+def unpack_conv_weight_f16x(packed, cout, cin):
+    """The f16 filter [Cout,Cin,3,3] a ``pack_conv_weight_f16x`` result holds."""
+    ct, nch = cout // 16, cin // HX_CK
+    u = packed.view(torch.float16).reshape(ct, nch, 9, 4, 16, 8).permute(0, 4, 1, 3, 5, 2)               # ct li chunk g j tap
+    return u.reshape(cout, cin, 3, 3).contiguous()
 
 
 def pack_for_kind(w, kind):

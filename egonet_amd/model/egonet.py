@@ -43,7 +43,7 @@ def _dev_f64(a, device):
 
 class EgoNet(nn.Module):
     def __init__(self, cfgs, pre_trained=False, precision=None):
-        """``precision``: None (what ``cfgs['heatmapModel']['precision']`` says, default 'f32'), 'f32', 'f16' or 'f16s2' -- the
+        """``precision``: None (what ``cfgs['heatmapModel']['precision']`` says, default 'f32'), 'f32', 'f16', 'f16s2' or 'f16x' -- the
         opt-in fast inference modes of HC's HIP program (PoseHighResolutionNet.precision).  The lifter, training and
         every CPU path compute in fp32 whatever it says."""
         super().__init__()
@@ -52,8 +52,8 @@ class EgoNet(nn.Module):
         # plugin lookup by name, as in the reference (egonet.py:43-44)
         self.HC = eval('models.heatmapModel.' + hm['name'] + '.get_pose_net')(cfgs, is_train=False)
         if precision is not None:
-            if precision not in ('f32', 'f16', 'f16s2'):
-                raise ValueError("precision must be 'f32', 'f16' or 'f16s2', got %r" % (precision,))
+            if precision not in ('f32', 'f16', 'f16s2', 'f16x'):
+                raise ValueError("precision must be 'f32', 'f16', 'f16s2' or 'f16x', got %r" % (precision,))
             self.HC.precision = precision
         self.resolution = hm['input_size']
         self.xy_dict = {'flag': hm['add_xy']} if 'add_xy' in hm else None

@@ -298,9 +298,10 @@ class PoseHighResolutionNet(nn.Module):
         return self._torch_forward(x)
 
     hip_eval = True          # eval-mode CUDA forwards run the HIP program (see forward)
-    # 'f32' (default), 'f16' or 'f16s2': the opt-in fast inference modes.  'f16' runs the 3x3 / stride 1 convolutions that
+    # 'f32' (default), 'f16', 'f16s2' or 'f16x': the opt-in fast inference modes.  'f16' runs the 3x3 / stride 1 convolutions that
     # engine.f16_eligible names with f16 OPERANDS (round-to-nearest-even, fp32 accumulation, csrc/conv_h.hip); 'f16s2'
-    # those and the 3x3 / stride 2 convolutions that engine.f16s2_eligible names ('f16' keeps its bits).  Activations
+    # those and the 3x3 / stride 2 convolutions that engine.f16s2_eligible names ('f16' keeps its bits); 'f16x'
+    # those and the 3x3 convolutions of the 32-multiple widths that engine.f16x_eligible names.  Activations
     # stay fp32 in memory.  Only the eval-mode HIP program reads it: training, the autograd bridge and the torch graph
     # (so every CPU input, whatever the value) compute in fp32.  Any other value raises ValueError at the next forward.
     precision = 'f32'
@@ -438,7 +439,7 @@ def get_pose_net(cfgs, is_train, **kwargs):
     if hm.get('add_xy'):
         model.modify_input_channel(5)
     if hm.get('precision') is not None:
-        if hm['precision'] not in ('f32', 'f16', 'f16s2'):
-            raise ValueError("heatmapModel.precision must be 'f32', 'f16' or 'f16s2', got %r" % (hm['precision'],))
+        if hm['precision'] not in ('f32', 'f16', 'f16s2', 'f16x'):
+            raise ValueError("heatmapModel.precision must be 'f32', 'f16', 'f16s2' or 'f16x', got %r" % (hm['precision'],))
         model.precision = hm['precision']
     return model

@@ -727,6 +727,26 @@ int egn_conv3x3s2_h_f32(const float* x, const void* wpack_f16, const float* scal
 /* as a program op with a kind id of its own (13; egn_program_op_info: flops = 2 * 9 * N * Ho * Wo * Cout * Cin) */
 int egn_program_add_conv3x3s2_h(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift, egn_ref y,
                                 int N, int H, int W, int Cin, int Cout, int act);
+/* The same family for the 32-MULTIPLE widths (PoseHighResolutionNet.precision = 'f16x'): the same kernel walking the input
+ * channels in chunks of 32 instead of 48, stride 1 or 2 (H, W are the INPUT size; Ho = (H - 1) / stride + 1), the same
+ * rounding, accumulators and epilogue:
+ *     y = act(conv(f16(x), f16(w)) * scale + shift (+ res)),    act = EGN_ACT_NONE or EGN_ACT_RELU;  res at stride 1 only.
+ * The filter pack is engine.pack_conv_weight_f16x: [Cout/16][Cin/32][9 taps][64 lanes][8] f16, egn_conv3x3_hx_wpack_bytes
+ * = Cout * Cin * 9 * 2 bytes (0 for widths the family does not take).  egn_conv3x3_hx_applies is its one predicate,
+ * host-only: 1 where Cin in {32, 64, 128, 256}, Cout in {32, 64, 128, 256, 48, 96} with cs == C, N >= 1, H, W >= 2, input
+ * and output below 2 GiB, act none / ReLU, stride 1 or 2, no residual at stride 2 -- else 0 (Cin = 48 and its multiples
+ * belong to the two predicates above, whose answers do not change); the other entry points return EGN_E_BADARG where it
+ * says 0.  These are HRNet-W32's stage / transition / fuse layers and, in every width, layer1's 64 -> 64, the stem's
+ * second convolution and transition1 (256 -> C). */
+int egn_conv3x3_hx_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act,
+                           int stride);
+long egn_conv3x3_hx_wpack_bytes(int Cin, int Cout);
+int egn_conv3x3_hx_f32(const float* x, const void* wpack_f16, const float* scale, const float* shift,
+                       const float* res, float* y, int N, int H, int W, int Cin, int Cout, int act, int stride,
+                       void* stream);
+/* as a program op with a kind id of its own (14; egn_program_op_info: flops = 2 * 9 * N * Ho * Wo * Cout * Cin); res may be NULL */
+int egn_program_add_conv3x3_hx(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
+                               egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act, int stride);
 /* number of kernel launches issued through egn_program_run / _run_timed / _replay
  * since the library was loaded (process wide, all devices).  Test hook: a caller
  * can prove that a forward went through this library's kernels. */

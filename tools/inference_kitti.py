@@ -6,7 +6,7 @@ GPU crops -> HRNet key-points -> lifter -> pose solve -> KITTI result files ->
     python tools/inference_kitti.py --images <dir of png> --boxes <dir of KITTI label/detection txt>
         [--calib <dir>] --out <result dir> [--ckpt <dir with HC.pth L.pth LS.npy> | --synthetic]
         [--gt <label dir>] [--classes Car] [--conf-thres 0] [--alpha-mode proj|trans] [--frames-per-step 8]
-        [--refine pnp [--refine-max-shift 5.0] [--write-3d]] [--precision f32|f16|f16s2] [--draw <dir> [--draw-gt]]
+        [--refine pnp [--refine-max-shift 5.0] [--write-3d]] [--precision f32|f16|f16s2|f16x] [--draw <dir> [--draw-gt]]
 
 ``--draw DIR`` also draws every frame's predictions (2-D boxes, projected cuboids, key points) with the GPU rasteriser
 (EgoNet.post_process(visualize=True), csrc/overlay.hip) and writes ``DIR/<stem>.png`` plus, where the boxes carry 3-D
@@ -15,7 +15,8 @@ placements, the top view ``DIR/<stem>_bev.png``; ``--draw-gt`` (needs ``--gt``) 
 ``--precision f16`` (default f32) is the opt-in fast mode of the key-point network: the 3x3 / stride 1 convolutions of
 HRNet's stages 2-4 run with f16 operands and fp32 accumulation (csrc/conv_h.hip); results differ from the default's at
 the 1e-3 px level ("f16-operand mode").  ``--precision f16s2`` adds the 3x3 / stride 2 convolutions of the
-transition and fuse layers.
+transition and fuse layers; ``--precision f16x`` those and the 3x3 convolutions of the 32-multiple widths (HRNet-W32's
+stages; layer1, the stem's second convolution and transition1 in every width).
 
 ``--refine pnp`` fits every lifted cuboid rigidly to its own key points before the angles are read off
 (EgoNet.refine_pnp, the reference's ``pnp_refine`` flow without cv2); ``rot_y`` / ``alpha`` then come from the refined
@@ -125,9 +126,9 @@ def main(argv=None):
                     help='discard a fit whose root moved further than this (m) from the box it started at')
     ap.add_argument('--write-3d', action='store_true',
                     help="write the fit's own locations / dimensions for refined instances (needs --refine)")
-    ap.add_argument('--precision', default='f32', choices=['f32', 'f16', 'f16s2'],
+    ap.add_argument('--precision', default='f32', choices=['f32', 'f16', 'f16s2'] + ['f16x'],
                     help="f16: the key-point network's 3x3 stride-1 convolutions with f16 operands (opt-in fast mode); "
-                         "f16s2: those and the 3x3 stride-2 ones")
+                         "f16s2: those and the 3x3 stride-2 ones; f16x: those and the 3x3 convolutions of the 32-multiple widths")
     ap.add_argument('--draw', default=None, metavar='DIR', help='draw the predictions on the frames, PNGs into DIR')
     ap.add_argument('--draw-gt', action='store_true', help='add the label boxes of --gt to the top view')
     a = ap.parse_args(argv)

@@ -21,7 +21,14 @@ every 3x3 / stride 2 class of HRNet-W48 (the fuse layers' 48 -> 48 / 96 / 192 / 
 transitions' 96 -> 192, 192 -> 384, at the map sizes the network has them, with the fuse layers' epilogues) against the
 fp32 op of the shipped table; the step in 'f16' against 'f16s2'; the device-side deviation of 'f16s2' from 'f32'.  A class
 stays lowered only if it is faster by more than the spread at 64 crops and not slower beyond the spread at 16 crops at
-every map size (``keep``); the others are what engine.F16S2_FP32_CLASSES has to name."""
+every map size (``keep``); the others are what engine.F16S2_FP32_CLASSES has to name.
+
+``--x`` measures what precision = 'f16x' adds (default --out profiles/f16x_mode_bench.json): every (cin, cout, stride, map,
+epilogue) class the mode lowers on HRNet-W32 at 192 x 256 (the Pedestrian model) and the seven layers it adds on HRNet-W48,
+read off the recorded programs, each against the fp32 op of the shipped table at 64 and 16 crops; the Pedestrian
+``infer_crops`` step in 'f32' against 'f16x' and the W48 step in 'f16s2' against 'f16x'; the deviation of 'f16x' from 'f32'
+on the device for W32.  ``keep`` per (cin, cout, stride) by the rule above; the others are what engine.F16X_FP32_CLASSES
+has to name."""
 import argparse
 import ctypes as C
 import json
@@ -48,21 +55,22 @@ S2_CLASSES = ((48, 48, 64, RELU), (48, 48, 32, RELU), (48, 96, 64, NONE), (48, 1
               (96, 96, 32, RELU), (96, 192, 32, NONE), (96, 384, 16, NONE), (192, 384, 16, NONE))
 
 
-def class_row(n, c, hw, passes, cout=None, stride=1, act=RELU):
-    """Stride 1: c -> c with residual (the default).  Stride 2: c -> cout on an hw x hw INPUT, no residual."""
+def op_pair(n, cin, cout, h, w, stride, act, has_res, passes, seed, pack16, add16):
+    """The fp32 op the shipped table picks for a 3x3 / pad 1 layer on an h x w INPUT map and an f16-operand op of the same
+    layer (filter packed by ``pack16``, added to a program by ``add16(L, p, x, w16, scale, shift, res, y)``) as ops of ONE
+    program, in either order, alternating: (cfg, fp32 us per pass, f16 us per pass, max |y16 - y32|)."""
     L = _lib.lib()
     dev = torch.device('cuda')
-    cin, c = c, (c if cout is None else cout)
-    ho = (hw - 1) // stride + 1
-    g = torch.Generator().manual_seed(c + n)
-    x = torch.relu(torch.randn(n, hw, hw, cin, generator=g)).cuda()
-    wt = torch.randn(c, cin, 3, 3, generator=g) / (3.0 * cin ** 0.5)
-    key = (n, hw, hw, cin, cin, c, c, 3, 3, stride, 1, stride == 1, False)
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    g = torch.Generator().manual_seed(seed)
+    x = torch.relu(torch.randn(n, h, w, cin, generator=g)).cuda()
+    wt = torch.randn(cout, cin, 3, 3, generator=g) / (3.0 * cin ** 0.5)
+    key = (n, h, w, cin, cin, cout, cout, 3, 3, stride, 1, has_res, False)
     cfg = tuner.choose(dev, key, tuner.ALL_KINDS)
     w32 = engine.pack_for_kind(wt, tuner.kind_of(cfg)).cuda()
-    w16 = engine.pack_conv_weight_f16(wt).cuda()
-    sc, sh = (torch.rand(c, generator=g) + 0.5).cuda(), torch.randn(c, generator=g).cuda()
-    res = torch.randn(n, ho, ho, c, generator=g).cuda()          # (stride 2: bound to its slot, read by neither op)
+    w16 = pack16(wt).cuda()
+    sc, sh = (torch.rand(cout, generator=g) + 0.5).cuda(), torch.randn(cout, generator=g).cuda()
+    res = torch.randn(n, ho, wo, cout, generator=g).cuda()       # (bound to its slot; read only where has_res)
     y32, y16 = torch.empty_like(res), torch.empty_like(res)
     tensors = (x, w32, w16, sc, sh, res, y32, y16)
     progs = []
@@ -71,15 +79,13 @@ def class_row(n, c, hw, passes, cout=None, stride=1, act=RELU):
         for slot, t in enumerate(tensors):
             _lib.check(L.egn_program_bind(p, slot, _lib.ptr(t)))
         R = [_lib.Ref(s, 0) for s in range(8)]
+        rref = R[5] if has_res else _lib.NULL_REF
         for which in order:
             if which == 0:
-                _lib.check(L.egn_program_add_conv2d(p, R[0], R[1], R[3], R[4], R[5] if stride == 1 else _lib.NULL_REF, R[6],
-                                                    n, hw, hw, cin, cin, c, c, 3, 3, stride, 1, act, 0, cfg), 'fp32 op')
-            elif stride == 2:
-                _lib.check(L.egn_program_add_conv3x3s2_h(p, R[0], R[2], R[3], R[4], R[7], n, hw, hw, cin, c, act), 'f16 op')
+                _lib.check(L.egn_program_add_conv2d(p, R[0], R[1], R[3], R[4], rref, R[6],
+                                                    n, h, w, cin, cin, cout, cout, 3, 3, stride, 1, act, 0, cfg), 'fp32 op')
             else:
-                _lib.check(L.egn_program_add_conv3x3_h(p, R[0], R[2], R[3], R[4], R[5], R[7], n, hw, hw, c, c,
-                                                       engine.ACT_RELU), 'f16 op')
+                _lib.check(add16(L, p, R[0], R[2], R[3], R[4], rref, R[7]), 'f16 op')
         progs.append((p, order))
     st = _lib.current_stream()
     us = {0: [], 1: []}
@@ -99,18 +105,78 @@ def class_row(n, c, hw, passes, cout=None, stride=1, act=RELU):
     finally:
         for p, _ in progs:
             L.egn_program_destroy(p)
-    m32, m16 = statistics.median(us[0]), statistics.median(us[1])
-    s32, s16 = max(us[0]) - min(us[0]), max(us[1]) - min(us[1])
+    return cfg, us[0], us[1], diff
+
+
+def _row(n, label, cfg, us32, us16, diff, floor):
+    m32, m16 = statistics.median(us32), statistics.median(us16)
+    s32, s16 = max(us32) - min(us32), max(us16) - min(us16)
+    return {'crops': n, 'class': label, 'fp32_cfg': cfg, 'fp32_us': m32, 'fp32_spread_us': s32,
+            'f16_us': m16, 'f16_spread_us': s16, 'fp32_all_us': us32, 'f16_all_us': us16,
+            'speedup': m32 / m16, 'faster': bool(m32 - m16 > max(s32, s16)),
+            'f16_activation_bytes_floor_us': floor, 'max_abs_diff_f16_vs_fp32': diff}
+
+
+def class_row(n, c, hw, passes, cout=None, stride=1, act=RELU):
+    """Stride 1: c -> c with residual (the default).  Stride 2: c -> cout on an hw x hw INPUT, no residual."""
+    cin, c = c, (c if cout is None else cout)
+    ho = (hw - 1) // stride + 1
+
+    def add16(L, p, x, w16, sc, sh, res, y):
+        if stride == 2:
+            return L.egn_program_add_conv3x3s2_h(p, x, w16, sc, sh, y, n, hw, hw, cin, c, act)
+        return L.egn_program_add_conv3x3_h(p, x, w16, sc, sh, res, y, n, hw, hw, c, c, engine.ACT_RELU)
+    cfg, us32, us16, diff = op_pair(n, cin, c, hw, hw, stride, act, stride == 1, passes, c + n,
+                                    engine.pack_conv_weight_f16, add16)
     px = float(n * hw * hw)
     # x, res, y once at 8 TB/s (stride 2: x and y)
     floor = 4.0 * (px * c * 3 if stride == 1 else px * cin + float(n * ho * ho) * c) / 8.0e12 * 1e6
-    row = {'crops': n, 'class': '%d->%d@%dx%d' % (cin, c, hw, hw), 'fp32_cfg': cfg, 'fp32_us': m32, 'fp32_spread_us': s32,
-           'f16_us': m16, 'f16_spread_us': s16, 'fp32_all_us': us[0], 'f16_all_us': us[1],
-           'speedup': m32 / m16, 'faster': bool(m32 - m16 > max(s32, s16)),
-           'f16_activation_bytes_floor_us': floor, 'max_abs_diff_f16_vs_fp32': diff}
+    row = _row(n, '%d->%d@%dx%d' % (cin, c, hw, hw), cfg, us32, us16, diff, floor)
     if stride == 2:
-        row.update(stride=2, act=act, not_slower=bool(m16 - m32 <= max(s32, s16)))
+        s = max(row['fp32_spread_us'], row['f16_spread_us'])
+        row.update(stride=2, act=act, not_slower=bool(row['f16_us'] - row['fp32_us'] <= s))
     return row
+
+
+def x_classes(cfg, n):
+    """Every class precision = 'f16x' lowers to the CK = 32 instances on the model of ``cfg`` at ``n`` crops, whatever
+    engine.F16X_FP32_CLASSES holds: sorted unique (cin, cout, stride, h, w, act, residual), h x w the INPUT map."""
+    from egonet_amd.model.heatmapModel import hrnet
+    net = hrnet.get_pose_net(cfg, is_train=False).eval()
+    net.precision = 'f16x'
+    iw, ih = cfg['heatmapModel']['input_size']
+    shipped, engine.F16X_FP32_CLASSES = engine.F16X_FP32_CLASSES, ()
+    try:
+        with torch.no_grad():
+            rec, _, _ = engine.HRNetEngine(net)._record(n, 3, ih, iw, None)
+    finally:
+        engine.F16X_FP32_CLASSES = shipped
+    return sorted({(op['cin'], op['cout'], op['stride'], op['x'].h, op['x'].w, op['act'], op['res'] is not None)
+                   for kind, op in rec.ops if kind == 'convhx'})
+
+
+def class_row_x(n, cin, cout, stride, h, w, act, has_res, passes):
+    """As ``class_row`` for the 'f16x' op on an h x w INPUT map, with the layer's own epilogue."""
+    def add16(L, p, x, w16, sc, sh, res, y):
+        return L.egn_program_add_conv3x3_hx(p, x, w16, sc, sh, res, y, n, h, w, cin, cout, act, stride)
+    cfg, us32, us16, diff = op_pair(n, cin, cout, h, w, stride, act, has_res, passes, cin + cout + n,
+                                    engine.pack_conv_weight_f16x, add16)
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    # x, y (and res) once at 8 TB/s
+    floor = 4.0 * (float(n * h * w) * cin + float(n * ho * wo) * cout * (2 if has_res else 1)) / 8.0e12 * 1e6
+    row = _row(n, '%d->%d s%d@%dx%d' % (cin, cout, stride, h, w), cfg, us32, us16, diff, floor)
+    s = max(row['fp32_spread_us'], row['f16_spread_us'])
+    row.update(key=[cin, cout, stride], act=act, residual=has_res, not_slower=bool(row['f16_us'] - row['fp32_us'] <= s))
+    return row
+
+
+def _ped_ego():
+    cfg = configs.ped_config('coordinates')
+    ego = EgoNet(cfg, pre_trained=False)
+    ego.HC.load_state_dict(synth.synth_state_dict(ego.HC.state_dict(), seed=1))
+    ego.L.load_state_dict(synth.synth_state_dict(ego.L.state_dict(), seed=2))
+    ego.LS = synth.synth_lifter_stats(66, 96, seed=1)
+    return ego.eval().cuda()
 
 
 def _w48_ego():
@@ -122,8 +188,9 @@ def _w48_ego():
     return ego.eval().cuda()
 
 
-def step_row(ego, batch, passes, steps, modes=('f32', 'f16')):
-    crops = synth.synth_crops(batch, 3, 256, 256, seed=100).cuda()
+def step_row(ego, batch, passes, steps, modes=('f32', 'f16'), size=(256, 256)):
+    """``size``: (height, width) of the crops."""
+    crops = synth.synth_crops(batch, 3, size[0], size[1], seed=100).cuda()
     rets = [modify_bbox(b, 1.0) for b in synth.synth_boxes(batch, seed=5)]
     centers = torch.tensor(np.stack([r['c'] for r in rets]), dtype=torch.float64, device='cuda')
     scales = torch.tensor(np.stack([r['s'] for r in rets]), dtype=torch.float64, device='cuda')
@@ -199,19 +266,59 @@ def accuracy(ego, mode='f16'):
     return out
 
 
+def accuracy_x(ego):
+    """precision = 'f16x' on the device: the test model of tests/f16x_mode_case.py against its fp32 CPU forward beside
+    the CPU emulation's E, and HRNet-W32 at 192 x 256 on 8 crops, 'f16x' against 'f32' on the device."""
+    import f16x_mode_case as case
+    out = {}
+    with open(case.BOUNDS_PATH) as f:
+        bounds = json.load(f)
+    for head in case.HEADS:
+        net = case.model(head)
+        x = case.crops('forward')
+        ref = case.cpu_f32(net, x)
+        net = net.cuda()
+        row = {}
+        with torch.no_grad():
+            for prec in ('f32', 'f16x'):
+                net.precision = prec
+                row[prec] = case.deviations(case.quantities(net(x.cuda())), ref)
+        row['E_cpu_emulation'] = {k: bounds[head]['forward'][k] for k in row['f16x']}
+        out['test_model_%s_vs_fp32_cpu' % head] = row
+    x = synth.synth_crops(8, 3, case.HEIGHT, case.WIDTH, seed=100).cuda()
+    res = {}
+    with torch.no_grad():
+        for prec in ('f32', 'f16x'):
+            ego.HC.precision = prec
+            res[prec] = case.quantities(ego.HC(x))
+    ego.HC.precision = 'f32'
+    q32, q16 = res['f32'], res['f16x']
+    m32, m16 = q32['heatmap'], q16['heatmap']
+    out['w32_192x256_8_crops_f16x_vs_f32_device'] = {
+        'heatmap_max_abs_diff': float((m16 - m32).abs().max()), 'heatmap_max_abs': float(m32.abs().max()),
+        'coords_px_max_abs_diff': float((q16['coords_px'] - q32['coords_px']).abs().max()),
+        'softargmax_px_max_abs_diff': float((q16['softargmax_px'] - q32['softargmax_px']).abs().max()),
+        'argmax_agreement': float((m16.flatten(2).argmax(2) == m32.flatten(2).argmax(2)).double().mean())}
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--passes', type=int, default=7)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--no-step', action='store_true', help='the per-class table alone')
     ap.add_argument('--s2', action='store_true', help="what precision = 'f16s2' adds to 'f16' (the stride-2 classes)")
+    ap.add_argument('--x', action='store_true', help="what precision = 'f16x' adds (the 32-multiple widths)")
     ap.add_argument('--out', default=None)
     a = ap.parse_args(argv)
     if a.passes < 3:
         ap.error('--passes must be at least 3')
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'f16s2_mode_bench.json' if a.s2 else 'f16_mode_bench.json')
+        a.out = os.path.join(ROOT, 'profiles', 'f16x_mode_bench.json' if a.x else
+                             ('f16s2_mode_bench.json' if a.s2 else 'f16_mode_bench.json'))
     os.environ.setdefault('EGONET_AMD_AUTOTUNE', '0')
+    if a.x:
+        return main_x(a)
     if a.s2:
         return main_s2(a)
     out = {'what': 'us per op (egn_program_run_timed, medians of %d passes, spread = max - min) of the f16-operand 3x3 op '
@@ -267,6 +374,56 @@ def main_s2(a):
                                   for r in rows},
                       'step_ms': [[r['crops'], round(r['f16_ms_per_step'], 3), round(r['f16s2_ms_per_step'], 3), r['f16_ops'], r['f16s2_ops']]
                                   for r in out.get('infer_crops_step', [])]}))
+    return out
+
+
+def main_x(a):
+    rows = []
+    for n in (64, 16):
+        ped = x_classes(configs.ped_config('coordinates'), n)
+        w48 = [c for c in x_classes(configs.w48_config('coordinates'), n) if c not in ped]
+        for model, classes in (('w32_192x256', ped), ('w48_256x256', w48)):
+            for cin, cout, stride, h, w, act, has_res in classes:
+                rows.append(dict(class_row_x(n, cin, cout, stride, h, w, act, has_res, a.passes), model=model))
+    keep = {}
+    for r in rows:
+        k = '%d->%d s%d' % tuple(r['key'])
+        keep[k] = keep.get(k, True) and (r['faster'] if r['crops'] == 64 else r['not_slower'])
+    out = {'what': 'us per op (egn_program_run_timed, medians of %d passes, spread = max - min) of the f16-operand 3x3 op '
+                   'on chunks of 32 against the fp32 op of the shipped tile table; ms per infer_crops step of HRNet-W32 at '
+                   '192 x 256 in f32 and f16x modes and of HRNet-W48 in f16s2 and f16x modes (medians of alternating '
+                   'windows); deviation of f16x from f32 on the device' % a.passes,
+           'device': torch.cuda.get_device_name(0), 'classes': rows, 'keep': keep,
+           'F16X_FP32_CLASSES_measured': sorted(k for k, v in keep.items() if not v),
+           'F16X_FP32_CLASSES_shipped': [list(c) for c in engine.F16X_FP32_CLASSES]}
+    if not a.no_step:
+        ego = _ped_ego()
+        out['w32_infer_crops_step'] = [step_row(ego, b, a.passes, a.steps, modes=('f32', 'f16x'), size=(256, 192))
+                                       for b in (64, 16)]
+        out['accuracy'] = accuracy_x(ego)
+        del ego
+        torch.cuda.empty_cache()
+        ego = _w48_ego()
+        out['w48_infer_crops_step'] = [step_row(ego, b, a.passes, a.steps, modes=('f16s2', 'f16x')) for b in (64, 16)]
+        # the 16-crop step again in a model of its own that never ran 64 crops (as --s2: its time moves with where the
+        # programs' arenas lie)
+        del ego
+        torch.cuda.empty_cache()
+        ego = _w48_ego()
+        out['w48_infer_crops_step_16_crops_fresh_model'] = step_row(ego, 16, a.passes, a.steps, modes=('f16s2', 'f16x'))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    print(json.dumps({'out': a.out, 'keep': keep,
+                      'classes': {'%s n%d' % (r['class'], r['crops']): [round(r['fp32_us'], 1), round(r['fp32_spread_us'], 1),
+                                                                        round(r['f16_us'], 1), round(r['f16_spread_us'], 1)]
+                                  for r in rows},
+                      'w32_step_ms': [[r['crops'], round(r['f32_ms_per_step'], 3), round(r['f16x_ms_per_step'], 3), r['f16x_ops']]
+                                      for r in out.get('w32_infer_crops_step', [])],
+                      'w48_step_ms': [[r['crops'], round(r['f16s2_ms_per_step'], 3), round(r['f16x_ms_per_step'], 3),
+                                       r['f16s2_ops'], r['f16x_ops']] for r in out.get('w48_infer_crops_step', []) +
+                                      [out[k] for k in ('w48_infer_crops_step_16_crops_fresh_model',) if k in out]]}))
     return out
 
 
