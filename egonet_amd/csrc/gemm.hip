@@ -33,9 +33,10 @@
 //     the NT form goes through a wave-private LDS transpose for the same store width;
 //   * block index -> tile: XCD-aware (block b runs on XCD b % 8): the blocks of one XCD share rows of A.
 //
-// Shapes: M % BM == 0, N % BN == 0, K % 32 == 0 (per split), leading dimensions % 4 == 0; anything else stays on
-// the conv-kernel route (egn_gemm_supported).  Numerics: an fp32 fmaf chain in k order per split, splits added
-// in a fixed order -- deterministic.
+// Shapes: M % BM == 0, N % BN == 0, K % 32 == 0 (per split), leading dimensions % 4 == 0 and no smaller than the row
+// they stride, A and B below 0xF0000000 bytes (rows x leading dimension); anything else stays on the conv-kernel
+// route (egn_gemm_supported, which refuses exactly what the launcher refuses).  Numerics: an fp32 fmaf chain in k
+// order per split, splits added in a fixed order -- deterministic.
 #include <stdlib.h>
 
 #include "conv_common.h"
@@ -371,6 +372,10 @@ int gemm_launch(GemmArgs g, hipStream_t st) {
 
 }  // namespace
 
+// bytes the buffer descriptor of A / B spans: rows x leading dimension as the operand lies
+static size_t gemm_a_bytes(int form, int M, int K, int lda) { return (size_t)(form == 2 ? K : M) * lda * 4; }
+static size_t gemm_b_bytes(int form, int N, int K, int ldb) { return (size_t)(form == 0 ? N : K) * ldb * 4; }
+
 // variant: tile configuration (0 = default of the form); see egn_gemm_variants
 //   form 0 NT: C = A[M][K] B[N][K]^T (+bias)     form 1 NN: C = A[M][K] B[K][N]     form 2 TN: C = A[K][M]^T B[K][N]
 extern "C" int egn_gemm_supported(int form, int M, int N, int K, int lda, int ldb, int ldc) {
@@ -378,6 +383,12 @@ extern "C" int egn_gemm_supported(int form, int M, int N, int K, int lda, int ld
   if ((lda | ldb | ldc) & 3) return 0;
   if (M % 128 || N % 128 || K % GK) return 0;
   if (form == 2 && ((M / 128) * (N / 128)) % 8) return 0;
+  // a leading dimension below the row it strides (0 and negative values among them) folds rows onto each other:
+  // A is [M][K] (form 2: [K][M]), B is [N][K] (form 0) or [K][N], C is [M][N]
+  if (lda < (form == 2 ? M : K) || ldb < (form == 0 ? K : N) || ldc < N) return 0;
+  // the kernels address A and B through 32-bit buffer offsets: what the launcher cannot take is refused HERE, so
+  // that a caller who asks first falls back to the conv-kernel route instead of seeing the launch fail
+  if (gemm_a_bytes(form, M, K, lda) >= 0xF0000000ull || gemm_b_bytes(form, N, K, ldb) >= 0xF0000000ull) return 0;
   return 1;
 }
 
@@ -407,9 +418,8 @@ extern "C" int egn_gemm_ex_f32(int form, const float* A, const float* B, float* 
   GemmArgs g = {};
   g.A = A; g.B = B; g.C = C; g.bias = bias; g.addend = addend; g.stats = stats;
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.splits = 1;
-  g.a_bytes = (size_t)(form == 2 ? K : M) * lda * 4;
-  g.b_bytes = (size_t)(form == 0 ? N : K) * ldb * 4;
-  if (g.a_bytes >= 0xF0000000ull || g.b_bytes >= 0xF0000000ull) return EGN_E_BADARG;
+  g.a_bytes = gemm_a_bytes(form, M, K, lda);    // below 0xF0000000: egn_gemm_supported
+  g.b_bytes = gemm_b_bytes(form, N, K, ldb);
   if (form == 0) {
     switch (variant) {
       case 1: return gemm_launch<true, true, 128, 128, 2, 2, 3>(g, st);

@@ -360,6 +360,12 @@ int egn_pack_matrix_f32(const float* src, int ld, int cout, int cin,
  *                                                              `ws` of egn_gemm_ws_bytes bytes)
  * Row-major with leading dimensions lda / ldb / ldc (floats, multiples of 4).  egn_gemm_supported() = 1 for the
  * shapes the kernels take (M, N multiples of 128, K of 32); the callers keep the conv-kernel route for the rest.
+ * It answers 0 for a leading dimension smaller than the row it strides (form 0: lda >= K, ldb >= K; form 1: lda >= K,
+ * ldb >= N; form 2: lda >= M, ldb >= N; always ldc >= N -- zero and negative values among them: such rows would fold
+ * onto each other) and for an A or B of 0xF0000000 bytes or more (rows x leading dimension x 4: the range of the
+ * kernels' 32-bit buffer offsets).  The query and the launch agree: egn_gemm_f32 / egn_gemm_ex_f32 return
+ * EGN_E_BADARG exactly where the query says 0, or for a NULL A / B / C, a bias with form 2, an addend outside form 1,
+ * stats outside form 0 or with too few rows, or a missing / short `ws` where egn_gemm_ws_bytes is not 0.
  * variant 0 = default tile configuration of the form (others: tools/gemm_probe.py). */
 int egn_gemm_supported(int form, int M, int N, int K, int lda, int ldb, int ldc);
 long egn_gemm_ws_bytes(int form, int M, int N, int K);

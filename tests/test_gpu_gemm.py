@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
     (0, 4096, 1024, 1024, (3,)),           # the lifter's forward GEMM at the bench batch
     (1, 256, 256, 96, (0, 1, 2)),          # NN: da = dz W
     (1, 4096, 1024, 1024, (0,)),
-    (2, 1024, 1024, 256, (0, 1)),          # TN: dW = dz^T a (64 tiles, no split)
+    (2, 1024, 1024, 256, (0, 1)),          # TN: dW = dz^T a (64 tiles, two splits of K = 128)
     (2, 1024, 1024, 4096, (1,)),           # ... split along the batch, fixed-order reduction
 ])
 def test_gemm_forms_vs_float64(form, M, N, K, variants):
