@@ -67,7 +67,11 @@ __global__ __launch_bounds__(256) void cr_lines_kernel(const float* __restrict__
   float g;
   const float v = cr_crit(crit, cr - 1.f, &g);
   // d cr / d|AC|^2 = cr/|AC|^2 ... ; d|PQ|^2 / dQ = 2(Q-P), / dP = -2(Q-P)
-  const float gac = 2.f * g * cr / ac, gbd = 2.f * g * cr / bd;
+  // A kept line with A == C or B == D (the other distances pass the mask): cr = 0, and the reference's autograd gives
+  // every point of the line the gradient 0 (d cr / d|AC|^2 is finite, d|AC|^2 / dA = -2(C-A) = 0; d cr / d|BD|^2 =
+  // |AC|^2 / (...) = 0).  cr / |AC|^2 would be 0 / 0 here: that factor is 0.  B == C or A == D (a zero DENOMINATOR)
+  // is not finite in the reference either (cr = inf) and is left so.
+  const float gac = ac != 0.f ? 2.f * g * cr / ac : 0.f, gbd = bd != 0.f ? 2.f * g * cr / bd : 0.f;
   const float gbc = -2.f * g * cr / bc, gad = -2.f * g * cr / ad;
   const float acx = px[2] - px[0], acy = py[2] - py[0];
   const float bdx = px[3] - px[1], bdy = py[3] - py[1];

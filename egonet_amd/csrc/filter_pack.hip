@@ -26,7 +26,7 @@ static int pack_one(const float* w, float* dst, int Cout, int Cin, int taps, int
 //   transpose == 1: W[co][ci] = src[ci*ld + co]   (rows = Cin): the data-gradient view of a [cin][cout] weight
 extern "C" int egn_pack_matrix_f32(const float* src, int ld, int cout, int cin, int transpose, float* dst,
                                    void* stream) {
-  if (cout <= 0 || cin <= 0 || ld < (transpose ? cout : cin)) return EGN_E_BADARG;
+  if (!src || !dst || cout <= 0 || cin <= 0 || ld < (transpose ? cout : cin)) return EGN_E_BADARG;
   return transpose ? pack_one(src, dst, cin, cout, 1, FP_DGRAD, ld, stream)
                    : pack_one(src, dst, cout, cin, 1, 0, ld, stream);
 }

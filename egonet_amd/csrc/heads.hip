@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void pixel_unshuffle_kernel(const float* __res
 
 extern "C" int egn_pixel_unshuffle_nchw_to_nhwc_f32(const float* x, float* y, int N, int C, int H, int W, int cs,
                                                     int up, void* stream) {
-  if (N < 1 || H < 1 || W < 1 || up < 1 || C < 1 || cs % 4 || cs < C * up * up || ((uintptr_t)y & 15))
+  if (!x || !y || N < 1 || H < 1 || W < 1 || up < 1 || C < 1 || cs % 4 || cs < C * up * up || ((uintptr_t)y & 15))
     return EGN_E_BADARG;
   const size_t total = (size_t)N * H * W * (cs / 4);
   hipLaunchKernelGGL(pixel_unshuffle_kernel, dim3(heads_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, x,
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float4* __restri
 }
 
 extern "C" int egn_avgpool_fwd_f32(const float* x, float* y, int N, int H, int W, int cs, int k, void* stream) {
-  if (N < 1 || k < 1 || H < k || W < k || cs < 4 || cs % 4 || (((uintptr_t)x | (uintptr_t)y) & 15))
+  if (!x || !y || N < 1 || k < 1 || H < k || W < k || cs < 4 || cs % 4 || (((uintptr_t)x | (uintptr_t)y) & 15))
     return EGN_E_BADARG;
   const size_t total = (size_t)N * (H / k) * (W / k) * (cs / 4);
   hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(heads_grid(total, 256)), dim3(256), 0, (hipStream_t)stream,
@@ -247,7 +247,7 @@ extern "C" int egn_avgpool_fwd_f32(const float* x, float* y, int N, int H, int W
 
 extern "C" int egn_avgpool_bwd_f32(const float* dy, float* dx, int N, int H, int W, int cs, int k, int accumulate,
                                    void* stream) {
-  if (N < 1 || k < 1 || H < k || W < k || cs < 4 || cs % 4 || (((uintptr_t)dy | (uintptr_t)dx) & 15))
+  if (!dy || !dx || N < 1 || k < 1 || H < k || W < k || cs < 4 || cs % 4 || (((uintptr_t)dy | (uintptr_t)dx) & 15))
     return EGN_E_BADARG;
   const size_t total = (size_t)N * H * W * (cs / 4);
   hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(heads_grid(total, 256)), dim3(256), 0, (hipStream_t)stream,

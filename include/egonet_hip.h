@@ -348,7 +348,8 @@ int egn_conv2d_wgrad_plan_query(int N, int H, int W, int Cin, int cs_in, int Cou
                                 int cs_out, int KH, int KW, int stride, int pad,
                                 int* out);
 /* conv weights [nchunk][1][4][CoutP][4] from a row-major matrix:
- * transpose 0: W[co][ci] = src[co*ld+ci]; 1: W[co][ci] = src[ci*ld+co] */
+ * transpose 0: W[co][ci] = src[co*ld+ci]; 1: W[co][ci] = src[ci*ld+co].
+ * A NULL src / dst, cout / cin <= 0 or ld below the row length (cin; transposed: cout): EGN_E_BADARG. */
 int egn_pack_matrix_f32(const float* src, int ld, int cout, int cin,
                         int transpose, float* dst, void* stream);
 /* Dense fp32 GEMM on the matrix pipe (csrc/gemm.hip) for the lifter's nn.Linear layers -- reference
@@ -514,12 +515,14 @@ int egn_elem_loss_f32(const float* pred, const float* tgt, int rows, int cols,
  * (use_target_weight); crit as egn_elem_loss_f32.
  *   *loss += weight * mean(c(pred*w - tgt*w)) (zero it first);
  *   dx = weight * c'(pred*w - tgt*w) * w / (N*C*H*up*W*up) in the pre-shuffle layout
- *   (pad channels zero; dx may be NULL).  x, dx 16-byte aligned, cs % 4 == 0. */
+ *   (pad channels zero; dx may be NULL).  x, dx 16-byte aligned, cs % 4 == 0, else
+ *   EGN_E_BADARG; tgt at any 4-byte alignment (16 bytes: the vectorised path). */
 int egn_pixshuf_loss_f32(const float* x, const float* tgt, const float* tw, int N, int H,
                          int W, int C, int up, int cs, int crit, float weight, float* dx,
                          double* loss, void* stream);
 /* AvgPool2d(k) (stride k, no padding, floor) over NHWC: x [N,H,W,cs] -> y [N,H/k,W/k,cs],
- * the k*k taps summed, then / (k*k) (the angle head's AvgPool2d(4), hrnet.py:384-422) */
+ * the k*k taps summed, then / (k*k) (the angle head's AvgPool2d(4), hrnet.py:384-422).
+ * Both pools: a NULL or not 16-byte aligned operand, H or W < k, cs < 4 or cs % 4: EGN_E_BADARG. */
 int egn_avgpool_fwd_f32(const float* x, float* y, int N, int H, int W, int cs, int k,
                         void* stream);
 /* its backward: dx [N,H,W,cs] (= or, with accumulate, +=) dy[n, y/k, x/k, c] / (k*k);
@@ -536,7 +539,12 @@ int egn_l1_f32(const float* pred, const float* tgt, long n, float weight,
  * cr = |AC|^2|BD|^2 / (|BC|^2|AD|^2) / target_cr^2; a line counts when the
  * smallest non-zero distance among its four points > thres;
  * *loss += weight * sum(crit(cr,1)) / #lines kept; dcoords (may be NULL)
- * += the gradient.  crit: 0 mse, 1 l1, 2 smooth-l1.  ws: egn_cross_ratio_ws_bytes */
+ * += the gradient.  crit: 0 mse, 1 l1, 2 smooth-l1.  ws: egn_cross_ratio_ws_bytes.
+ * A kept line with A == C or B == D has cr = 0 and gradient 0 for its four points (the
+ * reference's autograd: d|AC|^2/dA = 0); with B == C or A == D cr is infinite, as in the
+ * reference, and so are the loss and the gradient of that line's points.  No line kept:
+ * *loss and dcoords keep their bits.  idx must hold joint indices in 0..K-1 (device memory:
+ * the entry point cannot check them). */
 long egn_cross_ratio_ws_bytes(int N, int L);
 int egn_cross_ratio_f32(const float* coords, int N, int K, const int* idx,
                         int L, double target_cr, float thres, int crit,
