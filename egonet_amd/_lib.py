@@ -101,6 +101,10 @@ SIGNATURES = {
     'egn_avgpool_bwd_f32': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     'egn_cross_ratio_ws_bytes': (C.c_long, [_i, _i]),
     'egn_cross_ratio_f32': (_i, [_p, _i, _i, _p, _i, _d, C.c_float, _i, C.c_float, _p, _p, _p, _p]),
+    'egn_softargmax_fwd_f32': (_i, [_p, _i, _i, _i, _i, _i, C.c_float, C.c_float, _p, _p, _p]),
+    'egn_softargmax_bwd_f32': (_i, [_p, _p, _p] + [_i] * 6 + [C.c_float, C.c_float, _i, _p, _p]),
+    'egn_softargmax_fwd_host_f32': (_i, [_p, _i, _i, _i, _i, _i, C.c_float, C.c_float, _p, _p]),
+    'egn_softargmax_bwd_host_f32': (_i, [_p, _p, _p] + [_i] * 6 + [C.c_float, C.c_float, _i, _p]),
     'egn_sigmoid_bwd_f32': (_i, [_p, _p, _p, C.c_long, _p]),
     'egn_packed_weight_floats': (C.c_long, [_i] * 5),
     'egn_pack_conv_weight_f32': (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),

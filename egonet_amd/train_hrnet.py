@@ -539,9 +539,12 @@ class TapeOwner(object):
         tape._accum(b, d)
 
 class HRNetTrainStep(TapeOwner):
-    """``step(images, target, joints_xy)`` = one iteration of trainer.py:183-209.  ``angle_type`` ('mse' | 'sl1'): the
-    criterion of the 'angleregression' head (MSELoss1D / SmoothL1Loss1D, function.py:204-228); ``step(images, target
-    [N,2])`` then, and ``last_angles`` holds the [N,2] prediction."""
+    """``step(images, target, joints_xy)`` = one iteration of trainer.py:183-209.  On the plain 'heatmap' head
+    ``w_coor`` and ``w_cr`` train the coordinate and cross-ratio terms on the soft-arg-max of the maps
+    (function.py:187-201, csrc/softargmax.hip) and ``last_coords`` holds it; with ``w_coor=0`` and no ``w_cr`` the map
+    term runs alone.  ``angle_type`` ('mse' | 'sl1'): the criterion of the 'angleregression' head (MSELoss1D /
+    SmoothL1Loss1D, function.py:204-228); ``step(images, target [N,2])`` then, and ``last_angles`` holds the [N,2]
+    prediction."""
 
     CR_CRITERIA = {'mse': 0, 'l1': 1, 'sl1': 2}      # loss_dict, function.py:17-20
 
@@ -573,8 +576,17 @@ class HRNetTrainStep(TapeOwner):
         elif angle_type is not None:
             raise ValueError('angle_type is the criterion of the angle head; this model has head_type %r'
                              % (model.head_type,))
-        if model.head_type == 'heatmap' and w_coor:
-            raise NotImplementedError("the 'heatmap' head trains with the heat-map term only (w_coor=0)")
+        # The plain 'heatmap' head trains the coordinate and cross-ratio terms on the soft-arg-max of its maps
+        # (function.py:187-201: coordinates_pred == None -> soft_arg_max(heatmaps_pred) / hm_size), csrc/softargmax.hip.
+        has_cr = w_cr not in (None, 'None')
+        if model.head_type == 'heatmap' and (w_coor or has_cr):
+            if model.pixel_shuffle:
+                raise NotImplementedError("the pixel-shuffle 'heatmap' head trains with the heat-map term only (w_coor=0, "
+                                          "no w_cr): the soft-arg-max kernel reads the maps of the plain head, not the "
+                                          "pre-shuffle activations this head's gradient enters at")
+            if use_target_weight:
+                raise NotImplementedError('use_target_weight is JointsMSELoss (function.py:22-46), which has no '
+                                          'coordinate or cross-ratio term: pass w_coor=0 and no w_cr with it')
         # JointsMSELoss(use_target_weight) (function.py:22-46, the heat-map head's criterion): both maps are multiplied
         # by target_weight[:, k] before the per-joint MSE.  JointsCompositeLoss (the coordinate head) stores the flag and
         # never uses it (function.py:95-111), so there it changes nothing -- like the reference.
@@ -595,8 +607,8 @@ class HRNetTrainStep(TapeOwner):
         self.apply_cr_loss = False
         self.cr_idx = None
         if self.w_cr is not None:
-            if model.head_type != 'coordinates':
-                raise NotImplementedError('the cross-ratio term needs the coordinate head')
+            if model.head_type not in ('coordinates', 'heatmap'):
+                raise NotImplementedError('the cross-ratio term needs the coordinate head or the plain heat-map head')
             if cr_indices is None:
                 from .common.img_proc import CR_INDICES_BBOX12
                 cr_indices = CR_INDICES_BBOX12
@@ -669,6 +681,59 @@ class HRNetTrainStep(TapeOwner):
                                           st), 'pixel-shuffle loss')
         tape._accum(u, du)
 
+    def _coord_terms_on(self):
+        return bool(self.w_coor) or (self.w_cr is not None and self.apply_cr_loss)
+
+    def _coord_terms(self, tape, cd, n, n_fs, n_cr, J, joints_xy, w, h, st):
+        """L_2d over the first ``n_fs`` rows of the compact coordinates ``cd`` [N, 2K] (function.py:159-168, 194-198)
+        and L_cr over the first ``n_cr`` (function.py:113-153, 199-201), added to ``loss_dev``.  Returns d loss /
+        d coords as [N * 2K], zero for the rows no term reads."""
+        L = self.L
+        dc = tape._empty(cd.numel())
+        if self.w_coor:
+            if joints_xy is None:
+                raise ValueError('the coordinate term needs joints_xy')
+            gt = torch.as_tensor(joints_xy, dtype=torch.float32).to(self.dev)[..., :2].clone()
+            gt[..., 0] /= w            # function.py:160-161 (img_size = (width, height))
+            gt[..., 1] /= h
+            gt = gt.contiguous()
+            if n_fs < n:
+                dc.zero_()                            # the unlabelled rows: no coordinate gradient
+            cnt = n_fs * 2 * J                        # the labelled rows come first (function.py:194-198)
+            _lib.check(L.egn_elem_loss_f32(_lib.ptr(cd), _lib.ptr(gt), 1, cnt, cnt, cnt,
+                                           self.coor_crit, self.w_coor, 0, _lib.ptr(dc),
+                                           _lib.ptr(self.loss_dev), st), 'coor loss')
+        else:
+            dc.zero_()
+        if self.w_cr is not None and self.apply_cr_loss:
+            nl = self.cr_idx.shape[0]
+            ws = tape._empty(L.egn_cross_ratio_ws_bytes(n_cr, nl) // 4)
+            _lib.check(L.egn_cross_ratio_f32(_lib.ptr(cd), n_cr, J, _lib.ptr(self.cr_idx), nl,
+                                             self.target_cr, self.cr_loss_thres, self.cr_crit, self.w_cr,
+                                             _lib.ptr(dc), _lib.ptr(self.loss_dev), _lib.ptr(ws), st),
+                       'cross_ratio')
+        return dc
+
+    def _integral_terms(self, tape, aug, da, n, n_fs, J, joints_xy, w, h, st):
+        """The heat-map head's L_2d and L_cr on the soft-arg-max of its maps (function.py:187-201), two launches of
+        csrc/softargmax.hip around the coordinate head's term kernels: the forward reads the padded NHWC maps where
+        the tape keeps them, the backward adds d loss / d maps to ``da``, which the heat-map term has written.
+
+        The reference's own arithmetic, quirks included: x is divided by hm_size[1] and y by hm_size[0] with hm_size =
+        [w, h] (function.py:192-193) -- on non-square maps each axis by the OTHER size; and on a mixed batch the maps
+        are cut to the labelled prefix for the heat-map term BEFORE the soft-arg-max (function.py:184-185 rebinds
+        heatmaps_pred), so with the heat-map term on L_cr sees the ``n_fs`` labelled crops only; without it all ``n``.
+        ``last_coords`` holds all ``n`` rows either way."""
+        from . import softargmax
+        div_x, div_y = float(aug.h), float(aug.w)     # hm_size[1], hm_size[0]
+        z = tape.data[id(aug)]
+        coords, save = softargmax.forward(z, n, aug.h, aug.w, J, aug.cs, div_x, div_y, st)
+        self.last_coords = coords
+        n_cr = n_fs if self.w_hm else n
+        dc = self._coord_terms(tape, coords.view(n, 2 * J), n, n_fs, n_cr, J, joints_xy, w, h, st)
+        rows = max(n_fs if self.w_coor else 0, n_cr if self.w_cr is not None and self.apply_cr_loss else 0)
+        softargmax.backward(z, save, dc, n, rows, aug.h, aug.w, J, aug.cs, div_x, div_y, da, True, st)
+
     def _labelled_rows(self, n, target, joints_xy):
         """``n_fs``: the rows of ``target`` when it holds fewer than the ``n`` images (a mixed batch: the labelled crops
         first), else ``n``.  Raises where the reference has no labelled-prefix slice or this step has none."""
@@ -707,6 +772,8 @@ class HRNetTrainStep(TapeOwner):
         over the labelled prefix (their means over ``n_fs`` rows, zero gradient for the rest), the cross-ratio term
         and the BatchNorm statistics over all ``N``; ``last_maps`` / ``last_coords`` keep ``N`` rows.  For the
         'coordinates' head and the plain 'heatmap' head with ``target`` given and ``use_target_weight`` off.
+        (The plain 'heatmap' head with ``w_coor`` / ``w_cr``: its coordinates are the soft-arg-max of the maps, which the
+        reference cuts to the labelled prefix first -- there L_cr covers ``n_fs`` rows too, see ``_integral_terms``.)
 
         The cyclic garbage collector is paused while the ~1 500 launches of the iteration are issued: a
         full collection in the middle (35 ms measured, every ~10 iterations) starves the GPU and doubles
@@ -744,31 +811,8 @@ class HRNetTrainStep(TapeOwner):
             if m.head_type == 'coordinates':
                 self.last_coords = outs[1].user
                 cd = self.last_coords.view(n, 2 * J)              # compact [N, 2K] = coords [N,K,2]
-                use_cr = self.w_cr is not None and self.apply_cr_loss
-                if self.w_coor or use_cr:
-                    dc = tape._empty(cd.numel())
-                    if self.w_coor:
-                        if joints_xy is None:
-                            raise ValueError('the coordinate term needs joints_xy')
-                        gt = torch.as_tensor(joints_xy, dtype=torch.float32).to(self.dev)[..., :2].clone()
-                        gt[..., 0] /= w            # function.py:160-161 (img_size = (width, height))
-                        gt[..., 1] /= h
-                        gt = gt.contiguous()
-                        if n_fs < n:
-                            dc.zero_()                            # the unlabelled rows: no coordinate gradient
-                        cnt = n_fs * 2 * J                        # the labelled rows come first (function.py:194-198)
-                        _lib.check(L.egn_elem_loss_f32(_lib.ptr(cd), _lib.ptr(gt), 1, cnt, cnt, cnt,
-                                                       self.coor_crit, self.w_coor, 0, _lib.ptr(dc),
-                                                       _lib.ptr(self.loss_dev), st), 'coor loss')
-                    else:
-                        dc.zero_()
-                    if use_cr:
-                        nl = self.cr_idx.shape[0]
-                        ws = tape._empty(L.egn_cross_ratio_ws_bytes(n, nl) // 4)
-                        _lib.check(L.egn_cross_ratio_f32(_lib.ptr(cd), n, J, _lib.ptr(self.cr_idx), nl,
-                                                         self.target_cr, self.cr_loss_thres, self.cr_crit, self.w_cr,
-                                                         _lib.ptr(dc), _lib.ptr(self.loss_dev), _lib.ptr(ws), st),
-                                   'cross_ratio')
+                if self._coord_terms_on():
+                    dc = self._coord_terms(tape, cd, n, n_fs, n, J, joints_xy, w, h, st)
                     self.seed_grad(tape, outs[1], dc)             # back to the padded NHWC row layout
             if m.head_type == 'angleregression':
                 self._angle_loss(tape, outs[0], target, n, st)    # loss and gradient seed in one launch
@@ -800,6 +844,8 @@ class HRNetTrainStep(TapeOwner):
                                                _lib.ptr(self.loss_dev), st), 'hm loss')
                 if wv is not None:
                     da = (da.view(n, aug.h, aug.w, aug.cs) * wv).reshape(-1)
+                if m.head_type == 'heatmap' and self._coord_terms_on():     # (the coordinate head has its own, above)
+                    self._integral_terms(tape, aug, da, n, n_fs, J, joints_xy, w, h, st)
                 tape._accum(aug, da)
             sess = begin_grad_sync(self, tape.back)
             for fn in reversed(tape.back):

@@ -195,6 +195,19 @@ def _angle_type(loss_func, cfgs):
                               % (name, cfg_name))
 
 
+def integral_terms(cfgs):
+    """cfgs['heatmapModel']['integral_terms']: train the heat-map head's coordinate and cross-ratio terms on the
+    soft-arg-max of its maps (off when absent; YAML booleans, or the strings a hand-written file may hold)."""
+    v = cfgs.get('heatmapModel', {}).get('integral_terms', False)
+    if isinstance(v, str):
+        if v.strip().lower() in ('true', 'yes', 'on', '1'):
+            return True
+        if v.strip().lower() in ('false', 'no', 'off', '0', 'none', ''):
+            return False
+        raise ValueError('heatmapModel.integral_terms must be a boolean, got %r' % (v,))
+    return bool(v)
+
+
 def make_step(model, cfgs, loss_func=None, optim=None):
     """The native step object for ``model`` (HC or L), configured like the reference's loss / optimizer."""
     lr = optim.param_groups[0]['lr'] if optim is not None else cfgs['optimizer']['lr']
@@ -210,7 +223,12 @@ def make_step(model, cfgs, loss_func=None, optim=None):
         w_hm, w_coor, cr = _loss_weights(loss_func, cfgs)
         sigma = cfgs.get('heatmapModel', {}).get('sigma', 1)
         if inner.head_type == 'heatmap':
-            w_coor, cr = 0.0, {k: v for k, v in cr.items() if k == 'hm_type'}
+            # The reference switches the heat-map head's terms by loss_type (JointsMSELoss: the map term alone;
+            # JointsCompositeLoss: L_2d and L_cr on the soft-arg-max as well, function.py:187-201).  Here the key
+            # heatmapModel.integral_terms does: a criterion object alone changes nothing, so the heat-map runs that
+            # exist keep their loss bit for bit.
+            if not integral_terms(cfgs):
+                w_coor, cr = 0.0, {k: v for k, v in cr.items() if k == 'hm_type'}
             # JointsMSELoss(use_target_weight=...) (tools/train_IGRs.py:42, function.py:22-46)
             cr['use_target_weight'] = bool(getattr(loss_func, 'use_target_weight',
                                                    cfgs.get('training_settings', {}).get('use_target_weight', False)))
@@ -364,6 +382,7 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
     step = make_step(model, cfgs, loss_func, optim)
     is_hc = isinstance(step, HRNetTrainStep)
     is_angle = is_hc and step.angle_crit is not None           # baselinealpha / baselinetheta: one term, no L_cr
+    maps_only = getattr(model.module if hasattr(model, 'module') else model, 'head_type', None) == 'heatmap'
     dev = step.dev
     # a metric with accumulate / read / reset (metric.criterions.DistanceSrcMeter) keeps its running sums on the device
     metric_on_device = metric_func is not None and hasattr(metric_func, 'accumulate')
@@ -399,7 +418,9 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
                     joints = meta['transformed_joints'] if step.w_coor else None
                     loss = step.step(data, target, joints,
                                      target_weight=weights if step.use_target_weight else None)
-                    prediction = (step.last_maps, step.last_coords) if step.last_coords is not None else step.last_maps
+                    # (the heat-map head's output is its maps, also when its integral terms fill last_coords)
+                    prediction = (step.last_maps, step.last_coords) \
+                        if step.last_coords is not None and not maps_only else step.last_maps
                 else:
                     loss = step.step(data, target)
                     prediction = None

@@ -550,6 +550,30 @@ int egn_cross_ratio_f32(const float* coords, int N, int K, const int* idx,
                         int L, double target_cr, float thres, int crit,
                         float weight, float* dcoords, double* loss, float* ws,
                         void* stream);
+/* Differentiable soft-arg-max of heat-maps (JointsCompositeLoss on a model that returns
+ * heat-maps only, function.py:187-201; soft_arg_max, img_proc.py:678-707) on the padded NHWC
+ * maps z [N,h,w,cs] f32, channels 0..K-1 live (csrc/softargmax.hip, softargmax_math.h).
+ * Forward, per map: m = max z, e_p = exp(z_p - m), ex = sum e_p x_p / sum e_p (x_p, y_p the
+ * integer column / row), ey alike; coords [N,K,2] = (ex / div_x, ey / div_y);
+ * save [N,K,4] = (ex, ey, m, sum e) for the backward.  fp32 sums in the fixed order the header
+ * documents: equal inputs give equal bits.  Logits of any finite size give finite results.
+ * Backward: dz [N,h,w,cs] (= or, with accumulate, +=) s_p ((x_p - ex) gx / div_x +
+ * (y_p - ey) gy / div_y) with s_p = e_p / sum e recomputed from z and save, (gx, gy) =
+ * dcoords [N,K,2]; channels K..cs-1 and the images n_rows..N-1 are neither read nor written.
+ * One launch each, counted by egn_launch_count().  The _host_ twins take host pointers and
+ * return the same bits.  EGN_E_BADARG: a NULL operand or one not aligned (z, dz, save: 16 bytes;
+ * coords, dcoords: 8), N < 1, K < 1, K > cs, cs % 4, h or w < 1, div_x or div_y not > 0,
+ * n_rows outside 0..N (device: n_rows > 65535). */
+int egn_softargmax_fwd_f32(const float* z, int N, int h, int w, int K, int cs, float div_x,
+                           float div_y, float* coords, float* save, void* stream);
+int egn_softargmax_bwd_f32(const float* z, const float* save, const float* dcoords, int N,
+                           int n_rows, int h, int w, int K, int cs, float div_x, float div_y,
+                           int accumulate, float* dz, void* stream);
+int egn_softargmax_fwd_host_f32(const float* z, int N, int h, int w, int K, int cs, float div_x,
+                                float div_y, float* coords, float* save);
+int egn_softargmax_bwd_host_f32(const float* z, const float* save, const float* dcoords, int N,
+                                int n_rows, int h, int w, int K, int cs, float div_x,
+                                float div_y, int accumulate, float* dz);
 /* dz = dy*y*(1-y): backward of the coordinate head's Sigmoid (hrnet.py:461-466) */
 int egn_sigmoid_bwd_f32(const float* dy, const float* y, float* dz, long n,
                         void* stream);

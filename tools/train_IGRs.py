@@ -67,13 +67,17 @@ def igr_cfgs(a):
         cfg = configs.clone(configs.hrnet_config(8, (256, 256), 33, 'angleregression', modules=(1, 1, 1), num_blocks=1)
                             if a.tiny else configs.w48_config('angleregression'))
     else:
-        cfg = configs.clone(configs.hrnet_config(8, (64, 64), 33, 'coordinates', modules=(1, 1, 1), num_blocks=1)
-                            if a.tiny else configs.w48_config('coordinates'))
+        # --integral-terms: the plain heat-map head, its L_2d / L_cr on the soft-arg-max of the maps (function.py:187-201)
+        head = 'heatmap' if getattr(a, 'integral_terms', False) else 'coordinates'
+        cfg = configs.clone(configs.hrnet_config(8, (64, 64), 33, head, modules=(1, 1, 1), num_blocks=1)
+                            if a.tiny else configs.w48_config(head))
     metric = 'AngleError' if angle else 'JointDistance2DSIP'
     cfg['heatmapModel'].update(jitter_bbox=True, jitter_params={'shift': [0.1, 0.1], 'scaling': [0.4, 0.4]},
                                loss_type='JointsCompositeLoss', loss_spec_list=['mse', 'l1', 'sl1'],
                                loss_weight_list=[1.0, 0.1, _cr_weight(a)], cr_loss_threshold=0.15,
                                target_type='gaussian', sigma=1)
+    if getattr(a, 'integral_terms', False) and not angle:
+        cfg['heatmapModel']['integral_terms'] = True            # the key trainer.make_step reads, not loss_type
     if angle:
         cfg['heatmapModel']['loss_type'] = a.loss_type          # one criterion: no spec / weight lists
         for key in ('loss_spec_list', 'loss_weight_list', 'cr_loss_threshold'):
@@ -187,6 +191,9 @@ def main(argv=None):
                     help='criterion of the angle baselines (libs/loss/function.py:204-228)')
     ap.add_argument('--cr-weight', type=float, default=None, metavar='W',
                     help="weight of the cross-ratio term, from the second epoch on (default: off, the shipped 'None')")
+    ap.add_argument('--integral-terms', action='store_true',
+                    help="train the plain heat-map head (head_type 'heatmap') with the coordinate and cross-ratio terms "
+                         'on the soft-arg-max of its maps (heatmapModel.integral_terms)')
     ap.add_argument('--ss-record', default=None, metavar='FILE',
                     help="the record of unlabelled frames (.npy dictionary with 'paths' and 'boxes'): mixed batches")
     ap.add_argument('--ss-img-root', default=None, metavar='DIR', help='directory of the unlabelled images')
@@ -202,6 +209,8 @@ def main(argv=None):
     if a.ss_record and _cr_weight(a) == 'None':
         ap.error('--ss-record without --cr-weight: the cross-ratio term is the only one that reads unlabelled crops; '
                  'unlabelled crops then only change BatchNorm statistics')
+    if a.integral_terms and a.exp_type in train_samples.EXP_TARGETS:
+        ap.error('--integral-terms belongs to the key-point model (instanceto2d)')
     if a.cr_weight is not None and a.exp_type in train_samples.EXP_TARGETS:
         ap.error('--cr-weight belongs to the key-point model (instanceto2d)')
     logging.basicConfig(level=logging.INFO, format='%(message)s')
