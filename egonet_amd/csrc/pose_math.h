@@ -181,7 +181,9 @@ EGN_HD inline double egn_pose_solve_one(const double* P, double kpt_x, double fx
   // reference re-orders to (x, y, z) = (b, a, c)  (egonet.py:273-276)
   double sb = R[2][1];
   sb = fmin(1.0, fmax(-1.0, sb));
-  const double b = asin(sb);
+  // cos(b) = |(R[2][0], R[2][2])|.  asin(sb) alone loses half the digits next to gimbal lock: one ulp below 1 is
+  // 1.5e-8 rad away from pi/2, and the matrix rebuilt from the angles is that far from R.
+  const double b = atan2(sb, sqrt(R[2][0] * R[2][0] + R[2][2] * R[2][2]));
   double a, c;
   if (fabs(sb) < 1.0 - 1e-12) {
     a = atan2(-R[2][0], R[2][2]);

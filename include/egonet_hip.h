@@ -187,7 +187,8 @@ int egn_keypoints_to_screen_f64(const float* local, int n, int K,
                                 const double* mean_in, const double* std_in,
                                 float* lifter_in, int ld_in, void* stream);
 
-/* pred3d[n,D] f64 = y[n,ld] fp32 * std_out + mean_out  (operations.py:49-51) */
+/* pred3d[n,D] f64 = y[n,ld] fp32 * std_out + mean_out  (operations.py:49-51): the product rounded, then the sum, as
+ * numpy does (no fused multiply-add), so the result is the reference's bit for bit */
 int egn_unnormalize_f64(const float* y, int n, int D, int ld,
                         const double* mean_out, const double* std_out,
                         double* pred3d, void* stream);
@@ -199,6 +200,9 @@ int egn_unnormalize_f64(const float* y, int n, int D, int ld,
  *   pred3d [n,32,3] f64;  kpt_x [n] f64 = screen x of key-point 0 (proj mode)
  *   euler [n,3] f64, alpha [n] f64;  alpha_mode 0 = 'proj' (needs fx,cx),
  *   1 = 'trans'
+ * A cuboid whose points span less than a plane (all 32 equal, say) has no
+ * rotation: its euler x, y and its alpha come back NaN, the other instances
+ * of the launch are not affected.
  * ---------------------------------------------------------------------- */
 int egn_pose_solve_f64(const double* pred3d, int n, const double* kpt_x,
                        double fx, double cx, int alpha_mode,
