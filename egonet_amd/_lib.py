@@ -119,6 +119,10 @@ SIGNATURES = {
     'egn_adam_step_dev_f32': (_i, [_p, _p, _p, _p, C.c_long, _p, C.c_float, C.c_float, C.c_float, _p, _p]),
     'egn_adam_l2_step_dev_f32': (_i, [_p, _p, _p, _p, C.c_long, _p, C.c_float, C.c_float, C.c_float, C.c_float, _p, _p]),
     'egn_sgd_step_dev_f32': (_i, [_p, _p, _p, C.c_long, _p, C.c_float, C.c_float, _p, _p]),
+    'egn_optim_item_floats': (_i, []),
+    'egn_optim_grouped_step_f32': (_i, [_i, _p, _p, _p, _p, _p, C.c_long, _p, _p, _i, _p, _p, C.c_long, _p, _p, _p]),
+    'egn_grad_norm_ws_bytes': (C.c_long, []),
+    'egn_grad_norm_clip_f32': (_i, [_p, C.c_long, C.c_float, _p, _p, _p]),
     'egn_program_create': (_p, [_i]),
     'egn_program_destroy': (None, [_p]),
     'egn_program_bind': (_i, [_p, _i, _p]),

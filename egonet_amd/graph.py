@@ -52,6 +52,8 @@ class GraphedStep(object):
         with torch.cuda.device(dev):
             # everything an iteration mutates, to undo the warm-up
             state = [flat.flat, flat.m, flat.v, flat.step_dev] + list(trainer.model.buffers())
+            if getattr(trainer, 'grouped', None) is not None:
+                state += trainer.grouped.state_tensors()        # the AMSGrad maximum, the clip scalars
             snap = [t.clone() for t in state]
             # warm up on a side stream (allocations, tile tuning, lazy inits), then capture
             side = torch.cuda.Stream()
@@ -74,7 +76,10 @@ class GraphedStep(object):
         invalidate(self.trainer.model)      # replays write the weights through raw pointers
 
     def __call__(self, *inputs):
-        self.trainer.flat.set_lr(self.trainer.lr)     # scheduler step since the last iteration
+        if getattr(self.trainer, 'grouped', None) is not None:
+            self.trainer.grouped.push_lrs()           # the group table's learning rates (step.set_lrs)
+        else:
+            self.trainer.flat.set_lr(self.trainer.lr)     # scheduler step since the last iteration
         for dst, src in zip(self.static, inputs):
             if dst is not None:
                 dst.copy_(src, non_blocking=True)

@@ -243,13 +243,18 @@ def begin_grad_sync(o, closures=()):
 
 
 def finish_step(o, sess, update, stream):
-    """After the backward (side stream joined): the gradient exchange, then the optimizer."""
+    """After the backward (side stream joined): the gradient exchange, then the optimizer.  A grouped update
+    (``o.grouped``, optim.py) takes its gradient norm here too, after the all-reduce of the whole buffer has completed
+    on this stream: every rank computes the same clip coefficient."""
     if sess is not None:
         sess.finish()
     elif o.grad_sync is not None:
         o.grad_sync(o.flat.grad)
     if update:
-        o.flat.update(o, stream)
+        if getattr(o, 'grouped', None) is not None:
+            o.grouped.update(stream)
+        else:
+            o.flat.update(o, stream)
 
 
 # -- bench.py: ``owner.timing = []`` collects (cfg, flops, start, end[, ...]) per forward / data-gradient launch ----

@@ -38,7 +38,7 @@ import os
 
 import torch
 
-from . import _lib, filters, tuner
+from . import _lib, filters, optim, tuner
 from .engine import invalidate
 from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID
 from .engine import Buf, HRNetEngine, _round_up
@@ -551,7 +551,7 @@ class HRNetTrainStep(TapeOwner):
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, w_hm=1.0, w_coor=0.1, grad_sync=None,
                  sigma=1, w_cr=None, cr_type='sl1', cr_indices=None, target_cr=4.0 / 3.0, cr_loss_thres=0.15,
                  hm_type='mse', coor_type='l1', optim_type='adam', momentum=0.0, weight_decay=0.0,
-                 use_target_weight=False, angle_type=None):
+                 use_target_weight=False, angle_type=None, optim_spec=None, max_grad_norm=None):
         self._init_tape_owner(model)
         p0 = next(model.parameters())
         self.angle_crit = None
@@ -622,9 +622,21 @@ class HRNetTrainStep(TapeOwner):
         self.sigma = sigma           # heatmapModel.sigma: targets drawn on the device when step(target=None)
         self.last_target_weight = None
         self.flat = FlatParams(model.parameters())
+        # parameter groups / AdamW / AMSGrad / Nesterov / dampening / clipping: the grouped update (optim.py); what the
+        # old entry points can express stays on them (self.grouped is None)
+        optim.attach(self, optim_spec, max_grad_norm)
         self.loss_dev = torch.zeros(1, dtype=torch.float64, device=self.dev)
         self.counters = StepCounters()
         self.last_maps = self.last_coords = self.last_angles = None
+
+    def set_lrs(self, lrs):
+        """One learning rate per parameter group (the scheduler's values); without groups, the one ``lr``."""
+        optim.set_lrs(self, lrs)
+
+    @property
+    def last_grad_norm(self):
+        """With ``max_grad_norm``: the last step's total gradient norm, a device scalar (no read-back); else None."""
+        return None if self.grouped is None else self.grouped.last_grad_norm
 
     def _drawn_target(self, joints_xy, joints_vis, n, h, w, mh, mw):
         """Gaussian heat-map targets drawn on the device from the joints at heatmap_size (img_proc.py:347-409): the

@@ -23,7 +23,7 @@ import os
 
 import torch
 
-from . import _lib, tuner
+from . import _lib, optim, tuner
 from .engine import _round_up, invalidate
 from .train_common import (FlatParams, PackedFilters, StepCounters, _gc_paused, begin_grad_sync, finish_step,
                            fork_wgrad, join_wgrad, timing_begin, timing_end, wgrad_side_stream)
@@ -370,7 +370,7 @@ class LifterCore(object):
 
 class LifterTrainStep(LifterCore):
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dropout=None, grad_sync=None,
-                 optim_type='adam', momentum=0.0, weight_decay=0.0):
+                 optim_type='adam', momentum=0.0, weight_decay=0.0, optim_spec=None, max_grad_norm=None):
         if optim_type not in ('adam', 'sgd'):
             raise NotImplementedError('optimizer %r (optimizer.py:8-40 knows adam and sgd)' % (optim_type,))
         # parameters / gradients / Adam moments as views of flat buffers: one Adam launch, one all-reduce buffer, step
@@ -387,6 +387,7 @@ class LifterTrainStep(LifterCore):
         self._noupdate_forwards = 0
         self.lr, self.betas, self.eps = lr, betas, eps
         self.optim_type, self.momentum, self.weight_decay = optim_type, float(momentum), float(weight_decay)
+        optim.attach(self, optim_spec, max_grad_norm)          # the grouped update, or None: the old entry points
         self.grad_sync = grad_sync
         self.p = float(model.p_dropout if dropout is None else dropout)
         self.params = self.flat.params
@@ -396,6 +397,15 @@ class LifterTrainStep(LifterCore):
 
     def grad_of(self, p):
         return self.grads[id(p)]
+
+    def set_lrs(self, lrs):
+        """One learning rate per parameter group (the scheduler's values); without groups, the one ``lr``."""
+        optim.set_lrs(self, lrs)
+
+    @property
+    def last_grad_norm(self):
+        """With ``max_grad_norm``: the last step's total gradient norm, a device scalar (no read-back); else None."""
+        return None if self.grouped is None else self.grouped.last_grad_norm
 
     @torch.no_grad()
     def step(self, x, target, update=True):

@@ -29,6 +29,7 @@ import time
 import numpy as np
 import torch
 
+from . import optim as optim_spec
 from . import parallel
 from .model import FCmodel
 from .model.heatmapModel.hrnet import PoseHighResolutionNet
@@ -49,19 +50,61 @@ def get_loader(dataset, cfgs, split, collate_fn=None):
     return torch.utils.data.DataLoader(dataset, **kw)
 
 
+def _flag(o, key):
+    """A boolean key of a config section (YAML booleans, or the strings a hand-written file may hold)."""
+    v = o.get(key, False)
+    if isinstance(v, str):
+        return v.strip().lower() in ('true', 'yes', 'on', '1')
+    return bool(v)
+
+
 def prepare_optim(model, cfgs):
     """optimizer.py:8-40 -- the torch objects carry the schedule; the native step does the update."""
     o = cfgs['optimizer']
     params = [p for p in model.parameters() if p.requires_grad]
     wd = float(o.get('weight_decay', 0.0) or 0.0)
-    if o['optim_type'] == 'adam':
-        optim = torch.optim.Adam(params, lr=o['lr'], weight_decay=wd)
+    # beyond the reference, all absent by default: optim_type 'adamw', amsgrad, nesterov, dampening, and
+    # no_decay_norm_bias -- two groups, the conv / linear weights keep weight_decay, BatchNorm gamma / beta and all
+    # biases get 0.  (max_grad_norm is read by make_step: it is the step's, not the torch object's.)
+    if _flag(o, 'no_decay_norm_bias'):
+        inner = model.module if hasattr(model, 'module') else model
+        params = [g for g in optim_spec.no_decay_groups(inner, wd) if g['params']]
+    if o['optim_type'] in ('adam', 'adamw'):
+        cls = torch.optim.Adam if o['optim_type'] == 'adam' else torch.optim.AdamW
+        more = dict(amsgrad=True) if _flag(o, 'amsgrad') else {}
+        optim = cls(params, lr=o['lr'], weight_decay=wd, **more)
     elif o['optim_type'] == 'sgd':
-        optim = torch.optim.SGD(params, lr=o['lr'], momentum=float(o.get('momentum', 0.0) or 0.0), weight_decay=wd)
+        more = {}
+        if _flag(o, 'nesterov'):
+            more['nesterov'] = True
+        if o.get('dampening'):
+            more['dampening'] = float(o['dampening'])
+        optim = torch.optim.SGD(params, lr=o['lr'], momentum=float(o.get('momentum', 0.0) or 0.0), weight_decay=wd,
+                                **more)
     else:
         raise NotImplementedError(o['optim_type'])              # as the reference (optimizer.py:27-28)
     sche = torch.optim.lr_scheduler.MultiStepLR(optim, milestones=o['milestones'], gamma=o['gamma'])
     return optim, sche
+
+
+def add_optim_arguments(ap):
+    """The optimizer switches of tools/train_IGRs.py and tools/train_lifting.py (argparse)."""
+    ap.add_argument('--optim', default='adam', choices=['adam', 'adamw', 'sgd'])
+    ap.add_argument('--weight-decay', type=float, default=0.0)
+    ap.add_argument('--no-decay-norm-bias', action='store_true',
+                    help='no weight decay on BatchNorm gamma / beta and on biases (two parameter groups)')
+    ap.add_argument('--max-grad-norm', type=float, default=None, metavar='X',
+                    help='clip the gradient to this 2-norm inside the update (off by default)')
+
+
+def optim_keys_from_args(args):
+    """-> the keys of cfgs['optimizer'] the switches above set."""
+    keys = {'optim_type': getattr(args, 'optim', 'adam'), 'weight_decay': getattr(args, 'weight_decay', 0.0)}
+    if getattr(args, 'no_decay_norm_bias', False):
+        keys['no_decay_norm_bias'] = True
+    if getattr(args, 'max_grad_norm', None) is not None:
+        keys['max_grad_norm'] = args.max_grad_norm
+    return keys
 
 
 def _rank():
@@ -214,9 +257,18 @@ def make_step(model, cfgs, loss_func=None, optim=None):
     sync = parallel.FlatGradSync() if torch.distributed.is_available() and torch.distributed.is_initialized() \
         and torch.distributed.get_world_size() > 1 else None
     inner = model.module if hasattr(model, 'module') else model          # DataParallel / DDP wrappers
+    # Parameter groups that differ (in their learning rate too), AdamW, AMSGrad, Nesterov, dampening or clipping go to
+    # the grouped update as a spec (optim.py); everything the one-launch update can express goes the old way.
+    max_grad_norm = _max_grad_norm(cfgs)
+    if optim is not None and optim_spec.needs_grouped(optim, max_grad_norm):
+        okw = dict(optim_spec=optim_spec.spec_from_torch(optim), max_grad_norm=max_grad_norm)
+    else:
+        okw = _optim_kwargs(optim, cfgs)
+        if max_grad_norm is not None:
+            okw['max_grad_norm'] = max_grad_norm
     if isinstance(inner, PoseHighResolutionNet) and inner.head_type == 'angleregression':
         step = HRNetTrainStep(inner, lr=lr, grad_sync=sync, angle_type=_angle_type(loss_func, cfgs),
-                              **_optim_kwargs(optim, cfgs))
+                              **okw)
         step.apply_cr_loss = False
         return step
     if isinstance(inner, PoseHighResolutionNet):
@@ -232,13 +284,19 @@ def make_step(model, cfgs, loss_func=None, optim=None):
             # JointsMSELoss(use_target_weight=...) (tools/train_IGRs.py:42, function.py:22-46)
             cr['use_target_weight'] = bool(getattr(loss_func, 'use_target_weight',
                                                    cfgs.get('training_settings', {}).get('use_target_weight', False)))
-        cr.update(_optim_kwargs(optim, cfgs))
+        cr.update(okw)
         step = HRNetTrainStep(inner, lr=lr, w_hm=w_hm, w_coor=w_coor, grad_sync=sync, sigma=sigma, **cr)
         step.apply_cr_loss = bool(getattr(loss_func, 'apply_cr_loss', False))
         return step
     if isinstance(inner, FCmodel.FCModel):
-        return LifterTrainStep(inner, lr=lr, grad_sync=sync, **_optim_kwargs(optim, cfgs))
+        return LifterTrainStep(inner, lr=lr, grad_sync=sync, **okw)
     raise TypeError('no native training step for %s' % type(inner).__name__)
+
+
+def _max_grad_norm(cfgs):
+    """cfgs['optimizer']['max_grad_norm'] (absent / None / 'None': no clipping)."""
+    v = (cfgs.get('optimizer') or {}).get('max_grad_norm')
+    return None if v in (None, 'None', '') else float(v)
 
 
 class _Acc(object):
@@ -399,7 +457,7 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
             if sche is not None:
                 sche.step()                                     # trainer.py:177, before the epoch like the reference
             if optim is not None:
-                step.lr = optim.param_groups[0]['lr']
+                step.set_lrs([g['lr'] for g in optim.param_groups])      # every group's, not the first alone
             loader = get_loader(train_dataset, cfgs, 'training', collate_fn)
             total_batches, t_epoch = len(loader), time.time()
             acc = _Acc()

@@ -655,6 +655,63 @@ int egn_sgd_step_dev_f32(float* p, const float* g, float* buf, long n,
                          int* step_dev, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The optimizer step for parameter groups (csrc/optim.hip): torch.optim.Adam / AdamW / SGD with any number of
+ * param_groups, AMSGrad, Nesterov, dampening, and torch.nn.utils.clip_grad_norm_ (norm_type 2) folded into the
+ * update.  The three entry points above are untouched and remain the path of everything they can express.
+ *
+ * A group is a row of 8 words (egn_optim_group); a work item is (begin, length, group) in floats of the flat buffer
+ * (egn_optim_item): begin and length are multiples of 4, 0 < length <= egn_optim_item_floats(), and the items in
+ * table order cover [0, n) exactly once (item k + 1 begins where item k ends).  An item never crosses the boundary
+ * between two groups' segments; a parameter's padding belongs to the parameter.  Both tables exist twice: the host
+ * copy is validated before anything is launched, the device copy is what the kernel reads -- the learning rates are
+ * rewritten there by the scheduler, so a captured step replays with the current ones.
+ *
+ * family 0 (Adam):   g' = coef g + wd p;  m' = b1 m + (1 - b1) g';  v' = b2 v + (1 - b2) g'^2;
+ *                    p -= lr / (1 - b1^t) * m' / (sqrt(v') / sqrt(1 - b2^t) + eps)
+ * family 1 (AdamW):  p *= 1 - lr wd first, then family 0 with wd = 0
+ *   EGN_OPTIM_AMSGRAD in a group's flags: vmax' = max(vmax, v') takes the place of v' in the denominator.
+ * family 2 (SGD):    g' = coef g + wd p;  buf' = g' where the step counter becomes 1, else mu buf + (1 - dampening) g'
+ *                    (m is buf, v is not read); p -= lr (EGN_OPTIM_NESTEROV ? g' + mu buf' : buf'); mu == 0: p -= lr g'.
+ * t = step_dev[0] after its increment (a launch of its own, before the one update launch); the bias corrections are
+ * computed in double from it on the device.  coef = clip[1] when clip is not NULL (egn_grad_norm_clip_f32), else 1.
+ * g is only read: the caller's gradient keeps its unclipped values.  Both launches are added to egn_launch_count().
+ *
+ * EGN_E_BADARG, before anything is launched: a NULL or not 16-byte aligned p / g (m, v for Adam; m for SGD where a
+ * group has momentum; vmax where a group has EGN_OPTIM_AMSGRAD), a NULL table or step_dev, a clip that is not 8-byte
+ * aligned, n < 1 or n % 4, 1 <= ngroups <= EGN_OPTIM_MAX_GROUPS violated, an item outside the buffer, items that
+ * overlap or leave a gap, a group index outside the table, beta outside [0, 1), eps <= 0, a negative or non-finite
+ * lr / weight_decay / momentum, dampening outside [0, 1], Nesterov with momentum 0 or dampening != 0, a flag
+ * that does not belong to the family. */
+#define EGN_OPTIM_ADAM 0
+#define EGN_OPTIM_ADAMW 1
+#define EGN_OPTIM_SGD 2
+#define EGN_OPTIM_AMSGRAD 1
+#define EGN_OPTIM_NESTEROV 2
+#define EGN_OPTIM_MAX_GROUPS 32
+typedef struct egn_optim_group {
+  float lr, weight_decay, beta1, beta2, eps, momentum, dampening;
+  int flags;
+} egn_optim_group;
+typedef struct egn_optim_item {
+  long long begin;
+  int length, group;
+} egn_optim_item;
+int egn_optim_item_floats(void);
+int egn_optim_grouped_step_f32(int family, float* p, const float* g, float* m, float* v, float* vmax, long n,
+                               const egn_optim_group* groups_host, const egn_optim_group* groups_dev, int ngroups,
+                               const egn_optim_item* items_host, const egn_optim_item* items_dev, long nitems,
+                               const float* clip, int* step_dev, void* stream);
+/* clip_grad_norm_(norm_type 2) without the pass that scales: clip[0] = total_norm = sqrt(sum g^2) and
+ * clip[1] = coef = min(1, max_norm / (total_norm + 1e-6)), both on the device, for egn_optim_grouped_step_f32 to
+ * multiply in as it loads g.  Two launches (added to egn_launch_count()): a fixed grid of per-block partial sums of
+ * squares in double (ws: egn_grad_norm_ws_bytes() bytes), then one block that adds them in a fixed order -- equal
+ * inputs give equal bits.  A non-finite norm gives what torch gives with error_if_nonfinite=False: coef NaN for a
+ * NaN norm, 0 for an infinite one.  The sum runs over the whole flat buffer: padding words must be 0.
+ * EGN_E_BADARG: a NULL or misaligned g (16 bytes) / ws / clip (8), n < 1 or n % 4, max_norm negative or NaN. */
+long egn_grad_norm_ws_bytes(void);
+int egn_grad_norm_clip_f32(const float* g, long n, float max_norm, double* ws, float* clip, void* stream);
+
+/* ------------------------------------------------------------------------
  * Programs: a recorded sequence of the launches above with every pointer
  * expressed as (slot, byte offset).  Slots are bound to base addresses before
  * a run (slot 0 = activation arena, 1 = packed weights, 2.. = user tensors),

@@ -99,6 +99,7 @@ def igr_cfgs(a):
                testing_settings={'batch_size': a.batch_frames, 'num_threads': 0, 'shuffle': False,
                                  'apply_dropout': False, 'unnormalize': False, 'arg_max': 'hard',
                                  'eval_metrics': [metric], 'alpha_mode': 'proj'})
+    cfg['optimizer'].update(trainer.optim_keys_from_args(a))    # --optim / --weight-decay / --no-decay-norm-bias / ...
     if getattr(a, 'out', None):
         cfg['dirs'] = {'output': a.out}
     if getattr(a, 'ss_record', None):
@@ -186,6 +187,7 @@ def main(argv=None):
     ap.add_argument('--workers', type=int, default=4)
     ap.add_argument('--report-every', type=int, default=30)
     ap.add_argument('--lr', type=float, default=1e-3)
+    trainer.add_optim_arguments(ap)
     ap.add_argument('--exp-type', default='instanceto2d', choices=['instanceto2d'] + sorted(train_samples.EXP_TARGETS))
     ap.add_argument('--loss-type', default='MSELoss1D', choices=['MSELoss1D', 'SmoothL1Loss1D'],
                     help='criterion of the angle baselines (libs/loss/function.py:204-228)')

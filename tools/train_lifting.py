@@ -51,6 +51,7 @@ def lifting_cfgs(args):
                                   'lft_aug_times': args.aug_times},
                testing_settings={'batch_size': args.batch_size, 'num_threads': 4, 'shuffle': False,
                                  'unnormalize': True})
+    cfg['optimizer'].update(trainer.optim_keys_from_args(args))
     return cfg
 
 
@@ -80,6 +81,7 @@ def main():
     ap.add_argument('--epochs', type=int, default=300)
     ap.add_argument('--batch-size', type=int, default=2048)
     ap.add_argument('--lr', type=float, default=1e-3)
+    trainer.add_optim_arguments(ap)
     ap.add_argument('--neurons', type=int, default=1024)
     ap.add_argument('--blocks', type=int, default=2)
     ap.add_argument('--dropout', type=float, default=0.5)
