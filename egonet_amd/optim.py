@@ -264,6 +264,26 @@ class GroupedUpdate(object):
             self.clip = torch.zeros(2, dtype=torch.float32, device=dev)
             self.norm_ws = norm_workspace(dev)
         self._dirty = False
+        self.host_lrs = [g['lr'] for g in sp.groups]      # as given (the table holds them rounded to float32)
+
+    # -- save / resume (train_state.py): this object's part -----------------------------------------------------
+    def describe(self):
+        """family, ``max_grad_norm`` and the groups: the spec's rows (``params`` the tensors) with the current
+        learning rates."""
+        return {'family': self.family, 'max_grad_norm': self.max_grad_norm,
+                'groups': [dict(g, lr=lr) for g, lr in zip(self.spec.groups, self.host_lrs)]}
+
+    def state(self):
+        """CPU copies of ``vmax`` and the clip scalars, each where it exists."""
+        return {k: t.detach().to('cpu', copy=True) for k, t in (('vmax', self.vmax), ('clip', self.clip))
+                if t is not None}
+
+    def load_state(self, vmax, clip):
+        """In place; None zeroes.  The tables are not touched: learning rates come through ``set_lrs``."""
+        with torch.no_grad():
+            for t, src in ((self.vmax, vmax), (self.clip, clip)):
+                if t is not None:
+                    t.zero_() if src is None else t.copy_(src)
 
     @property
     def lrs(self):
@@ -286,6 +306,7 @@ class GroupedUpdate(object):
                 raise ValueError('learning rates must be finite and >= 0: %r' % (lrs,))
             self.groups_host['lr'] = new
             self._dirty = True
+        self.host_lrs = lrs
 
     def push_lrs(self):
         """Refill the device table if ``set_lrs`` changed it (never inside a graph: ``GraphedStep`` calls this before

@@ -66,6 +66,31 @@ class FlatParams(object):
     def t(self):
         return int(self.step_dev.item())
 
+    # -- save / resume (train_state.py): this object's part -----------------------------------------------------
+    def layout(self, names):
+        """Per parameter, in order: its name (``names``: id(parameter) -> name), its shape and its offset in floats."""
+        return [{'name': names[id(p)], 'shape': [int(s) for s in p.shape], 'offset': int(off)}
+                for p, off in zip(self.params, self.offsets)]
+
+    def cut(self, buf, i):
+        """Parameter ``i``'s own elements of a flat buffer with this layout (a view, in the parameter's shape)."""
+        p, off = self.params[i], self.offsets[i]
+        return buf[off:off + p.numel()].view(p.shape)
+
+    def state(self):
+        """CPU copies of the moments, padding included, and the step count (one read-back)."""
+        return {'step': self.t, 'm': self.m.detach().to('cpu', copy=True), 'v': self.v.detach().to('cpu', copy=True)}
+
+    def load_state(self, m, v, step):
+        """In place: the buffers and the counter keep their addresses.  ``v`` None (SGD): zeroed."""
+        with torch.no_grad():
+            self.m.copy_(m)
+            if v is None:
+                self.v.zero_()
+            else:
+                self.v.copy_(v)
+            self.step_dev.fill_(int(step))
+
     def set_lr(self, lr):
         """The learning rate the next optimizer launch reads from device memory: refilled only when the scheduler
         changed it on the host (never inside a graph; ``GraphedStep`` calls this before each replay)."""

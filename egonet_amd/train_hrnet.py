@@ -38,7 +38,7 @@ import os
 
 import torch
 
-from . import _lib, filters, optim, tuner
+from . import _lib, filters, optim, train_state, tuner
 from .engine import invalidate
 from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID
 from .engine import Buf, HRNetEngine, _round_up
@@ -637,6 +637,17 @@ class HRNetTrainStep(TapeOwner):
     def last_grad_norm(self):
         """With ``max_grad_norm``: the last step's total gradient norm, a device scalar (no read-back); else None."""
         return None if self.grouped is None else self.grouped.last_grad_norm
+
+    state_kind = 'hrnet'
+
+    def state_dict(self):
+        """Everything but the parameters that continues this step's run (train_state.py): a snapshot in plain
+        containers and CPU tensors, ``apply_cr_loss`` included."""
+        return train_state.state_dict(self)
+
+    def load_state_dict(self, sd, strict=True):
+        """In place, after validation (train_state.load_state_dict)."""
+        train_state.load_state_dict(self, sd, strict)
 
     def _drawn_target(self, joints_xy, joints_vis, n, h, w, mh, mw):
         """Gaussian heat-map targets drawn on the device from the joints at heatmap_size (img_proc.py:347-409): the

@@ -23,7 +23,7 @@ import os
 
 import torch
 
-from . import _lib, optim, tuner
+from . import _lib, optim, train_state, tuner
 from .engine import _round_up, invalidate
 from .train_common import (FlatParams, PackedFilters, StepCounters, _gc_paused, begin_grad_sync, finish_step,
                            fork_wgrad, join_wgrad, timing_begin, timing_end, wgrad_side_stream)
@@ -406,6 +406,17 @@ class LifterTrainStep(LifterCore):
     def last_grad_norm(self):
         """With ``max_grad_norm``: the last step's total gradient norm, a device scalar (no read-back); else None."""
         return None if self.grouped is None else self.grouped.last_grad_norm
+
+    state_kind = 'lifter'
+
+    def state_dict(self):
+        """Everything but the parameters that continues this step's run (train_state.py): a snapshot in plain
+        containers and CPU tensors, the dropout seed and the count of forwards without an update included."""
+        return train_state.state_dict(self)
+
+    def load_state_dict(self, sd, strict=True):
+        """In place, after validation (train_state.load_state_dict)."""
+        train_state.load_state_dict(self, sd, strict)
 
     @torch.no_grad()
     def step(self, x, target, update=True):

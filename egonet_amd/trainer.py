@@ -107,6 +107,24 @@ def optim_keys_from_args(args):
     return keys
 
 
+def add_checkpoint_arguments(ap):
+    """``--checkpoint FILE`` / ``--resume FILE`` of tools/train_IGRs.py and tools/train_lifting.py (argparse)."""
+    ap.add_argument('--checkpoint', default=None, metavar='FILE',
+                    help='write a training checkpoint (model, optimizer state, schedule, generators) after every epoch')
+    ap.add_argument('--resume', default=None, metavar='FILE',
+                    help='continue the run a training checkpoint holds, at the epoch after its last')
+
+
+def checkpoint_keys_from_args(args):
+    """-> the keys of cfgs['training_settings'] the two switches set (none when neither is given)."""
+    keys = {}
+    if getattr(args, 'checkpoint', None):
+        keys.update(checkpoint=args.checkpoint, checkpoint_every=1)
+    if getattr(args, 'resume', None):
+        keys['resume'] = args.resume
+    return keys
+
+
 def _rank():
     import torch.distributed as dist
     return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
@@ -299,6 +317,118 @@ def _max_grad_norm(cfgs):
     return None if v in (None, 'None', '') else float(v)
 
 
+# -- training checkpoints (training_settings.checkpoint / checkpoint_every / resume) --------------------------------------
+_FINGERPRINT_OPTIM_KEYS = ('optim_type', 'weight_decay', 'momentum', 'amsgrad', 'nesterov', 'dampening',
+                           'no_decay_norm_bias', 'max_grad_norm')
+
+
+def _world():
+    import torch.distributed as dist
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
+def _path_or_none(v):
+    """A path key of training_settings: absent, None, False, '' and the strings 'False' / 'None' are off."""
+    return None if v in (None, False, '', 'False', 'false', 'None') else str(v)
+
+
+def _fingerprint(model, cfgs):
+    inner = model.module if hasattr(model, 'module') else model
+    o = cfgs.get('optimizer') or {}
+    keys = {}
+    for k in _FINGERPRINT_OPTIM_KEYS:
+        v = o.get(k)
+        keys[k] = v if v is None or isinstance(v, (bool, str)) else float(v)
+    return {'exp_type': str(cfgs.get('exp_type')), 'head_type': str(getattr(inner, 'head_type', type(inner).__name__)),
+            'optimizer': keys, 'world_size': _world()}
+
+
+def rank_file(path, rank=None):
+    """``<path>.rank<r>``: the per-rank part of a training checkpoint."""
+    return '%s.rank%d' % (path, _rank() if rank is None else rank)
+
+
+def _write(obj, path):
+    tmp = path + '.tmp'
+    torch.save(obj, tmp)
+    os.replace(tmp, path)
+
+
+def save_checkpoint(path, model, step, optim, sche, cfgs, epochs, x_buffer=(), y_buffer=()):
+    """A training checkpoint after ``epochs`` completed epochs.  Rank 0 writes ``path`` (tmp + ``os.replace``): the
+    model's ``state_dict()`` after ``parallel.broadcast_buffers``, the step's ``state_dict()``, ``optimizer`` -- the same
+    state in ``torch.optim.Optimizer.state_dict()`` form, what a reference-style reader looks for --, the scheduler's
+    ``state_dict()``, the torch optimizer's ``param_groups`` hyper-parameters, the loss history and a fingerprint of the
+    configuration.  Every rank writes ``<path>.rank<r>`` itself: Python's, numpy's and torch's CPU and CUDA generator
+    states and the lifter's dropout seed.  Then the barrier: nobody resumes from a file before it is complete.  Both
+    files load with ``torch.load(..., weights_only=True)``.  ``optim`` (may be None) is read, never changed."""
+    from . import train_state
+    parallel.broadcast_buffers(model, src=0)
+    rank_part = {'rank': _rank(), 'world_size': _world(), 'rng': train_state.rng_state(step.flat.flat.device),
+                 'drop_seed': int(step.drop_seed) if hasattr(step, 'drop_seed') else None}
+    _write(rank_part, rank_file(path))
+    if _rank() == 0:       # one writer, like the snapshots
+        inner = model.module if hasattr(model, 'module') else model
+        groups = None if optim is None else [{k: v for k, v in g.items() if k != 'params'} for g in optim.param_groups]
+        _write({'format': train_state.FORMAT, 'epochs': int(epochs),
+                'model': {k: v.detach().cpu().clone() for k, v in inner.state_dict().items()},
+                'step': step.state_dict(), 'optimizer': train_state.optimizer_state_dict(step),
+                'scheduler': None if sche is None else sche.state_dict(), 'param_groups': groups,
+                'batch_idx': [int(x) for x in x_buffer], 'loss': [float(y) for y in y_buffer],
+                'fingerprint': _fingerprint(model, cfgs)}, path)
+    _barrier()
+
+
+def load_checkpoint(path, model, step, optim, sche, cfgs, total_epochs=None):
+    """The inverse of ``save_checkpoint`` on freshly built objects: model, step, scheduler, the torch optimizer's
+    ``param_groups`` hyper-parameters and this rank's generator states.  Returns the checkpoint's dict (``epochs``,
+    ``batch_idx``, ``loss``, ...).  ``ValueError``, before anything is written, when the fingerprint or the world size
+    differs, this rank's file is missing, or ``total_epochs`` is given and the run has already completed them."""
+    from . import train_state
+    if not os.path.isfile(path):
+        raise ValueError('no training checkpoint at %s' % path)
+    ck = torch.load(path, map_location='cpu', weights_only=True)
+    if ck.get('format') != train_state.FORMAT:
+        raise ValueError('training-checkpoint format %r (this version reads %d)' % (ck.get('format'), train_state.FORMAT))
+    want, have = ck['fingerprint'], _fingerprint(model, cfgs)
+    if want['world_size'] != have['world_size']:
+        raise ValueError('the checkpoint was written by %d ranks, this run has %d' % (want['world_size'],
+                                                                                    have['world_size']))
+    for k in ('exp_type', 'head_type'):
+        if want[k] != have[k]:
+            raise ValueError('the checkpoint has %s %r, this run %r' % (k, want[k], have[k]))
+    for k in _FINGERPRINT_OPTIM_KEYS:
+        if want['optimizer'].get(k) != have['optimizer'].get(k):
+            raise ValueError('the checkpoint has optimizer.%s %r, this run %r'
+                             % (k, want['optimizer'].get(k), have['optimizer'].get(k)))
+    mine = rank_file(path)
+    if not os.path.isfile(mine):
+        raise ValueError('the per-rank file %s is missing' % mine)
+    if total_epochs is not None and ck['epochs'] >= total_epochs:
+        raise ValueError('the checkpoint has completed %d epochs, total_epochs is %d: nothing left to run'
+                         % (ck['epochs'], total_epochs))
+    rank_part = torch.load(mine, map_location='cpu', weights_only=True)
+    if rank_part['world_size'] != have['world_size'] or rank_part['rank'] != _rank():
+        raise ValueError('%s was written by rank %d of %d' % (mine, rank_part['rank'], rank_part['world_size']))
+    if optim is not None and ck.get('param_groups') is not None and len(ck['param_groups']) != len(optim.param_groups):
+        raise ValueError('%d param_groups in the checkpoint, the optimizer has %d'
+                         % (len(ck['param_groups']), len(optim.param_groups)))
+    inner = model.module if hasattr(model, 'module') else model
+    step.load_state_dict(ck['step'])                    # validates first: nothing is written when it refuses
+    inner.load_state_dict(ck['model'])                  # in place: the parameters stay views of the flat buffer
+    from .engine import invalidate
+    invalidate(inner)
+    if rank_part.get('drop_seed') is not None and hasattr(step, 'drop_seed'):
+        step.drop_seed = int(rank_part['drop_seed'])    # this rank's own (the step state is rank 0's)
+    if optim is not None and ck.get('param_groups') is not None:
+        for g, saved in zip(optim.param_groups, ck['param_groups']):
+            g.update(saved)
+    if sche is not None and ck.get('scheduler') is not None:
+        sche.load_state_dict(ck['scheduler'])
+    train_state.set_rng_state(rank_part['rng'], step.flat.flat.device)
+    return ck
+
+
 class _Acc(object):
     """The reference's AverageMeter for the optional training metric (utils.py:149-182)."""
 
@@ -420,7 +550,12 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
     (``visualization.debug.save_debug_images``, gated by ``training_settings.debug``) are composed on the device and
     handed to a ``DebugPictureWriter``, closed when the loop ends; heat-map and coordinate heads on rank 0 only -- the
     angle head and the lifter have no maps and skip silently.  Off (the default), no writer is made and the step's
-    launches are unchanged."""
+    launches are unchanged.
+    ``training_settings.checkpoint`` (a path; ``checkpoint_every`` epochs, default 1) writes a training checkpoint at
+    the end of an epoch (``save_checkpoint``); ``training_settings.resume`` (a path, or False: the reference's key)
+    loads one into the freshly built step, model, scheduler and optimizer groups and continues with the epoch after its
+    last (``load_checkpoint``, which refuses with ValueError before any step runs); the record then holds the whole
+    run's loss history.  All three absent or false (the default): nothing differs."""
     ts = cfgs['training_settings']
     total_epochs, report_every = ts['total_epochs'], ts['report_every']
     eval_during = bool(ts.get('eval_during', False)) and valid_dataset is not None
@@ -445,12 +580,23 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
     # a metric with accumulate / read / reset (metric.criterions.DistanceSrcMeter) keeps its running sums on the device
     metric_on_device = metric_func is not None and hasattr(metric_func, 'accumulate')
     x_buffer, y_buffer = [], []
+    # training checkpoints: all three keys absent or false by default, and then nothing below differs from a run
+    # without them
+    ckpt_path, resume = _path_or_none(ts.get('checkpoint')), _path_or_none(ts.get('resume'))
+    ckpt_every = max(int(ts.get('checkpoint_every') or 1), 1)
+    first_epoch = 1
+    if resume is not None:
+        ck = load_checkpoint(resume, model, step, optim, sche, cfgs, total_epochs=total_epochs)
+        first_epoch = ck['epochs'] + 1
+        x_buffer, y_buffer = list(ck['batch_idx']), list(ck['loss'])
+        logger.info('=> Resumed from %s: %d epochs completed, starting at epoch %d' % (resume, ck['epochs'], first_epoch))
+        del ck
     frozen = False
     writer = debug_pictures.DebugPictureWriter() if save_debug and is_hc and not is_angle and _rank() == 0 else None
     if eval_during:
         _make_host_group()      # all ranks are here together: the group exists before anyone has to wait in it
     try:
-        for epoch in range(1, total_epochs + 1):
+        for epoch in range(first_epoch, total_epochs + 1):
             if epoch > 1 and is_hc and not is_angle:
                 step.apply_cr_loss = True                       # trainer.py:168-169: L_cr from the second epoch on
             model.train()
@@ -540,6 +686,9 @@ def train(train_dataset, model, loss_func, optim, sche, cfgs, logger, metric_fun
                     torch.save(inner.state_dict(), tmp)
                     os.replace(tmp, path)
                 _barrier()             # nobody reads / resumes from the file before it is complete
+            if ckpt_path is not None and (epoch % ckpt_every == 0 or epoch == total_epochs):
+                logger.info('=> Training checkpoint after epoch {:d} to {}'.format(epoch, ckpt_path))
+                save_checkpoint(ckpt_path, model, step, optim, sche, cfgs, epoch, x_buffer, y_buffer)
     finally:
         if frozen:
             gc.unfreeze()

@@ -6,6 +6,7 @@
         [--tiny] [--max-steps N] [--workers 4] [--report-every 30] [--lr 1e-3]
         [--exp-type instanceto2d|baselinealpha|baselinetheta] [--loss-type MSELoss1D|SmoothL1Loss1D]
         [--cr-weight W] [--ss-record FILE --ss-img-root DIR [--ss-max-per-img 6]] [--no-debug-pictures]
+        [--checkpoint FILE] [--resume FILE]
 
 Labels + calibration -> ``PoseAnnotBuilder`` (the 2-D pose annotations, built on the device:
 egonet_amd.common.pose_annot) -> ``PoseFrames`` -> ``DataLoader(collate_fn=collate_frames)`` (frames decoded in the
@@ -40,6 +41,13 @@ run writes the reference's debug pictures on every report batch -- ``<out>/inter
 <epoch>_<batch>_{keypoints,hm_gt,hm_pred}.jpg``, composed on the device and encoded on a background thread
 (egonet_amd/visualization/debug.py); ``--no-debug-pictures`` sets ``debug.save`` to False.  The angle baselines have
 no maps and write none (train_IGRs.py:83-88).
+
+``--checkpoint FILE`` writes a training checkpoint after every epoch (``training_settings.checkpoint``): the model, the
+native step's optimizer state -- also in ``torch.optim`` form --, the schedule, the loss history, and beside it
+``FILE.rank<r>`` with the generators' states.  ``--resume FILE`` (``training_settings.resume``, the reference's key)
+loads one into the freshly built run and continues at the epoch after its last, on the schedule the uninterrupted run
+would follow; ``--epochs`` is the total, and a run that already completed it is refused.  The same seed and settings
+are the caller's part: a differing optimizer family, head or world size is refused.
 """
 import argparse
 import json
@@ -100,6 +108,7 @@ def igr_cfgs(a):
                                  'apply_dropout': False, 'unnormalize': False, 'arg_max': 'hard',
                                  'eval_metrics': [metric], 'alpha_mode': 'proj'})
     cfg['optimizer'].update(trainer.optim_keys_from_args(a))    # --optim / --weight-decay / --no-decay-norm-bias / ...
+    cfg['training_settings'].update(trainer.checkpoint_keys_from_args(a))       # --checkpoint / --resume
     if getattr(a, 'out', None):
         cfg['dirs'] = {'output': a.out}
     if getattr(a, 'ss_record', None):
@@ -188,6 +197,7 @@ def main(argv=None):
     ap.add_argument('--report-every', type=int, default=30)
     ap.add_argument('--lr', type=float, default=1e-3)
     trainer.add_optim_arguments(ap)
+    trainer.add_checkpoint_arguments(ap)
     ap.add_argument('--exp-type', default='instanceto2d', choices=['instanceto2d'] + sorted(train_samples.EXP_TARGETS))
     ap.add_argument('--loss-type', default='MSELoss1D', choices=['MSELoss1D', 'SmoothL1Loss1D'],
                     help='criterion of the angle baselines (libs/loss/function.py:204-228)')

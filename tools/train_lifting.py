@@ -3,7 +3,7 @@
 
     python tools/train_lifting.py --label-dir <label_2> --calib-dir <calib> --train-list train.txt \
         --valid-list val.txt --out <dir> [--size 1242 375] [--epochs 300] [--batch-size 2048]
-        [--eval-every 500 --eval-start-epoch 250 --metrics RError3D]
+        [--eval-every 500 --eval-start-epoch 250 --metrics RError3D] [--checkpoint FILE] [--resume FILE]
     python tools/train_lifting.py --synthetic 2000 --out <dir>       # seeded synthetic labels, no KITTI tree
 
 Pairs are built on the device (egonet_amd.common.lifter_pairs), normalised with the train set's statistics, fed to
@@ -15,7 +15,14 @@ where that matters).
 ``--eval-every N`` validates every N batches after ``--eval-start-epoch`` like the reference's ``eval_during``
 (configs/KITTI_train_lifting.yml: eval_every 500, eval_start_epoch 250) with the metrics of ``--metrics``
 (``RError3D``; ``RTError3D`` for ``--out-rep R3d+T``): rotation error and MPJPE of the unnormalised cuboids, computed
-on the device (egonet_amd.metric.criterions).  The run ends with one more pass over the valid pairs."""
+on the device (egonet_amd.metric.criterions).  The run ends with one more pass over the valid pairs.
+
+``--checkpoint FILE`` writes a training checkpoint after every epoch (``training_settings.checkpoint``): the model, the
+native step's optimizer state -- also in ``torch.optim`` form --, the schedule, the loss history, and beside it
+``FILE.rank<r>`` with the generators' states and the dropout seed.  ``--resume FILE`` (``training_settings.resume``, the
+reference's key) continues such a run at the epoch after its last, with the moments, the step counter, the learning
+rates and the dropout stream where the uninterrupted run would have them; ``--epochs`` is the total.  The tool trains
+one cascade stage, which is the stage the file belongs to."""
 import argparse
 import logging
 import os
@@ -52,6 +59,7 @@ def lifting_cfgs(args):
                testing_settings={'batch_size': args.batch_size, 'num_threads': 4, 'shuffle': False,
                                  'unnormalize': True})
     cfg['optimizer'].update(trainer.optim_keys_from_args(args))
+    cfg['training_settings'].update(trainer.checkpoint_keys_from_args(args))       # --checkpoint / --resume
     return cfg
 
 
@@ -82,6 +90,7 @@ def main():
     ap.add_argument('--batch-size', type=int, default=2048)
     ap.add_argument('--lr', type=float, default=1e-3)
     trainer.add_optim_arguments(ap)
+    trainer.add_checkpoint_arguments(ap)
     ap.add_argument('--neurons', type=int, default=1024)
     ap.add_argument('--blocks', type=int, default=2)
     ap.add_argument('--dropout', type=float, default=0.5)
