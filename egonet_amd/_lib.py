@@ -152,6 +152,7 @@ SIGNATURES = {
     'egn_program_fork': (_i, [_p]),
     'egn_program_join': (_i, [_p]),
     'egn_program_set_lane': (_i, [_p, _i]),
+    'egn_program_set_deps': (_i, [_p, _i, C.POINTER(_i), _i]),
     'egn_program_tag': (_i, [_p, C.c_char_p, _d, _d]),
     'egn_program_run': (_i, [_p, _p]),
     'egn_program_run_timed': (_i, [_p, _p, C.POINTER(C.c_float), _i]),

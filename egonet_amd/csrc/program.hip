@@ -178,6 +178,10 @@ struct Op {
   int i[12];
   std::string tag;
   double flops, bytes;
+  // point-to-point ordering between lanes (egn_program_set_deps): after the launch record event `signal` of the
+  // program's pool on the op's lane; before it the lane waits for the events `waits` (all of EARLIER ops)
+  int signal = -1;
+  std::vector<int> waits;
 };
 
 struct egn_program {
@@ -191,6 +195,8 @@ struct egn_program {
   hipStream_t side[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr;
   hipEvent_t ev_join[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
+  int n_signals = 0;                 // ops that signal: the size of the event pool
+  std::vector<hipEvent_t> ev_sig;    // the pool (timing disabled), created before the first run / capture
   // "a program never runs beside itself" (one arena, one set of side streams, one set of ticket words) is enforced, not
   // assumed [round 5]: every eager run / replay records ev_done on its stream, and a run on ANOTHER stream waits for it
   hipEvent_t ev_done = nullptr;
@@ -297,6 +303,7 @@ extern "C" void egn_program_destroy(egn_program* p) {
     if (p->side[k]) hipStreamDestroy(p->side[k]);
     if (p->ev_join[k]) hipEventDestroy(p->ev_join[k]);
   }
+  for (hipEvent_t e : p->ev_sig) hipEventDestroy(e);
   if (p->ev_fork) hipEventDestroy(p->ev_fork);
   if (p->ev_done) hipEventDestroy(p->ev_done);
   delete p;
@@ -589,6 +596,25 @@ extern "C" int egn_program_set_lane(egn_program* p, int lane) {
   return 0;
 }
 
+// Dependencies of the op added last.  `signal` != 0: the op records an event of the program's pool on its lane after its
+// launch.  `waits`: op indices (egn_program_num_ops order) of EARLIER ops that signal; the op's lane waits for their events
+// before the launch.  Only earlier ops can be named, so the waits cannot form a cycle.
+extern "C" int egn_program_set_deps(egn_program* p, int signal, const int* waits, int nwaits) {
+  if (!p || p->ops.empty()) return EGN_E_STATE;
+  if (nwaits < 0 || (nwaits > 0 && !waits)) return EGN_E_BADARG;
+  const int self = (int)p->ops.size() - 1;
+  Op& op = p->ops[self];
+  if (op.kind == OP_FORK || op.kind == OP_JOIN) return EGN_E_BADARG;
+  std::vector<int> evs;
+  for (int k = 0; k < nwaits; ++k) {
+    if (waits[k] < 0 || waits[k] >= self || p->ops[waits[k]].signal < 0) return EGN_E_BADARG;
+    evs.push_back(p->ops[waits[k]].signal);
+  }
+  op.waits = evs;
+  if (signal && op.signal < 0) op.signal = p->n_signals++;
+  return 0;
+}
+
 extern "C" int egn_program_tag(egn_program* p, const char* tag, double flops, double bytes) {
   if (!p || p->ops.empty()) return EGN_E_STATE;
   Op& op = p->ops.back();
@@ -689,6 +715,15 @@ static int launch_op(egn_program* p, Op& op, hipStream_t s) {
   return EGN_E_BADARG;
 }
 
+static int ensure_signals(egn_program* p) {
+  while ((int)p->ev_sig.size() < p->n_signals) {
+    hipEvent_t e = nullptr;
+    EGN_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    p->ev_sig.push_back(e);
+  }
+  return 0;
+}
+
 static int ensure_lanes(egn_program* p) {
   if (p->ev_fork) return 0;
   EGN_CHECK_HIP(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
@@ -703,11 +738,18 @@ static int ensure_lanes(egn_program* p) {
 // is the caller's stream, lanes 1.. are side streams that wait for the fork
 // point and are waited for at the join (the HRNet branches / fuse outputs are
 // independent, so their kernels fill each other's prologue, epilogue and tail
-// gaps).  Works unchanged under stream capture (the events become graph edges).
+// gaps).  An op with dependencies (egn_program_set_deps) makes its lane wait for the events of the ops it names and
+// records its own behind its launch: ordering between two lanes without a join of all of them.
+// Under stream capture the fork / join events become graph edges; the dependencies do NOT: a captured graph keeps the
+// plain fork / join shape.  There the first wait for a signal given since the last barrier is lowered to a join of every
+// lane followed by a fork (`open_sig`), which orders more than the wait asks for -- the same results, the graph of the
+// program recorded with joins.  (A graph with lane-to-lane edges crashed the process that replayed it)
 extern "C" int egn_program_run(egn_program* p, void* stream) {
   if (!p) return EGN_E_BADARG;
+  { int rc_s = ensure_signals(p); if (rc_s) return rc_s; }
   hipStream_t main = (hipStream_t)stream;
   bool used[kMaxLanes] = {false, false, false, false};
+  std::vector<char> open_sig(p->n_signals, 0);   // capture only: signals given since the last join of all lanes
   bool capturing = false;
   int rc_o = order_behind_last_run(p, main, &capturing);
   if (rc_o) return rc_o;
@@ -730,7 +772,23 @@ extern "C" int egn_program_run(egn_program* p, void* stream) {
           EGN_CHECK_HIP(hipStreamWaitEvent(main, p->ev_join[k], 0));
           used[k] = false;
         }
+      open_sig.assign(open_sig.size(), 0);
       continue;
+    }
+    if (capturing && p->ev_fork) {
+      // a wait for a signal given since the last barrier: join every lane and fork again (stronger than the wait)
+      bool need = false;
+      for (int w : op.waits) need = need || open_sig[w];
+      if (need) {
+        for (int k = 1; k < kMaxLanes; ++k)
+          if (used[k]) {
+            EGN_CHECK_HIP(hipEventRecord(p->ev_join[k], p->side[k]));
+            EGN_CHECK_HIP(hipStreamWaitEvent(main, p->ev_join[k], 0));
+            used[k] = false;
+          }
+        EGN_CHECK_HIP(hipEventRecord(p->ev_fork, main));
+        open_sig.assign(open_sig.size(), 0);
+      }
     }
     hipStream_t s = main;
     if (op.lane > 0 && p->ev_fork) {
@@ -740,8 +798,14 @@ extern "C" int egn_program_run(egn_program* p, void* stream) {
       }
       s = p->side[op.lane];
     }
+    if (!capturing)
+      for (int w : op.waits) EGN_CHECK_HIP(hipStreamWaitEvent(s, p->ev_sig[w], 0));
     int rc = launch_op(p, op, s);
     if (rc) return rc;
+    if (op.signal >= 0) {
+      if (capturing) open_sig[op.signal] = 1;
+      else EGN_CHECK_HIP(hipEventRecord(p->ev_sig[op.signal], s));
+    }
   }
   if (!capturing || p->err_ptrs) {             // (a capture records the check only if its buffers exist already)
     int rc = issue_ticket_check(p, main);
@@ -799,6 +863,7 @@ extern "C" int egn_program_capture(egn_program* p, void* stream) {
       if (rc0) return rc0;
       break;
     }
+  { int rc0 = ensure_signals(p); if (rc0) return rc0; }
   EGN_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   t_recording = true;      // (recorded, not executed: egn_launch_count counts launches that ran -- replays count themselves)
   int rc = egn_program_run(p, stream);

@@ -18,6 +18,7 @@ A program is recorded once per (device, batch shape):
 A forward is then a single C call that issues ~320 kernel launches.
 """
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -213,13 +214,19 @@ class _Recorder(object):
         self.bufs = []
         self.region = 0        # fork/join regions are totally ordered
         self.cur_lane = 0      # launch lane inside the current region
+        self._pending = {}     # lane -> tokens its next op waits for (``wait``)
+        self._before = None    # happens_before's closure, rebuilt after every new op
         self.f16 = False       # precision = 'f16': eligible 3x3 convs are recorded as 'convh' ops (csrc/conv_h.hip)
         self.f16s2 = False     # precision = 'f16s2': ... and eligible 3x3 stride-2 convs as 'convh2' ops
         self.f16x = False      # precision = 'f16x': ... and the 3x3 convs of the 32-multiple widths as 'convhx' ops
 
     def _push(self, kind, op):
         op['region'], op['lane'] = self.region, self.cur_lane
+        if kind not in ('fork', 'join'):
+            # waits asked for on this lane (``wait``) belong to the first op recorded on it afterwards
+            op['waits'] = self._pending.pop(self.cur_lane, [])
         self.ops.append((kind, op))
+        self._before = None
 
     def fork(self):
         """Ops recorded until ``join`` may run concurrently when they are on
@@ -232,15 +239,42 @@ class _Recorder(object):
         self.cur_lane = k % 4
 
     def join(self):
+        assert not self._pending, 'a wait with no op behind it on lanes %s' % sorted(self._pending)
         self.cur_lane = 0
         self._push('join', {})
         self.region += 1
 
+    def signal(self):
+        """Mark the op recorded last: its lane records an event behind it.  Returns the token ``wait`` takes."""
+        kind, op = self.ops[-1]
+        assert kind not in ('fork', 'join')
+        op['signal'] = True
+        return len(self.ops) - 1
+
+    def wait(self, token):
+        """The next op recorded on the current lane starts only after the op ``token`` names is complete."""
+        assert self.ops[token][1].get('signal'), token
+        self._pending.setdefault(self.cur_lane, []).append(token)
+
     def happens_before(self, u, d):
-        """Op u is complete before op d starts: earlier region, or same region
-        and same lane (stream order)."""
-        (ru, lu), (rd, ld) = [(self.ops[i][1]['region'], self.ops[i][1]['lane']) for i in (u, d)]
-        return ru < rd or (ru == rd and lu == ld and u < d)
+        """Op u is complete before op d starts: the transitive closure of "earlier region", "same region and same
+        lane, in op order (stream order)" and the signal -> wait edges."""
+        if self.ops[u][1]['region'] < self.ops[d][1]['region']:
+            return True
+        if self._before is None:
+            # before[d]: bit set of the ops complete before d through lane order and signal -> wait edges alone (a
+            # chain through an earlier region ends in an earlier region: the first test has it)
+            before, last = [], {}
+            for i, (kind, op) in enumerate(self.ops):
+                at = (op['region'], op['lane'])
+                preds = ([last[at]] if at in last else []) + list(op.get('waits', ()))
+                m = 0
+                for p in preds:
+                    m |= before[p] | (1 << p)
+                before.append(m)
+                last[at] = i
+            self._before = before
+        return bool((self._before[d] >> u) & 1)
 
     # -- storage --
     def new(self, n, h, w, c, name=''):
@@ -637,6 +671,10 @@ class Program(object):
         else:
             raise ValueError(kind)
         L.egn_program_tag(h, (op.get('tag') or klass).encode(), flops, nbytes)
+        if op.get('signal') or op.get('waits'):     # (tokens are op indices: the program has one op per recorded op)
+            waits = op.get('waits', [])
+            _lib.check(L.egn_program_set_deps(h, int(bool(op.get('signal'))), (C.c_int * len(waits))(*waits),
+                                              len(waits)), op.get('tag', ''))
         self.meta.append(dict(kind=kind, klass=klass, tag=op.get('tag', ''), flops=flops, bytes=nbytes,
                               cfg=op.get('cfg', 0) if kind == 'conv' else 0))
 
@@ -736,6 +774,10 @@ class HRNetEngine(object):
         self.fuse_layer1 = os.environ.get('EGONET_AMD_PW_FUSE', '1') != '0'      # layer1's 1x1 pairs on csrc/conv_pw.hip
         # fuse output i -> branch i of the next module on the same lane, no join in between
         self.chain_regions = os.environ.get('EGONET_AMD_CHAIN', '1') != '0'
+        # fuse term (i, j) waits for branch j alone instead of a join of all branches (_module); 0: the joins, for A/B runs
+        self.deps = os.environ.get('EGONET_AMD_DEPS', '1') != '0'
+        # ... from this many crops on: measured at 1 and 16 crops, only the larger was free of any regression
+        self.deps_min_n = int(os.environ.get('EGONET_AMD_DEPS_MIN_N', '16'))
         self.last_f16_ops = []    # tags of the layers the last recording lowered to the f16-operand ops (precision = 'f16' / 'f16s2' / 'f16x')
 
     @property
@@ -876,6 +918,15 @@ class HRNetEngine(object):
         # lane each, so their kernels overlap each other's prologue / epilogue /
         # tail and the small coarse-branch grids do not leave the chip idle
         lanes = self.lanes and mod.num_branches > 1
+        # point-to-point dependencies (EGONET_AMD_DEPS, default on): no join between the branches and the fuse rows.
+        # Branch j signals behind its last block; on lane i the first op of term (i, j) waits for that signal alone, so
+        # a term conv starts when ITS branch is done, not when the slowest one is, and fuse_i -- behind its row's term
+        # convs in lane order -- has waited for all of them.  The paired launch (opt-in) and the training tape (its
+        # recorder has no ``signal``) keep the join, and so do batches below ``deps_min_n`` crops: at 1 crop the graph
+        # replay of the dependency recording measured slower than the joined one (profiles/deps_small_batch.txt).
+        deps = lanes and self.deps and hasattr(r, 'signal') and mod.fuse_layers is not None and \
+            xs[0].n >= self.deps_min_n and os.environ.get('EGONET_AMD_PAIR', tuner.PAIR_DEFAULT) == '0'
+        sig, eta = {}, {}
         if lanes and not region_open:
             r.fork()
         for b, branch in enumerate(mod.branches):
@@ -892,31 +943,42 @@ class HRNetEngine(object):
                     xs[ia], xs[ib] = r.conv_pair(ha, ba.conv2, ba.bn2, ACT_RELU, xs[ia],
                                                  hb, bb.conv2, bb.bn2, ACT_RELU, xs[ib], tag=q + '.conv2')
                 continue
+            first = len(r.ops) if deps else 0
             for k, blk in enumerate(branch):
                 xs[b] = self._block(r, xs[b], blk, '%s.branches.%d.%d' % (tag, b, k))
-        if lanes:
+            if deps:
+                assert len(r.ops) > first, 'branch %d of %s recorded no op to signal behind' % (b, tag)
+                sig[b] = r.signal()
+                # when the lane is expected to be done: the tabled times of the branch's convs
+                eta[b] = sum(tuner.tabled_ms(Program._conv_key(op)) for kind, op in r.ops[first:] if kind == 'conv')
+        if lanes and not deps:
             r.join()
         if mod.fuse_layers is None:
             return xs, False
         outs = []
         stay = lanes and keep_open and self.chain_regions and len(mod.fuse_layers) == mod.num_branches
         pair_next = self._pair_branches(r, xs, nxt) if stay else None
-        if lanes:                       # the fuse outputs are independent too (hrnet.py:291-298)
+        if lanes and not deps:          # the fuse outputs are independent too (hrnet.py:291-298)
             r.fork()
+        # with dependencies a row records first the term whose source lane is expected to be done first (ties: by j);
+        # fuse_kernel takes the terms in the reference's association order either way
+        order = sorted(range(mod.num_branches), key=lambda j: (eta[j], j)) if deps else range(mod.num_branches)
         for i, row in enumerate(mod.fuse_layers):
             if lanes:
                 r.lane(min(pair_next) if pair_next is not None and i in pair_next else i)
-            terms = []
-            for j in range(mod.num_branches):
+            terms = [None] * mod.num_branches
+            for j in order:
                 q = '%s.fuse_layers.%d.%d' % (tag, i, j)
+                if deps and j != i:
+                    r.wait(sig[j])
                 if row[j] is None:
-                    terms.append((xs[j], 0))
+                    terms[j] = (xs[j], 0)
                 elif j > i:
                     conv, bn = row[j][0], row[j][1]
                     t = r.conv(xs[j], conv.weight, None, bn, ACT_NONE, None, 1, 0, tag=q)
-                    terms.append((t, j - i))
+                    terms[j] = (t, j - i)
                 else:
-                    terms.append((self._unit_chain(r, xs[j], row[j], q), 0))
+                    terms[j] = (self._unit_chain(r, xs[j], row[j], q), 0)
             outs.append(r.fuse(terms, True, tag='%s.fuse%d' % (tag, i)))
         if lanes and not stay:
             r.join()

@@ -211,6 +211,16 @@ def choose(device, key, kinds=DIRECT, ticket_cap=None, inplace_res=False):
     return _pick(entry, key, kinds, ticket_cap, inplace_res)
 
 
+def tabled_ms(key):
+    """What the shipped table measured for the shape ``key`` under the configuration it names (ms; 0.0 where the table
+    has no entry or no time): the recorder's estimate of when a chain of convs is done.  Never tunes."""
+    entry = _load().get(shape_key(*key))
+    if not entry:
+        return 0.0
+    ms = entry.get('ms', {})
+    return float(ms.get(str(entry.get('cfg')), min(ms.values()) if ms else 0.0))
+
+
 # ---------------------------------------------------------------------------
 # paired launches: two independent 3x3 convolutions as one op (csrc/conv_wino4.hip, conv_wino4_pair_kernel)
 # ---------------------------------------------------------------------------

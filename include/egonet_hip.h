@@ -753,6 +753,16 @@ int egn_program_add_decode(egn_program* p, egn_ref hm, int N, int K, int H,
 int egn_program_fork(egn_program* p);
 int egn_program_join(egn_program* p);
 int egn_program_set_lane(egn_program* p, int lane);
+/* Point-to-point ordering between lanes, as attributes of the op added last (not an op of its own).  signal != 0: after
+ * the op's launch an event is recorded on its lane.  waits[0..nwaits): indices (in egn_program_num_ops order) of EARLIER
+ * ops that signal; the op's lane waits for their events before the launch (hipStreamWaitEvent).  Anything else -- the op
+ * itself, a later index, an op that does not signal, a fork / join -- is EGN_E_BADARG, so waits cannot form a cycle.  The
+ * events (timing disabled) belong to the program and are destroyed with it.  Fork / join keep their meaning: every side
+ * lane is still joined at the region's end.  egn_program_run_timed is serial on one stream and ignores both fields.
+ * Under egn_program_capture the dependencies are not recorded as graph edges: the first wait for a signal given since
+ * the last join is lowered to a join of every lane followed by a fork, so a captured graph keeps the plain fork / join
+ * shape (same results; the waits only order less than that in an eager run). */
+int egn_program_set_deps(egn_program* p, int signal, const int* waits, int nwaits);
 /* tag the most recently added op (shown by the profiler); copied */
 int egn_program_tag(egn_program* p, const char* tag, double flops, double bytes);
 
