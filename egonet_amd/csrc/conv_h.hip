@@ -304,45 +304,22 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
 static bool h_width(int c) { return c == 48 || c == 96 || c == 192 || c == 384; }
 static int h_pow2_ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 static int h_log2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
-// Host-only: 1 where the family runs the layer.  The W48 widths with unpadded channel strides, a plain epilogue (scale /
-// shift, optional residual added before the activation, ReLU or none), tensors below 2 GiB (32-bit buffer offsets).  The
-// Pedestrian widths (32 / 64 / 128 / 256) and 256 -> 48 are REFUSED: 48-channel chunks do not divide them
-// (egn_conv3x3_hx_applies below takes them, in chunks of 32).
-extern "C" int egn_conv3x3_h_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act) {
-  if (N < 1 || H < 2 || W < 2 || !h_width(Cin) || !h_width(Cout) || cs_in != Cin || cs_out != Cout) return 0;
-  if (act != EGN_ACT_NONE && act != EGN_ACT_RELU) return 0;     // (sigmoid, leaky and RES_AFTER stay on the fp32 kernels)
-  if (has_res != 0 && has_res != 1) return 0;
-  const long long px = (long long)N * H * W;
-  if (px * Cin * 4 >= (1ll << 31) || px * Cout * 4 >= (1ll << 31)) return 0;
-  return 1;
-}
-
-extern "C" long egn_conv3x3_h_wpack_bytes(int Cin, int Cout) {
-  if (!h_width(Cin) || !h_width(Cout)) return 0;
-  return (long)(Cout / 16) * (Cin / H_CK) * H_KS * 64 * 16;
-}
-
-// Host-only: 1 where the family runs the layer at STRIDE 2 (input N x H x W, output (H - 1) / 2 + 1 x (W - 1) / 2 + 1).  As
-// above without a residual: no stride-2 layer of HRNet has one.  256 -> 96 (transition1) is refused like 256 -> 48.
-extern "C" int egn_conv3x3s2_h_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int act) {
-  if (N < 1 || H < 2 || W < 2 || !h_width(Cin) || !h_width(Cout) || cs_in != Cin || cs_out != Cout) return 0;
-  if (act != EGN_ACT_NONE && act != EGN_ACT_RELU) return 0;
-  const long long pxo = (long long)N * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1);
-  if ((long long)N * H * W * Cin * 4 >= (1ll << 31) || pxo * Cout * 4 >= (1ll << 31)) return 0;
-  return 1;
-}
-
 // 'f16x': the 32-multiple widths, walked in chunks of 32 (K step = tap, lane group = channel group; the header).
 static bool hx_cin(int c) { return c == 32 || c == 64 || c == 128 || c == 256; }
 static bool hx_cout(int c) { return hx_cin(c) || c == 48 || c == 96; }
+// the width classes of a chunk size: one clause per chunk size, here alone
+static bool h_widths(int ck, int Cin, int Cout) {
+  return ck == 48 ? h_width(Cin) && h_width(Cout) : ck == 32 && hx_cin(Cin) && hx_cout(Cout);
+}
 
-// Host-only: 1 where the CK = 32 instances run the layer -- Cin in {32, 64, 128, 256}, Cout in those or {48, 96}
-// (transition1's 256 -> 48 / 256 -> 96), stride 1 or 2 (stride 2: no residual); the rest as the two predicates above.
-extern "C" int egn_conv3x3_hx_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act,
-                                      int stride) {
-  if (N < 1 || H < 2 || W < 2 || !hx_cin(Cin) || !hx_cout(Cout) || cs_in != Cin || cs_out != Cout) return 0;
-  if (act != EGN_ACT_NONE && act != EGN_ACT_RELU) return 0;
+// THE predicate of the family, per chunk size `ck`: 1 where its instances run the layer (input N x H x W, output
+// (H - 1) / stride + 1 x (W - 1) / stride + 1).  ck = 48: the W48 widths; ck = 32: Cin in {32, 64, 128, 256}, Cout in those or
+// {48, 96} (transition1's 256 -> 48 / 256 -> 96).  Unpadded channel strides, a plain epilogue (scale / shift, optional
+// residual added before the activation, ReLU or none; no stride-2 layer of HRNet has a residual), stride 1 or 2, tensors
+// below 2 GiB (32-bit buffer offsets).
+static int h_applies(int ck, int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act, int stride) {
+  if (N < 1 || H < 2 || W < 2 || !h_widths(ck, Cin, Cout) || cs_in != Cin || cs_out != Cout) return 0;
+  if (act != EGN_ACT_NONE && act != EGN_ACT_RELU) return 0;     // (sigmoid, leaky and RES_AFTER stay on the fp32 kernels)
   if (stride != 1 && stride != 2) return 0;
   if (has_res != 0 && (has_res != 1 || stride == 2)) return 0;
   const long long pxo = (long long)N * ((H - 1) / stride + 1) * ((W - 1) / stride + 1);
@@ -350,8 +327,30 @@ extern "C" int egn_conv3x3_hx_applies(int N, int H, int W, int Cin, int cs_in, i
   return 1;
 }
 
+// Host-only, 'f16': the chunks of 48 at stride 1.  The Pedestrian widths (32 / 64 / 128 / 256) and 256 -> 48 are REFUSED:
+// 48-channel chunks do not divide them (egn_conv3x3_hx_applies below takes them, in chunks of 32).
+extern "C" int egn_conv3x3_h_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act) {
+  return h_applies(48, N, H, W, Cin, cs_in, Cout, cs_out, has_res, act, 1);
+}
+
+// Host-only, 'f16s2': the chunks of 48 at STRIDE 2, without a residual.  256 -> 96 (transition1) is refused like 256 -> 48.
+extern "C" int egn_conv3x3s2_h_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int act) {
+  return h_applies(48, N, H, W, Cin, cs_in, Cout, cs_out, 0, act, 2);
+}
+
+// Host-only, 'f16x': the chunks of 32 at either stride.
+extern "C" int egn_conv3x3_hx_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act,
+                                      int stride) {
+  return h_applies(32, N, H, W, Cin, cs_in, Cout, cs_out, has_res, act, stride);
+}
+
+extern "C" long egn_conv3x3_h_wpack_bytes(int Cin, int Cout) {
+  if (!h_widths(48, Cin, Cout)) return 0;
+  return (long)(Cout / 16) * (Cin / H_CK) * H_KS * 64 * 16;
+}
+
 extern "C" long egn_conv3x3_hx_wpack_bytes(int Cin, int Cout) {
-  if (!hx_cin(Cin) || !hx_cout(Cout)) return 0;
+  if (!h_widths(32, Cin, Cout)) return 0;
   return (long)(Cout / 16) * (Cin / 32) * ConvHChunk<32>::KS * 64 * 16;
 }
 
@@ -425,34 +424,30 @@ int egn_conv_h_launch(const ConvHArgs& a, hipStream_t stream) {
 
 extern std::atomic<long> g_egn_direct_convs;
 
-extern "C" int egn_conv3x3_h_f32(const float* x, const void* wpack_f16, const float* scale, const float* shift,
-                                 const float* res, float* y, int N, int H, int W, int Cin, int Cout, int act,
-                                 void* stream) {
+// the three direct entry points: plan by the chunk size's predicate, launch
+static int h_direct(int ck, const float* x, const void* wpack_f16, const float* scale, const float* shift, const float* res,
+                    float* y, int N, int H, int W, int Cin, int Cout, int act, int stride, void* stream) {
   g_egn_direct_convs.fetch_add(1, std::memory_order_relaxed);
   ConvHArgs a;
-  int rc = egn_conv_h_plan(a, N, H, W, Cin, Cout, res != nullptr, act, 1);
+  int rc = (ck == 48 ? egn_conv_h_plan : egn_conv_hx_plan)(a, N, H, W, Cin, Cout, res != nullptr, act, stride);
   if (rc) return rc;
   a.x = x; a.w = wpack_f16; a.scale = scale; a.shift = shift; a.res = res; a.y = y;
   return egn_conv_h_launch(a, (hipStream_t)stream);
 }
 
+extern "C" int egn_conv3x3_h_f32(const float* x, const void* wpack_f16, const float* scale, const float* shift,
+                                 const float* res, float* y, int N, int H, int W, int Cin, int Cout, int act,
+                                 void* stream) {
+  return h_direct(48, x, wpack_f16, scale, shift, res, y, N, H, W, Cin, Cout, act, 1, stream);
+}
+
 extern "C" int egn_conv3x3s2_h_f32(const float* x, const void* wpack_f16, const float* scale, const float* shift, float* y,
                                    int N, int H, int W, int Cin, int Cout, int act, void* stream) {
-  g_egn_direct_convs.fetch_add(1, std::memory_order_relaxed);
-  ConvHArgs a;
-  int rc = egn_conv_h_plan(a, N, H, W, Cin, Cout, 0, act, 2);
-  if (rc) return rc;
-  a.x = x; a.w = wpack_f16; a.scale = scale; a.shift = shift; a.y = y;
-  return egn_conv_h_launch(a, (hipStream_t)stream);
+  return h_direct(48, x, wpack_f16, scale, shift, nullptr, y, N, H, W, Cin, Cout, act, 2, stream);
 }
 
 extern "C" int egn_conv3x3_hx_f32(const float* x, const void* wpack_f16, const float* scale, const float* shift,
                                   const float* res, float* y, int N, int H, int W, int Cin, int Cout, int act, int stride,
                                   void* stream) {
-  g_egn_direct_convs.fetch_add(1, std::memory_order_relaxed);
-  ConvHArgs a;
-  int rc = egn_conv_hx_plan(a, N, H, W, Cin, Cout, res != nullptr, act, stride);
-  if (rc) return rc;
-  a.x = x; a.w = wpack_f16; a.scale = scale; a.shift = shift; a.res = res; a.y = y;
-  return egn_conv_h_launch(a, (hipStream_t)stream);
+  return h_direct(32, x, wpack_f16, scale, shift, res, y, N, H, W, Cin, Cout, act, stride, stream);
 }

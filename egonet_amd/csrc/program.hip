@@ -423,70 +423,48 @@ extern "C" int egn_program_add_conv2d_pair(egn_program* p, egn_ref xa, egn_ref w
   return 0;
 }
 
-// the f16-operand 3x3 / stride 1 / pad 1 convolution (conv_h.hip, egn_conv3x3_h_f32) as one op
-extern "C" int egn_program_add_conv3x3_h(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
-                                         egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act) {
+// An f16-operand 3x3 / pad 1 convolution (conv_h.hip) as one op of `kind`, planned by `plan`; H, W are the input size.  Only
+// the residual may be NULL.
+typedef int (*ConvHPlan)(ConvHArgs&, int, int, int, int, int, int, int, int);
+static int add_convh(egn_program* p, int kind, ConvHPlan plan, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
+                     egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act, int stride) {
   if (!p) return EGN_E_BADARG;
   Op op;
-  op.kind = OP_CONVH;
-  int rc = egn_conv_h_plan(op.convh, N, H, W, Cin, Cout, res.slot >= 0, act, 1);
+  op.kind = kind;
+  const bool has_res = res.slot >= 0;
+  int rc = plan(op.convh, N, H, W, Cin, Cout, has_res, act, stride);
   if (rc) return rc;
   op.cfg = 0;
   const egn_ref refs[6] = {x, wpack, scale, shift, res, y};
   for (int k = 0; k < 6; ++k) {
-    if (!ref_ok(p, refs[k]) || (refs[k].slot < 0 && k != 4)) return EGN_E_BADARG;    // (only the residual may be NULL)
-    op.r[k] = refs[k];
-  }
-  op.flops = 2.0 * 9.0 * N * H * W * (double)Cout * Cin;
-  op.bytes = 4.0 * N * H * W * (Cin + Cout * (res.slot >= 0 ? 2.0 : 1.0)) + 2.0 * 9.0 * Cout * Cin;
-  op.lane = p->cur_lane;
-  p->ops.push_back(op);
-  return 0;
-}
-
-// its stride-2 sibling (egn_conv3x3s2_h_f32) as one op; H, W are the input size; no residual
-extern "C" int egn_program_add_conv3x3s2_h(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
-                                           egn_ref y, int N, int H, int W, int Cin, int Cout, int act) {
-  if (!p) return EGN_E_BADARG;
-  Op op;
-  op.kind = OP_CONVH2;
-  int rc = egn_conv_h_plan(op.convh, N, H, W, Cin, Cout, 0, act, 2);
-  if (rc) return rc;
-  op.cfg = 0;
-  const egn_ref refs[6] = {x, wpack, scale, shift, egn_ref{-1, 0}, y};
-  for (int k = 0; k < 6; ++k) {
-    if (k != 4 && (!ref_ok(p, refs[k]) || refs[k].slot < 0)) return EGN_E_BADARG;
+    if (!ref_ok(p, refs[k]) || (refs[k].slot < 0 && k != 4)) return EGN_E_BADARG;
     op.r[k] = refs[k];
   }
   const double pxo = (double)N * op.convh.Ho * op.convh.Wo;
   op.flops = 2.0 * 9.0 * pxo * Cout * Cin;
-  op.bytes = 4.0 * ((double)N * H * W * Cin + pxo * Cout) + 2.0 * 9.0 * Cout * Cin;
+  op.bytes = 4.0 * ((double)N * H * W * Cin + pxo * Cout * (has_res ? 2.0 : 1.0)) + 2.0 * 9.0 * Cout * Cin;
   op.lane = p->cur_lane;
   p->ops.push_back(op);
   return 0;
 }
 
-// the 32-multiple widths (egn_conv3x3_hx_f32) as one op, either stride; H, W are the input size; res may be NULL at stride 1
+// stride 1, the W48 widths (egn_conv3x3_h_f32)
+extern "C" int egn_program_add_conv3x3_h(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
+                                         egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act) {
+  return add_convh(p, OP_CONVH, egn_conv_h_plan, x, wpack, scale, shift, res, y, N, H, W, Cin, Cout, act, 1);
+}
+
+// its stride-2 sibling (egn_conv3x3s2_h_f32); no residual
+extern "C" int egn_program_add_conv3x3s2_h(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
+                                           egn_ref y, int N, int H, int W, int Cin, int Cout, int act) {
+  return add_convh(p, OP_CONVH2, egn_conv_h_plan, x, wpack, scale, shift, egn_ref{-1, 0}, y, N, H, W, Cin, Cout, act, 2);
+}
+
+// the 32-multiple widths (egn_conv3x3_hx_f32), either stride; res may be given at stride 1
 extern "C" int egn_program_add_conv3x3_hx(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
                                           egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act,
                                           int stride) {
-  if (!p) return EGN_E_BADARG;
-  Op op;
-  op.kind = OP_CONVHX;
-  int rc = egn_conv_hx_plan(op.convh, N, H, W, Cin, Cout, res.slot >= 0, act, stride);
-  if (rc) return rc;
-  op.cfg = 0;
-  const egn_ref refs[6] = {x, wpack, scale, shift, res, y};
-  for (int k = 0; k < 6; ++k) {
-    if (!ref_ok(p, refs[k]) || (refs[k].slot < 0 && k != 4)) return EGN_E_BADARG;    // (only the residual may be NULL)
-    op.r[k] = refs[k];
-  }
-  const double pxo = (double)N * op.convh.Ho * op.convh.Wo;
-  op.flops = 2.0 * 9.0 * pxo * Cout * Cin;
-  op.bytes = 4.0 * ((double)N * H * W * Cin + pxo * Cout * (res.slot >= 0 ? 2.0 : 1.0)) + 2.0 * 9.0 * Cout * Cin;
-  op.lane = p->cur_lane;
-  p->ops.push_back(op);
-  return 0;
+  return add_convh(p, OP_CONVHX, egn_conv_hx_plan, x, wpack, scale, shift, res, y, N, H, W, Cin, Cout, act, stride);
 }
 
 extern "C" int egn_program_add_fuse(egn_program* p, egn_ref y, int N, int H, int W, int C, int cs, int nterms,

@@ -17,6 +17,7 @@ A program is recorded once per (device, batch shape):
     (slot, offset) pairs: slot 0 arena, 1 weights, 2.. user tensors.
 A forward is then a single C call that issues ~320 kernel launches.
 """
+import collections
 import ctypes as C
 import os
 
@@ -33,79 +34,129 @@ from .filters import (CK, H_CK, H_KS, _round_up, pack_conv_weight, wino_cot, pac
 ACT_RES_AFTER = 0x10
 BN_EPS_DEFAULT = 1e-5
 SLOT_ARENA, SLOT_WEIGHTS, SLOT_USER0 = 0, 1, 2
-PRECISIONS = ('f32', 'f16', 'f16s2')
 # (cin, cout) classes of 3x3 stride-2 layers that precision = 'f16s2' leaves on their fp32 kernels because the f16-operand
 # op was measured not to win on them (tools/precision_bench.py --s2); empty unless a measurement fills it.
 #   48 -> 48: faster at 64 crops (64^2 input 35.7 -> 19.0 us, 32^2 input 14.7 -> 9.9 us) but SLOWER beyond the spread at 16
 #   crops on the 32^2 input: fp32 (cfg 85) 7.8 us (spread 0.9), f16-operand op 8.9 us (spread 0.7) -- 64 blocks, the
 #   latency of one block.  (64^2 input at 16 crops: 14.7 -> 9.6 us.)
 F16S2_FP32_CLASSES = ((48, 48),)
-# Every value the switch takes.  'f16x' lowers what 'f16s2' lowers (the same kernel instances, the same bits) plus the 3x3 /
-# pad 1 layers of the 32-MULTIPLE widths, stride 1 or 2 (``f16x_eligible``): HRNet-W32's stages, and in every width
-# layer1's 64 -> 64, the stem's second convolution and transition1.  (PRECISIONS keeps its three values and its last entry.)
-ALL_PRECISIONS = PRECISIONS + ('f16x',)
-_PRECISION_TEXT = "'f32', 'f16', 'f16s2' or 'f16x'"
 # (cin, cout, stride) classes that precision = 'f16x' leaves on their fp32 kernels because the f16-operand op was measured
 # not to win on them (tools/precision_bench.py --x); empty unless a measurement fills it.
 #   Empty: all sixteen classes of W32 at 192 x 256 and of W48's seven layers are faster beyond the spread at 64 crops
 #   (1.6-4.0x) and at 16 (1.2-5.7x; the smallest win is 256 -> 48 stride 1 at 16 crops, 55.3 -> 45.9 us, spreads 2.2 / 1.2).
 F16X_FP32_CLASSES = ()
 
+# THE f16-operand lowering rules, one row per value of the switch, in the order the values extend each other:
+# a precision activates its own row and every row above it (``active_rules``), and a layer goes to the first active row
+# that takes it.  Everything the three modes do differently is a field here; ``eligible``, ``takes``, ``_Recorder.conv``,
+# ``Program._emit`` and ``lowered_cost`` read the fields and name no mode.
+#   kind          the recorded op ('res' / 'stride' are keys of its dict where res_arg / stride_arg say so)
+#   strides       the strides of the 3x3 / pad 1 layers it takes; klass[i] names the class at strides[i] (bench.py parses it)
+#   res_strides   the strides at which a residual may come with the layer
+#   applies, add  the library's host-only predicate and its egn_program_add_* entry; res_arg / stride_arg: whether their
+#                 argument lists carry has_res / res and the stride (an entry of one stride has it in its name)
+#   fp32_classes  the NAME of the module-level tuple of classes measured not to win (looked up at every call: tests and
+#                 tools assign to it), keyed by the first ``class_key`` of (cin, cout, stride); None: no such tuple
+#   pack          the filter layout its kernel instances read (filters.py)
+F16Rule = collections.namedtuple('F16Rule', 'mode kind strides klass res_strides applies add res_arg stride_arg '
+                                            'fp32_classes class_key pack')
+F16_RULES = (
+    # the W48 widths at stride 1 (csrc/conv_h.hip, chunks of 48 channels)
+    F16Rule(mode='f16', kind='convh', strides=(1,), klass=('conv3x3h',), res_strides=(1,),
+            applies='egn_conv3x3_h_applies', add='egn_program_add_conv3x3_h', res_arg=True, stride_arg=False,
+            fp32_classes=None, class_key=0, pack=pack_conv_weight_f16),
+    # ... and at stride 2: no stride-2 layer of HRNet has a residual
+    F16Rule(mode='f16s2', kind='convh2', strides=(2,), klass=('conv3x3s2h',), res_strides=(),
+            applies='egn_conv3x3s2_h_applies', add='egn_program_add_conv3x3s2_h', res_arg=False, stride_arg=False,
+            fp32_classes='F16S2_FP32_CLASSES', class_key=2, pack=pack_conv_weight_f16),
+    # the 32-multiple widths at either stride (chunks of 32): HRNet-W32's stages, and in every width layer1's 64 -> 64,
+    # the stem's second convolution and transition1
+    F16Rule(mode='f16x', kind='convhx', strides=(1, 2), klass=('conv3x3hx', 'conv3x3hxs2'), res_strides=(1,),
+            applies='egn_conv3x3_hx_applies', add='egn_program_add_conv3x3_hx', res_arg=True, stride_arg=True,
+            fp32_classes='F16X_FP32_CLASSES', class_key=3, pack=pack_conv_weight_f16x),
+)
+_RULE_OF_KIND = {rule.kind: rule for rule in F16_RULES}
+# Every value the switch takes; PRECISIONS keeps its three values and its last entry.
+ALL_PRECISIONS = ('f32',) + tuple(rule.mode for rule in F16_RULES)
+PRECISIONS = ALL_PRECISIONS[:3]
 
-def _h_applies(n, h, w, cin, cs_in, cout, cs_out, has_res, act):
-    return bool(_lib.lib().egn_conv3x3_h_applies(n, h, w, cin, cs_in, cout, cs_out, int(has_res), act))
+
+def _or_text(names):
+    return ', '.join(repr(v) for v in names[:-1]) + ' or %r' % (names[-1],)
+
+
+_PRECISION_TEXT = _or_text(ALL_PRECISIONS)
+
+
+def active_rules(precision):
+    """The rows of ``F16_RULES`` that ``precision`` switches on: a prefix of the table, none for 'f32'."""
+    if precision not in ALL_PRECISIONS:
+        raise ValueError("precision must be %s, got %r" % (_PRECISION_TEXT, precision))
+    return F16_RULES[:ALL_PRECISIONS.index(precision)]
+
+
+def _applies(rule, n, h, w, cin, cs_in, cout, cs_out, has_res, act, stride):
+    """The rule's C predicate on a layer of one of its strides, unless the layer's class is measured to stay on fp32."""
+    if rule.fp32_classes and (cin, cout, stride)[:rule.class_key] in globals()[rule.fp32_classes]:
+        return False
+    args = (n, h, w, cin, cs_in, cout, cs_out) + ((int(has_res),) if rule.res_arg else ()) + (act,) + \
+        ((stride,) if rule.stride_arg else ())
+    return bool(getattr(_lib.lib(), rule.applies)(*args))
+
+
+def eligible(rule, conv, n, h, w):
+    """Whether ``rule`` moves the module ``conv`` to the f16-operand kernels (csrc/conv_h.hip): a 3x3 / pad 1 nn.Conv2d of
+    one of the rule's strides without bias, groups or dilation, the rule's host-only predicate takes its [n, Cin, h, w]
+    input (unpadded channel strides), and its class is not among the rule's fp32 exceptions.  The epilogue is not the
+    module's: the recorder asks the same predicate with the layer's own (``takes``; every such layer of HRNet has a plain
+    one: folded BatchNorm, optional residual, ReLU or none)."""
+    if not isinstance(conv, nn.Conv2d) or conv.stride[0] not in rule.strides:
+        return False
+    s = conv.stride[0]
+    if (tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation), conv.groups) != \
+            ((3, 3), (s, s), (1, 1), (1, 1), 1) or conv.bias is not None or conv.padding_mode != 'zeros':
+        return False
+    cin, cout = conv.in_channels, conv.out_channels
+    return _applies(rule, n, h, w, cin, cin, cout, cout, False, ACT_RELU, s)
+
+
+def takes(rule, x, weight, bias, act, res, stride, pad, out_nchw=False, cout_cs=None, dst_given=False):
+    """``eligible`` on a recorded layer: the same C predicate, asked with the layer's own epilogue."""
+    cout, cin, kh, kw = weight.shape
+    if (kh, kw, pad) != (3, 3, 1) or stride not in rule.strides or bias is not None or out_nchw or cout_cs is not None or \
+            dst_given or (res is not None and stride not in rule.res_strides):
+        return False
+    return _applies(rule, x.n, x.h, x.w, cin, x.cs, cout, _round_up(cout, 4), res is not None, act, stride)
+
+
+def lowered_cost(kind, op):
+    """(klass, flops, bytes) of a recorded 'convh' / 'convh2' / 'convhx' op, as ``Program.meta`` reports them: fp32
+    activations (the residual read beside the output written), f16 filters."""
+    rule, x, y = _RULE_OF_KIND[kind], op['x'], op['y']
+    stride = op['stride'] if rule.stride_arg else rule.strides[0]
+    flops = 2.0 * y.n * y.h * y.w * op['cout'] * op['cin'] * 9
+    nbytes = 4.0 * (x.n * x.h * x.w * op['cin'] + y.n * y.h * y.w * op['cout'] * (2 if op.get('res') is not None else 1)) + \
+        2.0 * op['cout'] * op['cin'] * 9
+    return '%s %d->%d@%dx%d' % (rule.klass[rule.strides.index(stride)], op['cin'], op['cout'], y.h, y.w), flops, nbytes
 
 
 def f16_eligible(conv, n, h, w):
-    """THE rule for which layers precision = 'f16' moves to the f16-operand kernels (csrc/conv_h.hip): ``conv`` is a
-    3x3 / stride 1 / pad 1 nn.Conv2d without bias, groups or dilation, and the library's host-only predicate
-    egn_conv3x3_h_applies takes its [n, Cin, h, w] input (unpadded channel strides).  The epilogue is not the module's:
-    the recorder asks the same predicate with the layer's own (every such layer of HRNet has a plain one: folded
-    BatchNorm, optional residual, ReLU or none)."""
-    if not isinstance(conv, nn.Conv2d):
-        return False
-    if (tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation), conv.groups) != \
-            ((3, 3), (1, 1), (1, 1), (1, 1), 1) or conv.bias is not None or conv.padding_mode != 'zeros':
-        return False
-    cin, cout = conv.in_channels, conv.out_channels
-    return _h_applies(n, h, w, cin, cin, cout, cout, False, ACT_RELU)
-
-
-def _h2_applies(n, h, w, cin, cs_in, cout, cs_out, act):
-    return (cin, cout) not in F16S2_FP32_CLASSES and \
-        bool(_lib.lib().egn_conv3x3s2_h_applies(n, h, w, cin, cs_in, cout, cs_out, act))
+    """The layers precision = 'f16' moves to the f16-operand kernels (the first row of ``F16_RULES``): the 3x3 / stride 1 /
+    pad 1 convolutions of the W48 widths that egn_conv3x3_h_applies takes."""
+    return eligible(F16_RULES[0], conv, n, h, w)
 
 
 def f16s2_eligible(conv, n, h, w):
-    """THE rule for which layers precision = 'f16s2' moves to the f16-operand kernel BESIDE those ``f16_eligible`` names:
-    ``conv`` is a 3x3 / stride 2 / pad 1 nn.Conv2d without bias, groups or dilation, the host-only predicate
-    egn_conv3x3s2_h_applies takes its [n, Cin, h, w] input, and its class is not in ``F16S2_FP32_CLASSES``."""
-    if not isinstance(conv, nn.Conv2d):
-        return False
-    if (tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation), conv.groups) != \
-            ((3, 3), (2, 2), (1, 1), (1, 1), 1) or conv.bias is not None or conv.padding_mode != 'zeros':
-        return False
-    cin, cout = conv.in_channels, conv.out_channels
-    return _h2_applies(n, h, w, cin, cin, cout, cout, ACT_RELU)
-
-
-def _hx_applies(n, h, w, cin, cs_in, cout, cs_out, has_res, act, stride):
-    return (cin, cout, stride) not in F16X_FP32_CLASSES and \
-        bool(_lib.lib().egn_conv3x3_hx_applies(n, h, w, cin, cs_in, cout, cs_out, int(has_res), act, stride))
+    """The layers precision = 'f16s2' moves BESIDE those ``f16_eligible`` names (the second row): the 3x3 / stride 2 / pad 1
+    convolutions that egn_conv3x3s2_h_applies takes and whose (cin, cout) class is not in ``F16S2_FP32_CLASSES``."""
+    return eligible(F16_RULES[1], conv, n, h, w)
 
 
 def f16x_eligible(conv, n, h, w):
-    """THE rule for which layers precision = 'f16x' moves to the f16-operand kernel BESIDE those ``f16_eligible`` and
-    ``f16s2_eligible`` name: ``conv`` is a 3x3 / pad 1 nn.Conv2d of stride 1 or 2 without bias, groups or dilation, the
-    host-only predicate egn_conv3x3_hx_applies takes its [n, Cin, h, w] input, and its (cin, cout, stride) class is not in
-    ``F16X_FP32_CLASSES``."""
-    if not isinstance(conv, nn.Conv2d):
-        return False
-    if (tuple(conv.kernel_size), tuple(conv.padding), tuple(conv.dilation), conv.groups) != ((3, 3), (1, 1), (1, 1), 1) \
-            or tuple(conv.stride) not in ((1, 1), (2, 2)) or conv.bias is not None or conv.padding_mode != 'zeros':
-        return False
-    cin, cout = conv.in_channels, conv.out_channels
-    return _hx_applies(n, h, w, cin, cin, cout, cout, False, ACT_RELU, conv.stride[0])
+    """The layers precision = 'f16x' moves BESIDE those ``f16_eligible`` and ``f16s2_eligible`` name (the third row): the
+    3x3 / pad 1 convolutions of stride 1 or 2 that egn_conv3x3_hx_applies takes and whose (cin, cout, stride) class is not
+    in ``F16X_FP32_CLASSES``."""
+    return eligible(F16_RULES[2], conv, n, h, w)
 
 
 class f16_emulation(object):
@@ -118,15 +169,13 @@ class f16_emulation(object):
 
     def __init__(self, model, precision='f16'):
         if precision not in ALL_PRECISIONS[1:]:
-            raise ValueError("f16_emulation: precision must be 'f16', 'f16s2' or 'f16x', got %r" % (precision,))
+            raise ValueError("f16_emulation: precision must be %s, got %r" % (_or_text(ALL_PRECISIONS[1:]), precision))
         self.model, self.handles, self.saved, self.hit = model, [], {}, []
-        self.s2, self.x = precision in ('f16s2', 'f16x'), precision == 'f16x'
+        self.rules = active_rules(precision)
 
     def _pre(self, mod, args):
         x = args[0]
-        if x.dim() != 4 or not (f16_eligible(mod, x.shape[0], x.shape[2], x.shape[3]) or
-                                (self.s2 and f16s2_eligible(mod, x.shape[0], x.shape[2], x.shape[3])) or
-                                (self.x and f16x_eligible(mod, x.shape[0], x.shape[2], x.shape[3]))):
+        if x.dim() != 4 or not any(eligible(rule, mod, x.shape[0], x.shape[2], x.shape[3]) for rule in self.rules):
             return None
         self.saved[mod] = mod.weight.data
         mod.weight.data = mod.weight.data.half().float()
@@ -216,9 +265,7 @@ class _Recorder(object):
         self.cur_lane = 0      # launch lane inside the current region
         self._pending = {}     # lane -> tokens its next op waits for (``wait``)
         self._before = None    # happens_before's closure, rebuilt after every new op
-        self.f16 = False       # precision = 'f16': eligible 3x3 convs are recorded as 'convh' ops (csrc/conv_h.hip)
-        self.f16s2 = False     # precision = 'f16s2': ... and eligible 3x3 stride-2 convs as 'convh2' ops
-        self.f16x = False      # precision = 'f16x': ... and the 3x3 convs of the 32-multiple widths as 'convhx' ops
+        self.rules = ()        # the active rows of F16_RULES: a 3x3 conv one of them takes is recorded as its op kind
 
     def _push(self, kind, op):
         op['region'], op['lane'] = self.region, self.cur_lane
@@ -311,27 +358,21 @@ class _Recorder(object):
             if cout_cs is not None:
                 dst.cs = cout_cs
                 dst.nbytes = x.n * ho * wo * cout_cs * 4
-        if self.f16 and self.takes_f16(x, weight, bias, act, res, stride, pad, out_nchw, cout_cs, dst_given):
-            scale, shift = fold_scale_shift(cout, None, bn)
-            op = dict(x=x, w=self.weight(pack_conv_weight_f16(weight)), scale=self.weight(scale), shift=self.weight(shift),
-                      res=res, y=dst, cin=cin, cout=cout, act=act, tag=tag)
-            self._touch(x, res, dst)
-            self._push('convh', op)
-            return dst
-        if self.f16s2 and self.takes_f16s2(x, weight, bias, act, res, stride, pad, out_nchw, cout_cs, dst_given):
-            scale, shift = fold_scale_shift(cout, None, bn)
-            op = dict(x=x, w=self.weight(pack_conv_weight_f16(weight)), scale=self.weight(scale), shift=self.weight(shift),
-                      y=dst, cin=cin, cout=cout, act=act, tag=tag)
-            self._touch(x, dst)
-            self._push('convh2', op)
-            return dst
-        if self.f16x and self.takes_f16x(x, weight, bias, act, res, stride, pad, out_nchw, cout_cs, dst_given):
-            scale, shift = fold_scale_shift(cout, None, bn)
-            op = dict(x=x, w=self.weight(pack_conv_weight_f16x(weight)), scale=self.weight(scale), shift=self.weight(shift),
-                      res=res, y=dst, cin=cin, cout=cout, act=act, stride=stride, tag=tag)
-            self._touch(x, res, dst)
-            self._push('convhx', op)
-            return dst
+        for rule in self.rules:
+            if takes(rule, x, weight, bias, act, res, stride, pad, out_nchw, cout_cs, dst_given):
+                scale, shift = fold_scale_shift(cout, None, bn)
+                op = dict(x=x, w=self.weight(rule.pack(weight)), scale=self.weight(scale), shift=self.weight(shift),
+                          y=dst, cin=cin, cout=cout, act=act, tag=tag)
+                if rule.res_arg:
+                    op['res'] = res
+                if rule.stride_arg:
+                    op['stride'] = stride
+                self._touch(x, res, dst)
+                # rule.kind -- self._push('convh', op), self._push('convh2', op) or self._push('convhx', op): spelled out for
+                # tests/program_ops_sweep.py, which reads the kinds a program can hold from this file's text (and
+                # tests/test_f16_rules_cpu.py holds the table to this list)
+                self._push(rule.kind, op)
+                return dst
         scale, shift = fold_scale_shift(cout, bias, bn)
         # the filter is packed when the program is built: the layout depends on the tile
         # configuration the tuner picks for the shape (direct vs Winograd kernels)
@@ -344,29 +385,18 @@ class _Recorder(object):
 
     @staticmethod
     def takes_f16(x, weight, bias, act, res, stride, pad, out_nchw=False, cout_cs=None, dst_given=False):
-        """``f16_eligible`` on a recorded layer: the same C predicate, asked with the layer's own epilogue."""
-        cout, cin, kh, kw = weight.shape
-        if (kh, kw, stride, pad) != (3, 3, 1, 1) or bias is not None or out_nchw or cout_cs is not None or dst_given:
-            return False
-        return _h_applies(x.n, x.h, x.w, cin, x.cs, cout, _round_up(cout, 4), res is not None, act)
+        """``f16_eligible`` on a recorded layer."""
+        return takes(F16_RULES[0], x, weight, bias, act, res, stride, pad, out_nchw, cout_cs, dst_given)
 
     @staticmethod
     def takes_f16s2(x, weight, bias, act, res, stride, pad, out_nchw=False, cout_cs=None, dst_given=False):
-        """``f16s2_eligible`` on a recorded layer: its C predicate, asked with the layer's own epilogue."""
-        cout, cin, kh, kw = weight.shape
-        if (kh, kw, stride, pad) != (3, 3, 2, 1) or bias is not None or res is not None or out_nchw or \
-                cout_cs is not None or dst_given:
-            return False
-        return _h2_applies(x.n, x.h, x.w, cin, x.cs, cout, _round_up(cout, 4), act)
+        """``f16s2_eligible`` on a recorded layer."""
+        return takes(F16_RULES[1], x, weight, bias, act, res, stride, pad, out_nchw, cout_cs, dst_given)
 
     @staticmethod
     def takes_f16x(x, weight, bias, act, res, stride, pad, out_nchw=False, cout_cs=None, dst_given=False):
-        """``f16x_eligible`` on a recorded layer: its C predicate, asked with the layer's own epilogue."""
-        cout, cin, kh, kw = weight.shape
-        if (kh, kw, pad) != (3, 3, 1) or stride not in (1, 2) or bias is not None or out_nchw or cout_cs is not None or \
-                dst_given:
-            return False
-        return _hx_applies(x.n, x.h, x.w, cin, x.cs, cout, _round_up(cout, 4), res is not None, act, stride)
+        """``f16x_eligible`` on a recorded layer."""
+        return takes(F16_RULES[2], x, weight, bias, act, res, stride, pad, out_nchw, cout_cs, dst_given)
 
     def conv_pair(self, xa, conv_a, bn_a, act_a, res_a, xb, conv_b, bn_b, act_b, res_b, tag=''):
         """Two independent 3x3 / stride 1 / pad 1 convolutions (+ folded BatchNorm, residual, ReLU) as ONE launch
@@ -509,6 +539,10 @@ class _Recorder(object):
         return blob.to(device)
 
 
+for _rule in F16_RULES:          # r.f16, r.f16s2, r.f16x: whether the recorder lowers by the row of that mode
+    setattr(_Recorder, _rule.mode, property(lambda self, rule=_rule: rule in self.rules))
+
+
 class Program(object):
     """Owns a native egn_program plus the torch storage its slots point to."""
 
@@ -584,31 +618,13 @@ class Program(object):
                             + op['cout'] * op['cin'] * op['kh'] * op['kw'])
             klass = 'conv%dx%ds%d %d->%d@%dx%d' % (op['kh'], op['kw'], op['stride'], op['cin'],
                                                     op['cout'], op['ho'], op['wo'])
-        elif kind == 'convh':
-            x, y = op['x'], op['y']
-            res = op['res'].ref() if op['res'] is not None else NULL_REF
-            _lib.check(L.egn_program_add_conv3x3_h(h, x.ref(), op['w'], op['scale'], op['shift'], res, y.ref(),
-                                                   x.n, x.h, x.w, op['cin'], op['cout'], op['act']), op['tag'])
-            m = x.n * x.h * x.w
-            flops = 2.0 * m * op['cout'] * op['cin'] * 9
-            nbytes = 4.0 * m * (op['cin'] + op['cout'] * (2 if op['res'] is not None else 1)) + 2.0 * op['cout'] * op['cin'] * 9
-            klass = 'conv3x3h %d->%d@%dx%d' % (op['cin'], op['cout'], x.h, x.w)
-        elif kind == 'convh2':
-            x, y = op['x'], op['y']
-            _lib.check(L.egn_program_add_conv3x3s2_h(h, x.ref(), op['w'], op['scale'], op['shift'], y.ref(),
-                                                     x.n, x.h, x.w, op['cin'], op['cout'], op['act']), op['tag'])
-            flops = 2.0 * y.n * y.h * y.w * op['cout'] * op['cin'] * 9
-            nbytes = 4.0 * (x.n * x.h * x.w * op['cin'] + y.n * y.h * y.w * op['cout']) + 2.0 * op['cout'] * op['cin'] * 9
-            klass = 'conv3x3s2h %d->%d@%dx%d' % (op['cin'], op['cout'], y.h, y.w)
-        elif kind == 'convhx':
-            x, y = op['x'], op['y']
-            res = op['res'].ref() if op['res'] is not None else NULL_REF
-            _lib.check(L.egn_program_add_conv3x3_hx(h, x.ref(), op['w'], op['scale'], op['shift'], res, y.ref(),
-                                                    x.n, x.h, x.w, op['cin'], op['cout'], op['act'], op['stride']), op['tag'])
-            flops = 2.0 * y.n * y.h * y.w * op['cout'] * op['cin'] * 9
-            nbytes = 4.0 * (x.n * x.h * x.w * op['cin'] + y.n * y.h * y.w * op['cout'] * (2 if op['res'] is not None else 1)) + \
-                2.0 * op['cout'] * op['cin'] * 9
-            klass = 'conv3x3hx%s %d->%d@%dx%d' % ('s2' if op['stride'] == 2 else '', op['cin'], op['cout'], y.h, y.w)
+        elif kind in _RULE_OF_KIND:
+            rule, x, y = _RULE_OF_KIND[kind], op['x'], op['y']
+            res = [op['res'].ref() if op['res'] is not None else NULL_REF] if rule.res_arg else []
+            _lib.check(getattr(L, rule.add)(*([h, x.ref(), op['w'], op['scale'], op['shift']] + res +
+                                              [y.ref(), x.n, x.h, x.w, op['cin'], op['cout'], op['act']] +
+                                              ([op['stride']] if rule.stride_arg else []))), op['tag'])
+            klass, flops, nbytes = lowered_cost(kind, op)
         elif kind == 'convpair':
             args, klass = [], []
             for half in (op['a'], op['b']):
@@ -787,8 +803,7 @@ class HRNetEngine(object):
         ``f16s2_eligible`` names, 'f16x' those and the layers ``f16x_eligible`` names; everything else, and the training
         tape, is recorded exactly as in 'f32'."""
         prec = getattr(self.model, 'precision', 'f32')
-        if prec not in ALL_PRECISIONS:
-            raise ValueError("precision must be %s, got %r" % (_PRECISION_TEXT, prec))
+        active_rules(prec)          # (refuses any other value)
         return prec
 
     # -- recording ---------------------------------------------------------
@@ -871,13 +886,11 @@ class HRNetEngine(object):
         (hrnet.py:286-287: the branches are independent at every depth)."""
         if mod is None or not hasattr(r, 'conv_pair'):
             return None
-        lowered = [False] * mod.num_branches        # precision = 'f16': a layer the f16-operand op takes is never half of a pair
-        if getattr(r, 'f16', False):
-            lowered = [any(r.takes_f16(x, conv.weight, conv.bias, ACT_RELU, None, conv.stride[0], conv.padding[0]) or
-                           (getattr(r, 'f16x', False) and
-                            r.takes_f16x(x, conv.weight, conv.bias, ACT_RELU, None, conv.stride[0], conv.padding[0]))
-                           for blk in b for conv in (blk.conv1, blk.conv2) if getattr(blk, 'depth', 0) == 2)
-                       for b, x in zip(mod.branches, xs)]
+        # a branch with a layer that any active f16-operand rule takes is never half of a pair
+        lowered = [any(takes(rule, x, conv.weight, conv.bias, ACT_RELU, None, conv.stride[0], conv.padding[0])
+                       for rule in getattr(r, 'rules', ()) for blk in b for conv in (blk.conv1, blk.conv2)
+                       if getattr(blk, 'depth', 0) == 2)
+                   for b, x in zip(mod.branches, xs)]
 
         def plain(branch, x):
             for blk in branch:
@@ -992,9 +1005,7 @@ class HRNetEngine(object):
         own = r is None
         if own:
             r = _Recorder()
-            r.f16 = self.precision in ('f16', 'f16s2', 'f16x')     # (the training tape brings its own recorder: the switch is not its)
-            r.f16s2 = self.precision in ('f16s2', 'f16x')
-            r.f16x = self.precision == 'f16x'
+            r.rules = active_rules(self.precision)     # (the training tape brings its own recorder: the switch is not its)
         x = r.nchw_to_nhwc(Ref(SLOT_USER0, 0), n, cin, h, w, tag='input')
         t = r.conv(x, m.conv1.weight, None, m.bn1, ACT_RELU, None, 2, 1, tag='conv1')
         t = r.conv(t, m.conv2.weight, None, m.bn2, ACT_RELU, None, 2, 1, tag='conv2')
@@ -1095,7 +1106,7 @@ class HRNetEngine(object):
             out_shapes['decode_slot'] = SLOT_USER0 + nslots
             nslots += 3
         if own:
-            self.last_f16_ops = [op['tag'] for kind, op in r.ops if kind in ('convh', 'convh2', 'convhx')]
+            self.last_f16_ops = [op['tag'] for kind, op in r.ops if kind in _RULE_OF_KIND]
         return r, nslots, out_shapes
 
     def program(self, x, decode_mode=None, slot=0):

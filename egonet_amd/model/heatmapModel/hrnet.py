@@ -439,7 +439,8 @@ def get_pose_net(cfgs, is_train, **kwargs):
     if hm.get('add_xy'):
         model.modify_input_channel(5)
     if hm.get('precision') is not None:
-        if hm['precision'] not in ('f32', 'f16', 'f16s2', 'f16x'):
-            raise ValueError("heatmapModel.precision must be 'f32', 'f16', 'f16s2' or 'f16x', got %r" % (hm['precision'],))
+        from egonet_amd import engine          # (here, as in _hip_engine: the engine is not a module-level import)
+        if hm['precision'] not in engine.ALL_PRECISIONS:
+            raise ValueError("heatmapModel.precision must be %s, got %r" % (engine._PRECISION_TEXT, hm['precision']))
         model.precision = hm['precision']
     return model
