@@ -617,6 +617,16 @@ static int c48_launch(const ConvArgs& a, size_t lds, int grid, hipStream_t strea
   return (int)hipGetLastError();
 }
 
+// the shapes these kernels take: exactly the 48 -> 48 3x3 stride-1 pad-1 NHWC layers
+bool egn_conv_c48_applies(const ConvArgs& a) {
+  return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin == 48 && a.cs_in == 48 && a.Cout == 48 &&
+         a.cs_out == 48 && !a.out_nchw;
+}
+// the filter + a ring of three halo chunks (C48_Ring) / two halo buffers of three chunks; a: planned (npixp of the row's tile)
+size_t egn_conv_c48_lds_bytes(const ConvArgs& a, C48Kernel k) {
+  return (size_t)((k == C48_Ring ? 3 : 2 * 3) * a.npixp * EGN_CKQ + 3 * 9 * EGN_CKQ * 48) * 16;
+}
+
 int egn_conv_launch_c48(const ConvArgs& a, size_t lds, C48Kernel k, hipStream_t stream) {
   const int cus = egn_device_cus();
   const int ntiles = a.tiles_x * a.tiles_y * a.N;

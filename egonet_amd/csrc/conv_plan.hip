@@ -24,7 +24,10 @@
 int egn_conv_launch_staged(const ConvArgs& a, DirectTile tile, size_t lds, hipStream_t stream);   // conv_mfma.hip
 int egn_conv_launch_dma(const ConvArgs& a, DirectTile tile, size_t lds, hipStream_t stream);      // conv_dma.hip
 int egn_conv_launch_c48(const ConvArgs& a, size_t lds, C48Kernel k, hipStream_t stream);          // conv_c48.hip
+bool egn_conv_c48_applies(const ConvArgs& a);
+size_t egn_conv_c48_lds_bytes(const ConvArgs& a, C48Kernel k);
 int egn_conv_launch_wino(const ConvArgs& a, size_t lds, WinoKernel k, int abl, hipStream_t stream);   // conv_wino.hip
+bool egn_conv_wino_applies(const ConvArgs& a, WinoKernel k);
 size_t egn_conv_wino_lds_bytes(WinoKernel k, int abl, int cout);
 int egn_conv_wino_stats_rows(const ConvArgs& a, WinoKernel k, int abl);
 int egn_conv_launch_stem(const ConvArgs& a, size_t lds, hipStream_t stream);   // conv_stem.hip
@@ -269,8 +272,7 @@ static size_t lds_bytes_for(const ConvArgs& a, const ConvConfig& cf) {
     case F::Staged:
     case F::Dma: return lds_stage_bytes(a, cf) + (size_t)cf.tile_m() * 4;
     case F::Retired: return 0;
-    // the filter + a ring of three halo chunks (C48_Ring) / two halo buffers of three chunks
-    case F::C48: return (size_t)((cf.kernel.c48 == C48_Ring ? 3 : 2 * 3) * a.npixp * EGN_CKQ + 3 * 9 * EGN_CKQ * 48) * 16;
+    case F::C48: return egn_conv_c48_lds_bytes(a, cf.kernel.c48);
     case F::Wino: return egn_conv_wino_lds_bytes(cf.kernel.wino, cf.abl, a.Cout);
     case F::Stem: return egn_conv_stem_lds_bytes();
     case F::Wino4: return egn_conv_wino4_lds_bytes(cf.kernel.wino4);
@@ -286,23 +288,8 @@ static bool family_applies(const ConvArgs& a, const ConvConfig& cf) {
     case F::Staged:
     case F::Dma:
     case F::Retired: return false;
-    case F::C48:
-      // conv_c48.hip: exactly the 48 -> 48 3x3 stride-1 pad-1 NHWC layers
-      return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.Cin == 48 && a.cs_in == 48 && a.Cout == 48 &&
-             a.cs_out == 48 && !a.out_nchw;
-    case F::Wino: {
-      // conv_wino.hip: 3x3 stride-1 pad-1 NHWC layers with unpadded channel strides, even maps
-      if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Cin % EGN_CK || a.cs_in != a.Cin ||
-          a.cs_out != a.Cout || a.out_nchw || (a.Ho & 1) || (a.Wo & 1))
-        return false;
-      const WinoKernel k = cf.kernel.wino;
-      // conv_wino43_kernel: 16 x 16 pixel tiles of whole-tile maps, 4-channel K steps, 48-channel co-tiles
-      if (k == Wino43) return !(a.Cout % 48 || a.Cin % 4 || (a.Ho % 16) || (a.Wo % 16));
-      // co-tile 48 (every kernel) or 32 (not the 4-wave conv_wino_kernel): egn_wino_cot in conv_wino.hip
-      const bool cot32 = k != Wino_16x16 && k != Wino_8x8x4;
-      if (a.Cout % 48 != 0 && !(a.Cout % 32 == 0 && cot32)) return false;
-      return !(a.TH == 8 && a.TW == 8 && (a.Ho > 8 || a.Wo > 8));   // the batched variants are for the 8 x 8 maps
-    }
+    case F::C48: return egn_conv_c48_applies(a);
+    case F::Wino: return egn_conv_wino_applies(a, cf.kernel.wino);
     case F::Stem: return egn_conv_stem_applies(a);
     case F::Wino4: return egn_conv_wino4_applies(a, cf.kernel.wino4);
     case F::Fc: return egn_conv_fc_applies(a);

@@ -31,131 +31,19 @@
 //   * persistent blocks walk over (spatial tile, co-tile) items; a K step = one 16-channel chunk:
 //     halo chunk + U slab arrive by LDS-DMA in double-buffered stages, ONE barrier per step.
 //
-// Two kernels in this file.  conv_wino_kernel (configs 45 / 46) is the design just described: 4 waves,
-// all 16 frequencies in one wave.  conv_wino8_kernel (configs 51 / 52 / 56 / 57, further down) is what
-// the measured table selects: the frequency rows of an m-tile split between two waves (96 accumulators,
-// two waves per SIMD), a partial exchange through LDS at the end of an item, BatchNorm statistics in
-// the epilogue for the training step.  Kernel symbol <-> config: egn_conv_config_name (conv_plan.hip).
+// Four kernels in this file.  conv_wino_kernel (configs 45 / 46) is the design just described: 4 waves,
+// all 16 frequencies in one wave.  conv_wino8_kernel (configs 51 / 52 / 56 / 57, further down) splits the
+// frequency rows of an m-tile between two waves (96 accumulators, two waves per SIMD), with a partial
+// exchange through LDS at the end of an item and BatchNorm statistics in the epilogue for the training
+// step.  conv_wino9_kernel (configs 59 .. 62, 67 / 68) is that kernel with half the VALU instructions: what
+// the measured table selects.  conv_wino43_kernel (config 65) is the first F(4x4,3x3) kernel.  The block-tile
+// geometries and every part the F(2x2,3x3) bodies share are in conv_wino.h; the kernels and their launchers
+// are listed once in WINO_KERNELS below.  Kernel symbol <-> config: egn_conv_config_name (conv_plan.hip).
 //
 // Numerics: exact fp32 products, fp32 accumulation; the +/- transforms add a few ulp relative to
 // the direct sum (the filter transform is done in float64).  Not bit-identical to the direct
 // kernels -- the parity bar is the reference's (1e-3 px on key-points, arg-max indices exact).
-#include "conv_common.h"
-
-// Output channels per block (co-tile, egn_wino_cot in egn_internal.h): 48 (NT = 3 MFMA column tiles)
-// where Cout allows -- the widths of HRNet-W48 (48 / 96 / 192 / 384) -- else 32 (NT = 2): the W32 /
-// Pedestrian widths (32 / 64 / 128 / 256) and the 64-channel stem layers.  The SAME rule in the filter
-// packing, the planner and the launcher.
-
-namespace {
-constexpr int WN_CO = 48;                          // the 4-wave kernel: 48 output channels per block (NT = 3)
-constexpr int WN_NT = 3;
-constexpr int WN_USLOTS = 16 * EGN_CKQ * WN_CO;    // float4 per (chunk, co-tile) slab of U: 3072 = 48 KB
-constexpr int WN_NTH = 256;
-constexpr int WN_UIT = WN_USLOTS / WN_NTH;         // 12 DMA instructions per lane and slab
-}  // namespace
-
-// Geometry of a block tile (64 Winograd tiles = 4 waves x 16) and the LDS image of its halo chunk.
-//
-// The halo lives in LDS as FOUR CHANNEL-QUAD PLANES  sH[quad][pixel slot]  (16 B per slot), not pixel
-// major: a patch read (one ds_read_b128 per lane) is served in 4 groups of 16 lanes, each group holding
-// all 16 tiles (li) of the wave with only two quad values, so it is conflict free exactly when the 16
-// tiles' pixel slots are distinct mod 16 (and the plane size is a multiple of 256 B).  Tiles step by TWO
-// pixels, so plain row-major slots collide; each geometry therefore skews its rows / images:
-//   <16,16,1>  tile li = (ty = li>>3, tx = li&7): slot = y*24 + ((y>>1)&1) + x.  The two tile rows of a
-//              wave are 2 pixel rows apart = 48 slots (= 0 mod 16) +- 1 from the skew: 2tx + {0,1}.
-//   <8,8,4>    wave = tile row, li = (image b = li>>2, tx = li&3): slot = b*112 + g(b) + y*10 + x with
-//              g = {0,1,8,9}: 2tx + g(b) covers 0..15.
-// (pixel-major slots measured 4-way conflicts: 16 instead of 4 LDS cycles per read, 16 % of a K step.)
-template <int TH, int TW, int TNB>
-struct WinoGeom;
-
-template <>
-struct WinoGeom<16, 16, 1> {
-  static constexpr int TH = 16, TW = 16, TNB = 1, HH = 18, HW = 18;
-  static constexpr int RP = 24, PLANE = 432;     // 18 rows x 24 slots; 6912 B = 27 x 256
-  static constexpr int ROFF = RP;                // slot step of one patch row
-  // DMA slot p of a plane -> halo pixel (b, hy, hx) or -1
-  static __device__ __forceinline__ int decode(int p) {
-    const int y = p / RP, x = p - y * RP - ((y >> 1) & 1);
-    return (y < HH && x >= 0 && x < HW) ? ((y << 8) | x) : -1;
-  }
-  // slot of the patch origin of tile li of wave w, for patch rows {0,1} (k = 0) / {2,3} (k = 1)
-  static __device__ __forceinline__ int patch_base(int w, int li, int k) {
-    const int tyl = li >> 3, tx = li & 7;
-    return (4 * w + 2 * tyl) * RP + 2 * tx + ((tyl + k) & 1);
-  }
-  // tile index (b << 16 | ty << 8 | tx) of MFMA result row m (0..15) of wave w
-  static __device__ __forceinline__ int out_tile(int w, int m) { return ((2 * w + (m >> 3)) << 8) | (m & 7); }
-};
-
-template <>
-struct WinoGeom<8, 8, 4> {
-  static constexpr int TH = 8, TW = 8, TNB = 4, HH = 10, HW = 10;
-  static constexpr int RP = 10, IMGP = 112, PLANE = 448;   // 7168 B = 28 x 256
-  static constexpr int ROFF = RP;
-  static __device__ __forceinline__ int skew(int b) { return (b & 1) + ((b & 2) << 2); }  // 0, 1, 8, 9
-  static __device__ __forceinline__ int decode(int p) {
-    const int b = p / IMGP, r = p - b * IMGP - skew(b);
-    const int y = r / RP, x = r - y * RP;
-    return (r >= 0 && r < HH * RP) ? ((b << 16) | (y << 8) | x) : -1;
-  }
-  static __device__ __forceinline__ int patch_base(int w, int li, int) {
-    const int b = li >> 2, tx = li & 3;
-    return b * IMGP + skew(b) + 2 * w * RP + 2 * tx;
-  }
-  static __device__ __forceinline__ int out_tile(int w, int m) { return ((m >> 2) << 16) | (w << 8) | (m & 3); }
-};
-
-// half of the 16 x 16 tile (8 rows x 16 columns = 32 Winograd tiles, conv_wino8_kernel with 4 waves): twice
-// the work items for maps / batches that leave CUs idle with the 64-tile form.  Same slots, fewer rows.
-template <>
-struct WinoGeom<8, 16, 1> {
-  static constexpr int TH = 8, TW = 16, TNB = 1, HH = 10, HW = 18;
-  static constexpr int RP = 24, PLANE = 256;     // 10 rows x 24 slots = 240, padded to 16 x 256 B
-  static constexpr int ROFF = RP;
-  static __device__ __forceinline__ int decode(int p) {
-    const int y = p / RP, x = p - y * RP - ((y >> 1) & 1);
-    return (y < HH && x >= 0 && x < HW) ? ((y << 8) | x) : -1;
-  }
-  static __device__ __forceinline__ int patch_base(int w, int li, int k) {
-    const int tyl = li >> 3, tx = li & 7;
-    return (4 * w + 2 * tyl) * RP + 2 * tx + ((tyl + k) & 1);
-  }
-  static __device__ __forceinline__ int out_tile(int w, int m) { return ((2 * w + (m >> 3)) << 8) | (m & 7); }
-};
-
-// two 8 x 8 images per block (32 Winograd tiles = 2 m-tiles; conv_wino8_kernel with 4 waves): m-tile mt
-// holds tile rows {2mt, 2mt+1} of both images, li = (b = li>>3, row = (li>>2)&1, tx = li&3):
-// slot = b*128 + b + y*12 + x -- 2tx + {0, 24 = 8 mod 16} + {0, 1} covers 0..15.
-template <>
-struct WinoGeom<8, 8, 2> {
-  static constexpr int TH = 8, TW = 8, TNB = 2, HH = 10, HW = 10;
-  static constexpr int RP = 12, IMGP = 128, PLANE = 256;   // 4096 B = 16 x 256
-  static constexpr int ROFF = RP;
-  static __device__ __forceinline__ int decode(int p) {
-    const int b = p / IMGP, r = p - b * IMGP - b;
-    const int y = r / RP, x = r - y * RP;
-    return (r >= 0 && r < HH * RP && x < HW) ? ((b << 16) | (y << 8) | x) : -1;
-  }
-  static __device__ __forceinline__ int patch_base(int mt, int li, int) {
-    const int b = li >> 3, tyl = (li >> 2) & 1, tx = li & 3;
-    return b * IMGP + b + 2 * (2 * mt + tyl) * RP + 2 * tx;
-  }
-  static __device__ __forceinline__ int out_tile(int mt, int m) {
-    return ((m >> 3) << 16) | ((2 * mt + ((m >> 2) & 1)) << 8) | (m & 3);
-  }
-};
-
-template <int TH, int TW, int TNB>
-struct WinoDims {
-  using G = WinoGeom<TH, TW, TNB>;
-  static constexpr int SLOTS = EGN_CKQ * G::PLANE;
-  static constexpr int IT = (SLOTS + WN_NTH - 1) / WN_NTH;  // DMA instructions per lane and halo chunk
-  static constexpr int BUF = IT * WN_NTH;                   // every wave issues IT whole instructions
-  static_assert(G::PLANE % 16 == 0, "planes must start on a 256-byte boundary");
-  static_assert(TNB * (TH / 2) * (TW / 2) == 64 || TNB * (TH / 2) * (TW / 2) == 32, "m-tiles of 16 Winograd tiles");
-};
+#include "conv_wino.h"
 
 // ABL != 0 are timing ablations (wrong results by construction; cfg ids 47..50, tools/wino_probe.py only):
 //   bit 0 no DMA after the prologue, bit 1 no patch reads / input transform, bit 2 no residual loads /
@@ -164,11 +52,15 @@ template <int TH, int TW, int TNB, int ABL = 0>
 __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
   using G = WinoGeom<TH, TW, TNB>;
   using D = WinoDims<TH, TW, TNB>;
-  constexpr int IT = D::IT;
+  constexpr int NTH = WN_NTH, NT = WN_NT, CO_T = WN_CO;
+  constexpr int KQ = EGN_CKQ, HS = 1, USL = WN_USLOTS, UCH = USL;  // whole-chunk stages
+  constexpr int SLOTS = D::SLOTS, IT = D::IT;
+  constexpr int BUF = D::BUF;          // padded to whole 256-thread pieces: every wave issues all of them
+  constexpr bool WHOLE_PIECES = true;
   constexpr int NPIECE = IT + WN_UIT;  // DMA instructions per lane and K step
   extern __shared__ float4 smem[];
-  float4* sU = smem;                  // [2][WN_USLOTS]   (f, quad, co) of one chunk and co-tile
-  float4* sH = smem + 2 * WN_USLOTS;  // [2][D::BUF]      quad planes of one halo chunk
+  float4* sU = smem;            // [2][USL]   (f, quad, co) of one chunk and co-tile
+  float4* sH = smem + 2 * USL;  // [2][BUF]   quad planes of one halo chunk
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -178,26 +70,12 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
 
   const int C = a.Cin;        // cs_in == Cin (planner)
   const int Co = a.Cout;      // cs_out == Cout, multiple of 48
-  const int nct = Co / WN_CO;
+  const int nct = Co / CO_T;
   const int nchunk = a.nchunk;
 
-  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C * 4);
-  const u32x4 ruv = egn_rsrc(a.w, (size_t)nct * nchunk * WN_USLOTS * 16);
-  const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
-  const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
-
-  // halo slot e = it*256 + tid -> (quad plane, pixel slot) -> (image b, hy, hx); item independent
-  int hmeta[IT];  // b << 16 | hy << 8 | hx, -1 = pad slot;  the quad is e / PLANE
-  unsigned hq[IT];
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int e = it * WN_NTH + tid;
-    const int q = e / G::PLANE;
-    hmeta[it] = q < EGN_CKQ ? G::decode(e - q * G::PLANE) : -1;
-    hq[it] = (unsigned)q * 16u;
-  }
+  WINO_DESCRIPTORS((size_t)nct * nchunk * UCH * 16)
+  WINO_HALO_SLOTS()
+  WINO_FILTER_SLOTS()
 
   // this lane's patch origin (float4 index in a halo buffer) for patch rows {0,1} and {2,3}
   const int pb01 = kq * G::PLANE + G::patch_base(wave, li, 0);
@@ -210,45 +88,6 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
   const int tiles_xy = a.tiles_x * a.tiles_y;
   const int ntile = tiles_xy * ((a.N + TNB - 1) / TNB);
   const int nwork = ((ntile + 7) >> 3) * nct * 8;  // work index space, see WINO_ITEM
-
-// work index w -> (spatial tile, co-tile).  Blocks w, w+8, w+16 ... run on one XCD (block b -> XCD
-// b % 8): the co-tiles of ONE spatial tile are consecutive slots of one XCD, so the halo they all read
-// is fetched into that XCD's L2 once.
-#define WINO_ITEM(Wi, TILE_, CT_)            \
-  {                                          \
-    const int x_ = (Wi)&7, q_ = (Wi) >> 3;   \
-    TILE_ = (q_ / nct) * 8 + x_;             \
-    CT_ = q_ - (q_ / nct) * nct;             \
-  }
-// halo DMA byte offsets (chunk 0) of a spatial tile; out-of-image and pad slots get the OOB offset
-// and are written as zeros by the same DMA (= the convolution's zero padding)
-#define WINO_DOFF(TILE_, OUT)                                                                       \
-  {                                                                                                 \
-    const int tb_ = (TILE_) / tiles_xy;                                                             \
-    const int r_ = (TILE_)-tb_ * tiles_xy;                                                          \
-    const int ty_ = r_ / a.tiles_x, tx_ = r_ - ty_ * a.tiles_x;                                     \
-    const int n0_ = tb_ * TNB, iy0_ = ty_ * TH - 1, ix0_ = tx_ * TW - 1;                            \
-    _Pragma("unroll") for (int it = 0; it < IT; ++it) {                                             \
-      const int m_ = hmeta[it];                                                                     \
-      const int n_ = n0_ + (m_ >> 16), iy_ = iy0_ + ((m_ >> 8) & 255), ix_ = ix0_ + (m_ & 255);     \
-      const bool in_ = m_ >= 0 && (TILE_) < ntile && n_ < a.N && iy_ >= 0 && iy_ < a.H && ix_ >= 0 && ix_ < a.W; \
-      OUT[it] = in_ ? (unsigned)(((n_ * a.H + iy_) * a.W + ix_) * C) * 4u + hq[it] : EGN_OOB;       \
-    }                                                                                               \
-  }
-// DMA instruction K (0 .. NPIECE-1) of a K step: halo chunk CH of the tile with offsets OFF (K < IT),
-// then the U slab (CT, CH), into stage buffer P
-#define WINO_PIECE(K, P, OFF, CT, CH)                                                                \
-  {                                                                                                  \
-    if ((K) < IT) {                                                                                  \
-      egn_lds_dma16(rxv, egn_lds_addr(sH + (P)*D::BUF + wave * 64) + (K)*WN_NTH * 16, OFF[(K) < IT ? (K) : 0], \
-                 (unsigned)(CH)*64u);                                                                \
-    } else {                                                                                         \
-      egn_lds_dma16(ruv, egn_lds_addr(sU + (P)*WN_USLOTS + wave * 64) + ((K)-IT) * WN_NTH * 16, (unsigned)tid * 16u, \
-                 (unsigned)(((CT)*nchunk + (CH)) * WN_USLOTS) * 16u + ((K)-IT) * WN_NTH * 16);       \
-    }                                                                                                \
-  }
-#define WINO_ISSUE(P, OFF, CT, CH) \
-  { _Pragma("unroll") for (int k_ = 0; k_ < NPIECE; ++k_) WINO_PIECE(k_, P, OFF, CT, CH) }
 
   int w = blockIdx.x;
   int tile = 0, ct = 0;
@@ -271,33 +110,9 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
     const bool more = (w + (int)gridDim.x) < nwork;
     unsigned doff_n[IT];
     WINO_DOFF(tile_n, doff_n)
-    unsigned voff[4];
-    {
-      const int tb_ = tile / tiles_xy;
-      const int r_ = tile - tb_ * tiles_xy;
-      const int ty_ = r_ / a.tiles_x, tx_ = r_ - ty_ * a.tiles_x;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = tb_ * TNB + (og[r] >> 16);
-        const int oy = ty_ * TH + 2 * ((og[r] >> 8) & 255), ox = tx_ * TW + 2 * (og[r] & 255);
-        voff[r] = (tile < ntile && n < a.N && oy < a.Ho && ox < a.Wo)
-                      ? (unsigned)(((n * a.Ho + oy) * a.Wo + ox) * Co + ct * WN_CO + li) * 4u
-                      : EGN_OOB;
-      }
-    }
-    float sc[WN_NT], sh[WN_NT];
-#pragma unroll
-    for (int nt = 0; nt < WN_NT; ++nt) {
-      sc[nt] = a.scale[ct * WN_CO + nt * 16 + li];
-      sh[nt] = a.shift[ct * WN_CO + nt * 16 + li];
-    }
-
-    f32x4 acc[16][WN_NT];
-#pragma unroll
-    for (int f = 0; f < 16; ++f)
-#pragma unroll
-      for (int nt = 0; nt < WN_NT; ++nt) acc[f][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float rv[4][2][2][WN_NT];  // residual of this lane's outputs: [tile r][a][b][nt]
+    WINO_VOFF(0)
+    WINO_SCALE_ACC(16)
+    float rv[4][2][2][NT];  // residual of this lane's outputs: [tile r][a][b][nt]
 
     for (int c = 0; c < nchunk; ++c) {
       const bool last = c + 1 == nchunk;
@@ -318,13 +133,7 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
       unsigned nxo[IT];
 #pragma unroll
       for (int it = 0; it < IT; ++it) nxo[it] = last ? doff_n[it] : doff[it];
-#define WINO_NEXT(K)                                     \
-  {                                                      \
-    __builtin_amdgcn_sched_barrier(0x0106);              \
-    if (nx_issue) WINO_PIECE(K, par ^ 1, nxo, nx_ct, nx_ch) \
-    __builtin_amdgcn_sched_barrier(0x0106);              \
-  }
-      WINO_NEXT(0) WINO_NEXT(1) WINO_NEXT(2)
+      WINO_NEXT(0, nxo) WINO_NEXT(1, nxo) WINO_NEXT(2, nxo)
       static_assert(NPIECE <= 19, "3 DMA pieces at the top + one per frequency");
       if (last) {
         // the vmcnt(48) above counts on program order DMA -> residual loads -> stores: the loads go
@@ -332,8 +141,8 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
       }
 
       // ---- input transform V = B^T d B of this lane's (tile, channel quad), row by row ----
-      const float4* hb01 = sH + par * D::BUF + pb01;
-      const float4* hb23 = sH + par * D::BUF + pb23;
+      const float4* hb01 = sH + par * BUF + pb01;
+      const float4* hb23 = sH + par * BUF + pb23;
       f32x4 d[4][4], t[4][4], V[16];
 #define WINO_LOADROW(R)                                                                                   \
   _Pragma("unroll") for (int cc = 0; cc < 4; ++cc) {                                                      \
@@ -355,16 +164,16 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
       WINO_LOADROW(3)
 
       // ---- 16 frequencies x 3 co sub-tiles x 4 k-steps ----
-      const float4* ub = sU + par * WN_USLOTS + kq * WN_CO + li;
-      f32x4 bf[2][WN_NT];
+      const float4* ub = sU + par * USL + kq * CO_T + li;
+      f32x4 bf[2][NT];
 #pragma unroll
-      for (int nt = 0; nt < WN_NT; ++nt) bf[0][nt] = *reinterpret_cast<const f32x4*>(&ub[nt * 16]);
+      for (int nt = 0; nt < NT; ++nt) bf[0][nt] = *reinterpret_cast<const f32x4*>(&ub[nt * 16]);
 #pragma unroll
       for (int f = 0; f < 16; ++f) {
         if (f + 1 < 16) {
 #pragma unroll
-          for (int nt = 0; nt < WN_NT; ++nt)
-            bf[(f + 1) & 1][nt] = *reinterpret_cast<const f32x4*>(&ub[(f + 1) * EGN_CKQ * WN_CO + nt * 16]);
+          for (int nt = 0; nt < NT; ++nt)
+            bf[(f + 1) & 1][nt] = *reinterpret_cast<const f32x4*>(&ub[(f + 1) * EGN_CKQ * CO_T + nt * 16]);
         }
         // the next frequency row's V: in source order here so that its adds land between the MFMAs
         if (f == 0) {
@@ -386,11 +195,10 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
-          for (int nt = 0; nt < WN_NT; ++nt)
+          for (int nt = 0; nt < NT; ++nt)
             acc[f][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(V[f][s], bf[f & 1][nt][s], acc[f][nt], 0, 0, 0);
-        if (3 + f < NPIECE) WINO_NEXT(3 + f)
+        if (3 + f < NPIECE) WINO_NEXT(3 + f, nxo)
       }
-#undef WINO_NEXT
 #undef WINO_LOADROW
 #undef WINO_VROW
       if (last) {
@@ -407,7 +215,7 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
 #pragma unroll
             for (int pb = 0; pb < 2; ++pb)
 #pragma unroll
-              for (int nt = 0; nt < WN_NT; ++nt)
+              for (int nt = 0; nt < NT; ++nt)
                 rv[r][pa][pb][nt] = egn_buf_load4(rr, ro, pa * rowpitch + pb * colpitch + nt * 64u);
         }
       }
@@ -416,7 +224,7 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
 
     // ---- output transform Y = A^T M A, epilogue, stores ----
 #pragma unroll
-    for (int nt = 0; nt < WN_NT; ++nt)
+    for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float tt[4][2];
@@ -442,10 +250,6 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
     tile = tile_n;
     ct = ct_n;
   }
-#undef WINO_ITEM
-#undef WINO_DOFF
-#undef WINO_PIECE
-#undef WINO_ISSUE
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -471,7 +275,8 @@ __global__ __launch_bounds__(WN_NTH, 1) void conv_wino_kernel(ConvArgs a) {
 template <int TH, int TW, int TNB, int ABL = 0, int NW = 8, int NT = 3>
 __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
   constexpr int CO_T = 16 * NT;                             // output channels per block
-  constexpr int USL = 16 * EGN_CKQ * CO_T;                  // float4 per (chunk, co-tile) slab of U
+  constexpr int KQ = EGN_CKQ, HS = 1;                       // whole-chunk stages
+  constexpr int USL = 16 * EGN_CKQ * CO_T, UCH = USL;       // float4 per (chunk, co-tile) slab of U
   using G = WinoGeom<TH, TW, TNB>;
   constexpr int NTH = 64 * NW;
   constexpr int MTILES = NW / 2;
@@ -479,6 +284,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
   constexpr int SLOTS = EGN_CKQ * G::PLANE;                 // multiple of 64: whole waves
   constexpr int IT = (SLOTS + NTH - 1) / NTH;               // halo DMA instructions (the last one partial)
   constexpr int BUF = SLOTS;
+  constexpr bool WHOLE_PIECES = false;
   constexpr int UIT = USL / NTH;                      // 6 (12 with 4 waves)
   constexpr int NPIECE = IT + UIT;                          // 10 (16)
   constexpr int TOPP = 2;                                   // DMA pieces issued at the top of a K step ...
@@ -489,18 +295,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
   float4* sU = smem;                  // [2][USL]
   float4* sH = smem + 2 * USL;  // [2][BUF]
   double* sS = reinterpret_cast<double*>(smem + 2 * USL + 2 * BUF);  // [NW][2][CO_T] BatchNorm partial sums
-  // ABL & 32 (tools/wino_clk.py only): s_memtime stamps of every wave's lane 0 -- kept in LDS, copied to the
-  // buffer passed as `res` at the end of the kernel (no residual then), so the vmcnt bookkeeping is untouched
-  unsigned long long* sT = reinterpret_cast<unsigned long long*>(sS + NW * 2 * CO_T);   // [NW][W8_NTK]
-  constexpr int W8_NTK = 48;
+  constexpr bool STAMPS = (ABL & 32) != 0;   // WINO_CLK (tools/wino_clk.py only), `res` = the stamp buffer
+  unsigned long long* sT = reinterpret_cast<unsigned long long*>(sS + NW * 2 * CO_T);   // [NW][WINO_NTK]
   int ntk = 0;
-#define W8_CLK()                                                                     \
-  {                                                                                  \
-    if constexpr ((ABL & 32) != 0) {                                                 \
-      if (lane == 0 && ntk < W8_NTK) sT[wave * W8_NTK + ntk] = __builtin_readcyclecounter(); \
-      ++ntk;                                                                         \
-    }                                                                                \
-  }
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -514,22 +311,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
   const int nct = Co / CO_T;
   const int nchunk = a.nchunk;
 
-  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C * 4);
-  const u32x4 ruv = egn_rsrc(a.w, (size_t)nct * nchunk * USL * 16);
-  const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
-  const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
-
-  int hmeta[IT];
-  unsigned hq[IT];
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int e = it * NTH + tid;
-    const int q = e / G::PLANE;
-    hmeta[it] = (e < SLOTS && q < EGN_CKQ) ? G::decode(e - q * G::PLANE) : -1;
-    hq[it] = (unsigned)q * 16u;
-  }
+  WINO_DESCRIPTORS((size_t)nct * nchunk * UCH * 16)
+  WINO_HALO_SLOTS()
+  WINO_FILTER_SLOTS()
   // patch rows fh, fh+1, fh+2 of this lane's tile: float4 index of column 0 in a halo buffer
   int prow[3];
 #pragma unroll
@@ -545,119 +329,51 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
   const int ntile = tiles_xy * ((a.N + TNB - 1) / TNB);
   const int nwork = ((ntile + 7) >> 3) * nct * 8;
 
-#define W8_ITEM(Wi, TILE_, CT_)              \
-  {                                          \
-    const int x_ = (Wi)&7, q_ = (Wi) >> 3;   \
-    TILE_ = (q_ / nct) * 8 + x_;             \
-    CT_ = q_ - (q_ / nct) * nct;             \
-  }
-#define W8_DOFF(TILE_, OUT)                                                                         \
-  {                                                                                                 \
-    const int tb_ = (TILE_) / tiles_xy;                                                             \
-    const int r_ = (TILE_)-tb_ * tiles_xy;                                                          \
-    const int ty_ = r_ / a.tiles_x, tx_ = r_ - ty_ * a.tiles_x;                                     \
-    const int n0_ = tb_ * TNB, iy0_ = ty_ * TH - 1, ix0_ = tx_ * TW - 1;                            \
-    _Pragma("unroll") for (int it = 0; it < IT; ++it) {                                             \
-      const int m_ = hmeta[it];                                                                     \
-      const int n_ = n0_ + (m_ >> 16), iy_ = iy0_ + ((m_ >> 8) & 255), ix_ = ix0_ + (m_ & 255);     \
-      const bool in_ = m_ >= 0 && (TILE_) < ntile && n_ < a.N && iy_ >= 0 && iy_ < a.H && ix_ >= 0 && ix_ < a.W; \
-      OUT[it] = in_ ? (unsigned)(((n_ * a.H + iy_) * a.W + ix_) * C) * 4u + hq[it] : EGN_OOB;       \
-    }                                                                                               \
-  }
-// DMA instruction K (0 .. NPIECE-1) of a K step; a wave beyond the end of the halo image skips its
-// share of the last halo piece (wave-uniform)
-#define W8_PIECE(K, P, OFF, CT, CH)                                                                  \
-  {                                                                                                  \
-    if ((K) < IT) {                                                                                  \
-      if ((K)*NTH + wave * 64 < SLOTS)                                                               \
-        egn_lds_dma16(rxv, egn_lds_addr(sH + (P)*BUF + wave * 64) + (K)*NTH * 16, OFF[(K) < IT ? (K) : 0], \
-                   (unsigned)(CH)*64u);                                                              \
-    } else {                                                                                         \
-      egn_lds_dma16(ruv, egn_lds_addr(sU + (P)*USL + wave * 64) + ((K)-IT) * NTH * 16, (unsigned)tid * 16u, \
-                 (unsigned)(((CT)*nchunk + (CH)) * USL) * 16u + ((K)-IT) * NTH * 16);          \
-    }                                                                                                \
-  }
-
   int w = blockIdx.x;
   int tile = 0, ct = 0;
-  W8_ITEM(w, tile, ct)
+  WINO_ITEM(w, tile, ct)
   const int ct_block = ct;            // constant over the block's items (the launcher sizes the grid for it)
-  if (a.stats != nullptr) {           // own-wave rows only: no barrier needed before the first use
-    for (int e = lane; e < 2 * CO_T; e += 64) sS[wave * 2 * CO_T + e] = 0.0;
-  }
+  WINO_STATS_ZERO()   // own-wave rows only: no barrier needed before the first use
   unsigned doff[IT];
-  W8_DOFF(tile, doff)
-  if (w < nwork) {
-#pragma unroll
-    for (int k_ = 0; k_ < NPIECE; ++k_) W8_PIECE(k_, 0, doff, ct, 0)
-  }
+  WINO_DOFF(tile, doff)
+  if (w < nwork) WINO_ISSUE(0, doff, ct, 0)
   int par = 0;
   bool first = true;
 
   const float act_lo = (a.act & EGN_ACT_MASK) == EGN_ACT_RELU ? 0.f : -__builtin_inff();
-  const bool has_res = (ABL & 32) ? false : a.res != nullptr;
-  const unsigned rowpitch = (unsigned)(a.Wo * Co) * 4u, colpitch = (unsigned)Co * 4u;
-  W8_CLK()   // 0: kernel start (prologue DMA issued)
+  const bool has_res = STAMPS ? false : a.res != nullptr;
+  const unsigned colpitch = (unsigned)Co * 4u;
+  WINO_CLK()   // 0: kernel start (prologue DMA issued)
 
   for (; w < nwork; w += gridDim.x) {
     int tile_n = 0, ct_n = 0;
-    W8_ITEM(w + (int)gridDim.x, tile_n, ct_n)
+    WINO_ITEM(w + (int)gridDim.x, tile_n, ct_n)
     const bool more = (w + (int)gridDim.x) < nwork;
     unsigned doff_n[IT];
-    W8_DOFF(tile_n, doff_n)
-    unsigned voff[4];   // this wave's output rows: a = fh of each of its 4 tiles
-    {
-      const int tb_ = tile / tiles_xy;
-      const int r_ = tile - tb_ * tiles_xy;
-      const int ty_ = r_ / a.tiles_x, tx_ = r_ - ty_ * a.tiles_x;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = tb_ * TNB + (og[r] >> 16);
-        const int oy = ty_ * TH + 2 * ((og[r] >> 8) & 255) + fh, ox = tx_ * TW + 2 * (og[r] & 255);
-        voff[r] = (tile < ntile && n < a.N && oy < a.Ho && ox < a.Wo)
-                      ? (unsigned)(((n * a.Ho + oy) * a.Wo + ox) * Co + ct * CO_T + li) * 4u
-                      : EGN_OOB;
-      }
-    }
-    float sc[NT], sh[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      sc[nt] = a.scale[ct * CO_T + nt * 16 + li];
-      sh[nt] = a.shift[ct * CO_T + nt * 16 + li];
-    }
-
-    f32x4 acc[8][NT];
-#pragma unroll
-    for (int f = 0; f < 8; ++f)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) acc[f][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    WINO_DOFF(tile_n, doff_n)
+    WINO_VOFF(fh)        // this wave's output rows: a = fh of each of its 4 tiles
+    WINO_SCALE_ACC(8)
     float rv[4][2][NT];  // residual of this lane's outputs: [tile r][b][nt]
     f32x4 Vkeep[8];         // (ABL & 16 only: the transform of chunk 0 re-used by every K step)
 
     for (int c = 0; c < nchunk; ++c) {
       const bool last = c + 1 == nchunk;
       asm volatile("" ::: "memory");
-      W8_CLK()   // step top
+      WINO_CLK()   // step top
       if constexpr (!(ABL & 8)) {
         if (c == 0 && !first) __builtin_amdgcn_s_waitcnt(0x4078);  // vmcnt(24): all but the last item's stores
         else __builtin_amdgcn_s_waitcnt(0x0070);                   // vmcnt(0)
-        if constexpr ((ABL & 32) != 0) { asm volatile("" ::: "memory"); W8_CLK() asm volatile("" ::: "memory"); }  // own DMA landed
+        if constexpr (STAMPS) { asm volatile("" ::: "memory"); WINO_CLK() asm volatile("" ::: "memory"); }  // own DMA landed
         __builtin_amdgcn_s_barrier();
       }
       asm volatile("" ::: "memory");
-      W8_CLK()   // past the barrier
+      WINO_CLK()   // past the barrier
       first = false;
       const bool nx_issue = !(ABL & 1) && (!last || more);
       const int nx_ct = last ? ct_n : ct, nx_ch = last ? 0 : c + 1;
       unsigned nxo[IT];
 #pragma unroll
       for (int it = 0; it < IT; ++it) nxo[it] = last ? doff_n[it] : doff[it];
-#define W8_NEXT(K)                                        \
-  {                                                       \
-    __builtin_amdgcn_sched_barrier(0x0106);               \
-    if (nx_issue) W8_PIECE(K, par ^ 1, nxo, nx_ct, nx_ch) \
-    __builtin_amdgcn_sched_barrier(0x0106);               \
-  }
       // ---- this wave's two rows of V = B^T d B ----
       const float4* hb = sH + par * BUF;
       f32x4 d[3][4], V[8];
@@ -669,7 +385,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
           else if ((ABL & 16) && c != 0) d[k][cc] = f32x4{0.f, 0.f, 0.f, 0.f};
           else d[k][cc] = *reinterpret_cast<const f32x4*>(&hb[prow[k] + cc]);
         }
-      W8_NEXT(0) W8_NEXT(1)
+      WINO_NEXT(0, nxo) WINO_NEXT(1, nxo)
       static_assert(TOPP == 2 && NPIECE <= TOPP + 8 * PERF, "every DMA piece has a slot");
       {
         f32x4 ta[4], tb[4];
@@ -719,26 +435,17 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
             acc[f][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(V[f][s], bf[f & 1][nt][s], acc[f][nt], 0, 0, 0);
 #pragma unroll
         for (int k_ = 0; k_ < PERF; ++k_)
-          if (TOPP + f * PERF + k_ < NPIECE) W8_NEXT(TOPP + f * PERF + k_)
+          if (TOPP + f * PERF + k_ < NPIECE) WINO_NEXT(TOPP + f * PERF + k_, nxo)
       }
-#undef W8_NEXT
       if (last) {
 #pragma unroll
         for (int it = 0; it < IT; ++it) doff[it] = doff_n[it];
-        asm volatile("" ::: "memory");  // program order DMA -> residual loads (the vmcnt(24) above counts on it)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const unsigned ro = (has_res && !(ABL & 4)) ? voff[r] : EGN_OOB;
-#pragma unroll
-          for (int pb = 0; pb < 2; ++pb)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) rv[r][pb][nt] = egn_buf_load4(rr, ro, pb * colpitch + nt * 64u);
-        }
+        WINO_RES_LOAD(has_res && !(ABL & 4))
       }
       par ^= 1;
     }
 
-    W8_CLK()   // K loop done
+    WINO_CLK()   // K loop done
     // ---- output transform: this wave's frequency rows, then the exchange with the partner wave ----
     float keep[NT][4][2], send[NT][4][2];
 #pragma unroll
@@ -759,39 +466,8 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
           keep[nt][r][pb] = fh == 0 ? t0 + t1 : -t0 - t1;
           send[nt][r][pb] = fh == 0 ? t1 : t0;
         }
-    {
-      // the U buffer of the last K step (par ^ 1 after the toggle) is free once every wave is past its
-      // MFMAs: barrier, write, barrier, read the partner's
-      float4* xch = sU + (par ^ 1) * USL;
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0) only
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int k4 = 0; k4 < 2 * NT; ++k4) {
-        f32x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int idx = k4 * 4 + e;  // (nt*4 + r)*2 + pb
-          v[e] = send[idx >> 3][(idx >> 1) & 3][idx & 1];
-        }
-        *reinterpret_cast<f32x4*>(&xch[(wave * 2 * NT + k4) * 64 + lane]) = v;
-      }
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int k4 = 0; k4 < 2 * NT; ++k4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(&xch[((wave ^ MTILES) * 2 * NT + k4) * 64 + lane]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int idx = k4 * 4 + e;
-          keep[idx >> 3][(idx >> 1) & 3][idx & 1] += v[e];
-        }
-      }
-    }
-    W8_CLK()   // exchange done
+    WINO_EXCHANGE(keep_ + recv_)
+    WINO_CLK()   // exchange done
     float st1[NT], st2[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) st1[nt] = st2[nt] = 0.f;
@@ -806,57 +482,13 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
           egn_buf_store4(ry, ((ABL & 4) && v != 12345.678f) ? EGN_OOB : voff[r], pb * colpitch + nt * 64u, v);
           if (voff[r] != EGN_OOB) { st1[nt] += v; st2[nt] += v * v; }
         }
-    if (a.stats != nullptr) {
-      // BatchNorm batch statistics ride in the epilogue (training: raw conv output, scale 1 / shift 0):
-      // this wave's column sums over its 16 tiles x 2 pixels -- lanes li + 16*kq hold the same channel --
-      // are added to the wave's own row of a small LDS table (doubles); the block writes ONE partial
-      // row at the end of the kernel (its co-tile is the same for all its items, see wino8_grid)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        st1[nt] += __shfl_xor(st1[nt], 16);
-        st1[nt] += __shfl_xor(st1[nt], 32);
-        st2[nt] += __shfl_xor(st2[nt], 16);
-        st2[nt] += __shfl_xor(st2[nt], 32);
-      }
-      if (kq == 0) {
-        double* srow = sS + wave * 2 * CO_T + li;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-          srow[nt * 16] += (double)st1[nt];
-          srow[CO_T + nt * 16] += (double)st2[nt];
-        }
-      }
-    }
-    W8_CLK()   // stores issued
+    WINO_STATS_ADD()   // BatchNorm statistics ride in the epilogue
+    WINO_CLK()   // stores issued
     tile = tile_n;
     ct = ct_n;
   }
-  if constexpr ((ABL & 32) != 0) {
-    __syncthreads();
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res)) +
-                              (size_t)blockIdx.x * (NW * W8_NTK + 1);
-    for (int e = tid; e < NW * W8_NTK; e += NTH) out[1 + e] = sT[e];
-    if (tid == 0) out[0] = (unsigned long long)ntk;
-  }
-  if (a.stats != nullptr) {
-    // one partial row per block: [2][Cout] doubles, the block's 48 columns = its waves' sums in wave
-    // order, zeros elsewhere (egn_bn_stats_finalize_f32 adds the rows of all blocks in a fixed order)
-    __syncthreads();
-    double* row = a.stats + (size_t)blockIdx.x * 2 * Co;
-    for (int e = tid; e < 2 * Co; e += NTH) {
-      const int which = e / Co, c = e - which * Co;
-      const int cl = c - ct_block * CO_T;
-      double v = 0.0;
-      if (cl >= 0 && cl < CO_T) {
-        for (int k = 0; k < NW; ++k) v += sS[(k * 2 + which) * CO_T + cl];
-      }
-      row[e] = v;
-    }
-  }
-#undef W8_ITEM
-#undef W8_DOFF
-#undef W8_PIECE
-#undef W8_CLK
+  if constexpr (STAMPS) wino_stamp_dump<NW>(a, sT, ntk, tid);
+  WINO_STATS_ROW()
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -878,20 +510,13 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino8_kernel(ConvArgs a) {
 //     order (row 3, row 2), the patch rows each role reads are per-wave LDS offsets, the one sign that
 //     differs is a wave-uniform multiplier in a v_fma -- no branches, no register shuffles (the branchy
 //     form cost 29 v_mov per K step), `keep = t0 + t1`, `send = t1` for both;
-//   * transforms as single v_add / v_sub / v_fma through asm wrappers: the compiler's SLP pass packed them
-//     into v_pk_add_f32, which costs more than two plain adds beside MFMAs (MI355X_MICROARCH.md);
+//   * transforms in plain arithmetic, each V row formed right before its first use (asm wrappers that forced
+//     single v_add / v_sub / v_fma pinned all 64 instructions in front of the first MFMA and were dropped: the
+//     few v_pk_*_f32 the SLP pass forms measured no difference, see the body);
 //   * the next stage's DMA pieces all go out in the first quarter of a K step (they cost nothing to issue;
 //     spread over the step the last ones had no time to land before the barrier).
 // Same LDS layout, same filter packing (the U rows of wave fh = 1 are read in swapped order), same
 // exchange, same BatchNorm statistics, same results bit for bit as conv_wino8_kernel.
-__device__ __forceinline__ float wn_add(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float wn_sub(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float wn_fma(float a, float b, float c) { float r; asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ float wn_fma_s(float s, float b, float c) { float r; asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "s"(s), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ float wn_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ f32x4 wn_sub4(f32x4 a, f32x4 b) { return f32x4{wn_sub(a[0], b[0]), wn_sub(a[1], b[1]), wn_sub(a[2], b[2]), wn_sub(a[3], b[3])}; }
-__device__ __forceinline__ f32x4 wn_add4(f32x4 a, f32x4 b) { return f32x4{wn_add(a[0], b[0]), wn_add(a[1], b[1]), wn_add(a[2], b[2]), wn_add(a[3], b[3])}; }
-__device__ __forceinline__ f32x4 wn_fma4_s(float s, f32x4 b, f32x4 c) { return f32x4{wn_fma_s(s, b[0], c[0]), wn_fma_s(s, b[1], c[1]), wn_fma_s(s, b[2], c[2]), wn_fma_s(s, b[3], c[3])}; }
 
 // KQ = channel quads per K stage: 4 (a whole 16-channel chunk of the packed filter, one 140 KB block per CU) or
 // 2 (half a chunk: 8-channel stages, 68 KB of LDS -- TWO 4-wave blocks per CU, one wave of each on every SIMD.
@@ -918,6 +543,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
   constexpr int SLOTS = KQ * G::PLANE;
   constexpr int IT = (SLOTS + NTH - 1) / NTH;
   constexpr int BUF = SLOTS;
+  constexpr bool WHOLE_PIECES = false;
   constexpr int UIT = USL / NTH;
   constexpr int NPIECE = IT + UIT;
   static_assert(SLOTS % 64 == 0 && USL % NTH == 0, "whole-wave DMA pieces");
@@ -926,17 +552,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
   float4* sU = smem;
   float4* sH = smem + 2 * USL;
   double* sS = reinterpret_cast<double*>(smem + 2 * USL + 2 * BUF);
-  // CLK (tools/wino_clk.py only): s_memtime stamps like conv_wino8_kernel's ABL & 32 build, `res` = the stamp buffer
+  constexpr bool STAMPS = CLK != 0;   // WINO_CLK (tools/wino_clk.py only), `res` = the stamp buffer
   unsigned long long* sT = reinterpret_cast<unsigned long long*>(sS + NW * 2 * CO_T);
-  constexpr int W9_NTK = 48;
   int ntk = 0;
-#define W9_CLK()                                                                     \
-  {                                                                                  \
-    if constexpr (CLK != 0) {                                                        \
-      if (lane == 0 && ntk < W9_NTK) sT[wave * W9_NTK + ntk] = __builtin_readcyclecounter(); \
-      ++ntk;                                                                         \
-    }                                                                                \
-  }
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -952,12 +570,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
   const int nct = Co / CO_T;
   const int nchunk = a.nchunk;
 
-  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C * 4);
-  const u32x4 ruv = egn_rsrc(a.w, (size_t)nct * nchunk * UCH * 16);
-  const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
-  const __amdgpu_buffer_rsrc_t rr =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
+  WINO_DESCRIPTORS((size_t)nct * nchunk * UCH * 16)
 
   // ---- per-lane, item-independent: halo slot -> (image, hy, hx) and its byte offset relative to the tile's
   // origin pixel (n0, iy0, ix0); the tile origin is a wave-uniform base added per item
@@ -1005,81 +618,23 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
   const int nwork = ((ntile + 7) >> 3) * nct * 8;
   const int gsz = __builtin_amdgcn_readfirstlane((int)gridDim.x);
 
-  // wave-uniform item decode (scalar unit): w -> (tile, ct) -> (tb, ty, tx)
-#define W9_ITEM(Wi, TILE_, CT_, TB_, TY_, TX_)                                   \
-  {                                                                              \
-    const unsigned wi_ = (unsigned)__builtin_amdgcn_readfirstlane((int)(Wi));    \
-    const unsigned x_ = wi_ & 7u, q_ = wi_ >> 3;                                 \
-    const unsigned qq_ = egn_udiv_magic(q_, a.mg_nct);                           \
-    TILE_ = (int)(qq_ * 8u + x_);                                                \
-    CT_ = (int)(q_ - qq_ * (unsigned)nct);                                       \
-    const unsigned tb_ = egn_udiv_magic((unsigned)TILE_, a.mg_txy);              \
-    const unsigned r_ = (unsigned)TILE_ - tb_ * (unsigned)tiles_xy;              \
-    const unsigned ty_ = egn_udiv_magic(r_, a.mg_tx);                            \
-    TB_ = (int)tb_; TY_ = (int)ty_; TX_ = (int)(r_ - ty_ * (unsigned)a.tiles_x); \
-  }
-  // halo DMA byte offsets (chunk 0) of a tile: uniform base + per-lane relative offset; pad slots and
-  // out-of-image pixels get the OOB offset (the DMA writes zeros there = the convolution's zero padding)
-#define W9_DOFF(TILE_, TB_, TY_, TX_, OUT)                                                                   \
-  {                                                                                                          \
-    const int n0_ = (TB_)*TNB, iy0_ = (TY_)*TH - 1, ix0_ = (TX_)*TW - 1;                                     \
-    const int base_ = ((n0_ * a.H + iy0_) * a.W + ix0_) * C * 4;                                             \
-    const bool tok_ = (TILE_) < ntile;                                                                       \
-    _Pragma("unroll") for (int it = 0; it < IT; ++it) {                                                      \
-      const unsigned iy_ = (unsigned)(iy0_ + (hyx[it] >> 16)), ix_ = (unsigned)(ix0_ + (hyx[it] & 0xffff));  \
-      bool in_ = tok_ && hyx[it] >= 0 && iy_ < (unsigned)a.H && ix_ < (unsigned)a.W;                         \
-      if (TNB > 1) in_ = in_ && (n0_ + hb[it]) < a.N;                                                        \
-      OUT[it] = in_ ? (unsigned)(base_ + hrel[it]) : EGN_OOB;                                                \
-    }                                                                                                        \
-  }
-  // CH = stage index: chunk CH / HS, quads (CH % HS) * KQ ... of it
-#define W9_PIECE(K, P, OFF, CT, CH)                                                                  \
-  {                                                                                                  \
-    if ((K) < IT) {                                                                                  \
-      if ((K)*NTH + wave * 64 < SLOTS)                                                               \
-        egn_lds_dma16(rxv, egn_lds_addr(sH + (P)*BUF + wave * 64) + (K)*NTH * 16, OFF[(K) < IT ? (K) : 0], \
-                   (unsigned)(CH) * (KQ * 16u));                                                     \
-    } else if constexpr (KQ == EGN_CKQ) {                                                            \
-      egn_lds_dma16(ruv, egn_lds_addr(sU + (P)*USL + wave * 64) + ((K)-IT) * NTH * 16, (unsigned)tid * 16u, \
-                 (unsigned)(((CT)*nchunk + (CH)) * USL) * 16u + ((K)-IT) * NTH * 16);                \
-    } else {                                                                                         \
-      const unsigned ch_ = (unsigned)(CH) / HS, hs_ = (unsigned)(CH) - ch_ * HS;                     \
-      egn_lds_dma16(ruv, egn_lds_addr(sU + (P)*USL + wave * 64) + ((K)-IT) * NTH * 16, urel[(K) >= IT ? (K)-IT : 0], \
-                 (((unsigned)(CT)*nchunk + ch_) * UCH + hs_ * (KQ * CO_T)) * 16u);                   \
-    }                                                                                                \
-  }
-  // filter stage slot e = piece * NTH + tid -> frequency e / (KQ * CO_T): its KQ * CO_T slots sit EGN_CKQ * CO_T apart
-  // in the packed chunk
-  unsigned urel[KQ == EGN_CKQ ? 1 : UIT];
-  if constexpr (KQ != EGN_CKQ) {
-#pragma unroll
-    for (int k_ = 0; k_ < UIT; ++k_) {
-      const int e = k_ * NTH + tid, f_ = e / (KQ * CO_T);
-      urel[k_] = (unsigned)(f_ * (EGN_CKQ * CO_T) + (e - f_ * (KQ * CO_T))) * 16u;
-    }
-  }
+  WINO_FILTER_SLOTS()   // the DMA pieces (WINO_PIECE) take a STAGE index: chunk CH / HS, quads (CH % HS) * KQ ... of it
 
   int w = blockIdx.x;
   int tile = 0, ct = 0, tb = 0, ty = 0, tx = 0;
   W9_ITEM(w, tile, ct, tb, ty, tx)
   const int ct_block = ct;
-  if (a.stats != nullptr) {
-    for (int e = lane; e < 2 * CO_T; e += 64) sS[wave * 2 * CO_T + e] = 0.0;
-  }
+  WINO_STATS_ZERO()   // own-wave rows only: no barrier needed before the first use
   unsigned doff[IT];
   W9_DOFF(tile, tb, ty, tx, doff)
-  if (w < nwork) {
-#pragma unroll
-    for (int k_ = 0; k_ < NPIECE; ++k_) W9_PIECE(k_, 0, doff, ct, 0)
-  }
+  if (w < nwork) WINO_ISSUE(0, doff, ct, 0)
   int par = 0;
   bool first = true;
 
   const float act_lo = (a.act & EGN_ACT_MASK) == EGN_ACT_RELU ? 0.f : -__builtin_inff();
-  const bool has_res = CLK ? false : a.res != nullptr;
-  const unsigned rowpitch = (unsigned)(a.Wo * Co) * 4u, colpitch = (unsigned)Co * 4u;
-  (void)rowpitch;
-  W9_CLK()
+  const bool has_res = STAMPS ? false : a.res != nullptr;
+  const unsigned colpitch = (unsigned)Co * 4u;
+  WINO_CLK()
 
   for (; w < nwork; w += gsz) {
     int tile_n = 0, ct_n = 0, tb_n = 0, ty_n = 0, tx_n = 0;
@@ -1100,31 +655,20 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
         voff[r] = in_ ? (unsigned)(base_ + orel[r]) : EGN_OOB;
       }
     }
-    float sc[NT], sh[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      sc[nt] = a.scale[ct * CO_T + nt * 16 + li];
-      sh[nt] = a.shift[ct * CO_T + nt * 16 + li];
-    }
-
-    f32x4 acc[8][NT];
-#pragma unroll
-    for (int f = 0; f < 8; ++f)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) acc[f][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    WINO_SCALE_ACC(8)
     float rv[4][2][NT];
 
     const int nstage = nchunk * HS;
     for (int c = 0; c < nstage; ++c) {
       const bool last = c + 1 == nstage;
       asm volatile("" ::: "memory");
-      W9_CLK()
+      WINO_CLK()
       if (c == 0 && !first) __builtin_amdgcn_s_waitcnt(0x4078);  // vmcnt(24): all but the last item's stores
       else __builtin_amdgcn_s_waitcnt(0x0070);                   // vmcnt(0)
-      if constexpr (CLK != 0) { asm volatile("" ::: "memory"); W9_CLK() asm volatile("" ::: "memory"); }
+      if constexpr (STAMPS) { asm volatile("" ::: "memory"); WINO_CLK() asm volatile("" ::: "memory"); }
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      W9_CLK()
+      WINO_CLK()
       first = false;
       const bool nx_issue = !last || more;
       const int nx_ct = last ? ct_n : ct, nx_ch = last ? 0 : c + 1;
@@ -1132,12 +676,6 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
 #pragma unroll
         for (int it = 0; it < IT; ++it) doff[it] = doff_n[it];
       }
-#define W9_NEXT(K)                                         \
-  {                                                        \
-    __builtin_amdgcn_sched_barrier(0x0106);                \
-    if (nx_issue) W9_PIECE(K, par ^ 1, doff, nx_ct, nx_ch) \
-    __builtin_amdgcn_sched_barrier(0x0106);                \
-  }
       // ---- this wave's two rows of V = B^T d B: ta = X - Y, tb = Z + sigma W, then the column transform.
       // Plain arithmetic: the scheduler sinks each V row to its first use, so the MFMAs of row 0 start while row
       // 1 is still being formed -- asm wrappers pinned all 64 instructions in front of the first MFMA.  (The SLP
@@ -1155,7 +693,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
           dx[cc] = *reinterpret_cast<const vk_t*>(reinterpret_cast<const float*>(&hb_[prow[0] + cc]) + kqc);
           dy[cc] = *reinterpret_cast<const vk_t*>(reinterpret_cast<const float*>(&hb_[prow[1] + cc]) + kqc);
         }
-        W9_NEXT(0) W9_NEXT(1)
+        WINO_NEXT(0, doff) WINO_NEXT(1, doff)
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) ta[cc] = dx[cc] - dy[cc];
         V[0] = ta[0] - ta[2]; V[1] = ta[1] + ta[2]; V[2] = ta[2] - ta[1]; V[3] = ta[1] - ta[3];
@@ -1195,24 +733,13 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
             acc[f][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(V[f][s], bf[f & 1][nt][s], acc[f][nt], 0, 0, 0);
 #pragma unroll
         for (int k_ = 0; k_ < PERF; ++k_)
-          if (TOPP + f * PERF + k_ < NPIECE) W9_NEXT(TOPP + f * PERF + k_)
+          if (TOPP + f * PERF + k_ < NPIECE) WINO_NEXT(TOPP + f * PERF + k_, doff)
       }
-#undef W9_NEXT
-      if (last) {
-        asm volatile("" ::: "memory");  // program order DMA -> residual loads (the vmcnt(24) above counts on it)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const unsigned ro = has_res ? voff[r] : EGN_OOB;
-#pragma unroll
-          for (int pb = 0; pb < 2; ++pb)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) rv[r][pb][nt] = egn_buf_load4(rr, ro, pb * colpitch + nt * 64u);
-        }
-      }
+      if (last) WINO_RES_LOAD(has_res)
       par ^= 1;
     }
 
-    W9_CLK()
+    WINO_CLK()
     // ---- output transform: t of the wave's first / second frequency row; keep = t0 + t1, send = t1 ----
     float keep[NT][4][2], send[NT][4][2];
 #pragma unroll
@@ -1228,38 +755,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
         send[nt][r][0] = t10;
         send[nt][r][1] = t11;
       }
-    {
-      float4* xch = sU + (par ^ 1) * USL;
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int k4 = 0; k4 < 2 * NT; ++k4) {
-        f32x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int idx = k4 * 4 + e;
-          v[e] = send[idx >> 3][(idx >> 1) & 3][idx & 1];
-        }
-        *reinterpret_cast<f32x4*>(&xch[(wave * 2 * NT + k4) * 64 + lane]) = v;
-      }
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      // fh = 0: Y0 = (t0 + t1) + t2 = keep + recv;  fh = 1: Y1 = t1 - (t2 + t3) = recv - keep = sigma * keep + recv
-#pragma unroll
-      for (int k4 = 0; k4 < 2 * NT; ++k4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(&xch[((wave ^ MTILES) * 2 * NT + k4) * 64 + lane]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int idx = k4 * 4 + e;
-          keep[idx >> 3][(idx >> 1) & 3][idx & 1] = sigma * keep[idx >> 3][(idx >> 1) & 3][idx & 1] + v[e];
-        }
-      }
-    }
-    W9_CLK()
+    // fh = 0: Y0 = (t0 + t1) + t2 = keep + recv;  fh = 1: Y1 = t1 - (t2 + t3) = recv - keep = sigma * keep + recv
+    WINO_EXCHANGE(sigma * keep_ + recv_)
+    WINO_CLK()
     float st1[NT], st2[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) st1[nt] = st2[nt] = 0.f;
@@ -1273,63 +771,31 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_wino9_kernel(ConvArgs a) {
           egn_buf_store4(ry, voff[r], pb * colpitch + nt * 64u, v);
           if (a.stats != nullptr && voff[r] != EGN_OOB) { st1[nt] += v; st2[nt] += v * v; }
         }
-    if (a.stats != nullptr) {
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        st1[nt] += __shfl_xor(st1[nt], 16);
-        st1[nt] += __shfl_xor(st1[nt], 32);
-        st2[nt] += __shfl_xor(st2[nt], 16);
-        st2[nt] += __shfl_xor(st2[nt], 32);
-      }
-      if (kq == 0) {
-        double* srow = sS + wave * 2 * CO_T + li;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-          srow[nt * 16] += (double)st1[nt];
-          srow[CO_T + nt * 16] += (double)st2[nt];
-        }
-      }
-    }
-    W9_CLK()
+    WINO_STATS_ADD()   // BatchNorm statistics ride in the epilogue
+    WINO_CLK()
     tile = tile_n; ct = ct_n; tb = tb_n; ty = ty_n; tx = tx_n;
   }
-  if constexpr (CLK != 0) {
-    __syncthreads();
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res)) +
-                              (size_t)blockIdx.x * (NW * W9_NTK + 1);
-    for (int e = tid; e < NW * W9_NTK; e += NTH) out[1 + e] = sT[e];
-    if (tid == 0) out[0] = (unsigned long long)ntk;
-  }
-  if (a.stats != nullptr) {
-    __syncthreads();
-    double* row = a.stats + (size_t)blockIdx.x * 2 * Co;
-    for (int e = tid; e < 2 * Co; e += NTH) {
-      const int which = e / Co, c = e - which * Co;
-      const int cl = c - ct_block * CO_T;
-      double v = 0.0;
-      if (cl >= 0 && cl < CO_T) {
-        for (int k = 0; k < NW; ++k) v += sS[(k * 2 + which) * CO_T + cl];
-      }
-      row[e] = v;
-    }
-  }
-#undef W9_ITEM
-#undef W9_DOFF
-#undef W9_PIECE
-#undef W9_CLK
+  if constexpr (STAMPS) wino_stamp_dump<NW>(a, sT, ntk, tid);
+  WINO_STATS_ROW()
+}
+
+// every kernel of this file takes more than 64 KB of dynamic LDS: raise KERN's limit once per device, then launch it
+template <void (*KERN)(ConvArgs)>
+static int wino_launch_kernel(const ConvArgs& a, int grid, int threads, size_t lds, hipStream_t stream) {
+  static bool raised[EGN_MAX_DEVICES];  // per kernel and device
+  EGN_CHECK_HIP(egn_allow_big_lds(KERN, EGN_BIG_LDS_BYTES, raised));
+  hipLaunchKernelGGL(KERN, dim3(grid), dim3(threads), lds, stream, a);
+  return (int)hipGetLastError();
 }
 
 template <int TH, int TW, int TNB, int ABL = 0>
 static int wino_launch(const ConvArgs& a, size_t lds, hipStream_t stream) {
-  static bool raised[EGN_MAX_DEVICES];
-  EGN_CHECK_HIP(egn_allow_big_lds(&conv_wino_kernel<TH, TW, TNB, ABL>, EGN_BIG_LDS_BYTES, raised));
   int cus = egn_device_cus() & ~7;  // whole XCD rounds
   if (cus <= 0) cus = 8;
   const int ntile = a.tiles_x * a.tiles_y * ((a.N + TNB - 1) / TNB);
   const int nwork = ((ntile + 7) / 8) * 8 * (a.Cout / WN_CO);
   const int grid = nwork < cus ? nwork : cus;
-  hipLaunchKernelGGL((conv_wino_kernel<TH, TW, TNB, ABL>), dim3(grid), dim3(WN_NTH), lds, stream, a);
-  return (int)hipGetLastError();
+  return wino_launch_kernel<conv_wino_kernel<TH, TW, TNB, ABL>>(a, grid, WN_NTH, lds, stream);
 }
 
 // persistent grid of the frequency-halves kernel: at most one block per CU, a multiple of 8 * nct so that
@@ -1345,11 +811,7 @@ static int wino8_grid(const ConvArgs& a, int tnb, int blocks_per_cu = 1) {
 
 template <int TH, int TW, int TNB, int ABL, int NW, int NT>
 static int wino8_launch_nt(const ConvArgs& a, size_t lds, hipStream_t stream) {
-  static bool raised[EGN_MAX_DEVICES];
-  EGN_CHECK_HIP(egn_allow_big_lds(&conv_wino8_kernel<TH, TW, TNB, ABL, NW, NT>, EGN_BIG_LDS_BYTES, raised));
-  const int grid = wino8_grid(a, TNB);
-  hipLaunchKernelGGL((conv_wino8_kernel<TH, TW, TNB, ABL, NW, NT>), dim3(grid), dim3(64 * NW), lds, stream, a);
-  return (int)hipGetLastError();
+  return wino_launch_kernel<conv_wino8_kernel<TH, TW, TNB, ABL, NW, NT>>(a, wino8_grid(a, TNB), 64 * NW, lds, stream);
 }
 template <int TH, int TW, int TNB, int ABL = 0, int NW = 8>
 static int wino8_launch(const ConvArgs& a, size_t lds, hipStream_t stream) {
@@ -1423,11 +885,7 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
   const int C = a.Cin, Co = a.Cout;
   const int nct = Co / 48;
   const int nsteps = C / 4;
-  const u32x4 rxv = egn_rsrc(a.x, (size_t)a.N * a.H * a.W * C * 4);
-  const u32x4 ruv = egn_rsrc(a.w, (size_t)nct * nsteps * W43_UF * 4);
-  const unsigned out_bytes = (unsigned)((size_t)a.N * a.Ho * a.Wo * Co * 4);
-  const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, out_bytes, EGN_RSRC_WORD3);
-  const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, out_bytes, EGN_RSRC_WORD3);
+  WINO_DESCRIPTORS((size_t)nct * nsteps * W43_UF * 4)
 
   // ---- halo pieces of this wave: k = 0 -> p = wave (all 12 are halo pieces), k = 1 -> p = 12 + wave (waves 0, 1) ----
   int hyx[2], hrel[2], hmt[2];
@@ -1469,16 +927,10 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
   const int nwork = ((npair + 7) >> 3) * nct * 8;
   const int gsz = __builtin_amdgcn_readfirstlane((int)gridDim.x);
 
+  constexpr bool STAMPS = CLK != 0;   // WINO_CLK (tools/wino_clk.py only), `res` = the stamp buffer
   unsigned long long* sT = nullptr;
   int ntk = 0;
-  if constexpr (CLK != 0) sT = reinterpret_cast<unsigned long long*>(sm + W43_RING * W43_STAGE);
-#define W43_CLK()                                                                        \
-  {                                                                                      \
-    if constexpr (CLK != 0) {                                                            \
-      if (lane == 0 && ntk < 48) sT[wave * 48 + ntk] = __builtin_readcyclecounter();     \
-      ++ntk;                                                                             \
-    }                                                                                    \
-  }
+  if constexpr (STAMPS) sT = reinterpret_cast<unsigned long long*>(sm + W43_RING * W43_STAGE);
 
 // work index -> (tile pair, co-tile); TILE (0 / 1) = 2 * pair + m-tile -> (n, ty, tx), all on the scalar unit
 #define W43_ITEM(Wi, PAIR_, CT_)                                                 \
@@ -1539,7 +991,7 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
   const unsigned colpitch = (unsigned)Co * 4u;
   const bool fin = fr < 4;                       // waves with fr = 0..3 finish output row a = fr of every tile of their m-tile
   const bool pw4 = wave < W43_NP - (W43_KP - 1) * W43_NW;   // this wave has a piece in the last slot (4 pieces per stage, else 3)
-  W43_CLK()
+  WINO_CLK()
 
   for (; w < nwork; w += gsz) {
     int pair_n = 0, ct_n = 0;
@@ -1570,7 +1022,7 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
 
     for (int c = 0; c < nsteps; ++c) {
       asm volatile("" ::: "memory");
-      W43_CLK()
+      WINO_CLK()
       // The stage of this K step has landed in this wave's share.  In flight behind it (issue order): the next
       // K step's pieces (3 or 4 of this wave) -- except at the last step of an item, whose successor was not
       // issued yet -- and, at the first step after an epilogue, the 48 stores of a finishing wave.
@@ -1589,7 +1041,7 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
       }
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      W43_CLK()
+      WINO_CLK()
       // ---- issue: K step c + 2 of this item into the stage step c - 1 consumed; the item's first step also issues
       // its step 1 (deferred: at the end of the previous item only stage 0 of this one was prefetched, the other
       // two stages served the exchange); the item's LAST-BUT-ONE step prefetches the next item's step 0 ----
@@ -1640,7 +1092,7 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
 #undef W43_NEXT
       if (++rs == W43_RING) rs = 0;
     }
-    W43_CLK()
+    WINO_CLK()
 
     // ---- output transform, first half: t_i[b] = sum_j M[i][j] A[j][b]  (vectors over the 4 tile columns r) ----
     f32x4 tb[3][4];
@@ -1707,30 +1159,22 @@ __global__ __launch_bounds__(W43_NTH, 3) void conv_wino43_kernel(ConvArgs a) {
         }
       }
     }
-    W43_CLK()
+    WINO_CLK()
     pair = pair_n; ct = ct_n;
     doff[0] = doff_n[0]; doff[1] = doff_n[1];
   }
-  if constexpr (CLK != 0) {
-    __syncthreads();
-    unsigned long long* out = reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res)) + (size_t)blockIdx.x * (W43_NW * 48 + 1);
-    for (int e = tid; e < W43_NW * 48; e += W43_NTH) out[1 + e] = sT[e];
-    if (tid == 0) out[0] = (unsigned long long)ntk;
-  }
+  if constexpr (STAMPS) wino_stamp_dump<W43_NW>(a, sT, ntk, tid);
 #undef W43_ITEM
 #undef W43_TILE
 #undef W43_DOFF
 #undef W43_PIECE
 #undef W43_ISSUE
-#undef W43_CLK
 }
 
-size_t egn_conv_wino43_lds_bytes(int clk) { return (size_t)W43_RING * W43_STAGE * 4 + (clk ? W43_NW * 48 * 8 : 0); }
+size_t egn_conv_wino43_lds_bytes(int clk) { return (size_t)W43_RING * W43_STAGE * 4 + (clk ? W43_NW * WINO_NTK * 8 : 0); }
 
 template <int TH, int TW, int TNB, int NW, int NT, int CLK = 0, int KQ = EGN_CKQ>
 static int wino9_launch_nt(ConvArgs a, size_t lds, hipStream_t stream) {
-  static bool raised[EGN_MAX_DEVICES];
-  EGN_CHECK_HIP(egn_allow_big_lds(&conv_wino9_kernel<TH, TW, TNB, NW, NT, CLK, KQ>, EGN_BIG_LDS_BYTES, raised));
   // the kernel divides its item / tile indices by nct, tiles_x * tiles_y and tiles_x with ONE multiply-high by
   // ceil(2^32 / d): exact while dividend * d < 2^32.  Dividends stay below (tiles + 8) * nct; shapes beyond that bound
   // (far outside the 2 GB tensor guards for any HRNet map, but a legal call) are refused, not mis-decoded
@@ -1744,8 +1188,7 @@ static int wino9_launch_nt(ConvArgs a, size_t lds, hipStream_t stream) {
   a.mg_txy = egn_magic_u32(a.tiles_x * a.tiles_y);
   a.mg_tx = egn_magic_u32(a.tiles_x);
   const int grid = wino8_grid(a, TNB, KQ == EGN_CKQ ? 1 : 2);     // half-chunk stages: two blocks per CU
-  hipLaunchKernelGGL((conv_wino9_kernel<TH, TW, TNB, NW, NT, CLK, KQ>), dim3(grid), dim3(64 * NW), lds, stream, a);
-  return (int)hipGetLastError();
+  return wino_launch_kernel<conv_wino9_kernel<TH, TW, TNB, NW, NT, CLK, KQ>>(a, grid, 64 * NW, lds, stream);
 }
 template <int TH, int TW, int TNB, int NW = 8, int KQ = EGN_CKQ>
 static int wino9_launch(const ConvArgs& a, size_t lds, hipStream_t stream) {
@@ -1756,8 +1199,6 @@ static int wino9_launch(const ConvArgs& a, size_t lds, hipStream_t stream) {
 
 template <int CLK>
 static int wino43_launch(ConvArgs a, size_t lds, hipStream_t stream) {
-  static bool raised[EGN_MAX_DEVICES];
-  EGN_CHECK_HIP(egn_allow_big_lds(&conv_wino43_kernel<CLK>, EGN_BIG_LDS_BYTES, raised));
   const int nct = a.Cout / 48;
   a.mg_nct = egn_magic_u32(nct);
   a.mg_txy = egn_magic_u32(a.tiles_x * a.tiles_y);
@@ -1766,71 +1207,116 @@ static int wino43_launch(ConvArgs a, size_t lds, hipStream_t stream) {
   const int npair = (ntile + 1) / 2;
   const int nwork = ((npair + 7) / 8) * 8 * nct;
   const int grid = egn_persistent_grid(nwork, 8 * nct);   // one 126 KB block per CU, whole XCD rounds
-  hipLaunchKernelGGL((conv_wino43_kernel<CLK>), dim3(grid), dim3(W43_NTH), lds, stream, a);
-  return (int)hipGetLastError();
+  return wino_launch_kernel<conv_wino43_kernel<CLK>>(a, grid, W43_NTH, lds, stream);
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// The kernels of this file, ONE row per WinoKernel (egn_internal.h): block tile TH x TW x TNB, waves, channel quads per
+// K stage, kernel family, build.  What the planner asks about a kernel (LDS bytes, BatchNorm statistics rows, the
+// shapes it takes) is read from its row; the launcher's switch is generated from the rows.  ProbeOnly = the families
+// measured and retired -- the 4-wave kernel (cfg 45 / 46), the first F(4x4,3x3) kernel (65), two 4-wave blocks per CU
+// (67 / 68): compiled and launched in -DEGN_PROBES builds only.  (Rows in the order of the launch switch this list
+// replaced: the compiler emits the kernels in that order.)
+enum WinoFamily { FamWino, FamWino8, FamWino9, FamWino43 };   // conv_wino_kernel, conv_wino8_kernel, conv_wino9_kernel, conv_wino43_kernel
+constexpr bool Product = false, ProbeOnly = true;
+//  kernel        TH  TW TNB waves KQ family     build
+#define WINO_KERNELS(X)                                     \
+  X(Wino8_16x16,  16, 16, 1,  8, 4, FamWino8,  Product)     \
+  X(Wino8_8x8x4,   8,  8, 4,  8, 4, FamWino8,  Product)     \
+  X(Wino8_8x8x2,   8,  8, 2,  4, 4, FamWino8,  Product)     \
+  X(Wino8_8x16,    8, 16, 1,  4, 4, FamWino8,  Product)     \
+  X(Wino9_16x16,  16, 16, 1,  8, 4, FamWino9,  Product)     \
+  X(Wino9_8x8x4,   8,  8, 4,  8, 4, FamWino9,  Product)     \
+  X(Wino9_8x8x2,   8,  8, 2,  4, 4, FamWino9,  Product)     \
+  X(Wino9_8x16,    8, 16, 1,  4, 4, FamWino9,  Product)     \
+  X(Wino_16x16,   16, 16, 1,  4, 4, FamWino,   ProbeOnly)   \
+  X(Wino_8x8x4,    8,  8, 4,  4, 4, FamWino,   ProbeOnly)   \
+  X(Wino43,       16, 16, 1, 12, 1, FamWino43, ProbeOnly)   /* 4-channel K steps; its LDS image is its own */ \
+  X(Wino9h_8x16,   8, 16, 1,  4, 2, FamWino9,  ProbeOnly)   /* 8-channel stages, two blocks per CU */ \
+  X(Wino9h_8x8x2,  8,  8, 2,  4, 2, FamWino9,  ProbeOnly)
+
+struct WinoRow {
+  WinoKernel k;
+  int TH, TW, TNB, waves, KQ;
+  WinoFamily fam;
+  bool probe_only;
+  int plane, buf4w;   // WinoGeom::PLANE; WinoDims::BUF (the 4-wave kernel's halo buffer, padded to whole 256-thread pieces)
+};
+static const WinoRow kWinoKernels[] = {
+#define X(K, TH, TW, TNB, NW, KQ, FAM, BUILD) \
+  {K, TH, TW, TNB, NW, KQ, FAM, BUILD, WinoGeom<TH, TW, TNB>::PLANE, WinoDims<TH, TW, TNB>::BUF},
+    WINO_KERNELS(X)
+#undef X
+};
+static const WinoRow* wino_row(WinoKernel k) {
+  for (const WinoRow& r : kWinoKernels)
+    if (r.k == k) return &r;
+  return nullptr;
+}
+
+// the shapes the kernels take: 3x3 stride-1 pad-1 NHWC layers with unpadded channel strides, even maps; a.TH / TW are
+// the planned (= the row's) tile
+bool egn_conv_wino_applies(const ConvArgs& a, WinoKernel k) {
+  const WinoRow* r = wino_row(k);
+  if (!r || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.Cin % EGN_CK || a.cs_in != a.Cin ||
+      a.cs_out != a.Cout || a.out_nchw || (a.Ho & 1) || (a.Wo & 1))
+    return false;
+  // conv_wino43_kernel: 16 x 16 pixel tiles of whole-tile maps, 4-channel K steps, 48-channel co-tiles
+  if (r->fam == FamWino43) return !(a.Cout % 48 || a.Cin % 4 || (a.Ho % 16) || (a.Wo % 16));
+  // co-tile 48 (every kernel) or 32 (not the 4-wave conv_wino_kernel): egn_wino_cot
+  const bool cot32 = r->fam != FamWino;
+  if (a.Cout % 48 != 0 && !(a.Cout % 32 == 0 && cot32)) return false;
+  return !(a.TH == 8 && a.TW == 8 && (a.Ho > 8 || a.Wo > 8));   // the batched variants are for the 8 x 8 maps
+}
+
+// rows of the BatchNorm partial table a launch writes (0 = this kernel has no fused statistics); a: planned
+int egn_conv_wino_stats_rows(const ConvArgs& a, WinoKernel k, int abl) {
+  const WinoRow* r = wino_row(k);
+  if (abl || !r || (r->fam != FamWino8 && r->fam != FamWino9)) return 0;
+  return wino8_grid(a, r->TNB, r->KQ == EGN_CKQ ? 1 : 2);   // one partial row per block; half-chunk stages: two blocks per CU
 }
 
 constexpr int W8_ABL_STAMPS = 32;     // conv_wino8_kernel's stamp build (its ABL & 32)
 
-// rows of the BatchNorm partial table a launch writes (0 = this kernel has no fused statistics); a: planned
-int egn_conv_wino_stats_rows(const ConvArgs& a, WinoKernel k, int abl) {
-  if (abl) return 0;
-  switch (k) {
-    case Wino_16x16:
-    case Wino_8x8x4:
-    case Wino43: return 0;
-    case Wino8_16x16:
-    case Wino8_8x8x4:
-    case Wino8_8x8x2:
-    case Wino8_8x16:
-    case Wino9_16x16:
-    case Wino9_8x8x4:
-    case Wino9_8x8x2:
-    case Wino9_8x16: return wino8_grid(a, a.TNB, 1);       // one partial row per block
-    case Wino9h_8x16:
-    case Wino9h_8x8x2: return wino8_grid(a, a.TNB, 2);     // two blocks per CU
+// abl: the kernel's ABL (conv_wino_kernel, conv_wino8_kernel) or CLK (conv_wino9_kernel, conv_wino43_kernel) argument
+size_t egn_conv_wino_lds_bytes(WinoKernel k, int abl, int cout) {
+  const WinoRow* r = wino_row(k);
+  if (!r) return 0;
+  const int cot = egn_wino_cot(cout) ? egn_wino_cot(cout) : WN_CO;
+  switch (r->fam) {
+    // conv_wino_kernel: 48-channel co-tiles only, halo buffers padded to whole 256-thread pieces, no statistics
+    case FamWino: return (2 * (size_t)WN_USLOTS + 2 * (size_t)r->buf4w) * 16;
+    // conv_wino8_kernel / conv_wino9_kernel: two filter stages and two halo buffers of KQ float4 planes, the
+    // [waves][2][cot] double table of the BatchNorm partial sums, and the stamp area of the stamp builds
+    case FamWino8:
+    case FamWino9: {
+      const bool stamps = r->fam == FamWino8 ? abl == W8_ABL_STAMPS : abl != 0;
+      return (2 * (size_t)(16 * r->KQ * cot) + 2 * (size_t)r->KQ * r->plane) * 16 +
+             (size_t)r->waves * 2 * cot * sizeof(double) + (stamps ? r->waves * WINO_NTK * sizeof(unsigned long long) : 0);
+    }
+    case FamWino43: return egn_conv_wino43_lds_bytes(abl);
   }
   return 0;
 }
 
-// conv_wino8_kernel / conv_wino9_kernel: two U slabs and two halo buffers of kq float4 planes, the [waves][2][cot]
-// double table of the BatchNorm partial sums, and the stamp area of the stamp builds
-template <int TH, int TW, int TNB>
-static size_t wino8_lds_bytes(int kq, int nw, int cot, bool stamps) {
-  return (2 * (size_t)(16 * kq * cot) + 2 * (size_t)kq * WinoGeom<TH, TW, TNB>::PLANE) * 16 +
-         (size_t)nw * 2 * cot * sizeof(double) + (stamps ? nw * 48 * sizeof(unsigned long long) : 0);
+// the unablated kernel of a row -- where this build has it
+template <WinoFamily FAM, int TH, int TW, int TNB, int NW, int KQ, bool BUILT>
+static int wino_launch_row(const ConvArgs& a, size_t lds, hipStream_t stream) {
+  if constexpr (!BUILT) return EGN_E_BADARG;      // probe builds only
+  else if constexpr (FAM == FamWino) return wino_launch<TH, TW, TNB>(a, lds, stream);
+  else if constexpr (FAM == FamWino8) return wino8_launch<TH, TW, TNB, 0, NW>(a, lds, stream);
+  else if constexpr (FAM == FamWino9) return wino9_launch<TH, TW, TNB, NW, KQ>(a, lds, stream);
+  else return a.stats ? EGN_E_BADARG : wino43_launch<0>(a, lds, stream);
 }
-// conv_wino_kernel: 48-channel co-tiles only, halo buffers padded to whole 256-thread pieces, no statistics
-template <int TH, int TW, int TNB>
-static size_t wino_lds_bytes() {
-  return (2 * (size_t)(16 * EGN_CKQ * WN_CO) + 2 * (size_t)WinoDims<TH, TW, TNB>::BUF) * 16;
-}
-size_t egn_conv_wino_lds_bytes(WinoKernel k, int abl, int cout) {
-  const int cot = egn_wino_cot(cout) ? egn_wino_cot(cout) : WN_CO;
-  switch (k) {
-    case Wino_16x16: return wino_lds_bytes<16, 16, 1>();
-    case Wino_8x8x4: return wino_lds_bytes<8, 8, 4>();
-    case Wino8_16x16: return wino8_lds_bytes<16, 16, 1>(EGN_CKQ, 8, cot, abl == W8_ABL_STAMPS);
-    case Wino8_8x8x4: return wino8_lds_bytes<8, 8, 4>(EGN_CKQ, 8, cot, abl == W8_ABL_STAMPS);
-    case Wino8_8x8x2: return wino8_lds_bytes<8, 8, 2>(EGN_CKQ, 4, cot, abl == W8_ABL_STAMPS);
-    case Wino8_8x16: return wino8_lds_bytes<8, 16, 1>(EGN_CKQ, 4, cot, abl == W8_ABL_STAMPS);
-    case Wino9_16x16: return wino8_lds_bytes<16, 16, 1>(EGN_CKQ, 8, cot, abl != 0);      // (abl = its CLK)
-    case Wino9_8x8x4: return wino8_lds_bytes<8, 8, 4>(EGN_CKQ, 8, cot, abl != 0);
-    case Wino9_8x8x2: return wino8_lds_bytes<8, 8, 2>(EGN_CKQ, 4, cot, abl != 0);
-    case Wino9_8x16: return wino8_lds_bytes<8, 16, 1>(EGN_CKQ, 4, cot, abl != 0);
-    case Wino9h_8x16: return wino8_lds_bytes<8, 16, 1>(2, 4, cot, abl != 0);             // 8-channel stages
-    case Wino9h_8x8x2: return wino8_lds_bytes<8, 8, 2>(2, 4, cot, abl != 0);
-    case Wino43: return egn_conv_wino43_lds_bytes(abl);
-  }
-  return 0;
-}
-// abl: the kernel's ABL (conv_wino_kernel, conv_wino8_kernel) or CLK (conv_wino9_kernel, conv_wino43_kernel) argument
+
 int egn_conv_launch_wino(const ConvArgs& a, size_t lds, WinoKernel k, int abl, hipStream_t stream) {
   const int act = a.act & EGN_ACT_MASK;
   if ((act != EGN_ACT_NONE && act != EGN_ACT_RELU) || (a.act & EGN_ACT_RES_AFTER)) return EGN_E_BADARG;
 #ifdef EGN_PROBES
+  constexpr bool probes = true;
   // -DEGN_PROBES (python -m egonet_amd.build --probes; tools/ only): the timing-ablation / s_memtime-stamp builds
-  // (WRONG RESULTS; cfg 47-50, 53-55, 58, 63, 66, 69)
+  // (WRONG RESULTS; cfg 47-50, 53-55, 58, 63, 66, 69) of the kernels that have one
   if (abl) {
     switch (k) {
       case Wino_16x16:
@@ -1851,57 +1337,22 @@ int egn_conv_launch_wino(const ConvArgs& a, size_t lds, WinoKernel k, int abl, h
         }
       // s_memtime stamps (tools/wino_clk.py): CLK = 1; conv_wino9_kernel's on 48-channel co-tiles only
       case Wino9_16x16:
-        switch (abl) {
-          case 1: return egn_wino_cot(a.Cout) == 48 ? wino9_launch_nt<16, 16, 1, 8, 3, 1>(a, lds, stream) : EGN_E_BADARG;
-          default: return EGN_E_BADARG;
-        }
+        return abl == 1 && egn_wino_cot(a.Cout) == 48 ? wino9_launch_nt<16, 16, 1, 8, 3, 1>(a, lds, stream) : EGN_E_BADARG;
       case Wino9h_8x16:
-        switch (abl) {
-          case 1: return egn_wino_cot(a.Cout) == 48 ? wino9_launch_nt<8, 16, 1, 4, 3, 1, 2>(a, lds, stream) : EGN_E_BADARG;
-          default: return EGN_E_BADARG;
-        }
-      case Wino43:
-        switch (abl) {
-          case 1: return wino43_launch<1>(a, lds, stream);
-          default: return EGN_E_BADARG;
-        }
-      case Wino_8x8x4:
-      case Wino8_8x8x4:
-      case Wino8_8x8x2:
-      case Wino8_8x16:
-      case Wino9_8x8x4:
-      case Wino9_8x8x2:
-      case Wino9_8x16:
-      case Wino9h_8x8x2: return EGN_E_BADARG;      // no ablation build
+        return abl == 1 && egn_wino_cot(a.Cout) == 48 ? wino9_launch_nt<8, 16, 1, 4, 3, 1, 2>(a, lds, stream) : EGN_E_BADARG;
+      case Wino43: return abl == 1 ? wino43_launch<1>(a, lds, stream) : EGN_E_BADARG;
+      default: return EGN_E_BADARG;      // no ablation build
     }
   }
+#else
+  constexpr bool probes = false;
 #endif
   if (abl) return EGN_E_BADARG;
   switch (k) {
-    // what the shipped table / the tuner can select (egn_conv_config_kind >= 0 in the product build)
-    case Wino8_16x16: return wino8_launch<16, 16, 1>(a, lds, stream);
-    case Wino8_8x8x4: return wino8_launch<8, 8, 4>(a, lds, stream);
-    case Wino8_8x8x2: return wino8_launch<8, 8, 2, 0, 4>(a, lds, stream);
-    case Wino8_8x16: return wino8_launch<8, 16, 1, 0, 4>(a, lds, stream);
-    case Wino9_16x16: return wino9_launch<16, 16, 1>(a, lds, stream);
-    case Wino9_8x8x4: return wino9_launch<8, 8, 4>(a, lds, stream);
-    case Wino9_8x8x2: return wino9_launch<8, 8, 2, 4>(a, lds, stream);
-    case Wino9_8x16: return wino9_launch<8, 16, 1, 4>(a, lds, stream);
-#ifdef EGN_PROBES
-    // the families measured and retired: the 4-wave kernel (cfg 45 / 46), the first F(4x4,3x3) kernel (65), two
-    // 4-wave blocks per CU (67 / 68)
-    case Wino_16x16: return wino_launch<16, 16, 1>(a, lds, stream);
-    case Wino_8x8x4: return wino_launch<8, 8, 4>(a, lds, stream);
-    case Wino43: return a.stats ? EGN_E_BADARG : wino43_launch<0>(a, lds, stream);
-    case Wino9h_8x16: return wino9_launch<8, 16, 1, 4, 2>(a, lds, stream);   // 8-channel stages, two blocks per CU
-    case Wino9h_8x8x2: return wino9_launch<8, 8, 2, 4, 2>(a, lds, stream);
-#else
-    case Wino_16x16:
-    case Wino_8x8x4:
-    case Wino43:
-    case Wino9h_8x16:
-    case Wino9h_8x8x2: return EGN_E_BADARG;      // probe builds only
-#endif
+#define X(K, TH, TW, TNB, NW, KQ, FAM, BUILD) \
+    case K: return wino_launch_row<FAM, TH, TW, TNB, NW, KQ, probes || BUILD == Product>(a, lds, stream);
+    WINO_KERNELS(X)
+#undef X
   }
   return EGN_E_BADARG;
 }

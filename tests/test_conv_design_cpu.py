@@ -287,3 +287,62 @@ def test_wino4_item_pipeline_is_stated_once():
         for use in ('W4_STAMPS(', 'W4_ITEM_DECODE(', 'w4_item_region<', 'W4_PROLOGUE(', 'W4_TRANS(', 'W4_HSTORE(',
                     'W4_RES_LOAD(', 'w4_stamp_dump<'):
             assert use in text[name], (name, use)
+
+
+def test_wino_shared_parts_are_stated_once():
+    """The F(2x2,3x3) kernels of conv_wino.hip (conv_wino_kernel, conv_wino8_kernel, conv_wino9_kernel; conv_wino43_kernel
+    for descriptors and stamps) share ONE definition of each common part -- descriptors, item walk, halo slots and DMA
+    offsets, the DMA piece and its place between two scheduling barriers, stamps, per-item registers, residual loads,
+    the two-barrier partial exchange, the BatchNorm statistics (csrc/conv_wino.h) -- so a hazard fix (the wave-uniform
+    skip of the last halo piece, the DMA -> residual-load order the vmcnt(24) ties count on, the once-per-block
+    statistics row) is made once.  The planner's predicates of the C48 and Wino families live with their kernels."""
+    import glob
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.abspath(engine.__file__)), 'csrc')
+    files = sorted(p for ext in ('*.hip', '*.h', '*.cpp') for p in glob.glob(os.path.join(csrc, ext)))
+    text = {os.path.basename(p): open(p, encoding='utf-8').read() for p in files}
+    for pattern in ('struct WinoGeom;', 'struct WinoDims {', '#define WINO_DESCRIPTORS(', '#define WINO_CLK(',
+                    'void wino_stamp_dump(const', '#define WINO_ITEM(', '#define WINO_HALO_SLOTS(', '#define WINO_DOFF(',
+                    '#define W9_ITEM(', '#define W9_DOFF(', '#define WINO_FILTER_SLOTS(', '#define WINO_PIECE(',
+                    '#define WINO_ISSUE(', '#define WINO_NEXT(', '#define WINO_VOFF(', '#define WINO_SCALE_ACC(',
+                    '#define WINO_RES_LOAD(', '#define WINO_EXCHANGE(', '#define WINO_STATS_ZERO(',
+                    '#define WINO_STATS_ADD(', '#define WINO_STATS_ROW('):
+        hits = [name for name, t in text.items() if pattern in t]
+        assert hits == ['conv_wino.h'], (pattern, hits)
+    # none of the copies the bodies used to define locally is left
+    hip = text['conv_wino.hip']
+    old = re.findall(r'#\s*define\s+((?:WINO|W8|W9)_(?:ITEM|DOFF|PIECE|NEXT|CLK))\b', hip)
+    assert not old, old
+    assert 'wn_add' not in hip and 'wn_fma' not in hip and 'rowpitch' not in hip.split('conv_wino8_kernel(ConvArgs a)')[1]
+
+    def body(kernel):           # from the kernel's signature to the next __global__ (or the launchers)
+        rest = hip.split('void %s(ConvArgs a) {' % kernel)[1]
+        return re.split(r'__global__|\nstatic int ', rest)[0]
+    both = ('WINO_DESCRIPTORS(', 'WINO_CLK()', 'wino_stamp_dump<', 'WINO_FILTER_SLOTS()', 'WINO_ISSUE(', 'WINO_NEXT(',
+            'WINO_SCALE_ACC(8)', 'WINO_RES_LOAD(', 'WINO_EXCHANGE(', 'WINO_STATS_ZERO()', 'WINO_STATS_ADD()',
+            'WINO_STATS_ROW()')
+    for kernel, uses in (('conv_wino_kernel', ('WINO_DESCRIPTORS(', 'WINO_ITEM(', 'WINO_HALO_SLOTS()', 'WINO_DOFF(',
+                                               'WINO_ISSUE(', 'WINO_NEXT(', 'WINO_VOFF(0)', 'WINO_SCALE_ACC(16)')),
+                         ('conv_wino8_kernel', both + ('WINO_ITEM(', 'WINO_HALO_SLOTS()', 'WINO_DOFF(', 'WINO_VOFF(fh)')),
+                         ('conv_wino9_kernel', both + ('W9_ITEM(', 'W9_DOFF(')),
+                         ('conv_wino43_kernel', ('WINO_DESCRIPTORS(', 'WINO_CLK()', 'wino_stamp_dump<'))):
+        b = body(kernel)
+        for use in uses:
+            assert use in b, (kernel, use)
+        # the hazard-sensitive instructions of the shared parts appear in no body any more
+        if kernel != 'conv_wino43_kernel':
+            assert 'egn_lds_dma16(' not in b and '__shfl_xor' not in b and 'a.stats +' not in b, kernel
+    # one list of the kernels; the planner's predicates sit next to the kernels they describe
+    assert hip.count('#define WINO_KERNELS(X)') == 1 and hip.count('WINO_KERNELS(X)\n') == 2
+    assert hip.count('hipLaunchKernelGGL(') == 1 and hip.count('egn_allow_big_lds(') == 1
+    for fn, home in (('bool egn_conv_wino_applies(const ConvArgs& a, WinoKernel k) {', 'conv_wino.hip'),
+                     ('bool egn_conv_c48_applies(const ConvArgs& a) {', 'conv_c48.hip'),
+                     ('size_t egn_conv_c48_lds_bytes(const ConvArgs& a, C48Kernel k) {', 'conv_c48.hip')):
+        hits = [name for name, t in text.items() if fn in t]
+        assert hits == [home], (fn, hits)
+        assert text[home].count(fn) == 1
+    plan = text['conv_plan.hip']
+    assert 'case F::C48: return egn_conv_c48_applies(a);' in plan
+    assert 'case F::Wino: return egn_conv_wino_applies(a, cf.kernel.wino);' in plan
+    assert 'case F::C48: return egn_conv_c48_lds_bytes(a, cf.kernel.c48);' in plan
