@@ -86,6 +86,9 @@ SIGNATURES = {
     'egn_bn_act_fwd_f32': (_i, [_p, _p, _p, _p, _p, _p, C.c_float, _i, _p, _p, _i, _i, _i, _p]),
     'egn_bn_bwd_sums_f32': (_i, [_p, _p, _p, C.c_float, _p, _p, _p, _p, _i, _p, _i, _i, _i, _p, _p, _p, _p]),
     'egn_bn_bwd_dz_f32': (_i, [_p, _p, _p, C.c_float, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    'egn_bn_fold_desc_bytes': (_i, []),
+    'egn_bn_fold_batch_f32': (_i, [_p, _i, _p]),
+    'egn_bn_frozen_bwd_f32': (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _i, _p]),
     'egn_bn_act_fwd_drop_f32': (_i, [_p, _p, _p, _p, _p, C.c_float, C.c_ulonglong, _p, _i, _i, _p, _p, _i, _i, _i, _p]),
     'egn_bn_bwd_sums_drop_f32': (_i, [_p, _p, C.c_float, C.c_ulonglong, _p, _i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _p, _p,
                                       _p, _p]),

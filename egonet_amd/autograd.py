@@ -80,9 +80,12 @@ class HRNetAutograd(TapeOwner):
         with _gc_paused(), torch.cuda.device(self.dev):
             st = _lib.current_stream(self.dev)
             self.packs.pack_all(st)          # every forward / data-gradient filter, one launch (2nd call on)
+            self.folds.fold_all(st)          # eval-mode BatchNorm layers: their folded scale / shift, one launch
             tape = _Tape(self, images)
             self.walker._record(n, cin, h, w, None, r=tape)
-            torch._foreach_add_([bn.num_batches_tracked for bn in tape.bns], 1)
+            self.folds.finalize()
+            if tape.bns:                     # train-mode layers only: an eval-mode layer's counter does not move
+                torch._foreach_add_([bn.num_batches_tracked for bn in tape.bns], 1)
             invalidate(m)                    # BatchNorm running statistics were written through raw pointers
             outs = tuple(o.user for o in self.head_outputs(tape))
         return tape, outs
@@ -99,6 +102,7 @@ class HRNetAutograd(TapeOwner):
                 fn()
             tape.join_side()
             self.packs.finalize()     # first backward: the set of (filter, direction) pairs is known now
+            self.last_backward_launches = dict(tape.counts)
             if self.debug_hook is not None:
                 self.last_tape = tape
             else:

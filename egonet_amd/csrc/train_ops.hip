@@ -564,6 +564,90 @@ extern "C" int egn_bn_bwd_dz_drop_f32(const float* dy, const float* z, float p, 
                      dres, rows, cols, ld, make_drop(p, seed, step_dev, layer));
   return (int)hipGetLastError();
 }
+// ---------------------------------------------------------------------------
+// BatchNorm in eval mode inside a model that trains (a frozen layer of a fine-tune: nn.BatchNorm2d.forward with
+// training == False normalises with running_mean / running_var and writes nothing).  With gamma and beta frozen too the
+// layer is the inference epilogue of its conv, y = act(conv(x) * scale + shift (+ res)), and its backward has no
+// reduction: the two kernels below.
+//
+// Fold, one launch for every such layer of the model (a device table of BnFoldDesc, as the filter packer's):
+//   scale[c] = gamma[c] / sqrt(var[c] + eps)             (gamma NULL: 1 / sqrt(var[c] + eps), the layer's 1/sigma)
+//   shift[c] = beta[c] + (bias[c] - mean[c]) * scale[c]   (bias NULL: 0; shift NULL: not written)
+// in double, rounded once; columns cout..coutp-1 are written as zeros.  One block per layer.
+// ---------------------------------------------------------------------------
+struct BnFoldDesc {
+  const float* gamma; const float* beta; const float* mean; const float* var; const float* bias;
+  float* scale; float* shift;
+  double eps;
+  int cout, coutp;
+};
+
+__global__ __launch_bounds__(256) void bn_fold_batch_kernel(const BnFoldDesc* __restrict__ descs) {
+  const BnFoldDesc d = descs[blockIdx.x];
+  for (int c = threadIdx.x; c < d.coutp; c += 256) {
+    double sc = 0.0, sh = 0.0;
+    if (c < d.cout) {
+      sc = (d.gamma ? (double)d.gamma[c] : 1.0) / sqrt((double)d.var[c] + d.eps);
+      if (d.shift) sh = (double)d.beta[c] + ((d.bias ? (double)d.bias[c] : 0.0) - (double)d.mean[c]) * sc;
+    }
+    d.scale[c] = (float)sc;
+    if (d.shift) d.shift[c] = (float)sh;
+  }
+}
+extern "C" int egn_bn_fold_desc_bytes(void) { return (int)sizeof(BnFoldDesc); }
+extern "C" int egn_bn_fold_batch_f32(const void* descs_dev, int n, void* stream) {
+  if (!descs_dev || n <= 0) return EGN_E_BADARG;
+  hipLaunchKernelGGL(bn_fold_batch_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, (const BnFoldDesc*)descs_dev);
+  return (int)hipGetLastError();
+}
+
+// Backward of that layer in ONE pass: dpre = dy * [y > 0] (relu; else dy), dz = dpre * scale[c], dres (optional) = dpre.
+// The gate reads the layer's OUTPUT (relu(pre) > 0 <=> pre > 0), so neither the conv output nor the residual is kept.
+// Same row-streaming thread mapping as bn_bwd_dz_kernel; padding columns are written as zeros.
+__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
+                                                            const float* __restrict__ scale, int relu,
+                                                            float* __restrict__ dz, float* __restrict__ dres, int rows,
+                                                            int cols, int ld) {
+  const int ld4 = ld / 4;
+  const int cgb = min(256, ld4 - (int)blockIdx.y * 256);
+  const int rpi = 256 / cgb;
+  const int r_local = threadIdx.x / cgb;
+  if (r_local >= rpi) return;
+  const int c4 = blockIdx.y * 256 + threadIdx.x - r_local * cgb;
+  float ps[4];
+  bool ok[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = c4 * 4 + k;
+    ok[k] = c < cols;
+    ps[k] = ok[k] ? scale[c] : 0.f;
+  }
+  for (int r = blockIdx.x * rpi + r_local; r < rows; r += gridDim.x * rpi) {
+    const size_t e = (size_t)r * ld4 + c4;
+    const float4 dv = reinterpret_cast<const float4*>(dy)[e];
+    float4 yv = make_float4(1.f, 1.f, 1.f, 1.f);
+    if (relu) yv = reinterpret_cast<const float4*>(y)[e];
+    const float di[4] = {dv.x, dv.y, dv.z, dv.w};
+    const float yi[4] = {yv.x, yv.y, yv.z, yv.w};
+    float out[4], gated[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float d = (ok[k] && yi[k] > 0.f) ? di[k] : 0.f;
+      gated[k] = d;
+      out[k] = ok[k] ? d * ps[k] : 0.f;
+    }
+    reinterpret_cast<float4*>(dz)[e] = make_float4(out[0], out[1], out[2], out[3]);
+    if (dres) reinterpret_cast<float4*>(dres)[e] = make_float4(gated[0], gated[1], gated[2], gated[3]);
+  }
+}
+extern "C" int egn_bn_frozen_bwd_f32(const float* dy, const float* y, const float* scale, int relu, float* dz,
+                                     float* dres, int rows, int cols, int ld, void* stream) {
+  if (!dy || !scale || !dz || (relu && !y) || (relu != 0 && relu != 1) || rows <= 0 || cols <= 0 || ld % 4 || ld < cols)
+    return EGN_E_BADARG;
+  hipLaunchKernelGGL(bn_frozen_bwd_kernel, rowstream_grid(rows, ld), dim3(256), 0, (hipStream_t)stream, dy, y, scale,
+                     relu, dz, dres, rows, cols, ld);
+  return (int)hipGetLastError();
+}
 // the keep mask the *_drop_* kernels draw, written out (tests; tools): mask[rows][ld] of 0 / 1
 __global__ __launch_bounds__(256) void drop_mask_kernel(float4* __restrict__ mask, size_t n4, DropArgs drop) {
   const unsigned dstep = (unsigned)*drop.step;

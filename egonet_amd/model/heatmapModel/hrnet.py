@@ -281,8 +281,9 @@ class PoseHighResolutionNet(nn.Module):
         loop calls ``model.eval(); model(data)`` with grad enabled (libs/trainer/trainer.py:421) and
         ``EgoNet.get_keypoints`` has no ``no_grad`` of its own (libs/model/egonet.py:434).  The outputs are
         plain tensors (no autograd graph); a caller that wants to differentiate an eval-mode forward gives
-        an input with ``requires_grad`` (saliency) or sets ``model.hip_eval = False`` (frozen-BatchNorm
-        fine-tuning through the module graph) and gets the torch graph.
+        an input with ``requires_grad`` (saliency) or sets ``model.hip_eval = False`` and gets the
+        torch graph.  (Frozen-BatchNorm fine-tuning needs neither: ``model.train()`` with some BatchNorm modules in eval
+        mode is a train-mode forward, and the native tape honours the submodules' modes, egonet_amd/frozen_bn.py.)
         Train mode under autograd -- the reference's hot loop ``model(data); loss.backward(); optim.step()``
         (libs/trainer/trainer.py:183-209), unchanged: ONE autograd node whose forward / backward are the
         native train-mode tape (egonet_amd.autograd.HRNetAutograd); torch owns loss and optimiser.
@@ -339,7 +340,16 @@ class PoseHighResolutionNet(nn.Module):
         if mode:                 # the weights are about to change: drop programs and packed blobs
             self._engine = None
         self.__dict__.pop('_hook_dicts', None)      # (submodules may have been replaced since: _has_submodule_hooks)
-        return super().train(mode)
+        super().train(mode)
+        if mode and self.frozen_bn_prefixes:
+            # extra.freeze_bn: the BatchNorm layers of the frozen prefixes stay in eval mode (running statistics, nothing
+            # written) through every model.train() of the training loop (trainer.py:602, 677)
+            from egonet_amd import frozen_bn
+            for bn in frozen_bn.bn_modules_under(self, self.frozen_bn_prefixes):
+                bn.eval()
+        return self
+
+    frozen_bn_prefixes = ()      # get_pose_net: the freeze_layers prefixes when heatmapModel.extra.freeze_bn is set
 
     def _hip_engine(self):
         from egonet_amd import engine
@@ -436,6 +446,11 @@ def get_pose_net(cfgs, is_train, **kwargs):
         if is_freezed(name, frozen):
             param.requires_grad = False
             print('{:s} freezed during training.'.format(name))
+    if hm['extra'].get('freeze_bn', False):
+        # (not in the reference's YAMLs) the frozen-BatchNorm fine-tune: the BatchNorm layers under the frozen prefixes
+        # normalise with their running statistics and leave them alone, whatever model.train() is called later
+        model.frozen_bn_prefixes = tuple(frozen)
+        model.train(model.training)
     if hm.get('add_xy'):
         model.modify_input_channel(5)
     if hm.get('precision') is not None:

@@ -38,7 +38,7 @@ import os
 
 import torch
 
-from . import _lib, filters, optim, train_state, tuner
+from . import _lib, filters, frozen_bn, optim, train_state, tuner
 from .engine import invalidate
 from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID
 from .engine import Buf, HRNetEngine, _round_up
@@ -64,8 +64,10 @@ class _Tape(object):
         self.back = []            # backward closures, forward order
         self.named = {}           # tag -> Buf
         self.user = {}            # tag -> NCHW copy for the caller
-        self.no_grad = set()      # ids of Bufs that need no gradient (the input)
-        self.bns = []
+        self.no_grad = set()      # ids of Bufs that need no gradient: the input, and (pruning) what frozen_bn's rule finds
+        self.prune = owner.prune_backward
+        self.counts = frozen_bn.new_counts()      # backward launches issued: the owner's last_backward_launches
+        self.bns = []             # BatchNorm layers in train mode: their num_batches_tracked moves
         self.maps_user = None
 
     # -- recorder plumbing (concurrency hints are ignored: one stream) ------
@@ -110,12 +112,15 @@ class _Tape(object):
 
     # -- launches -----------------------------------------------------------
     def _conv_launch(self, x, wp, shift, y, n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, act,
-                     weight=None, dgrad=0, want_stats=False, res=None, f43_ok=True):
+                     weight=None, dgrad=0, want_stats=False, res=None, f43_ok=True, scale=None):
         """``wp``: the direct-packed filter (None: packed here from ``weight``).  With ``weight`` (+ ``dgrad``) given, the tuner may pick a
         Winograd configuration for 3x3 stride-1 layers (forward and data gradient alike: the data
         gradient is a stride-1 convolution with the rotated filter); the transformed filter then comes
-        from the step's PackedFilters like the direct one."""
-        key = (n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, False, False)
+        from the step's PackedFilters like the direct one.  ``scale``: the folded BatchNorm scale of a frozen layer (with its
+        ``shift``, ``res`` and ``act`` the inference epilogue); None: ones, a raw convolution."""
+        key = (n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, scale is not None and res is not None, False)
+        if scale is None:
+            scale = self.o.ones
         can_wino = weight is not None and act in (ACT_NONE, ACT_RELU) and self.o.allow_wino
         # [round 5] F(4x4,3x3) (csrc/conv_wino4.hip, filter kind 3) in the tape: the filter is transformed on the device
         # with all the others (PackedFilters), BatchNorm statistics come from conv_wino4s_kernel's item end, the K-split
@@ -136,7 +141,7 @@ class _Tape(object):
                 stats = (torch.empty(nrows * 2 * cout, dtype=torch.float64, device=self.dev), nrows)
         e0 = timing_begin(self.o.timing, self.dev)     # bench.py: hipEvents around every forward / data-gradient conv
         if kind == filters.WINO4:
-            _lib.check(self.L.egn_conv2d_ex_f32(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(self.o.ones), _lib.ptr(shift),
+            _lib.check(self.L.egn_conv2d_ex_f32(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(scale), _lib.ptr(shift),
                                                 _lib.ptr(res), _lib.ptr(y), n, h, w, cin, cs_in, cout, cs_out, kh, kw,
                                                 stride, pad, act, cfg, None if stats is None else _lib.ptr(stats[0]),
                                                 0 if stats is None else stats[1],
@@ -147,7 +152,7 @@ class _Tape(object):
                                                      _lib.ptr(y), n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride,
                                                      pad, cfg, _lib.ptr(stats[0]), stats[1], self.st), 'conv+stats')
         else:
-            _lib.check(self.L.egn_conv2d_f32(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(self.o.ones), _lib.ptr(shift),
+            _lib.check(self.L.egn_conv2d_f32(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(scale), _lib.ptr(shift),
                                              _lib.ptr(res), _lib.ptr(y), n, h, w, cin, cs_in, cout, cs_out, kh, kw,
                                              stride, pad, act, 0, cfg, self.st), 'conv')
         if e0 is not None:
@@ -163,6 +168,7 @@ class _Tape(object):
         if need < 0:
             raise NotImplementedError('weight gradient of a %dx%d convolution' % (kh, kw))
         ws = self.o.wgrad_ws(need)
+        self.counts['wgrad'] += 1
         st = self.st
         if self.side is not None:
             fork_wgrad(self.side, self.dev, self.side_keep, (xd, dy))
@@ -202,6 +208,7 @@ class _Tape(object):
     def _dgrad(self, dy, ho, wo, cs_out, weight, stride, pad, x, into=None):
         cout, cin, kh, kw = weight.shape
         L = self.L
+        self.counts['dgrad'] += 1
         if kh != kw:
             # the Pedestrian model's final 4x3 'valid' conv over the whole 4x3 map (hrnet.py:457-460):
             # one output pixel, so dx[n, (ky,kx), ci] = sum_co dy[n, co] * W[co, ci, ky, kx] is a GEMM
@@ -241,6 +248,14 @@ class _Tape(object):
                           ACT_NONE, weight=weight, dgrad=1, res=into, f43_ok=(stride == 1))
         return dx
 
+    def _dead(self, y, inputs, *params):
+        """Pruning: the output ``y`` of an op without a trainable parameter among ``params`` and without an input that
+        needs a gradient needs none either (frozen_bn.op_needs_grad) -- the caller registers no backward for it."""
+        if self.prune and not frozen_bn.op_needs_grad(self.no_grad, inputs, *params):
+            self.no_grad.add(id(y))
+            return True
+        return False
+
     # -- ops (engine._Recorder interface) -----------------------------------
     def nchw_to_nhwc(self, x_ext, n, c, h, w, tag=''):
         y = self.new(n, h, w, c, name=tag)
@@ -271,6 +286,8 @@ class _Tape(object):
         xd, yd = self.data[id(x)], self.data[id(y)]
         _lib.check(L.egn_avgpool_fwd_f32(_lib.ptr(xd), _lib.ptr(yd), x.n, x.h, x.w, x.cs, k, self.st), 'avgpool')
         self.named[tag] = y
+        if self._dead(y, (x,)):
+            return y
 
         def backward():
             dy = self._take_grad(y)
@@ -300,10 +317,14 @@ class _Tape(object):
         # user-facing outputs (dst / out_nchw of the inference recording) are computed
         # into an internal NHWC tensor like every other layer -- the backward needs the
         # padded layout -- and copied out in the caller's NCHW format afterwards
-        z = self.new(x.n, ho, wo, cout, cs=cout_cs, name=tag)
-        xd, zd = self.data[id(x)], self.data[id(z)]
+        xd = self.data[id(x)]
         wp = None                        # packed by _conv_launch in the layout its tile configuration reads
         rows = x.n * ho * wo
+        form = None if bn is None else frozen_bn.bn_form(bn)
+        if form == frozen_bn.FUSED:
+            return self._conv_frozen(x, xd, param, weight, bias, bn, act, res, stride, pad, ho, wo, cout_cs, tag)
+        z = self.new(x.n, ho, wo, cout, cs=cout_cs, name=tag)
+        zd = self.data[id(z)]
         if bn is None:
             shift = self.o.zeros
             if bias is not None:
@@ -316,6 +337,8 @@ class _Tape(object):
                 _lib.check(L.egn_nhwc_to_nchw_f32(_lib.ptr(zd), _lib.ptr(u), x.n, cout, ho, wo, z.cs, self.st), 'to_nchw')
                 self.user[tag] = u
             self.named[tag] = z
+            if self._dead(z, (x,), param, bias):
+                return z
 
             def backward():
                 dy = self._take_grad(z)
@@ -345,11 +368,16 @@ class _Tape(object):
             # reference's; the statistics then come from the separate reduction over z
             shift = torch.zeros(_round_up(cout, 16), dtype=torch.float32, device=self.dev)
             shift[:cout].copy_(bias.detach())
+        frozen = form == frozen_bn.AFFINE      # eval mode, gamma / beta trainable: the running statistics, nothing written
         stats = self._conv_launch(xd, wp, shift, zd, x.n, x.h, x.w, cin, x.cs, cout, z.cs, kh, kw, stride, pad,
-                                  ACT_NONE, weight=weight, want_stats=bias is None)
-        mean, istd = self._empty(cout), self._empty(cout)
+                                  ACT_NONE, weight=weight, want_stats=bias is None and not frozen)
         mom = 0.1 if bn.momentum is None else bn.momentum
-        if stats is not None:      # the conv epilogue wrote per-tile partial sums: only the finalise stage is left
+        if not frozen:
+            mean, istd = self._empty(cout), self._empty(cout)
+            self.bns.append(bn)
+        if frozen:                 # no statistics launch, no finalise: the running mean and the folded 1/sigma
+            mean, istd = bn.running_mean, self.o.folds.get(bn, None, form, self.st)[0]
+        elif stats is not None:      # the conv epilogue wrote per-tile partial sums: only the finalise stage is left
             _lib.check(L.egn_bn_stats_finalize_f32(_lib.ptr(stats[0]), stats[1], rows, cout, bn.eps, _lib.ptr(mean),
                                                    _lib.ptr(istd), None, _lib.ptr(bn.running_mean),
                                                    _lib.ptr(bn.running_var), mom, self.st), 'bn_stats_finalize')
@@ -357,7 +385,6 @@ class _Tape(object):
             _lib.check(L.egn_bn_stats_f32(_lib.ptr(zd), rows, cout, z.cs, bn.eps, _lib.ptr(mean), _lib.ptr(istd), None,
                                           _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), mom,
                                           _lib.ptr(self.o.col_ws), self.st), 'bn_stats')
-        self.bns.append(bn)
         y = self.new(x.n, ho, wo, cout, cs=z.cs, name=tag)
         yd = self.data[id(y)]
         relu = 1 if act == ACT_RELU else 0
@@ -368,11 +395,15 @@ class _Tape(object):
                                         _lib.ptr(bn.bias), None, 1.0, relu, _lib.ptr(rd), _lib.ptr(yd), rows, cout,
                                         z.cs, self.st), 'bn_act_fwd')
         self.named[tag] = y
+        if self._dead(y, (x, res), param, bias, bn.weight, bn.bias):
+            del self.data[id(z)]         # no backward will read the pre-BatchNorm tensor
+            return y
 
         def backward():
             dy = self._take_grad(y)
             if dy is None:
                 return
+            self.counts['bn_bwd'] += 2
             dbeta = self.o.grad_of(bn.bias) if bn.bias.requires_grad else self._empty(cout)
             dgamma = self.o.grad_of(bn.weight) if bn.weight.requires_grad else self._empty(cout)
             _lib.check(L.egn_bn_bwd_sums_f32(_lib.ptr(dy), _lib.ptr(zd), None, 1.0, _lib.ptr(mean), _lib.ptr(istd),
@@ -382,10 +413,13 @@ class _Tape(object):
             dz = self._empty(dy.numel())
             dres = self._empty(dy.numel()) if (res is not None and id(res) not in self.no_grad) else None
             _lib.check(L.egn_bn_bwd_dz_f32(_lib.ptr(dy), _lib.ptr(zd), None, 1.0, _lib.ptr(mean), _lib.ptr(istd),
-                                           _lib.ptr(bn.weight), _lib.ptr(bn.bias), relu, _lib.ptr(rd), _lib.ptr(dbeta),
-                                           _lib.ptr(dgamma), _lib.ptr(dz), _lib.ptr(dres), rows, cout, z.cs, self.st),
-                       'bn_bwd_dz')
-            if self.o.debug_hook is not None:
+                                           _lib.ptr(bn.weight), _lib.ptr(bn.bias), relu, _lib.ptr(rd),
+                                           _lib.ptr(self.o.zeros if frozen else dbeta),
+                                           _lib.ptr(self.o.zeros if frozen else dgamma), _lib.ptr(dz), _lib.ptr(dres), rows,
+                                           cout, z.cs, self.st), 'bn_bwd_dz')
+            # (frozen statistics: zero sum vectors leave dz = gamma * istd * dpre, the derivative with constant mean and
+            # variance; the hook's dict describes the batch-statistics backward and is not called for such a layer)
+            if self.o.debug_hook is not None and not frozen:
                 self.o.debug_hook(dict(tag=tag, dy=dy, z=zd, mean=mean, istd=istd, bn=bn, res=rd, dbeta=dbeta,
                                        dgamma=dgamma, dz=dz, dres=dres, relu=relu, rows=rows, cols=cout, ld=z.cs))
             if dres is not None:
@@ -401,6 +435,47 @@ class _Tape(object):
         self.back.append(backward)
         return y
 
+    def _conv_frozen(self, x, xd, param, weight, bias, bn, act, res, stride, pad, ho, wo, cout_cs, tag):
+        """conv + BatchNorm in eval mode with gamma and beta frozen (frozen_bn.FUSED): ONE forward launch, the conv with
+        the folded scale / shift (the owner's FoldTable) plus residual and ReLU in its epilogue -- the inference form of
+        the layer, on whichever family the tuner hands the tape; no pre-BatchNorm tensor exists.  Backward:
+        egn_bn_frozen_bwd_f32 gates dy by the OUTPUT and scales it, one pass instead of two reductions and bn_bwd_dz."""
+        L = self.L
+        cout, cin, kh, kw = weight.shape
+        if act not in (ACT_NONE, ACT_RELU):
+            raise NotImplementedError('activation %d after BatchNorm' % act)
+        relu = 1 if act == ACT_RELU else 0
+        scale, shift = self.o.folds.get(bn, bias, frozen_bn.FUSED, self.st)
+        y = self.new(x.n, ho, wo, cout, cs=cout_cs, name=tag)
+        yd = self.data[id(y)]
+        rd = None if res is None else self.data[id(res)]
+        self._conv_launch(xd, None, shift, yd, x.n, x.h, x.w, cin, x.cs, cout, y.cs, kh, kw, stride, pad, act,
+                          weight=weight, res=rd, scale=scale)
+        self.named[tag] = y
+        if self._dead(y, (x, res), param, bias):
+            return y
+        rows = x.n * ho * wo
+
+        def backward():
+            dy = self._take_grad(y)
+            if dy is None:
+                return
+            dz = self._empty(dy.numel())
+            dres = self._empty(dy.numel()) if (res is not None and id(res) not in self.no_grad) else None
+            self.counts['bn_bwd'] += 1
+            frozen_bn.frozen_bwd(L, dy, yd, scale, relu, dz, dres, rows, cout, y.cs, self.st)
+            if dres is not None:
+                self._accum(res, dres)
+            if bias is not None and bias.requires_grad:
+                _lib.check(L.egn_colsum_f32(_lib.ptr(dz), rows, cout, y.cs, _lib.ptr(self.o.grad_of(bias)),
+                                            _lib.ptr(self.o.col_ws), self.st), 'bias grad')
+            if param.requires_grad:
+                self._wgrad(x, xd, dz, y.cs, weight, stride, pad)
+            self._accum_dgrad(x, dz, ho, wo, y.cs, weight, stride, pad)
+        backward.params = [param, bn.weight, bn.bias] + ([bias] if bias is not None else [])
+        self.back.append(backward)
+        return y
+
     def fuse(self, terms, relu, tag=''):
         L = self.L
         base = [t for t, s in terms if s == 0][0]
@@ -412,6 +487,8 @@ class _Tape(object):
         _lib.check(L.egn_fuse_sum_relu_f32(_lib.ptr(yd), y.n, y.h, y.w, y.c, y.cs, nt, ptrs, shifts, int(relu), self.st),
                    'fuse')
         self.named[tag] = y
+        if self._dead(y, [t for t, _ in terms]):
+            return y
 
         def backward():
             dy = self._take_grad(y)
@@ -468,6 +545,12 @@ class TapeOwner(object):
         self.wgrad_stream = wgrad_side_stream(self.dev, int(os.environ.get('EGONET_AMD_WGRAD_PRIORITY', '0')))
         self.walker = HRNetEngine(model)
         self.packs = PackedFilters(self.dev)
+        # frozen layers (frozen_bn.py): the folded scale / shift of the BatchNorm layers in eval mode, one launch per step;
+        # the backward stops at the frozen frontier (EGONET_AMD_PRUNE_BACKWARD=0: every op registers its backward as
+        # before, for A/B runs); what the last backward launched, plain host counters
+        self.folds = frozen_bn.FoldTable(self.dev)
+        self.prune_backward = frozen_bn.prune_enabled()
+        self.last_backward_launches = None        # {'dgrad': n, 'wgrad': n, 'bn_bwd': n}
         self.debug_hook = None        # tests/train_debug.py: per-layer checks of the BatchNorm backward
         self.timing = None            # bench.py: a list collects (cfg, flops, start, end) per conv launch
         # 3x3 stride-1 forward / data-gradient convolutions may run on the fused Winograd kernels
@@ -530,6 +613,8 @@ class TapeOwner(object):
         """The gradient ``g`` of ``out.user`` (contiguous fp32, the caller's layout) enters the tape: converted into
         the padded NHWC layout of ``out.buf``."""
         b = out.buf
+        if id(b) in tape.no_grad:
+            return
         d = tape._empty(b.n * b.h * b.w * b.cs)
         if out.shuffle:
             _lib.check(self.L.egn_pixel_unshuffle_nchw_to_nhwc_f32(_lib.ptr(g), _lib.ptr(d), b.n, out.c, b.h, b.w, b.cs,
@@ -823,6 +908,7 @@ class HRNetTrainStep(TapeOwner):
             st = _lib.current_stream(self.dev)
             self.flat.grad.zero_()
             self.packs.pack_all(st)          # every forward / data-gradient filter, one launch
+            self.folds.fold_all(st)          # scale / shift of every eval-mode BatchNorm layer, one launch (none: nothing)
             tape = _Tape(self, images)
             self.walker._record(n, cin, h, w, None, r=tape)
             J = m.num_joints
@@ -878,6 +964,8 @@ class HRNetTrainStep(TapeOwner):
             tape.join_side()
             finish_step(self, sess, update, st)
             self.packs.finalize()     # first step: the set of filters is known now
+            self.folds.finalize()
+            self.last_backward_launches = dict(tape.counts)
             invalidate(m)             # the inference engine caches folded weights (raw-pointer writes)
             if self.debug_hook is not None:
                 self.last_tape = tape

@@ -494,6 +494,23 @@ int egn_bn_bwd_dz_drop_f32(const float* dy, const float* z, float p, unsigned lo
                            float* dres, int rows, int cols, int ld, void* stream);
 int egn_dropout_mask_f32(float* mask, long n, float p, unsigned long long seed, const int* step_dev, int layer,
                          void* stream);
+/* BatchNorm in EVAL mode inside a model that trains (nn.BatchNorm2d.forward with training == False under
+ * trainer.py:183-209: a frozen layer of a fine-tune normalises with running_mean / running_var and writes nothing).
+ * egn_bn_fold_batch_f32: ONE launch folds every such layer of a model from a device table of `n` descriptors of
+ * egn_bn_fold_desc_bytes() bytes each, in this order, naturally aligned:
+ *     const float *gamma, *beta, *mean, *var, *bias;  float *scale, *shift;  double eps;  int cout, coutp;
+ *   scale[c] = gamma[c] / sqrt(var[c] + eps)              (gamma NULL: 1 / sqrt(var[c] + eps), the layer's 1/sigma)
+ *   shift[c] = beta[c] + (bias[c] - mean[c]) * scale[c]   (bias NULL: no conv bias; shift NULL: not written)
+ * computed in double and rounded once; entries cout..coutp-1 of both vectors are written as zeros.  scale / shift are
+ * what egn_conv2d_f32 / egn_conv2d_ex_f32 take: y = act(conv(x) * scale + shift (+ res)) is the layer's forward. */
+int egn_bn_fold_desc_bytes(void);
+int egn_bn_fold_batch_f32(const void* descs_dev, int n, void* stream);
+/* ... and its backward in one pass over [rows][ld] (no reduction: the statistics are constants):
+ *   dpre = dy * [y > 0] (relu = 1; relu = 0: dy, y may be NULL),  dz = dpre * scale[c],  dres (optional) = dpre
+ * y is the layer's OUTPUT (relu(pre) > 0 <=> pre > 0: torch's gate), so neither the conv output nor the residual is
+ * read.  Columns cols..ld-1 of dz / dres are written as zeros whatever dy holds there.  ld % 4 == 0. */
+int egn_bn_frozen_bwd_f32(const float* dy, const float* y, const float* scale, int relu, float* dz, float* dres,
+                          int rows, int cols, int ld, void* stream);
 int egn_add_f32(const float* a, const float* b, float* y, long n, void* stream);
 /* *loss += weight*mean((pred-tgt)^2) (zero it first);
  * dpred (= or, with accumulate, +=) weight*2(pred-tgt)/(rows*cols).

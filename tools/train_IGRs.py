@@ -109,6 +109,14 @@ def igr_cfgs(a):
                                  'eval_metrics': [metric], 'alpha_mode': 'proj'})
     cfg['optimizer'].update(trainer.optim_keys_from_args(a))    # --optim / --weight-decay / --no-decay-norm-bias / ...
     cfg['training_settings'].update(trainer.checkpoint_keys_from_args(a))       # --checkpoint / --resume
+    if getattr(a, 'freeze', None):
+        # --freeze PREFIX ...: heatmapModel.extra.freeze_layers (hrnet.py:675-690); --freeze-bn: their BatchNorm layers
+        # stay in eval mode too (extra.freeze_bn), the frozen-BatchNorm fine-tune
+        cfg['heatmapModel']['extra']['freeze_layers'] = list(a.freeze)
+    if getattr(a, 'freeze_bn', False):
+        if not getattr(a, 'freeze', None):
+            raise SystemExit('--freeze-bn needs --freeze PREFIX [PREFIX ...]: it freezes the BatchNorm layers under them')
+        cfg['heatmapModel']['extra']['freeze_bn'] = True
     if getattr(a, 'out', None):
         cfg['dirs'] = {'output': a.out}
     if getattr(a, 'ss_record', None):
@@ -196,6 +204,10 @@ def main(argv=None):
     ap.add_argument('--workers', type=int, default=4)
     ap.add_argument('--report-every', type=int, default=30)
     ap.add_argument('--lr', type=float, default=1e-3)
+    ap.add_argument('--freeze', nargs='+', default=None, metavar='PREFIX',
+                    help='parameter-name prefixes that do not train (freeze_layers), e.g. conv1 bn1 conv2 bn2 layer1')
+    ap.add_argument('--freeze-bn', action='store_true',
+                    help='keep the BatchNorm layers under --freeze in eval mode: running statistics, nothing written')
     trainer.add_optim_arguments(ap)
     trainer.add_checkpoint_arguments(ap)
     ap.add_argument('--exp-type', default='instanceto2d', choices=['instanceto2d'] + sorted(train_samples.EXP_TARGETS))
