@@ -33,6 +33,7 @@ SIGNATURES = {
     'egn_strerror': (C.c_char_p, [_i]),
     'egn_conv2d_f32': (_i, [_p] * 6 + [_i] * 14 + [_p]),
     'egn_conv_plan_query': (_i, [_i] * 13 + [C.POINTER(_i)]),
+    'egn_conv_plan_takes': (_i, [_i] * 14),
     'egn_conv_num_configs': (_i, []),
     'egn_conv_config_info': (_i, [_i, C.POINTER(_i), C.POINTER(_i)]),
     'egn_conv_config_name': (_i, [_i, C.c_char_p, _i]),

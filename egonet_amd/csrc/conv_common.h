@@ -99,6 +99,13 @@ __device__ __forceinline__ void egn_buf_store4(__amdgpu_buffer_rsrc_t r, unsigne
 // the OOB offset, which loads 0 and drops the store -- no branches.
 // Lane l of wave (wm, wn) owns C[(wm*MT+mt)*16 + 4*(l>>4) + r][n0 + (wn*NT+nt)*16 + (l&15)].
 // ---------------------------------------------------------------------------
+// Host: co-tiles of TN channels a Staged / Dma launch covers -- the filter's CoutP columns and, for an NHWC output, every
+// pad channel up to cs_out (a tile past CoutP loads zeros and stores zeros: the pad channels stay 0 for any stride)
+static inline int egn_co_tiles(const ConvArgs& a, int tn) {
+  const int c = (!a.out_nchw && a.cs_out > a.CoutP) ? a.cs_out : a.CoutP;
+  return (c + tn - 1) / tn;
+}
+
 template <int WM, int MT>
 __device__ __forceinline__ void conv_epi_pixels(const ConvArgs& a, float4* smem, int tid, int n_base, int oy0,
                                                 int ox0) {

@@ -261,7 +261,7 @@ static int launch_abl(const ConvArgs& a, size_t lds, hipStream_t stream) {
   static bool raised[EGN_MAX_DEVICES];  // per instantiation and device
   EGN_CHECK_HIP(egn_allow_big_lds(&conv_dma_kernel<WM, WN, MT, NT, 8, 8, ABL>, EGN_BIG_LDS_BYTES, raised));
   const int tiles_b = (a.N + a.TNB - 1) / a.TNB;
-  dim3 grid(a.tiles_x * a.tiles_y * tiles_b, (a.CoutP + WN * NT * 16 - 1) / (WN * NT * 16));
+  dim3 grid(a.tiles_x * a.tiles_y * tiles_b, egn_co_tiles(a, WN * NT * 16));
   hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 8, 8, ABL>), grid, dim3(256), lds, stream, a);
   return (int)hipGetLastError();
 }
@@ -271,7 +271,7 @@ static int launch_one(const ConvArgs& a, size_t lds, hipStream_t stream) {
   static bool raised[EGN_MAX_DEVICES];  // per instantiation and device
   EGN_CHECK_HIP(egn_allow_big_lds(&conv_dma_kernel<WM, WN, MT, NT, 8, 8>, EGN_BIG_LDS_BYTES, raised));
   const int tiles_b = (a.N + a.TNB - 1) / a.TNB;
-  dim3 grid(a.tiles_x * a.tiles_y * tiles_b, (a.CoutP + WN * NT * 16 - 1) / (WN * NT * 16));
+  dim3 grid(a.tiles_x * a.tiles_y * tiles_b, egn_co_tiles(a, WN * NT * 16));
   hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 8, 8>), grid, dim3(256), lds, stream, a);
   return (int)hipGetLastError();
 }

@@ -73,6 +73,15 @@ __global__ __launch_bounds__(256, 2) void conv_fc_kernel(ConvArgs a) {
     v = res_after ? rs + egn_act(v, act) : egn_act(v + rs, act);
     a.y[o] = v;
   }
+  // keep the pad channels of an NHWC output zero, as every other family does: the block of the last co-tile
+  if (!a.out_nchw && a.cs_out > a.Cout && n0 + 16 == a.Cout) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = m0 + 4 * kq + r;
+      if (row >= rows) continue;
+      for (int co = a.Cout + li; co < a.cs_out; co += 16) a.y[(size_t)row * a.cs_out + co] = 0.f;
+    }
+  }
 }
 
 bool egn_conv_fc_applies(const ConvArgs& a) {

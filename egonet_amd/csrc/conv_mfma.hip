@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256, 3) void conv_mfma_kernel(ConvArgs a) {
 template <int WM, int WN, int MT, int NT, int AI, int BI>
 static int launch_one(const ConvArgs& a, size_t lds, hipStream_t stream) {
   const int tiles_b = (a.N + a.TNB - 1) / a.TNB;
-  dim3 grid(a.tiles_x * a.tiles_y * tiles_b, (a.CoutP + WN * NT * 16 - 1) / (WN * NT * 16));
+  dim3 grid(a.tiles_x * a.tiles_y * tiles_b, egn_co_tiles(a, WN * NT * 16));
   hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, MT, NT, AI, BI>), grid, dim3(256), lds, stream, a);
   return (int)hipGetLastError();
 }

@@ -157,6 +157,20 @@ extern "C" int egn_conv_plan_query(int N, int H, int W, int Cin, int cs_in, int 
   return 0;
 }
 
+// 0 where cfg's planner takes the shape for a caller WITH / WITHOUT a residual in another buffer: egn_conv_plan_query is
+// not told about the residual, and the families whose kernels read none (Stem, S2r) and the NCHW epilogue refuse one.
+// What tuner.usable asks (host only).
+extern "C" int egn_conv_plan_takes(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int KH, int KW,
+                                   int stride, int pad, int has_res, int out_nchw, int cfg) {
+  static const float other = 0.f;      // (never read: a residual that is not y)
+  ConvArgs a;
+  int rc = fill_conv_args(a, nullptr, nullptr, nullptr, nullptr, has_res ? &other : nullptr, nullptr, N, H, W, Cin,
+                          cs_in, Cout, cs_out, KH, KW, stride, pad, 0, out_nchw);
+  if (rc) return rc;
+  size_t lds;
+  return egn_conv_plan(a, cfg, lds);
+}
+
 // ---------------------------------------------------------------------------
 // programs
 // ---------------------------------------------------------------------------

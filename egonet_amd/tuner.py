@@ -105,7 +105,7 @@ def kind_of(cfg):
 def _facts(key, cfg):
     """(kind, the planner takes ``key``, ticket words of a K split): what the loaded library says, asked once."""
     L = _lib.lib()
-    plans = L.egn_conv_plan_query(*key[:11], int(key[12]), cfg, (C.c_int * 12)()) == 0
+    plans = L.egn_conv_plan_takes(*key[:11], int(key[11]), int(key[12]), cfg) == 0       # (with the key's residual)
     return kind_of(cfg), plans, L.egn_conv2d_ticket_words(*key[:11], cfg)
 
 

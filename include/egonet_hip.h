@@ -72,6 +72,13 @@ int egn_conv_plan_query(int N, int H, int W, int Cin, int cs_in, int Cout,
                         int cs_out, int KH, int KW, int stride, int pad,
                         int out_nchw, int cfg, int* out);
 
+/* Host-only: 0 where config cfg takes the shape for a caller with (has_res) or
+ * without a residual in another buffer -- egn_conv_plan_query is not told about
+ * the residual; the stem and stride-2 kernels and an NCHW output take none. */
+int egn_conv_plan_takes(int N, int H, int W, int Cin, int cs_in, int Cout,
+                        int cs_out, int KH, int KW, int stride, int pad,
+                        int has_res, int out_nchw, int cfg);
+
 /* number of tile configurations compiled in; valid ids are 1..count */
 int egn_conv_num_configs(void);
 /* describe config id: tile_m (output pixels), tile_n (output channels) */

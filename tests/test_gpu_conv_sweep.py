@@ -15,12 +15,16 @@ K-split configurations also in egn_conv2d_f32's three-launch form -- and every l
   7. the tape's in-place residual (res is y) for its data-gradient requests.
 A summary per configuration (requests, worst |err| / (2^-24 A) and where) is printed, and written as JSON to
 conv_sweep.json in the directory EGONET_AMD_PARITY_DIR names, if it is set.
+
+The same launches and checks run on the hand-written edge list (conv_sweep.edge_requests, built for this device's CU
+count), one case per kernel family; each case then requires that every config of its family was run in every edge class
+the family admits, and adds an ``edge`` section to conv_sweep.json.  One step outside each predicate
+(conv_sweep.refusal_requests) the forced config is refused and nothing is written.
 """
 import ctypes as C
 import json
 import os
 import time
-import zlib
 
 import pytest
 import torch
@@ -40,28 +44,11 @@ class _Case(object):
         self.req = req
         self.ho, self.wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
         self.coutp = (cout + 15) // 16 * 16
-        g = torch.Generator().manual_seed(zlib.crc32(repr((req['key'], req['act'], req['entry'])).encode()))
-        self.x = S.act_like(n, h, w, cin, cs_in, g, 'cuda')
-        self.w = S.filt(cout, cin, kh, kw, g)
-        pad_val = 0.0 if req['entry'] == 'program' else 1.0     # fold_scale_shift zero-pads; the tape's ones do not
-        if req['stats']:
-            # the statistics entry points take the raw convolution (egonet_hip.h): the tape passes ones / zeros
-            sc, sh = torch.ones(self.coutp + 16), torch.zeros(self.coutp + 16)
-        else:
-            sgn = torch.where(torch.rand(cout, generator=g) < 0.3, -1.0, 1.0)
-            sc = torch.full((self.coutp + 16,), pad_val)
-            sc[:cout] = sgn * (0.5 + torch.rand(cout, generator=g))
-            sh = torch.zeros(self.coutp + 16)
-            sh[:cout] = 0.5 * torch.randn(cout, generator=g)
+        x, self.w, sc, sh, res = S.draw(req)                  # (seeded by the request; drawn on the CPU)
+        self.x = x.cuda()
         self.sc, self.sh = sc.cuda(), sh.cuda()
         self.ny = n * self.ho * self.wo * (cout if nchw else cs_out)
-        self.res = None
-        if has_res:
-            r = S.act_like(n, self.ho, self.wo, cout, cs_out, g, 'cuda') - 0.5 * (torch.rand(1, generator=g).item())
-            r.view(-1, cs_out)[:, cout:] = 0
-            if nchw:
-                r = r[..., :cout].permute(0, 3, 1, 2).contiguous()
-            self.res = r.reshape(-1)
+        self.res = None if res is None else res.cuda()
         self.packs = {}
         # the reference, float64 on the GPU
         x64 = self.x.view(n, h, w, cs_in)[..., :cin].permute(0, 3, 1, 2).double()
@@ -293,3 +280,124 @@ def test_every_candidate_config_matches_float64(sweep_pairs):
     assert {'program', 'ex', 'bnstats', 'conv2d'} <= {k.split('+')[0].split('(')[0] for k in per_entry}, per_entry
     assert any(k.startswith('ex') and 'tickets' in k for k in per_entry), per_entry
     assert any(p['alias'] for p in prs)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the edge list (conv_sweep.edge_requests): every config at the edges of its tile mapping
+# ---------------------------------------------------------------------------------------------------------------
+def _device_cus():
+    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+
+
+@pytest.fixture(scope='module')
+def edge_pairs():
+    cus = _device_cus()
+    reqs = S.edge_requests(cus)
+    return cus, reqs, S.pairs(reqs)
+
+
+def _mode_name(p, cfg, mode, stats, tickets):
+    k_split = tuner.ticket_words(p['key'], cfg) > 0
+    return mode + ('+stats' if stats else '') + ('+tickets' if tickets else '') + \
+        ('(3 launches)' if k_split and mode == 'conv2d' else '')
+
+
+@pytest.mark.parametrize('family', S.FAMILIES)
+def test_every_candidate_config_at_its_edges_matches_float64(edge_pairs, family):
+    """The pairs of the edge list whose config is of ``family``, through the same _Case / _run_pair as the recorded
+    corpus (the seven checks of this file's docstring); then: with this device's CU count, every config of the family
+    was run in every edge class its predicate admits."""
+    cus, reqs, prs = edge_pairs
+    t0 = time.time()
+    mine = [p for p in prs if S.family_of(p['cfg']) == family]
+    groups = {}
+    for p in mine:
+        groups.setdefault((p['key'], p['act'], p['entry'], p['alias'], p['stats']), []).append(p)
+    per_cfg, per_entry, fails, kinds_worst, reached = {}, {}, [], {}, {}
+    n_launch = 0
+    for gk, ps in groups.items():
+        case = _Case(ps[0])
+        for p in ps:
+            cfg = p['cfg']
+            ent = per_cfg.setdefault(cfg, dict(requests=0, launches=0, worst=0.0, where=''))
+            ent['requests'] += 1
+            reached.setdefault(cfg, set()).update(S.edge_classes(p, cfg, cus))
+            for mode, stats, tickets in _modes(p, cfg):
+                worst, f = _run_pair(case, cfg, mode, stats, tickets)
+                n_launch += 1
+                name = _mode_name(p, cfg, mode, stats, tickets)
+                per_entry[name] = per_entry.get(name, 0) + 1
+                ent['launches'] += 1
+                if worst >= ent['worst']:
+                    ent['worst'], ent['where'] = worst, '%s %s act %d %s' % (name, p['srcs'][0], p['act'],
+                                                                             'alias' if p['alias'] else '')
+                k = tuner.kind_of(cfg)
+                if worst >= kinds_worst.get(k, (0.0, ''))[0]:
+                    kinds_worst[k] = (worst, 'cfg %d %s key %s' % (cfg, p['srcs'][0], p['key']))
+                for msg in f:
+                    fails.append('cfg %d %s key %s act %d alias %d (%s): %s'
+                                 % (cfg, name, p['key'], p['act'], p['alias'], p['srcs'][0], msg))
+        del case
+    torch.cuda.empty_cache()
+    wall = time.time() - t0
+    L = _lib.lib()
+    print('\nconv edge sweep, %s: %d CUs, %d pairs of %d requests, %d checked launches, %.1f s'
+          % (family, cus, len(mine), len(groups), n_launch, wall))
+    print('entries: %s' % per_entry)
+    for c, v in sorted(per_cfg.items()):
+        buf = C.create_string_buffer(96)
+        if c > 0:
+            L.egn_conv_config_name(c, buf, 96)
+        print('cfg %2d %-44s %5d requests %5d launches  worst %7.2f  %s'
+              % (c, buf.value.decode() or 'cost model', v['requests'], v['launches'], v['worst'], v['where']))
+    for k, (v, where) in sorted(kinds_worst.items()):
+        print('worst |err| / (2^-24 A), %s: %.2f (bound %g) at %s' % (S.KIND_NAMES[k], v, S.C_BOUND[k], where))
+    summary = dict(cus=cus, pairs=len(mine), launches_checked=n_launch, sweep_s=round(wall, 1), entries=per_entry,
+                   worst_ratio_per_kind={S.KIND_NAMES[k]: dict(ratio=round(v, 2), where=where)
+                                         for k, (v, where) in kinds_worst.items()},
+                   configs={str(c): dict(v, worst=round(v['worst'], 2), classes=sorted(reached.get(c, ())))
+                            for c, v in sorted(per_cfg.items())},
+                   failures=fails[:200])
+    out_dir = os.environ.get('EGONET_AMD_PARITY_DIR')
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+        path, doc = os.path.join(out_dir, 'conv_sweep.json'), {}
+        if os.path.isfile(path):
+            with open(path) as fh:
+                doc = json.load(fh)
+        doc.setdefault('edge', {})[family] = summary
+        with open(path, 'w') as fh:
+            json.dump(doc, fh, indent=1)
+    assert not fails, '%d failing launches:\n%s' % (len(fails), '\n'.join(fails[:40]))
+    # every selectable config of the family, in every class the family admits
+    cfgs = [c for c in S.selectable_configs() if S.family_of(c) == family]
+    assert cfgs
+    missing = [(c, k) for c in cfgs for k in sorted(S.FAMILY_CLASSES[family])
+               if k not in reached.get(c, ()) and (c, k) not in S.NOT_REACHABLE and (family, k) not in S.NOT_REACHABLE]
+    assert not missing, missing
+
+
+def test_one_step_outside_each_predicate_is_refused_and_writes_nothing():
+    """conv_sweep.refusal_requests: egn_conv2d_f32 with the config forced returns non-zero before anything launches;
+    the output keeps its sentinel."""
+    L = _lib.lib()
+    stream = _lib.current_stream()
+    fails = []
+    for cfg, key, act, clause, at in S.refusal_requests():
+        n, h, w, cin, cs_in, cout, cs_out, kh, kw, stride, pad, has_res, nchw = key
+        ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+        ny = n * ho * wo * (cout if nchw else cs_out)
+        coutp = (cout + 15) // 16 * 16
+        x = torch.ones(n * h * w * cs_in, device='cuda')
+        wp = torch.ones(max((cin + 15) // 16 * kh * kw * 4 * coutp * 4, cout * cin * 48), device='cuda')
+        sc, sh = torch.ones(coutp + 16, device='cuda'), torch.zeros(coutp + 16, device='cuda')
+        res = torch.ones(ny, device='cuda') if has_res else None
+        ywhole, y = _guarded(ny, torch.float32, -7777.0)
+        rc = L.egn_conv2d_f32(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(sc), _lib.ptr(sh), _lib.ptr(res), _lib.ptr(y), n, h, w,
+                              cin, cs_in, cout, cs_out, kh, kw, stride, pad, act, int(nchw), cfg, stream)
+        torch.cuda.synchronize()
+        if rc == 0:
+            fails.append('cfg %d took %s (%s)' % (cfg, key, clause[1]))
+        if not bool((y == -7777.0).all()) or not _guards_intact(ywhole):
+            fails.append('cfg %d wrote on refusing %s' % (cfg, key))
+    assert not fails, '\n'.join(fails)
