@@ -202,7 +202,35 @@ SIGNATURES = {
     'egn_debug_mosaic_u8': (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p, C.c_long, _p]),
     'egn_debug_mosaic_host_u8': (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p, C.c_long]),
     'egn_program_op_info':(_i,[_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), C.c_char_p, _i]),
+    # inference plans (egonet_amd/plan.py)
+    'egn_conv_table_fingerprint': (C.c_uint, []),
+    'egn_plan_open': (_i, [C.c_char_p, C.POINTER(_p)]),
+    'egn_plan_parse': (_i, [_p, C.c_size_t, C.POINTER(_p)]),
+    'egn_plan_close': (None, [_p]),
+    'egn_plan_get_info': (_i, [_p, _p]),
+    'egn_plan_get_text': (_i, [_p, _i, C.c_char_p, _i]),
+    'egn_plan_get_stats': (_i, [_p, _i, _p, _i]),
+    'egn_plan_program_info': (_i, [_p, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                   C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i]),
+    'egn_plan_op_record': (_i, [_p, _i, _i, _p, _i, C.POINTER(_i)]),
+    'egn_plan_load': (_i, [_p, _i]),
+    'egn_plan_native_program': (_p, [_p, _i]),
+    'egn_plan_infer': (_i, [_p, _p, _i, _p, _p, _i, _d, _d, _i, _p, _p]),
+    'egn_box_to_crop_f64': (_i, [_p, _i, _d, _d, _i, _i, _p, _p, _p]),
 }
+
+
+class PlanInfo(C.Structure):
+    """egn_plan_info."""
+    _fields_ = [('format_version', _i), ('lib_version', _i), ('fingerprint', C.c_uint), ('arch', C.c_char * 32),
+                ('precision', _i), ('head_type', _i), ('decode', _i), ('J', _i), ('C', _i), ('H', _i), ('W', _i),
+                ('map_h', _i), ('map_w', _i), ('mul_x', _d), ('mul_y', _d), ('lifter_in', _i), ('lifter_out', _i),
+                ('ld_in', _i), ('n_sizes', _i), ('sizes', _i * 64), ('n_pieces', _i), ('n_programs', _i), ('loaded', _i)]
+
+
+class PlanOutputs(C.Structure):
+    """egn_plan_outputs."""
+    _fields_ = [('local', _p), ('kpts_2d', _p), ('kpts_3d', _p), ('euler', _p), ('alpha', _p)]
 
 _LIB = None
 

@@ -2,7 +2,8 @@
 
     python -m egonet_amd.build [--force]
 
-also builds ``tools/_build/kitti_eval_cli``, the KITTI evaluator as a stand-alone host program.
+also builds ``tools/_build/kitti_eval_cli``, the KITTI evaluator as a stand-alone host program, and
+``tools/_build/egonet_run``, the Python-free runner of inference plans.
 
 hipcc cross-compiles without a GPU.  The shared object is git-ignored but
 travels with the repo snapshot to the GPU box.  The library is linked to a
@@ -88,6 +89,28 @@ def build_cli(force=False, verbose=True):
     return CLI_OUT
 
 
+RUN_SRC = os.path.join(os.path.dirname(HERE), 'tools', 'egonet_run.cpp')
+RUN_OUT = os.path.join(os.path.dirname(HERE), 'tools', '_build', 'egonet_run')
+
+
+def build_run(force=False, verbose=True):
+    """tools/egonet_run.cpp -> tools/_build/egonet_run: the Python-free runner of inference plans (egonet_amd/plan.py),
+    host code compiled by hipcc (it calls the HIP runtime for its buffers) and linked against csrc/libegonet_hip.so,
+    which it finds beside the repository tree it was built in (rpath relative to the program)."""
+    build(verbose=verbose)
+    deps = [RUN_SRC, OUT, os.path.join(os.path.dirname(HERE), 'include', 'egonet_hip.h')]
+    if not force and os.path.isfile(RUN_OUT) and all(os.path.getmtime(d) <= os.path.getmtime(RUN_OUT) for d in deps):
+        return RUN_OUT
+    os.makedirs(os.path.dirname(RUN_OUT), exist_ok=True)
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    cmd = [hipcc, '--offload-arch=' + ARCH, '-O2', '-std=c++17', '-Wno-unused-result', '-I', os.path.join(os.path.dirname(HERE), 'include'), '-o',
+           RUN_OUT, RUN_SRC, '-L', CSRC, '-legonet_hip', '-Wl,-rpath,$ORIGIN/../../egonet_amd/csrc']
+    if verbose:
+        print(' '.join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return RUN_OUT
+
+
 def build(force=False, verbose=True, probes=False):
     """``probes``: the -DEGN_PROBES build for tools/ (timing-ablation / s_memtime-stamp builds and the kernel
     families that were measured and retired) -> tools/_build/libegonet_hip_probes.so; select it with
@@ -126,3 +149,4 @@ if __name__ == '__main__':
     print(build(force='--force' in sys.argv, probes='--probes' in sys.argv))
     if '--probes' not in sys.argv:
         print(build_cli(force='--force' in sys.argv))
+        print(build_run(force='--force' in sys.argv))

@@ -18,8 +18,10 @@
 //   85      S2r     3x3 s2 from the 48-channel branch                                                      conv_s2r.hip
 // The engine's tuner times the candidates on the real shape; cfg 0 = cost model (over the Staged family).
 #include <stdio.h>
+#include <string.h>
 
 #include "egn_internal.h"
+#include "plan_format.h"
 
 int egn_conv_launch_staged(const ConvArgs& a, DirectTile tile, size_t lds, hipStream_t stream);   // conv_mfma.hip
 int egn_conv_launch_dma(const ConvArgs& a, DirectTile tile, size_t lds, hipStream_t stream);      // conv_dma.hip
@@ -254,6 +256,20 @@ extern "C" int egn_conv_config_name(int cfg, char* buf, int len) {
   else
     snprintf(buf, len, "%s", c.name);
   return 0;
+}
+
+// what the ids MEAN, as one number: a plan file (plan.cpp) names configurations by id, and is refused by a library whose
+// table gives an id another kind, other tile sizes or another kernel
+extern "C" unsigned egn_conv_table_fingerprint(void) {
+  uint32_t crc = 0;
+  for (int cfg = 1; cfg <= kNumConfigs; ++cfg) {
+    char name[256] = {0};
+    egn_conv_config_name(cfg, name, (int)sizeof(name));
+    const int32_t row[4] = {cfg, egn_conv_config_kind(cfg), kConfigs[cfg - 1].tile_m(), kConfigs[cfg - 1].tile_n()};
+    crc = egn_plan_crc32(row, sizeof(row), crc);
+    crc = egn_plan_crc32(name, strlen(name), crc);
+  }
+  return crc;
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -19,6 +19,20 @@ extern "C" const char* egn_strerror(int code) {
   if (code == EGN_E_BADARG) return "egonet_hip: bad argument / unsupported shape";
   if (code == EGN_E_LDS) return "egonet_hip: tile does not fit in LDS";
   if (code == EGN_E_STATE) return "egonet_hip: program in wrong state";
+  switch (code) {      // plan files (csrc/plan.cpp)
+    case EGN_E_PLAN_IO: return "egonet_hip: plan file cannot be read";
+    case EGN_E_PLAN_TRUNCATED: return "egonet_hip: plan file is truncated";
+    case EGN_E_PLAN_MAGIC: return "egonet_hip: not a plan file (bad magic)";
+    case EGN_E_PLAN_VERSION: return "egonet_hip: plan file of another format or library version";
+    case EGN_E_PLAN_FINGERPRINT: return "egonet_hip: plan file written against another tile-config table";
+    case EGN_E_PLAN_CRC: return "egonet_hip: plan file section fails its CRC";
+    case EGN_E_PLAN_COUNT: return "egonet_hip: plan file count exceeds the bytes that remain";
+    case EGN_E_PLAN_OP: return "egonet_hip: plan file holds an unknown op kind";
+    case EGN_E_PLAN_SLOT: return "egonet_hip: plan file names a slot outside its program";
+    case EGN_E_PLAN_REF: return "egonet_hip: plan file reference lies outside its slot";
+    case EGN_E_PLAN_WAIT: return "egonet_hip: plan file op waits for a later or non-signalling op";
+    case EGN_E_PLAN_FORMAT: return "egonet_hip: plan file is inconsistent";
+  }
   if (code > 0) return hipGetErrorString((hipError_t)code);
   return "egonet_hip: unknown error";
 }

@@ -543,24 +543,61 @@ for _rule in F16_RULES:          # r.f16, r.f16s2, r.f16x: whether the recorder 
     setattr(_Recorder, _rule.mode, property(lambda self, rule=_rule: rule in self.rules))
 
 
-class Program(object):
-    """Owns a native egn_program plus the torch storage its slots point to."""
+class ProgramCalls(object):
+    """THE place every call that builds an egn_program goes through (``Program._emit``, for HRNet and lifter programs
+    alike): ``calls(name, *args)`` calls the library's entry ``name(handle, *args)`` and checks its code, and -- with
+    a ``log`` -- appends (name, args) first.  A list among the arguments (the fuse terms and shifts, the waits) becomes
+    the C array the entry takes.  Without a handle nothing is called: the log alone is the program, which is how
+    egonet_amd.plan writes the launch list of a model to a file (no GPU needed: K-split ops allocate device words when
+    they are added)."""
 
-    def __init__(self, rec, device, n_user_slots):
-        L = _lib.lib()
-        self.lib = L
+    def __init__(self, lib=None, handle=None, log=None):
+        self.lib, self.handle, self.log = lib, handle, log
+
+    def __call__(self, name, *args, what='', unchecked=False):
+        if self.log is not None:
+            self.log.append((name, args))
+        if self.handle is None:
+            return
+        cargs = []
+        for a in args:
+            if isinstance(a, list):
+                a = ((Ref if a and isinstance(a[0], Ref) else C.c_int) * len(a))(*a)
+            cargs.append(a)
+        code = getattr(self.lib, name)(self.handle, *cargs)
+        if not unchecked:
+            _lib.check(code, what)
+
+
+class Program(object):
+    """Owns a native egn_program plus the torch storage its slots point to.  ``log``: a list that receives every
+    building call (``ProgramCalls``); ``native=False``: only that log, the arena size and the packed weights are made --
+    no device storage, no egn_program (``device`` may then be None: nothing is measured, see ``_choose_and_pack``)."""
+
+    def __init__(self, rec, device, n_user_slots, log=None, native=True, pack=pack_for_kind):
         self.device = device
         arena_bytes = rec.plan_arena()
+        self.arena_bytes = arena_bytes
+        self.tags = []
+        self.meta = []
+        self._choose_and_pack(rec, device, pack)
+        if not native:
+            rec.pack_pending()
+            self.weight_bytes = rec.blob_off
+            self.lib = self.handle = None
+            self.call = ProgramCalls(log=log if log is not None else [])
+            for kind, op in rec.ops:
+                self._emit(kind, op)
+            return
+        L = _lib.lib()
+        self.lib = L
         self.arena = torch.zeros(max(arena_bytes, 256) // 4, dtype=torch.float32, device=device)
-        self._choose_and_pack(rec, device)
         self.weights = rec.weights_blob(device)
         self.handle = C.c_void_p(L.egn_program_create(SLOT_USER0 + n_user_slots))
         if not self.handle:
             raise _lib.EgonetHipError('egn_program_create failed')
-        self.arena_bytes = arena_bytes
         self.weight_bytes = rec.blob_off
-        self.tags = []
-        self.meta = []
+        self.call = ProgramCalls(L, self.handle, log)
         _lib.check(L.egn_program_bind(self.handle, SLOT_ARENA, _lib.ptr(self.arena)))
         _lib.check(L.egn_program_bind(self.handle, SLOT_WEIGHTS, _lib.ptr(self.weights)))
         # (ops may own device memory -- the ticket words of K-split convolutions: allocate it on the program's device)
@@ -581,37 +618,37 @@ class Program(object):
         plain_act = (op['act'] & 0xf) in (ACT_NONE, ACT_RELU) and not (op['act'] & ACT_RES_AFTER)
         return tuner.ALL_KINDS if plain_act else tuner.DIRECT
 
-    def _choose_and_pack(self, rec, device):
+    def _choose_and_pack(self, rec, device, pack=pack_for_kind):
         """Tile configuration per conv (measured table / autotune) and the filter in the layout
-        that configuration's kernel stages through LDS."""
+        that configuration's kernel stages through LDS.  ``device`` None: the table's choice or the cost model's 0,
+        never a measurement.  ``pack``: ``pack_for_kind`` or a caller's memo of it."""
         for kind, op in rec.ops:
             if kind == 'convpair':          # both halves read the F(4x4,3x3) register-feed layout (configs 86 / 82)
                 for half in (op['a'], op['b']):
                     if half['w'] is None:
-                        half['w'] = rec.weight(pack_for_kind(half['w_src'], 3))
+                        half['w'] = rec.weight(pack(half['w_src'], 3))
                 continue
             if kind != 'conv' or op.get('w') is not None:
                 continue
             if 'cfg' not in op:
-                op['cfg'] = tuner.choose(device, self._conv_key(op), self._conv_kinds(op))
-            op['w'] = rec.weight(pack_for_kind(op['w_src'], tuner.kind_of(op['cfg'])))
+                op['cfg'] = tuner.choose(device, self._conv_key(op), self._conv_kinds(op), measure=device is not None)
+            op['w'] = rec.weight(pack(op['w_src'], tuner.kind_of(op['cfg'])))
 
     def _emit(self, kind, op):
-        L, h = self.lib, self.handle
+        call = self.call
         flops, nbytes = 0.0, 0.0
         if kind in ('fork', 'join'):
-            _lib.check(L.egn_program_fork(h) if kind == 'fork' else L.egn_program_join(h))
+            call('egn_program_fork' if kind == 'fork' else 'egn_program_join')
             self.meta.append(dict(kind=kind, klass=kind, tag='', flops=0.0, bytes=0.0, cfg=0))
             return
-        _lib.check(L.egn_program_set_lane(h, op.get('lane', 0)))
+        call('egn_program_set_lane', op.get('lane', 0))
         if kind == 'conv':
             x, y = op['x'], op['y']
             res = op['res'].ref() if op['res'] is not None else NULL_REF
             cs_out = y.cs if not op['out_nchw'] else op['cout']
-            _lib.check(L.egn_program_add_conv2d(
-                h, x.ref(), op['w'], op['scale'], op['shift'], res, y.ref(),
-                x.n, x.h, x.w, op['cin'], x.cs, op['cout'], cs_out, op['kh'], op['kw'],
-                op['stride'], op['pad'], op['act'], op['out_nchw'], op.get('cfg', 0)), op['tag'])
+            call('egn_program_add_conv2d', x.ref(), op['w'], op['scale'], op['shift'], res, y.ref(),
+                 x.n, x.h, x.w, op['cin'], x.cs, op['cout'], cs_out, op['kh'], op['kw'],
+                 op['stride'], op['pad'], op['act'], op['out_nchw'], op.get('cfg', 0), what=op['tag'])
             m = x.n * op['ho'] * op['wo']
             flops = 2.0 * m * op['cout'] * op['cin'] * op['kh'] * op['kw']
             nbytes = 4.0 * (x.n * x.h * x.w * op['cin'] + m * op['cout'] * (2 if op['res'] is not None else 1)
@@ -621,9 +658,9 @@ class Program(object):
         elif kind in _RULE_OF_KIND:
             rule, x, y = _RULE_OF_KIND[kind], op['x'], op['y']
             res = [op['res'].ref() if op['res'] is not None else NULL_REF] if rule.res_arg else []
-            _lib.check(getattr(L, rule.add)(*([h, x.ref(), op['w'], op['scale'], op['shift']] + res +
-                                              [y.ref(), x.n, x.h, x.w, op['cin'], op['cout'], op['act']] +
-                                              ([op['stride']] if rule.stride_arg else []))), op['tag'])
+            call(rule.add, *([x.ref(), op['w'], op['scale'], op['shift']] + res +
+                             [y.ref(), x.n, x.h, x.w, op['cin'], op['cout'], op['act']] +
+                             ([op['stride']] if rule.stride_arg else [])), what=op['tag'])
             klass, flops, nbytes = lowered_cost(kind, op)
         elif kind == 'convpair':
             args, klass = [], []
@@ -637,60 +674,56 @@ class Program(object):
                 nbytes += 4.0 * (m * half['cin'] + m * half['cout'] * (2 if half['res'] is not None else 1)
                                  + half['cout'] * half['cin'] * 9)
                 klass.append('%d->%d@%dx%d' % (half['cin'], half['cout'], x.h, x.w))
-            _lib.check(L.egn_program_add_conv2d_pair(h, *(args + [0])), op['tag'])
+            call('egn_program_add_conv2d_pair', *(args + [0]), what=op['tag'])
             klass = 'convpair3x3s1 ' + ' + '.join(klass)
         elif kind == 'fuse':
             y = op['y']
             terms = op['terms']
-            refs = (Ref * len(terms))(*[t.ref() for t, _ in terms])
-            shifts = (C.c_int * len(terms))(*[s for _, s in terms])
-            _lib.check(L.egn_program_add_fuse(h, y.ref(), y.n, y.h, y.w, y.c, y.cs, len(terms), refs,
-                                              shifts, op['relu']), op['tag'])
+            call('egn_program_add_fuse', y.ref(), y.n, y.h, y.w, y.c, y.cs, len(terms), [t.ref() for t, _ in terms],
+                 [s for _, s in terms], op['relu'], what=op['tag'])
             nbytes = 4.0 * y.n * y.c * (y.h * y.w + sum((y.h >> s) * (y.w >> s) for _, s in terms))
             klass = 'fuse%d %d@%dx%d' % (len(terms), y.c, y.h, y.w)
         elif kind == 'to_nhwc':
             y = op['y']
-            _lib.check(L.egn_program_add_nchw_to_nhwc(h, op['x'], y.ref(), y.n, y.c, y.h, y.w, y.cs))
+            call('egn_program_add_nchw_to_nhwc', op['x'], y.ref(), y.n, y.c, y.h, y.w, y.cs)
             nbytes = 4.0 * y.n * y.h * y.w * (y.c + y.cs)
             klass = 'nchw2nhwc %d@%dx%d' % (y.c, y.h, y.w)
         elif kind == 'to_nchw':
             x = op['x']
-            _lib.check(L.egn_program_add_nhwc_to_nchw(h, x.ref(), op['y'], x.n, op['c'], x.h, x.w, x.cs))
+            call('egn_program_add_nhwc_to_nchw', x.ref(), op['y'], x.n, op['c'], x.h, x.w, x.cs)
             nbytes = 8.0 * x.n * x.h * x.w * op['c']
             klass = 'nhwc2nchw %d@%dx%d' % (op['c'], x.h, x.w)
         elif kind == 'pixshuf':
             x = op['x']
-            _lib.check(L.egn_program_add_pixel_shuffle(h, x.ref(), op['y'], x.n, op['c'], x.h, x.w, x.cs, op['up']))
+            call('egn_program_add_pixel_shuffle', x.ref(), op['y'], x.n, op['c'], x.h, x.w, x.cs, op['up'])
             nbytes = 8.0 * x.n * x.h * x.w * op['c'] * op['up'] ** 2
             klass = 'pixel_shuffle%d %d@%dx%d' % (op['up'], op['c'], x.h, x.w)
         elif kind == 'pwpair':
             hb, rb, ob, nb = op['h'], op['res'], op['out'], op['hn']
             none = NULL_REF
-            _lib.check(L.egn_program_add_pw_pair(h, hb.ref(), rb.ref() if rb is not None else none, op['w3'], op['shift3'],
-                                                 op['w1'] if nb is not None else none,
-                                                 op['shift1'] if nb is not None else none, ob.ref(),
-                                                 nb.ref() if nb is not None else none, op['m'], op['relu1']))
+            call('egn_program_add_pw_pair', hb.ref(), rb.ref() if rb is not None else none, op['w3'], op['shift3'],
+                 op['w1'] if nb is not None else none, op['shift1'] if nb is not None else none, ob.ref(),
+                 nb.ref() if nb is not None else none, op['m'], op['relu1'])
             flops = 2.0 * op['m'] * 64 * 256 * (2 if nb is not None else 1)
             nbytes = 4.0 * op['m'] * (64 + 256 * (2 if rb is not None else 1) + (64 if nb is not None else 0))
             klass = 'pwpair%d%d 64->256%s@%dx%d' % (int(rb is not None), op['relu1'], '->64' if nb is not None else '',
                                                     hb.h, hb.w)
         elif kind == 'ramps':
             y = op['y']
-            _lib.check(L.egn_program_add_ramps(h, y.ref(), y.n, y.h, y.w, y.cs, op['c0']))
+            call('egn_program_add_ramps', y.ref(), y.n, y.h, y.w, y.cs, op['c0'])
             nbytes = 8.0 * y.n * y.h * y.w
             klass = 'ramps'
         elif kind == 'decode':
-            _lib.check(L.egn_program_add_decode(h, op['hm'], op['n'], op['k'], op['h'], op['w'],
-                                                op['mode'], op['xy'], op['mx'], op['idx']))
+            call('egn_program_add_decode', op['hm'], op['n'], op['k'], op['h'], op['w'], op['mode'], op['xy'], op['mx'],
+                 op['idx'])
             nbytes = 4.0 * op['n'] * op['k'] * op['h'] * op['w']
             klass = 'decode%d %dx%d' % (op['mode'], op['h'], op['w'])
         else:
             raise ValueError(kind)
-        L.egn_program_tag(h, (op.get('tag') or klass).encode(), flops, nbytes)
+        call('egn_program_tag', (op.get('tag') or klass).encode(), flops, nbytes, unchecked=True)
         if op.get('signal') or op.get('waits'):     # (tokens are op indices: the program has one op per recorded op)
             waits = op.get('waits', [])
-            _lib.check(L.egn_program_set_deps(h, int(bool(op.get('signal'))), (C.c_int * len(waits))(*waits),
-                                              len(waits)), op.get('tag', ''))
+            call('egn_program_set_deps', int(bool(op.get('signal'))), list(waits), len(waits), what=op.get('tag', ''))
         self.meta.append(dict(kind=kind, klass=klass, tag=op.get('tag', ''), flops=flops, bytes=nbytes,
                               cfg=op.get('cfg', 0) if kind == 'conv' else 0))
 

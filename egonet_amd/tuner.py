@@ -176,11 +176,12 @@ def _pick(entry, key, kinds, ticket_cap=None, inplace_res=False):
     return min(fit, key=fit.get) if fit else 0
 
 
-def choose(device, key, kinds=DIRECT, ticket_cap=None, inplace_res=False):
+def choose(device, key, kinds=DIRECT, ticket_cap=None, inplace_res=False, measure=True):
     """The fastest measured configuration the caller can use (``usable``) for the shape ``key`` (the ``shape_key``
     arguments): the shipped table, else the in-process autotune, else 0.  EGONET_AMD_WINO=0 never returns a Winograd
     configuration, =1 always the F(2x2,3x3) one where one is usable, =43 / =43b / =43w an F(4x4,3x3) one where one is
-    (cfg 70 / cfg 80 / cfg 86, conv_wino4w_kernel, first; else F(2x2,3x3)); EGONET_AMD_F43=0 keeps F(4x4,3x3) out."""
+    (cfg 70 / cfg 80 / cfg 86, conv_wino4w_kernel, first; else F(2x2,3x3)); EGONET_AMD_F43=0 keeps F(4x4,3x3) out.
+    ``measure=False`` (an export without a GPU, egonet_amd.plan): the table or 0, never a measurement."""
     key, kinds = tuple(key), frozenset(kinds)
     mode = os.environ.get('EGONET_AMD_WINO', '')
     if os.environ.get('EGONET_AMD_F43', '1') == '0' or mode in ('0', '1'):
@@ -202,7 +203,7 @@ def choose(device, key, kinds=DIRECT, ticket_cap=None, inplace_res=False):
         kinds = kinds - F43_KINDS
     entry = _load().get(name)
     if entry is None:
-        if os.environ.get('EGONET_AMD_AUTOTUNE', '1') == '0':
+        if not measure or os.environ.get('EGONET_AMD_AUTOTUNE', '1') == '0':
             return 0           # deterministic: the shipped table or the cost model, whatever was tuned earlier
         if name not in _tuned_here:
             cfg, times = tune(device, key)

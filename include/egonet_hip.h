@@ -19,6 +19,7 @@
 #ifndef EGONET_HIP_H
 #define EGONET_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -1148,6 +1149,107 @@ int egn_debug_mosaic_u8(const float* img, int C, int H, int W, const float* maps
                         const float* lohi, const uint8_t* lut, uint8_t* out, long stride, void* stream);
 int egn_debug_mosaic_host_u8(const float* img, int C, int H, int W, const float* maps, int n, int J, int h, int w,
                              const float* lohi, const uint8_t* lut, uint8_t* out, long stride);
+
+/* ------------------------------------------------------------------------
+ * Inference plans (.egnplan): the planned, tuned and packed network of EgoNet.infer_crops(refine=None), written once
+ * by egonet_amd.plan.export_plan and run from here with nothing but this library -- no Python, no model, no filter
+ * packing, no autotune.  A file holds, per exported batch size, one HRNet and one lifter launch program as the list of
+ * egn_program_* calls the engine made, the packed weights as pieces stored once, and the constants of the chain
+ * (csrc/plan_format.h).  The reference has no counterpart (it builds its torch modules at every start).
+ *
+ * egn_plan_open / egn_plan_parse (a file in memory; the bytes are copied) are HOST-ONLY (csrc/plan.cpp, no HIP call).
+ * Before they return 0 they have checked: magic, format version, egn_version and egn_conv_table_fingerprint of the
+ * writer against this library's, the CRC-32 of every section; every count against the bytes that remain, before
+ * anything is allocated; every op kind, argument count and dimension; every slot index; every wait (an earlier op
+ * that signals); and for every pointer reference its offset and -- where the op's shape gives one -- its extent
+ * against the size of the slot it points into.  A file that fails is never loaded:
+ *   EGN_E_PLAN_IO           the file cannot be read
+ *   EGN_E_PLAN_TRUNCATED    the file ends inside or before a section (the END section closes a file)
+ *   EGN_E_PLAN_MAGIC / _VERSION (format or library) / _FINGERPRINT (the tile-config ids mean something else) / _CRC
+ *   EGN_E_PLAN_COUNT        a count or length larger than the bytes that remain in its section (or than its cap)
+ *   EGN_E_PLAN_OP           an unknown op kind
+ *   EGN_E_PLAN_SLOT         a slot index outside the program's slots (or NULL where a pointer is required)
+ *   EGN_E_PLAN_REF          an offset, or offset + extent, past its slot; an offset that is not 16-byte aligned
+ *   EGN_E_PLAN_WAIT         a wait on a later op, on itself or on an op that does not signal
+ *   EGN_E_PLAN_FORMAT       anything else inconsistent (section order, roles, dimensions, missing programs)
+ * egn_plan_get_info / _get_text (what = 0 arch, 1 the EGONET_AMD_* switches of the recording) / _get_stats (which =
+ * 0..3: mean_in, std_in, mean_out, std_out; n must be the vector's length) / _program_info (per program: type 0 HRNet /
+ * 1 lifter, its batch size, arena and weight bytes, op count, ops with waits, the op kinds -- kinds may be NULL) /
+ * _op_record (the canonical little-endian record of one op: u32 kind, lane, signal, nwaits, waits[], nints, i32 ints[],
+ * u32 nrefs, {i32 slot, i64 off}[], f64 flops, f64 bytes, u32 tag length, tag; buf NULL: only *used) read a parsed plan.
+ *
+ * egn_plan_load (device >= 0: hipSetDevice first; < 0: the current device) uploads every piece once, assembles each
+ * program's weights slot on the device, replays the calls into egn_programs (the filter extent of every convolution
+ * is checked against its tile config's layout first) and allocates ONE arena and one set of temporaries for the
+ * largest exported size.  Everything is freed by egn_plan_close.
+ * egn_plan_infer runs infer_crops' chain on `stream`: all pointers are DEVICE pointers; crops [n,C,H,W] fp32,
+ * centers / scales [n,2] f64; outputs local [n,J,2] fp32, kpts_2d [n,2J] f64, kpts_3d [n,D] f64 and, for the 96-output
+ * lifter, euler [n,3] f64 and alpha [n] f64 (alpha_mode 0 'proj' needs has_K with fx, cx; without K it is 'trans', as
+ * in infer_crops).  It allocates nothing and never waits for the device.  An n that is not an exported size runs as
+ * chunks of exported sizes, greedy from the largest; an n that cannot be composed is EGN_E_BADARG before anything is
+ * launched.  Eager runs only (no capture / replay); one plan runs one call at a time (a call on another stream is
+ * ordered behind the previous one).  Out of scope: refine = 'pnp', kpts_x_for_alpha, the second in-flight copy
+ * (slot = 1), training.
+ * egn_plan_native_program: the egn_program of program index `program` of a LOADED plan (NULL otherwise), owned by the
+ * plan -- for egn_program_num_ops / _op_info / _ticket_ops / _run_timed.
+ *
+ * egn_conv_table_fingerprint (host only): CRC-32 over every tile-config id's kind, tile sizes and kernel symbol.
+ * egn_box_to_crop_f64 (host only, HOST pointers): boxes [n,4] (left, top, right, bottom) -> modify_bbox's center [n,2]
+ * and scale [n,2] (enlarge about the centre, then grow to target_ar = height / width of the crop) and, unless M is
+ * NULL, the forward affines M [n,6] image -> crop that egn_crop_frames_warp_normalize_u8 takes: the float64 bits of
+ * common/img_proc.py::modify_bbox and common/crop_gpu.py::forward_affines (egonet.py:105-155, img_proc.py:26-64).
+ * ---------------------------------------------------------------------- */
+#define EGN_E_PLAN_IO          (-10)
+#define EGN_E_PLAN_TRUNCATED   (-11)
+#define EGN_E_PLAN_MAGIC       (-12)
+#define EGN_E_PLAN_VERSION     (-13)
+#define EGN_E_PLAN_FINGERPRINT (-14)
+#define EGN_E_PLAN_CRC         (-15)
+#define EGN_E_PLAN_COUNT       (-16)
+#define EGN_E_PLAN_OP          (-17)
+#define EGN_E_PLAN_SLOT        (-18)
+#define EGN_E_PLAN_REF         (-19)
+#define EGN_E_PLAN_WAIT        (-20)
+#define EGN_E_PLAN_FORMAT      (-21)
+
+typedef struct egn_plan egn_plan;
+typedef struct egn_plan_info {
+  int format_version, lib_version;
+  unsigned fingerprint;
+  char arch[32];
+  int precision;              /* 0 f32, 1 f16, 2 f16s2, 3 f16x */
+  int head_type;              /* 0 coordinates, 1 heatmap */
+  int decode;                 /* 0 hard, 1 soft, 2 coords */
+  int J, C, H, W, map_h, map_w;
+  double mul_x, mul_y;
+  int lifter_in, lifter_out, ld_in;
+  int n_sizes, sizes[64];
+  int n_pieces, n_programs, loaded;
+} egn_plan_info;
+typedef struct egn_plan_outputs {
+  float* local;
+  double* kpts_2d;
+  double* kpts_3d;
+  double* euler;
+  double* alpha;
+} egn_plan_outputs;
+
+unsigned egn_conv_table_fingerprint(void);
+int egn_plan_open(const char* path, egn_plan** plan);
+int egn_plan_parse(const void* bytes, size_t n, egn_plan** plan);
+void egn_plan_close(egn_plan* plan);
+int egn_plan_get_info(const egn_plan* plan, egn_plan_info* info);
+int egn_plan_get_text(const egn_plan* plan, int what, char* buf, int len);
+int egn_plan_get_stats(const egn_plan* plan, int which, double* out, int n);
+int egn_plan_program_info(const egn_plan* plan, int program, int* type, int* n, long long* arena_bytes,
+                          long long* weight_bytes, int* n_ops, int* ops_with_waits, int* kinds, int kinds_len);
+int egn_plan_op_record(const egn_plan* plan, int program, int op, void* buf, int len, int* used);
+int egn_plan_load(egn_plan* plan, int device);
+egn_program* egn_plan_native_program(const egn_plan* plan, int program);
+int egn_plan_infer(egn_plan* plan, const float* crops, int n, const double* centers, const double* scales, int has_K,
+                   double fx, double cx, int alpha_mode, const egn_plan_outputs* outputs, void* stream);
+int egn_box_to_crop_f64(const double* boxes, int n, double target_ar, double enlarge, int out_w, int out_h,
+                        double* center, double* scale, double* M);
 
 #ifdef __cplusplus
 }
