@@ -150,6 +150,9 @@ SIGNATURES = {
     'egn_conv3x3_hx_wpack_bytes': (C.c_long, [_i, _i]),
     'egn_conv3x3_hx_f32': (_i, [_p] * 6 + [_i] * 7 + [_p]),
     'egn_program_add_conv3x3_hx': (_i, [_p] + [Ref] * 6 + [_i] * 7),
+    'egn_conv3x3_h16_applies': (_i, [_i] * 13),
+    'egn_conv3x3_h16_f32': (_i, [_p] * 6 + [_i] * 10 + [_p]),
+    'egn_program_add_conv3x3_h16': (_i, [_p] + [Ref] * 6 + [_i] * 10),
     'egn_pw_pair_f32': (_i, [_p] * 8 + [_i, _i, _p]),
     'egn_program_add_ramps': (_i, [_p, Ref, _i, _i, _i, _i, _i]),
     'egn_program_add_decode': (_i, [_p, Ref, _i, _i, _i, _i, _i, Ref, Ref, Ref]),

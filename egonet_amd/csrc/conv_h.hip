@@ -2,7 +2,9 @@
 // v_mfma_f32_16x16x32_f16 with fp32 accumulators (precision = 'f16', DESIGN "f16-operand mode").  It lives BESIDE the
 // config table and the tuner (no kConfigs row, no filter kind of theirs): egn_conv3x3_h_applies is the one predicate.
 //
-// Activations stay fp32 NHWC in HBM.  A block owns TM output pixels (TNB images x TH x TW, all powers of two, so a map
+// Activations stay fp32 NHWC in HBM -- except a tensor between two ops of this family that activations = 'f16' stores as f16
+// (ConvHArgs::x16 / y16, DESIGN 3.16d: the producer applies h_round_f16, the reader stages the f16 as it lies; the same
+// operand bits).  A block owns TM output pixels (TNB images x TH x TW, all powers of two, so a map
 // smaller than 8 x 8 packs several images into the tile) x TN output channels.  The input channels are walked in chunks
 // of 48: per chunk the block stages the halo tile [TNB][TH+2][TW+2][48] into LDS, converting fp32 -> f16 on the way
 // (clamp to +-65504, then the compiler's v_cvt_pk_f16_f32 under the default mode: round-to-nearest-even -- not the
@@ -51,6 +53,7 @@
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // What follows from the input-channel chunk CK (48: the W48 widths; 32: the 32-multiple widths, 'f16x').
 template <int CK>
@@ -65,6 +68,18 @@ constexpr int H_CK = 48;      // input channels per chunk of the 'f16' / 'f16s2'
 constexpr int H_KS = ConvHChunk<48>::KS;
 constexpr float H_F16_MAX = 65504.0f;
 
+// THE rounding of an activation to f16: clamp to +-65504, then round to nearest even.  The fp32 staging applies it to what
+// it loads and the f16 epilogue (ConvHArgs::y16) to what it stores, so a tensor stored as f16 holds the very bits its
+// reader would have put into LDS.
+__device__ __forceinline__ _Float16 h_round_f16(float v) {
+  return (_Float16)__builtin_fminf(__builtin_fmaxf(v, -H_F16_MAX), H_F16_MAX);
+}
+
+// 8 bytes per lane at voff (a vector store: out-of-range offsets drop it)
+__device__ __forceinline__ void egn_buf_store8(__amdgpu_buffer_rsrc_t r, unsigned voff, u32x2 v) {
+  __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, 0, 0);
+}
+
 // a 16-byte B fragment: lane offset in a VGPR, wave-uniform offset in an SGPR (non-template wrapper, as conv_common.h's)
 __device__ __forceinline__ f16x8 h_load_b(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
   return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
@@ -75,13 +90,23 @@ struct ConvHTile {
   static constexpr int TM = WM * MT * 16, TN = WN * NT * 16;
   static constexpr int SC_LD = NT * 16 + 4;                         // floats per row of a wave's epilogue slab
   static constexpr int EPI_BYTES = WM * WN * MT * 16 * SC_LD * 4;
-  // float4 a thread stages per batch: 5 * 256 covers the 100-pixel halo of an 8 x 8 tile, the 180 pixels of 8 x 16 are two
-  static constexpr int SB = 5;
   // the next chunk's batch 0 in flight during the products: not for the 48-output-channel tile, whose layers in HRNet have
   // one chunk (48 -> 48) and whose staging registers, live across the products, would cost it a wave per SIMD
   // (the same holds for the stride-2 64 x 48 tile)
   // (CK = 32: the 64-channel tile prefetches too; the 32-channel tile's layers have one chunk)
   static constexpr bool PREFETCH = TN == 96 || TN == 64;
+};
+
+// Staging items (16 bytes: 4 fp32 or 8 f16 channels of one halo pixel) a thread holds per batch.
+//   fp32 input: stride 1, 5 * 256 covers the 100-pixel halo of an 8 x 8 tile at CK = 48; stride 2, the 289-pixel halo of an
+//   8 x 8 tile is 13.5 items per thread: two batches of 7 (two round trips to memory, not three; one batch of 14 spills).
+//   f16 input (X16): half the items.  Stride 1: 100 pixels are 600 items at CK = 48 (3 per thread) and 400 at CK = 32 (2);
+//   stride 2: 289 pixels are 1734 (one batch of 7) and 1156 (one batch of 5).
+template <int CK, int S, bool X16>
+struct ConvHStage {
+  static constexpr int SB = !X16 ? (S == 1 ? 5 : 7) : (S == 1 ? (CK == 48 ? 3 : 2) : (CK == 48 ? 7 : 5));
+  static constexpr int CPI = X16 ? 8 : 4;       // channels per item
+  static constexpr int EB = X16 ? 2 : 4;        // bytes per element of x
 };
 
 // Stride 2: the row bits of a tile row index, rotated right by one.  The 16 rows of an A fragment are then 8 columns of
@@ -91,14 +116,15 @@ __device__ __forceinline__ int h_tile_row(int r, int lth) {
   return S == 1 || lth == 0 ? r : (r >> 1) | ((r & 1) << (lth - 1));
 }
 
-template <int CK, int S, int WM, int WN, int MT, int NT>
+// X16: x is stored as f16 (the bits h_round_f16 gives): an item is 8 channels, one 16-byte load and one 16-byte LDS write,
+// no conversion.  The LDS layout, the fragment reads and the products do not know the difference.
+template <int CK, int S, int WM, int WN, int MT, int NT, bool X16>
 __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
   using T = ConvHTile<WM, WN, MT, NT>;
+  using G = ConvHStage<CK, S, X16>;
   constexpr int H_CK = CK, H_KS = ConvHChunk<CK>::KS, H_PIXB = ConvHChunk<CK>::PIXB;
   static_assert(WM * WN == 4, "four waves");
-  // stride 2: the 289-pixel halo of an 8 x 8 tile is 13.5 float4 per thread: two batches of 7 (two round trips to memory,
-  // not three; one batch of 14 spills)
-  constexpr int SB = S == 1 ? T::SB : 7;
+  constexpr int SB = G::SB, CPI = G::CPI, EB = G::EB;
   extern __shared__ float4 smem_f4[];
   char* smem = reinterpret_cast<char*>(smem_f4);
   unsigned* sOff = reinterpret_cast<unsigned*>(smem);        // [npix] byte offset of halo pixel (channel 0) in x, or EGN_OOB
@@ -128,7 +154,7 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
     const int hx = S == 1 ? col : (col <= a.TW ? 2 * col : 2 * (col - a.TW) - 1);   // stride 2: even columns first
     const int n = n_base + b, iy = S * oy0 + hy - 1, ix = S * ox0 + hx - 1;
     const bool ok = n < a.N && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-    sOff[p] = ok ? (unsigned)((n * a.H + iy) * a.W + ix) * (unsigned)(a.Cin * 4) : EGN_OOB;
+    sOff[p] = ok ? (unsigned)((n * a.H + iy) * a.W + ix) * (unsigned)(a.Cin * EB) : EGN_OOB;
   }
 
   // per lane: LDS byte offset of the top-left tap of its MT tile rows, and per K step the offset of its 8 channels
@@ -165,9 +191,9 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
     for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.x), 0, (unsigned)((size_t)a.N * a.H * a.W * a.Cin * 4), EGN_RSRC_WORD3);
+      const_cast<float*>(a.x), 0, (unsigned)((size_t)a.N * a.H * a.W * a.Cin * EB), EGN_RSRC_WORD3);
   const int nchunk = a.Cin / H_CK;
-  const int nstage = a.npix * (H_CK / 4);   // float4 items of a chunk's halo tile
+  const int nstage = a.npix * (H_CK / CPI);   // 16-byte items of a chunk's halo tile
   // B fragments: [cout tile][chunk][step][lane] x 16 bytes -- one lane offset in a register, the rest is wave-uniform
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(a.w), 0, (unsigned)((a.Cout / 16) * nchunk * (H_KS * 1024)), EGN_RSRC_WORD3);
@@ -176,7 +202,7 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) wb[nt] = (ct * (T::TN / 16) + wn * NT + nt) * nchunk * (H_KS * 1024);
 
-  // Staging of a chunk's halo tile, SB float4 per thread and batch: all loads of a batch are issued before the first
+  // Staging of a chunk's halo tile, SB items per thread and batch: all loads of a batch are issued before the first
   // is converted, and (T::PREFETCH) batch 0 of the NEXT chunk is issued before the current chunk's products, so its HBM latency
   // hides behind them (an 8 x 8 tile is one batch, 8 x 16 two; tiles of many tiny images have more).
   f32x4 sv[SB];
@@ -184,25 +210,29 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
 #pragma unroll
     for (int j = 0; j < SB; ++j) {
       const int idx = (batch * SB + j) * 256 + tid;
-      const int p = idx / (H_CK / 4);
-      const int c4 = idx - p * (H_CK / 4);
+      const int p = idx / (H_CK / CPI);
+      const int ci = idx - p * (H_CK / CPI);
       const unsigned off = idx < nstage ? sOff[p] : EGN_OOB;
-      sv[j] = egn_buf_load16(rx, off == EGN_OOB ? EGN_OOB : off + (unsigned)(chunk * H_CK + c4 * 4) * 4u);
+      sv[j] = egn_buf_load16(rx, off == EGN_OOB ? EGN_OOB : off + (unsigned)(chunk * H_CK + ci * CPI) * (unsigned)EB);
     }
   };
   auto stage_store = [&](int batch) {
 #pragma unroll
     for (int j = 0; j < SB; ++j) {
       const int idx = (batch * SB + j) * 256 + tid;
-      const int p = idx / (H_CK / 4);
-      const int c4 = idx - p * (H_CK / 4);
+      const int p = idx / (H_CK / CPI);
+      const int ci = idx - p * (H_CK / CPI);
       const f32x4 v = sv[j];
-      f16x4 h;
-      h.x = (_Float16)__builtin_fminf(__builtin_fmaxf(v.x, -H_F16_MAX), H_F16_MAX);
-      h.y = (_Float16)__builtin_fminf(__builtin_fmaxf(v.y, -H_F16_MAX), H_F16_MAX);
-      h.z = (_Float16)__builtin_fminf(__builtin_fmaxf(v.z, -H_F16_MAX), H_F16_MAX);
-      h.w = (_Float16)__builtin_fminf(__builtin_fmaxf(v.w, -H_F16_MAX), H_F16_MAX);
-      if (idx < nstage) *reinterpret_cast<f16x4*>(slab + p * H_PIXB + c4 * 8) = h;
+      if constexpr (X16) {       // 8 f16 channels as they lie: 16 bytes at a 16-byte aligned address (H_PIXB % 16 == 0)
+        if (idx < nstage) *reinterpret_cast<f32x4*>(slab + p * H_PIXB + ci * 16) = v;
+      } else {
+        f16x4 h;
+        h.x = h_round_f16(v.x);
+        h.y = h_round_f16(v.y);
+        h.z = h_round_f16(v.z);
+        h.w = h_round_f16(v.w);
+        if (idx < nstage) *reinterpret_cast<f16x4*>(slab + p * H_PIXB + ci * 8) = h;
+      }
     }
   };
   const int nbatch = (nstage + SB * 256 - 1) / (SB * 256);
@@ -277,6 +307,7 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
   const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, ybytes, EGN_RSRC_WORD3);
   const __amdgpu_buffer_rsrc_t rr =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, ybytes, EGN_RSRC_WORD3);
+  const __amdgpu_buffer_rsrc_t ry16 = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, ybytes / 2, EGN_RSRC_WORD3);   // y as f16
   constexpr int C4 = NT * 4;   // float4 per slab row
 #pragma unroll
   for (int it = 0; it < MT * NT; ++it) {
@@ -288,13 +319,23 @@ __global__ __launch_bounds__(256, 4) void conv_h_kernel(const ConvHArgs a) {
     const int rem = m & px_mask;
     const int n = n_base + b, oy = oy0 + h_tile_row<S>(rem >> a.ltw, a.lth), ox = ox0 + (rem & (a.TW - 1));
     const bool ok = n < a.N && oy < a.Ho && ox < a.Wo;
-    const unsigned voff = ok ? (unsigned)(((n * a.Ho + oy) * a.Wo + ox) * a.Cout + cbase + c4 * 4) * 4u : EGN_OOB;
+    const unsigned eoff = (unsigned)(((n * a.Ho + oy) * a.Wo + ox) * a.Cout + cbase + c4 * 4);   // in elements
+    const unsigned voff = ok ? eoff * 4u : EGN_OOB;
     f32x4 v = *reinterpret_cast<const f32x4*>(&sC[row * T::SC_LD + c4 * 4]);
     if (a.res) v += egn_buf_load16(rr, voff);
     if (a.act == EGN_ACT_RELU) {
       v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
     }
-    egn_buf_store16(ry, voff, v);
+    if (a.y16) {     // (wave-uniform) f16 storage: the reader's rounding applied here, 8 bytes per lane; never with a residual
+      f16x4 h;
+      h.x = h_round_f16(v.x);
+      h.y = h_round_f16(v.y);
+      h.z = h_round_f16(v.z);
+      h.w = h_round_f16(v.w);
+      egn_buf_store8(ry16, ok ? eoff * 2u : EGN_OOB, __builtin_bit_cast(u32x2, h));
+    } else {
+      egn_buf_store16(ry, voff, v);
+    }
   }
 }
 
@@ -342,6 +383,16 @@ extern "C" int egn_conv3x3s2_h_applies(int N, int H, int W, int Cin, int cs_in, 
 extern "C" int egn_conv3x3_hx_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act,
                                       int stride) {
   return h_applies(32, N, H, W, Cin, cs_in, Cout, cs_out, has_res, act, stride);
+}
+
+// Host-only: the family predicate of chunk size ck and stride with the storage flags of its tensors -- x_f16: x holds f16
+// (what h_round_f16 gives), y_f16: y is written as f16; both 0: the three predicates above.  f16 output never comes with
+// a residual (the residual is fp32 and would be added to an fp32 sum: nothing in HRNet asks for it).  The 2 GiB
+// condition stays at fp32 sizes: a layer the family takes with f16 storage is one it takes without.
+extern "C" int egn_conv3x3_h16_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act,
+                                       int stride, int ck, int x_f16, int y_f16) {
+  if ((ck != 48 && ck != 32) || (x_f16 & ~1) || (y_f16 & ~1) || (y_f16 && has_res)) return 0;
+  return h_applies(ck, N, H, W, Cin, cs_in, Cout, cs_out, has_res, act, stride);
 }
 
 extern "C" long egn_conv3x3_h_wpack_bytes(int Cin, int Cout) {
@@ -398,11 +449,27 @@ int egn_conv_hx_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int h
   return h_plan(a, N, H, W, Cin, Cout, act, stride, 32);
 }
 
-#define EGN_H_LAUNCH(CK, S, WM, WN, MT, NT) \
-  hipLaunchKernelGGL((conv_h_kernel<CK, S, WM, WN, MT, NT>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a)
+// either chunk size with the storage flags (egn_conv3x3_h16_applies): the same geometry, the flags beside it
+int egn_conv_h16_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act, int stride, int ck,
+                      int x16, int y16) {
+  if (!egn_conv3x3_h16_applies(N, H, W, Cin, Cin, Cout, Cout, has_res, act, stride, ck, x16, y16)) return EGN_E_BADARG;
+  const int rc = h_plan(a, N, H, W, Cin, Cout, act, stride, ck);
+  if (rc) return rc;
+  a.x16 = x16; a.y16 = y16;
+  return 0;
+}
+
+// (x16 picks the instance; y16 is a branch of the epilogue)
+#define EGN_H_LAUNCH(CK, S, WM, WN, MT, NT)                                                                              \
+  do {                                                                                                                   \
+    if (a.x16)                                                                                                           \
+      hipLaunchKernelGGL((conv_h_kernel<CK, S, WM, WN, MT, NT, true>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a);  \
+    else                                                                                                                 \
+      hipLaunchKernelGGL((conv_h_kernel<CK, S, WM, WN, MT, NT, false>), dim3(a.blocks), dim3(256), a.lds_bytes, stream, a); \
+  } while (0)
 
 int egn_conv_h_launch(const ConvHArgs& a, hipStream_t stream) {
-  if (!a.x || !a.w || !a.scale || !a.shift || !a.y) return EGN_E_BADARG;
+  if (!a.x || !a.w || !a.scale || !a.shift || !a.y || (a.x16 & ~1) || (a.y16 & ~1) || (a.y16 && a.res)) return EGN_E_BADARG;
   const int s = a.stride;
   if (a.ck == 48) {
     if (a.tn == 96) { if (s == 2) EGN_H_LAUNCH(48, 2, 2, 2, 2, 3); else EGN_H_LAUNCH(48, 1, 2, 2, 2, 3); }
@@ -450,4 +517,17 @@ extern "C" int egn_conv3x3_hx_f32(const float* x, const void* wpack_f16, const f
                                   const float* res, float* y, int N, int H, int W, int Cin, int Cout, int act, int stride,
                                   void* stream) {
   return h_direct(32, x, wpack_f16, scale, shift, res, y, N, H, W, Cin, Cout, act, stride, stream);
+}
+
+// f16 STORAGE of x and / or y (x_f16, y_f16 in {0, 1}; PoseHighResolutionNet.activations = 'f16'): chunk size ck (48 / 32)
+// and stride as egn_conv3x3_h16_applies takes them.
+extern "C" int egn_conv3x3_h16_f32(const void* x, const void* wpack_f16, const float* scale, const float* shift,
+                                   const float* res, void* y, int N, int H, int W, int Cin, int Cout, int act, int stride,
+                                   int ck, int x_f16, int y_f16, void* stream) {
+  g_egn_direct_convs.fetch_add(1, std::memory_order_relaxed);
+  ConvHArgs a;
+  int rc = egn_conv_h16_plan(a, N, H, W, Cin, Cout, res != nullptr, act, stride, ck, x_f16, y_f16);
+  if (rc) return rc;
+  a.x = (const float*)x; a.w = wpack_f16; a.scale = scale; a.shift = shift; a.res = res; a.y = (float*)y;
+  return egn_conv_h_launch(a, (hipStream_t)stream);
 }

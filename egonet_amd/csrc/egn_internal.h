@@ -181,12 +181,12 @@ int egn_conv_launch_wino4_pair(ConvArgs a, ConvArgs b, int cus, hipStream_t stre
 // The f16-operand 3x3 / pad 1 family (conv_h.hip), stride 1 and stride 2: beside the config table, planned by its own
 // predicates.
 struct ConvHArgs {
-  const float* x;
+  const float* x;      // (x16: f16)
   const void* w;       // engine.pack_conv_weight_f16 (ck = 48) / pack_conv_weight_f16x (ck = 32)
   const float* scale;
   const float* shift;
   const float* res;    // stride 1 only
-  float* y;
+  float* y;            // (y16: f16)
   int N, H, W, Cin, Cout, act;
   int stride;          // 1 or 2
   int Ho, Wo;          // output size: (H - 1) / stride + 1, (W - 1) / stride + 1
@@ -197,10 +197,14 @@ struct ConvHArgs {
   int HH, HW, npix;    // halo tile per image (stride * T + 3 - stride a side), halo pixels per block
   int tiles_x, tiles_y;
   int tab_bytes, lds_bytes, blocks;
+  int x16, y16;        // 1: x / y is stored as f16, the rounding of the staging applied by the producer (egn_conv_h16_plan)
 };
 int egn_conv_h_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act, int stride);   // host-only
 // the 32-multiple widths in chunks of 32 (egn_conv3x3_hx_applies; precision = 'f16x'), either stride
 int egn_conv_hx_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act, int stride);  // host-only
+// either chunk size (ck) with f16 storage of x and / or y (egn_conv3x3_h16_applies)
+int egn_conv_h16_plan(ConvHArgs& a, int N, int H, int W, int Cin, int Cout, int has_res, int act, int stride, int ck, int x16,
+                      int y16);                                                                                    // host-only
 int egn_conv_h_launch(const ConvHArgs& a, hipStream_t stream);
 
 // adds n to egn_launch_count() (program.hip): entry points outside programs that want their launches provable

@@ -453,14 +453,17 @@ extern "C" int egn_program_add_conv2d_pair(egn_program* p, egn_ref xa, egn_ref w
 
 // An f16-operand 3x3 / pad 1 convolution (conv_h.hip) as one op of `kind`, planned by `plan`; H, W are the input size.  Only
 // the residual may be NULL.
+// plan == NULL: egn_conv_h16_plan with the chunk size and the storage flags (f16 tensors count 2 bytes an element).
 typedef int (*ConvHPlan)(ConvHArgs&, int, int, int, int, int, int, int, int);
 static int add_convh(egn_program* p, int kind, ConvHPlan plan, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
-                     egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act, int stride) {
+                     egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act, int stride, int ck = 0,
+                     int x16 = 0, int y16 = 0) {
   if (!p) return EGN_E_BADARG;
   Op op;
   op.kind = kind;
   const bool has_res = res.slot >= 0;
-  int rc = plan(op.convh, N, H, W, Cin, Cout, has_res, act, stride);
+  int rc = plan ? plan(op.convh, N, H, W, Cin, Cout, has_res, act, stride)
+                : egn_conv_h16_plan(op.convh, N, H, W, Cin, Cout, has_res, act, stride, ck, x16, y16);
   if (rc) return rc;
   op.cfg = 0;
   const egn_ref refs[6] = {x, wpack, scale, shift, res, y};
@@ -470,7 +473,8 @@ static int add_convh(egn_program* p, int kind, ConvHPlan plan, egn_ref x, egn_re
   }
   const double pxo = (double)N * op.convh.Ho * op.convh.Wo;
   op.flops = 2.0 * 9.0 * pxo * Cout * Cin;
-  op.bytes = 4.0 * ((double)N * H * W * Cin + pxo * Cout * (has_res ? 2.0 : 1.0)) + 2.0 * 9.0 * Cout * Cin;
+  op.bytes = (x16 ? 2.0 : 4.0) * N * H * W * Cin + pxo * Cout * ((y16 ? 2.0 : 4.0) + (has_res ? 4.0 : 0.0)) +
+             2.0 * 9.0 * Cout * Cin;
   op.lane = p->cur_lane;
   p->ops.push_back(op);
   return 0;
@@ -493,6 +497,14 @@ extern "C" int egn_program_add_conv3x3_hx(egn_program* p, egn_ref x, egn_ref wpa
                                           egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act,
                                           int stride) {
   return add_convh(p, OP_CONVHX, egn_conv_hx_plan, x, wpack, scale, shift, res, y, N, H, W, Cin, Cout, act, stride);
+}
+
+// the family with f16 storage of x and / or y (egn_conv3x3_h16_f32): the op kind its chunk size and stride have above
+extern "C" int egn_program_add_conv3x3_h16(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
+                                           egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act,
+                                           int stride, int ck, int x_f16, int y_f16) {
+  const int kind = ck == 32 ? OP_CONVHX : (stride == 2 ? OP_CONVH2 : OP_CONVH);
+  return add_convh(p, kind, nullptr, x, wpack, scale, shift, res, y, N, H, W, Cin, Cout, act, stride, ck, x_f16, y_f16);
 }
 
 extern "C" int egn_program_add_fuse(egn_program* p, egn_ref y, int N, int H, int W, int C, int cs, int nterms,

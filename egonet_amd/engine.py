@@ -45,6 +45,22 @@ F16S2_FP32_CLASSES = ((48, 48),)
 #   Empty: all sixteen classes of W32 at 192 x 256 and of W48's seven layers are faster beyond the spread at 64 crops
 #   (1.6-4.0x) and at 16 (1.2-5.7x; the smallest win is 256 -> 48 stride 1 at 16 crops, 55.3 -> 45.9 us, spreads 2.2 / 1.2).
 F16X_FP32_CLASSES = ()
+# (cin, cout, stride) classes of PRODUCERS that activations = 'f16' leaves on fp32 storage because the producer + consumer
+# pair was measured not to win with f16 storage (tools/precision_bench.py --a); empty unless a measurement
+# fills it.  Looked up at every call, like the tuples above.
+#   The rule (3.16b): a class keeps f16 storage only if its pair is faster by more than the spread (max - min of 7 passes,
+#   the larger of the two) at 64 crops and not slower beyond it at 16, in every pair it produces.  Measured
+#   (profiles/f16_storage_bench.json; us of producer + consumer, fp32 storage -> f16 storage, spreads in brackets): the f16
+#   median is the lower one in all 26 rows (1.03-1.18x), but only 48 -> 48 (77.8 -> 72.3 [3.6 / 4.8]), 64 -> 64 (30.2 -> 28.4
+#   [0.5 / 0.8]) and 64 -> 64 /2 (27.6 -> 23.4 [1.8 / 1.5]) win beyond the spread at 64 crops.  Within the spread there:
+#     32 -> 32       36.8 -> 33.7 [0.4 / 3.3]       32 -> 32 /2    20.4 -> 18.8 [1.5 / 5.0], 24.5 -> 22.4 [2.6 / 2.8]
+#     96 -> 96       53.8 -> 51.4 [6.5 / 0.8]       96 -> 96 /2    39.6 -> 37.6 [4.8 / 4.4]
+#     128 -> 128     42.5 -> 40.6 [0.6 / 7.2]       192 -> 192     59.7 -> 57.7 [1.2 / 7.2]
+#     256 -> 256     60.1 -> 53.3 [13.5 / 14.6]     384 -> 384     86.4 -> 84.2 [3.9 / 0.6]
+F16_STORAGE_FP32_CLASSES = ((32, 32, 1), (32, 32, 2), (96, 96, 1), (96, 96, 2), (128, 128, 1), (192, 192, 1), (256, 256, 1),
+                            (384, 384, 1))
+# Every value of the storage switch (PoseHighResolutionNet.activations), independent of ``precision``.
+ACTIVATIONS = ('f32', 'f16')
 
 # THE f16-operand lowering rules, one row per value of the switch, in the order the values extend each other:
 # a precision activates its own row and every row above it (``active_rules``), and a layer goes to the first active row
@@ -58,22 +74,24 @@ F16X_FP32_CLASSES = ()
 #   fp32_classes  the NAME of the module-level tuple of classes measured not to win (looked up at every call: tests and
 #                 tools assign to it), keyed by the first ``class_key`` of (cin, cout, stride); None: no such tuple
 #   pack          the filter layout its kernel instances read (filters.py)
+#   ck            the input channels per chunk of those instances: what egn_program_add_conv3x3_h16 -- the one entry of an
+#                 op with f16 storage (``f16_storage``) -- is told beside the stride
 F16Rule = collections.namedtuple('F16Rule', 'mode kind strides klass res_strides applies add res_arg stride_arg '
-                                            'fp32_classes class_key pack')
+                                            'fp32_classes class_key pack ck')
 F16_RULES = (
     # the W48 widths at stride 1 (csrc/conv_h.hip, chunks of 48 channels)
     F16Rule(mode='f16', kind='convh', strides=(1,), klass=('conv3x3h',), res_strides=(1,),
             applies='egn_conv3x3_h_applies', add='egn_program_add_conv3x3_h', res_arg=True, stride_arg=False,
-            fp32_classes=None, class_key=0, pack=pack_conv_weight_f16),
+            fp32_classes=None, class_key=0, pack=pack_conv_weight_f16, ck=H_CK),
     # ... and at stride 2: no stride-2 layer of HRNet has a residual
     F16Rule(mode='f16s2', kind='convh2', strides=(2,), klass=('conv3x3s2h',), res_strides=(),
             applies='egn_conv3x3s2_h_applies', add='egn_program_add_conv3x3s2_h', res_arg=False, stride_arg=False,
-            fp32_classes='F16S2_FP32_CLASSES', class_key=2, pack=pack_conv_weight_f16),
+            fp32_classes='F16S2_FP32_CLASSES', class_key=2, pack=pack_conv_weight_f16, ck=H_CK),
     # the 32-multiple widths at either stride (chunks of 32): HRNet-W32's stages, and in every width layer1's 64 -> 64,
     # the stem's second convolution and transition1
     F16Rule(mode='f16x', kind='convhx', strides=(1, 2), klass=('conv3x3hx', 'conv3x3hxs2'), res_strides=(1,),
             applies='egn_conv3x3_hx_applies', add='egn_program_add_conv3x3_hx', res_arg=True, stride_arg=True,
-            fp32_classes='F16X_FP32_CLASSES', class_key=3, pack=pack_conv_weight_f16x),
+            fp32_classes='F16X_FP32_CLASSES', class_key=3, pack=pack_conv_weight_f16x, ck=32),
 )
 _RULE_OF_KIND = {rule.kind: rule for rule in F16_RULES}
 # Every value the switch takes; PRECISIONS keeps its three values and its last entry.
@@ -129,15 +147,62 @@ def takes(rule, x, weight, bias, act, res, stride, pad, out_nchw=False, cout_cs=
     return _applies(rule, x.n, x.h, x.w, cin, x.cs, cout, _round_up(cout, 4), res is not None, act, stride)
 
 
+def check_activations(activations):
+    """Refuses any value of the storage switch but 'f32' and 'f16'."""
+    if activations not in ACTIVATIONS:
+        raise ValueError("activations must be %s, got %r" % (_or_text(ACTIVATIONS), activations))
+    return activations
+
+
 def lowered_cost(kind, op):
     """(klass, flops, bytes) of a recorded 'convh' / 'convh2' / 'convhx' op, as ``Program.meta`` reports them: fp32
-    activations (the residual read beside the output written), f16 filters."""
+    activations (the residual read beside the output written) unless the op carries ``x16`` / ``y16`` (2 bytes an
+    element), f16 filters."""
     rule, x, y = _RULE_OF_KIND[kind], op['x'], op['y']
     stride = op['stride'] if rule.stride_arg else rule.strides[0]
     flops = 2.0 * y.n * y.h * y.w * op['cout'] * op['cin'] * 9
-    nbytes = 4.0 * (x.n * x.h * x.w * op['cin'] + y.n * y.h * y.w * op['cout'] * (2 if op.get('res') is not None else 1)) + \
+    nbytes = (2.0 if op.get('x16') else 4.0) * x.n * x.h * x.w * op['cin'] + \
+        y.n * y.h * y.w * op['cout'] * ((2.0 if op.get('y16') else 4.0) + (4.0 if op.get('res') is not None else 0.0)) + \
         2.0 * op['cout'] * op['cin'] * 9
     return '%s %d->%d@%dx%d' % (rule.klass[rule.strides.index(stride)], op['cin'], op['cout'], y.h, y.w), flops, nbytes
+
+
+def f16_storage(rec):
+    """THE rule of activations = 'f16' (DESIGN 3.16d), applied to a finished recording before ``plan_arena``: the set of
+    ``Buf`` that are stored as f16.  A buffer qualifies iff it lies in the arena, exactly one op writes it -- a lowered
+    op (a kind of ``F16_RULES``) as its ``y``, without a residual, whose (cin, cout, stride) is not in
+    ``F16_STORAGE_FP32_CLASSES`` --, it has at least one reader, and every reader is a lowered op that takes it as ``x``
+    and never as ``res``.  Such a reader rounds every element to f16 while it stages it; the producer applies the same
+    rounding in its epilogue instead, so the reader's operand bits -- and every output of the network -- are the same.
+    A qualifying buffer gets ``f16 = True`` and half its bytes, its producer ``op['y16']``, its readers ``op['x16']``."""
+    fp32_classes = globals()['F16_STORAGE_FP32_CLASSES']
+    out = set()
+    for b in rec.bufs:
+        if b.slot != SLOT_ARENA or not b.uses:
+            continue
+        writers, readers, ok = [], [], True
+        for i in sorted(set(b.uses)):
+            kind, op = rec.ops[i]
+            if kind not in _RULE_OF_KIND or op.get('res') is b:
+                ok = False
+                break
+            if op['y'] is b:
+                writers.append((kind, op))
+            if op['x'] is b:
+                readers.append(op)
+        if not ok or len(writers) != 1 or not readers:
+            continue
+        rule, w = _RULE_OF_KIND[writers[0][0]], writers[0][1]
+        stride = w['stride'] if rule.stride_arg else rule.strides[0]
+        if w.get('res') is not None or (w['cin'], w['cout'], stride) in fp32_classes or b.cs != b.c:
+            continue
+        b.f16 = True
+        b.nbytes = b.n * b.h * b.w * b.c * 2
+        w['y16'] = True
+        for op in readers:
+            op['x16'] = True
+        out.add(b)
+    return out
 
 
 def f16_eligible(conv, n, h, w):
@@ -239,7 +304,7 @@ def fold_pw(weight, bn):
 class Buf(object):
     """Symbolic fp32 tensor.  NHWC [n,h,w,cs] (cs = channel stride) in the arena,
     or an external user tensor bound to ``slot``."""
-    __slots__ = ('n', 'h', 'w', 'c', 'cs', 'slot', 'off', 'nbytes', 'first', 'last', 'uses', 'name')
+    __slots__ = ('n', 'h', 'w', 'c', 'cs', 'slot', 'off', 'nbytes', 'first', 'last', 'uses', 'name', 'f16')
 
     def __init__(self, n, h, w, c, cs=None, slot=SLOT_ARENA, nbytes=None, name=''):
         self.n, self.h, self.w, self.c = n, h, w, c
@@ -250,6 +315,7 @@ class Buf(object):
         self.first = self.last = -1
         self.uses = []          # indices of every op that reads or writes the buffer
         self.name = name
+        self.f16 = False        # stored as f16 between two f16-operand convs (``f16_storage``)
 
     def ref(self):
         return Ref(self.slot, self.off)
@@ -467,7 +533,22 @@ class _Recorder(object):
         """Greedy best-fit packing of arena buffers by lifetime; returns bytes.
         A buffer's storage is re-used only by a buffer whose defining op starts
         after EVERY use of the old one has completed (``happens_before``), so
-        concurrent lanes never alias each other's live tensors."""
+        concurrent lanes never alias each other's live tensors.
+        With f16-stored buffers (``f16_storage``) the packing is never larger than that of the fp32 program: a greedy
+        packing of smaller buffers can come out larger, and then every f16 buffer keeps the place -- and the room -- of
+        its fp32 size."""
+        top = self._place(lambda b: b.nbytes)
+        if any(b.f16 for b in self.bufs):
+            offs = [b.off for b in self.bufs]
+            top32 = self._place(lambda b: 2 * b.nbytes if b.f16 else b.nbytes)
+            if top32 < top:
+                return top32
+            for b, off in zip(self.bufs, offs):
+                b.off = off
+        return top
+
+    def _place(self, size):
+        """``plan_arena`` with ``size(buf)`` bytes of room per buffer: sets every ``off``, returns the arena's bytes."""
         live = [b for b in self.bufs if b.slot == SLOT_ARENA and b.first >= 0]
         events = sorted(live, key=lambda b: b.first)
         free = []              # [off, size, uses]: uses = op indices that touched the bytes
@@ -481,7 +562,7 @@ class _Recorder(object):
             still = []
             for ab in active:
                 if ab.last < d:
-                    free.append([ab.off, _round_up(ab.nbytes, 256), list(ab.uses)])
+                    free.append([ab.off, _round_up(size(ab), 256), list(ab.uses)])
                 else:
                     still.append(ab)
             active = still
@@ -501,7 +582,7 @@ class _Recorder(object):
             def usable(blk):
                 return all(self.happens_before(u, d) for u in blk[2])
 
-            need = _round_up(b.nbytes, 256)
+            need = _round_up(size(b), 256)
             best = None
             for i, blk in enumerate(free):
                 if blk[1] >= need and usable(blk) and (best is None or blk[1] < free[best][1]):
@@ -657,10 +738,18 @@ class Program(object):
                                                     op['cout'], op['ho'], op['wo'])
         elif kind in _RULE_OF_KIND:
             rule, x, y = _RULE_OF_KIND[kind], op['x'], op['y']
-            res = [op['res'].ref() if op['res'] is not None else NULL_REF] if rule.res_arg else []
-            call(rule.add, *([x.ref(), op['w'], op['scale'], op['shift']] + res +
-                             [y.ref(), x.n, x.h, x.w, op['cin'], op['cout'], op['act']] +
-                             ([op['stride']] if rule.stride_arg else [])), what=op['tag'])
+            if op.get('x16') or op.get('y16'):
+                # f16 storage of x and / or y: the one entry of all three kinds (chunk size and stride say which)
+                res = op['res'].ref() if op.get('res') is not None else NULL_REF
+                call('egn_program_add_conv3x3_h16', x.ref(), op['w'], op['scale'], op['shift'], res, y.ref(), x.n, x.h, x.w,
+                     op['cin'], op['cout'], op['act'], op['stride'] if rule.stride_arg else rule.strides[0],
+                     rule.ck, int(bool(op.get('x16'))),
+                     int(bool(op.get('y16'))), what=op['tag'])
+            else:
+                res = [op['res'].ref() if op['res'] is not None else NULL_REF] if rule.res_arg else []
+                call(rule.add, *([x.ref(), op['w'], op['scale'], op['shift']] + res +
+                                 [y.ref(), x.n, x.h, x.w, op['cin'], op['cout'], op['act']] +
+                                 ([op['stride']] if rule.stride_arg else [])), what=op['tag'])
             klass, flops, nbytes = lowered_cost(kind, op)
         elif kind == 'convpair':
             args, klass = [], []
@@ -838,6 +927,14 @@ class HRNetEngine(object):
         prec = getattr(self.model, 'precision', 'f32')
         active_rules(prec)          # (refuses any other value)
         return prec
+
+    @property
+    def activations(self):
+        """The model's ``activations`` attribute ('f32', the default, or 'f16'): read at every forward, part of the program
+        key, independent of ``precision``.  'f16' stores the tensors ``f16_storage`` names -- written by one f16-operand
+        conv, read only by f16-operand convs as their input -- as f16; every output keeps its bits.  With
+        precision = 'f32' nothing is lowered and nothing qualifies.  The training tape ignores it."""
+        return check_activations(getattr(self.model, 'activations', 'f32'))
 
     # -- recording ---------------------------------------------------------
     def _block(self, r, x, blk, tag):
@@ -1140,6 +1237,8 @@ class HRNetEngine(object):
             nslots += 3
         if own:
             self.last_f16_ops = [op['tag'] for kind, op in r.ops if kind in _RULE_OF_KIND]
+            if self.activations == 'f16':
+                f16_storage(r)
         return r, nslots, out_shapes
 
     def program(self, x, decode_mode=None, slot=0):
@@ -1152,6 +1251,8 @@ class HRNetEngine(object):
         key = (x.device, n, c, h, w, decode_mode) if not slot else (x.device, n, c, h, w, decode_mode, slot)
         if self.precision != 'f32':
             key = key + (self.precision,)
+        if self.activations != 'f32':
+            key = key + ('a' + self.activations,)
         prog = self.programs.get(key)
         if prog is None:
             if h % 32 or w % 32:

@@ -42,10 +42,12 @@ def _dev_f64(a, device):
 
 
 class EgoNet(nn.Module):
-    def __init__(self, cfgs, pre_trained=False, precision=None):
+    def __init__(self, cfgs, pre_trained=False, precision=None, activations=None):
         """``precision``: None (what ``cfgs['heatmapModel']['precision']`` says, default 'f32'), 'f32', 'f16', 'f16s2' or 'f16x' -- the
         opt-in fast inference modes of HC's HIP program (PoseHighResolutionNet.precision).  The lifter, training and
-        every CPU path compute in fp32 whatever it says."""
+        every CPU path compute in fp32 whatever it says.
+        ``activations``: None (what ``cfgs['heatmapModel']['activations']`` says, default 'f32'), 'f32' or 'f16' -- f16
+        storage between f16-operand convolutions (PoseHighResolutionNet.activations): the same bits, fewer bytes."""
         super().__init__()
         hm = cfgs['heatmapModel']
         self.cfgs = cfgs
@@ -55,6 +57,10 @@ class EgoNet(nn.Module):
             if precision not in ('f32', 'f16', 'f16s2', 'f16x'):
                 raise ValueError("precision must be 'f32', 'f16', 'f16s2' or 'f16x', got %r" % (precision,))
             self.HC.precision = precision
+        if activations is not None:
+            if activations not in ('f32', 'f16'):
+                raise ValueError("activations must be 'f32' or 'f16', got %r" % (activations,))
+            self.HC.activations = activations
         self.resolution = hm['input_size']
         self.xy_dict = {'flag': hm['add_xy']} if 'add_xy' in hm else None
         fc = cfgs['FCModel']

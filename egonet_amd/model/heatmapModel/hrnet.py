@@ -306,6 +306,12 @@ class PoseHighResolutionNet(nn.Module):
     # stay fp32 in memory.  Only the eval-mode HIP program reads it: training, the autograd bridge and the torch graph
     # (so every CPU input, whatever the value) compute in fp32.  Any other value raises ValueError at the next forward.
     precision = 'f32'
+    # 'f32' (default) or 'f16': how the eval-mode HIP program STORES the tensors that one f16-operand convolution writes
+    # and only f16-operand convolutions read as their input (engine.f16_storage: conv1's output in a BasicBlock, the
+    # intermediates of the stride-2 chains).  'f16' moves the reader's rounding into the producer's epilogue: half the
+    # bytes, every output bit for bit the same.  Independent of ``precision`` (with 'f32' nothing qualifies); training,
+    # the autograd bridge and the torch graph ignore it.  Any other value raises ValueError at the next forward.
+    activations = 'f32'
 
     def _native_autograd_ok(self):
         """The train-mode bridge runs ONE autograd node on the native tape: the nn.Module graph below this module is
@@ -458,4 +464,7 @@ def get_pose_net(cfgs, is_train, **kwargs):
         if hm['precision'] not in engine.ALL_PRECISIONS:
             raise ValueError("heatmapModel.precision must be %s, got %r" % (engine._PRECISION_TEXT, hm['precision']))
         model.precision = hm['precision']
+    if hm.get('activations') is not None:
+        from egonet_amd import engine
+        model.activations = engine.check_activations(hm['activations'])
     return model

@@ -228,6 +228,9 @@ def export_plan(ego, path, batch_sizes=(1, 2, 4, 8, 16, 32, 64), decode='auto', 
         raise ValueError('export_plan: no plan for the %r head (infer_crops has none either)' % (HC.head_type,))
     if ego.LS is None:
         raise ValueError('lifter statistics LS are not loaded')
+    if HC._hip_engine().activations != 'f32':
+        raise ValueError("export_plan: plans hold fp32-storage programs only, got activations = %r (set it to 'f32')"
+                         % (HC._hip_engine().activations,))
     if decode == 'auto':
         decode = 'coords' if HC.head_type == 'coordinates' else 'soft'
     if decode not in DECODES or (decode == 'coords' and HC.head_type != 'coordinates'):

@@ -881,6 +881,24 @@ int egn_conv3x3_hx_f32(const float* x, const void* wpack_f16, const float* scale
 /* as a program op with a kind id of its own (14; egn_program_op_info: flops = 2 * 9 * N * Ho * Wo * Cout * Cin); res may be NULL */
 int egn_program_add_conv3x3_hx(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift,
                                egn_ref res, egn_ref y, int N, int H, int W, int Cin, int Cout, int act, int stride);
+/* f16 STORAGE between two ops of the family (PoseHighResolutionNet.activations = 'f16'): x_f16 = 1 reads x as f16
+ * [N][H][W][Cin] (8 channels per 16-byte load, staged as they lie), y_f16 = 1 writes y as f16 [N][Ho][Wo][Cout] -- after
+ * scale / shift and the activation every element goes through the very rounding the staging applies to an fp32 x (clamp to
+ * +-65504, nearest-even), so a reader with x_f16 = 1 sees the operand bits it would have made of the fp32 tensor and every
+ * fp32 output downstream keeps its bits.  ck (48 or 32) and stride (1 or 2) name the chunk size and stride the three
+ * predicates above stand for; egn_conv3x3_h16_applies is theirs with the flags: it also wants x_f16, y_f16 in {0, 1} and no
+ * residual beside y_f16 (the 2 GiB condition stays at fp32 sizes); host-only.  With both flags 0 the entries below compute
+ * what the entries above compute. */
+int egn_conv3x3_h16_applies(int N, int H, int W, int Cin, int cs_in, int Cout, int cs_out, int has_res, int act,
+                            int stride, int ck, int x_f16, int y_f16);
+int egn_conv3x3_h16_f32(const void* x, const void* wpack_f16, const float* scale, const float* shift, const float* res,
+                        void* y, int N, int H, int W, int Cin, int Cout, int act, int stride, int ck, int x_f16, int y_f16,
+                        void* stream);
+/* as a program op of the kind its chunk size and stride have above (12, 13 or 14); egn_program_op_info counts an f16 tensor
+ * as 2 bytes an element; res may be NULL */
+int egn_program_add_conv3x3_h16(egn_program* p, egn_ref x, egn_ref wpack, egn_ref scale, egn_ref shift, egn_ref res,
+                                egn_ref y, int N, int H, int W, int Cin, int Cout, int act, int stride, int ck, int x_f16,
+                                int y_f16);
 /* number of kernel launches issued through egn_program_run / _run_timed / _replay
  * since the library was loaded (process wide, all devices).  Test hook: a caller
  * can prove that a forward went through this library's kernels. */

@@ -6,7 +6,8 @@ GPU crops -> HRNet key-points -> lifter -> pose solve -> KITTI result files ->
     python tools/inference_kitti.py --images <dir of png> --boxes <dir of KITTI label/detection txt>
         [--calib <dir>] --out <result dir> [--ckpt <dir with HC.pth L.pth LS.npy> | --synthetic]
         [--gt <label dir>] [--classes Car] [--conf-thres 0] [--alpha-mode proj|trans] [--frames-per-step 8]
-        [--refine pnp [--refine-max-shift 5.0] [--write-3d]] [--precision f32|f16|f16s2|f16x] [--draw <dir> [--draw-gt]]
+        [--refine pnp [--refine-max-shift 5.0] [--write-3d]] [--precision f32|f16|f16s2|f16x] [--activations f32|f16]
+        [--draw <dir> [--draw-gt]]
 
 ``--draw DIR`` also draws every frame's predictions (2-D boxes, projected cuboids, key points) with the GPU rasteriser
 (EgoNet.post_process(visualize=True), csrc/overlay.hip) and writes ``DIR/<stem>.png`` plus, where the boxes carry 3-D
@@ -16,7 +17,8 @@ placements, the top view ``DIR/<stem>_bev.png``; ``--draw-gt`` (needs ``--gt``) 
 HRNet's stages 2-4 run with f16 operands and fp32 accumulation (csrc/conv_h.hip); results differ from the default's at
 the 1e-3 px level ("f16-operand mode").  ``--precision f16s2`` adds the 3x3 / stride 2 convolutions of the
 transition and fuse layers; ``--precision f16x`` those and the 3x3 convolutions of the 32-multiple widths (HRNet-W32's
-stages; layer1, the stem's second convolution and transition1 in every width).
+stages; layer1, the stem's second convolution and transition1 in every width).  ``--activations f16`` (default f32)
+stores the tensors between two f16-operand convolutions as f16: the results keep their bits.
 
 ``--refine pnp`` fits every lifted cuboid rigidly to its own key points before the angles are read off
 (EgoNet.refine_pnp, the reference's ``pnp_refine`` flow without cv2); ``rot_y`` / ``alpha`` then come from the refined
@@ -83,8 +85,8 @@ def build_model(a):
         8, (64, 64), 33, 'coordinates', modules=(1, 1, 1), num_blocks=1, lifter_neurons=128)
     if a.ckpt:
         cfg['dirs'] = {'ckpt': a.ckpt}
-        return EgoNet(cfg, pre_trained=True, precision=a.precision).eval().cuda()
-    ego = EgoNet(cfg, pre_trained=False, precision=a.precision)               # --synthetic: seeded random weights (no checkpoint offline)
+        return EgoNet(cfg, pre_trained=True, precision=a.precision, activations=a.activations).eval().cuda()
+    ego = EgoNet(cfg, pre_trained=False, precision=a.precision, activations=a.activations)               # --synthetic: seeded random weights (no checkpoint offline)
     ego.HC.load_state_dict(synth.synth_state_dict(ego.HC.state_dict(), seed=6))
     ego.L.load_state_dict(synth.synth_state_dict(ego.L.state_dict(), seed=7))
     ego.LS = synth.synth_lifter_stats(66, 96, seed=1)
@@ -129,6 +131,8 @@ def main(argv=None):
     ap.add_argument('--precision', default='f32', choices=['f32', 'f16', 'f16s2'] + ['f16x'],
                     help="f16: the key-point network's 3x3 stride-1 convolutions with f16 operands (opt-in fast mode); "
                          "f16s2: those and the 3x3 stride-2 ones; f16x: those and the 3x3 convolutions of the 32-multiple widths")
+    ap.add_argument('--activations', default='f32', choices=['f32', 'f16'],
+                    help='f16: tensors between two f16-operand convolutions are stored as f16 (the same results, fewer bytes)')
     ap.add_argument('--draw', default=None, metavar='DIR', help='draw the predictions on the frames, PNGs into DIR')
     ap.add_argument('--draw-gt', action='store_true', help='add the label boxes of --gt to the top view')
     a = ap.parse_args(argv)

@@ -28,7 +28,18 @@ epilogue) class the mode lowers on HRNet-W32 at 192 x 256 (the Pedestrian model)
 read off the recorded programs, each against the fp32 op of the shipped table at 64 and 16 crops; the Pedestrian
 ``infer_crops`` step in 'f32' against 'f16x' and the W48 step in 'f16s2' against 'f16x'; the deviation of 'f16x' from 'f32'
 on the device for W32.  ``keep`` per (cin, cout, stride) by the rule above; the others are what engine.F16X_FP32_CLASSES
-has to name."""
+has to name.
+
+``--a`` measures what activations = 'f16' (f16 STORAGE between two f16-operand convolutions) buys, default
+--out profiles/f16_storage_bench.json.  Results cannot differ (tests/test_gpu_f16_storage_mode.py), so only time is measured:
+every (producer, consumer) PAIR around a tensor ``engine.f16_storage`` names on HRNet-W48 and HRNet-W32 (192 x 256) under
+'f16x', read off the recorded programs with the consumer's own epilogue, as a two-op program with the tensor in fp32 against
+the same program with it in f16 -- both in one process, the order of the two alternating pass by pass, microseconds of
+both ops together from ``egn_program_run_timed``, medians and spread as above, at 64 and 16 crops, beside the bytes floor at
+8 TB/s.  Then the ``infer_crops`` step of both models under 'f16x' with the switch off against on (the switch-off program is
+the one the parent commit records, tests/test_f16_storage_cpu.py), and the 16-crop step in a fresh model.  ``keep`` per
+PRODUCER (cin, cout, stride): faster beyond the spread at 64 crops and not slower beyond it at 16 in every pair; the
+others are what engine.F16_STORAGE_FP32_CLASSES has to name."""
 import argparse
 import ctypes as C
 import json
@@ -188,15 +199,15 @@ def _w48_ego():
     return ego.eval().cuda()
 
 
-def step_row(ego, batch, passes, steps, modes=('f32', 'f16'), size=(256, 256)):
-    """``size``: (height, width) of the crops."""
+def step_row(ego, batch, passes, steps, modes=('f32', 'f16'), size=(256, 256), attr='precision'):
+    """``size``: (height, width) of the crops.  ``attr``: the switch of ``ego.HC`` the two modes are values of."""
     crops = synth.synth_crops(batch, 3, size[0], size[1], seed=100).cuda()
     rets = [modify_bbox(b, 1.0) for b in synth.synth_boxes(batch, seed=5)]
     centers = torch.tensor(np.stack([r['c'] for r in rets]), dtype=torch.float64, device='cuda')
     scales = torch.tensor(np.stack([r['s'] for r in rets]), dtype=torch.float64, device='cuda')
 
     def window(prec):
-        ego.HC.precision = prec
+        setattr(ego.HC, attr, prec)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -212,7 +223,7 @@ def step_row(ego, batch, passes, steps, modes=('f32', 'f16'), size=(256, 256)):
     for _ in range(passes):
         for prec in modes:
             t[prec].append(window(prec)[0])
-    ego.HC.precision = 'f32'
+    setattr(ego.HC, attr, 'f32')
     m32, m16 = statistics.median(t[ma]), statistics.median(t[mb])
     row = {'crops': batch, 'steps_per_window': steps, ma + '_ms_per_step': m32, mb + '_ms_per_step': m16,
            ma + '_all_ms': t[ma], mb + '_all_ms': t[mb], ma + '_crops_per_s': batch / m32 * 1e3,
@@ -302,6 +313,152 @@ def accuracy_x(ego):
     return out
 
 
+def a_pairs(cfg, n, precision='f16x'):
+    """Every (producer, consumer) pair around a tensor activations = 'f16' stores as f16 on the model of ``cfg`` at ``n``
+    crops, whatever engine.F16_STORAGE_FP32_CLASSES holds: sorted unique
+    ((cin, cout, stride, h, w, act, ck), (cout2, stride2, act2, residual2, ck2)), h x w the producer's INPUT map."""
+    from egonet_amd.model.heatmapModel import hrnet
+    net = hrnet.get_pose_net(cfg, is_train=False).eval()
+    net.precision = precision
+    iw, ih = cfg['heatmapModel']['input_size']
+    with torch.no_grad():
+        rec, _, _ = engine.HRNetEngine(net)._record(n, 3, ih, iw, None)
+    shipped, engine.F16_STORAGE_FP32_CLASSES = engine.F16_STORAGE_FP32_CLASSES, ()
+    try:
+        bufs = engine.f16_storage(rec)
+    finally:
+        engine.F16_STORAGE_FP32_CLASSES = shipped
+
+    def stride_ck(kind, op):
+        rule = engine._RULE_OF_KIND[kind]
+        return (op['stride'] if rule.stride_arg else rule.strides[0]), rule.ck
+    pairs = set()
+    for kind, op in rec.ops:
+        if op.get('x16'):
+            (pk, prod), = [(k, o) for k, o in rec.ops if o.get('y') is op['x']]
+            assert op['x'] in bufs and prod.get('y16')
+            ps, pck = stride_ck(pk, prod)
+            cs_, cck = stride_ck(kind, op)
+            pairs.add(((prod['cin'], prod['cout'], ps, prod['x'].h, prod['x'].w, prod['act'], pck),
+                       (op['cout'], cs_, op['act'], op.get('res') is not None, cck)))
+    return sorted(pairs)
+
+
+def pair_row(n, prod, cons, passes):
+    """Producer + consumer as a two-op program, the tensor between them in fp32 against f16 (both through
+    egn_program_add_conv3x3_h16, flags 0 / 1): us of both ops together per pass, the two programs in alternating order."""
+    L = _lib.lib()
+    cin, cmid, s1, h, w, act1, ck1 = prod
+    cout, s2, act2, has_res, ck2 = cons
+    h1, w1 = (h - 1) // s1 + 1, (w - 1) // s1 + 1
+    h2, w2 = (h1 - 1) // s2 + 1, (w1 - 1) // s2 + 1
+    g = torch.Generator().manual_seed(cin + cmid + cout + n)
+    x = torch.relu(torch.randn(n, h, w, cin, generator=g)).cuda()
+
+    def filt(co, ci, ck):
+        wt = torch.randn(co, ci, 3, 3, generator=g) / (3.0 * ci ** 0.5)
+        return (engine.pack_conv_weight_f16x if ck == 32 else engine.pack_conv_weight_f16)(wt).cuda()
+    wa, wb = filt(cmid, cin, ck1), filt(cout, cmid, ck2)
+    sa, ha = (torch.rand(cmid, generator=g) + 0.5).cuda(), torch.randn(cmid, generator=g).cuda()
+    sb, hb = (torch.rand(cout, generator=g) + 0.5).cuda(), torch.randn(cout, generator=g).cuda()
+    # the consumer's residual: the block's own input where the shapes agree (a BasicBlock), else a tensor of its own
+    res = x if has_res and tuple(x.shape) == (n, h2, w2, cout) else torch.randn(n, h2, w2, cout, generator=g).cuda()
+    mids = {0: torch.empty(n, h1, w1, cmid, device='cuda'), 1: torch.empty(n, h1, w1, cmid, device='cuda', dtype=torch.float16)}
+    ys = {0: torch.empty(n, h2, w2, cout, device='cuda'), 1: torch.empty(n, h2, w2, cout, device='cuda')}
+    progs = {}
+    for f16 in (0, 1):
+        p = C.c_void_p(L.egn_program_create(12))
+        tensors = (x, wa, sa, ha, mids[f16], wb, sb, hb, res, ys[f16])
+        for slot, t in enumerate(tensors):
+            _lib.check(L.egn_program_bind(p, slot, _lib.ptr(t)))
+        R = [_lib.Ref(k, 0) for k in range(len(tensors))]
+        _lib.check(L.egn_program_add_conv3x3_h16(p, R[0], R[1], R[2], R[3], _lib.NULL_REF, R[4], n, h, w, cin, cmid, act1, s1,
+                                                 ck1, 0, f16), 'producer')
+        _lib.check(L.egn_program_add_conv3x3_h16(p, R[4], R[5], R[6], R[7], R[8] if has_res else _lib.NULL_REF, R[9], n, h1, w1,
+                                                 cmid, cout, act2, s2, ck2, f16, 0), 'consumer')
+        progs[f16] = p
+    st = _lib.current_stream()
+    us = {0: [], 1: []}
+    ops = {0: [], 1: []}
+    ms = (C.c_float * 2)()
+    try:
+        for it in range(2 + passes):
+            for f16 in ((0, 1) if it % 2 == 0 else (1, 0)):
+                _lib.check(L.egn_program_run_timed(progs[f16], st, ms, 2))
+                if it >= 2:
+                    us[f16].append((ms[0] + ms[1]) * 1e3)
+                    ops[f16].append([ms[0] * 1e3, ms[1] * 1e3])
+        torch.cuda.synchronize()
+        same = bool(torch.equal(ys[0], ys[1]))
+    finally:
+        for p in progs.values():
+            L.egn_program_destroy(p)
+    m32, m16 = statistics.median(us[0]), statistics.median(us[1])
+    s32, s16 = max(us[0]) - min(us[0]), max(us[1]) - min(us[1])
+    spread = max(s32, s16)
+    px0, px1, px2 = float(n * h * w), float(n * h1 * w1), float(n * h2 * w2)
+    fixed = 4.0 * (px0 * cin + px2 * cout * (2 if has_res else 1))
+    return {'crops': n, 'class': '%d->%d s%d@%dx%d -> %d s%d%s' % (cin, cmid, s1, h, w, cout, s2, ' +res' if has_res else ''),
+            'producer_key': [cin, cmid, s1], 'consumer': [cmid, cout, s2, act2, has_res],
+            'f32_storage_us': m32, 'f32_storage_spread_us': s32, 'f16_storage_us': m16, 'f16_storage_spread_us': s16,
+            'f32_storage_all_us': us[0], 'f16_storage_all_us': us[1],
+            'f32_storage_ops_us': [statistics.median(o[k] for o in ops[0]) for k in (0, 1)],
+            'f16_storage_ops_us': [statistics.median(o[k] for o in ops[1]) for k in (0, 1)],
+            'speedup': m32 / m16, 'faster': bool(m32 - m16 > spread), 'not_slower': bool(m16 - m32 <= spread),
+            'bytes_floor_us': [(fixed + 8.0 * px1 * cmid) / 8.0e12 * 1e6, (fixed + 4.0 * px1 * cmid) / 8.0e12 * 1e6],
+            'outputs_bit_identical': same}
+
+
+def main_a(a):
+    rows = []
+    for n in (64, 16) if not a.no_pairs else ():
+        ped = a_pairs(configs.ped_config('coordinates'), n)
+        w48 = [c for c in a_pairs(configs.w48_config('coordinates'), n) if c not in ped]
+        for model, pairs in (('w32_192x256', ped), ('w48_256x256', w48)):
+            for prod, cons in pairs:
+                rows.append(dict(pair_row(n, prod, cons, a.passes), model=model))
+    keep = {}
+    for r in rows:
+        k = '%d->%d s%d' % tuple(r['producer_key'])
+        keep[k] = keep.get(k, True) and (r['faster'] if r['crops'] == 64 else r['not_slower'])
+    out = {'what': 'us of a producer + consumer pair of f16-operand 3x3 ops (egn_program_run_timed, both ops together, medians '
+                   'of %d passes, spread = max - min) with the tensor between them stored as fp32 against f16; ms per '
+                   'infer_crops step of HRNet-W48 and HRNet-W32 (192 x 256) under f16x with activations f32 against f16 '
+                   '(medians of alternating windows)' % a.passes,
+           'device': torch.cuda.get_device_name(0), 'pairs': rows, 'keep': keep,
+           'all_outputs_bit_identical': all(r['outputs_bit_identical'] for r in rows),
+           'F16_STORAGE_FP32_CLASSES_measured': sorted(k for k, v in keep.items() if not v),
+           'F16_STORAGE_FP32_CLASSES_shipped': [list(c) for c in engine.F16_STORAGE_FP32_CLASSES]}
+    if not a.no_step:
+        for name, mk, size in (('w48', _w48_ego, (256, 256)), ('w32', _ped_ego, (256, 192))):
+            ego = mk()
+            ego.HC.precision = 'f16x'
+            out[name + '_infer_crops_step'] = [step_row(ego, b, a.passes, a.steps, size=size, attr='activations')
+                                               for b in (64, 16)]
+            # the 16-crop step again in a model of its own that never ran 64 crops (as --s2 / --x: its time moves with
+            # where the programs' arenas lie)
+            del ego
+            torch.cuda.empty_cache()
+            ego = mk()
+            ego.HC.precision = 'f16x'
+            out[name + '_infer_crops_step_16_crops_fresh_model'] = step_row(ego, 16, a.passes, a.steps, size=size,
+                                                                            attr='activations')
+            del ego
+            torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    steps = {k: v if isinstance(v, list) else [v] for k, v in out.items() if 'infer_crops_step' in k}
+    print(json.dumps({'out': a.out, 'keep': keep, 'bit_identical': out['all_outputs_bit_identical'],
+                      'pairs': {'%s n%d' % (r['class'], r['crops']): [round(r['f32_storage_us'], 1), round(r['f32_storage_spread_us'], 1),
+                                                                      round(r['f16_storage_us'], 1), round(r['f16_storage_spread_us'], 1)]
+                                for r in rows},
+                      'step_ms': {k: [[r['crops'], round(r['f32_ms_per_step'], 3), round(r['f16_ms_per_step'], 3)] for r in v]
+                                  for k, v in steps.items()}}))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--passes', type=int, default=7)
@@ -309,14 +466,18 @@ def main(argv=None):
     ap.add_argument('--no-step', action='store_true', help='the per-class table alone')
     ap.add_argument('--s2', action='store_true', help="what precision = 'f16s2' adds to 'f16' (the stride-2 classes)")
     ap.add_argument('--x', action='store_true', help="what precision = 'f16x' adds (the 32-multiple widths)")
+    ap.add_argument('--no-pairs', action='store_true', help='with --a: the steps alone (under the shipped exception tuple)')
+    ap.add_argument('--a', action='store_true', help="what activations = 'f16' buys (f16 storage between f16-operand convs)")
     ap.add_argument('--out', default=None)
     a = ap.parse_args(argv)
     if a.passes < 3:
         ap.error('--passes must be at least 3')
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'f16x_mode_bench.json' if a.x else
+        a.out = os.path.join(ROOT, 'profiles', 'f16_storage_bench.json' if a.a else 'f16x_mode_bench.json' if a.x else
                              ('f16s2_mode_bench.json' if a.s2 else 'f16_mode_bench.json'))
     os.environ.setdefault('EGONET_AMD_AUTOTUNE', '0')
+    if a.a:
+        return main_a(a)
     if a.x:
         return main_x(a)
     if a.s2:
